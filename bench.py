@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: Gbp/s of ESA construction (suf+lcp+bwt).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
 
 A "step" is one complete build of the enhanced suffix array (.suf + .lcp/.llv +
 .bwt, resident in HBM) from the encoded sequence already resident in HBM in
@@ -34,6 +34,16 @@ The JSON line carries, besides the contract fields:
   cpu_baseline  the reference's own engine (oracle/_ref/gt_ref_sfx, kind
                 "reference") or the CPU restatement (kind "port") timed on
                 this host's cores on a bounded sample of the same model.
+
+--dump-outputs DIR writes, after the timed steps, the tables the last step left
+resident (what a caller of the engine copies out) as DIR/<name>.npy: suf, lcp
+and bwt on the same rows (rows.npy), the .llv pairs (llv.npy, N x 2) on theirs
+(llv_rows.npy).  A table of more than DUMP_RUNS x DUMP_RUN rows is sampled in
+runs of DUMP_RUN consecutive rows: the first run, the last and seeded ones
+between, the same rows for the same arguments.  Values are float64 (exact for
+these integers) except lcp and bwt (bytes, float32); 36 MB at most.  With
+N > 1 every rank writes its slice (rows counted in the whole table) with a
+suffix _rank<r>.
 """
 import argparse
 import hashlib
@@ -65,6 +75,51 @@ JOB_BYTES_PER_BP = 10.25       # 0.25 text + 8 suf + 1 lcp + 1 bwt
 DOMINANT = {0: ("k_rs_scatter (radix scatter pass of the LSD sort)", 12.0, 12.0),
             1: ("k_msd_local (last level of the MSD sort: LDS sort of a run + table emission)",
                 8.0, 14.125)}
+# --dump-outputs: runs of consecutive rows sampled from a large table
+DUMP_RUN = 1024
+DUMP_RUNS = {esa.TAB_SUF: 1024, esa.TAB_LLV: 512}
+DUMP_SEED = 0x5EED
+DUMP_LIMIT = 64 << 20
+
+
+def sample_runs(entries, runs, seed):
+    """(first row, rows) of every sampled run: the whole table when it is small,
+    else the first run, the last and `runs` - 2 seeded ones between them"""
+    if entries <= runs * DUMP_RUN:
+        return [(0, entries)] if entries else []
+    nrun = entries // DUMP_RUN
+    rng = np.random.default_rng(seed)
+    middle = 1 + rng.choice(nrun - 1, size=runs - 2, replace=False)
+    firsts = [0] + sorted(int(r) * DUMP_RUN for r in middle) + [entries - DUMP_RUN]
+    return [(f, DUMP_RUN) for f in firsts]
+
+
+def dump_outputs(eng, out_dir, suffix):
+    """the resident tables of the last run (sampled when large) as .npy files"""
+    os.makedirs(out_dir, exist_ok=True)
+    offset = eng.table_offset()
+    runs = sample_runs(eng.entries(esa.TAB_SUF), DUMP_RUNS[esa.TAB_SUF], DUMP_SEED)
+    llv_runs = sample_runs(eng.entries(esa.TAB_LLV), DUMP_RUNS[esa.TAB_LLV], DUMP_SEED + 1)
+
+    def gather(which, spans, dtype):
+        parts = [eng.table(which, first, count) for first, count in spans]
+        if not parts:
+            return np.empty((0, 2) if which == esa.TAB_LLV else 0, dtype=dtype)
+        return np.concatenate(parts).astype(dtype)
+
+    def rows(spans, base=0):
+        return np.concatenate([np.arange(first, first + count, dtype=np.float64)
+                               for first, count in spans] or [np.empty(0)]) + base
+
+    arrays = {"rows": rows(runs, offset),
+              "suf": gather(esa.TAB_SUF, runs, np.float64),
+              "lcp": gather(esa.TAB_LCP, runs, np.float32),
+              "bwt": gather(esa.TAB_BWT, runs, np.float32),
+              "llv_rows": rows(llv_runs),
+              "llv": gather(esa.TAB_LLV, llv_runs, np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def cpu_baseline(model, seed, sample_n):
@@ -110,7 +165,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="gloo + --same-device rehearses N>1 on one GPU")
     ap.add_argument("--same-device", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the tables of the last timed step to DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -184,6 +243,8 @@ def main():
         exchanged = float(t[4].item())
     else:
         exchanged = 0.0
+    if a.dump_outputs:
+        dump_outputs(eng, a.dump_outputs, "_rank%d" % rank if world > 1 else "")
     if rank == 0:
         ms_per_step = dt / a.steps * 1e3
         value = n / (dt / a.steps) / 1e9
