@@ -903,14 +903,6 @@ template <typename P> struct RankUpdates {
   }
 };
 
-template <typename P>
-__global__ __launch_bounds__(256) void k_isa_store(const u32 *__restrict__ off,
-                                                   const P *__restrict__ rank, u64 cnt,
-                                                   P *__restrict__ isa) {
-  const u64 i = (u64) blockIdx.x * 256 + threadIdx.x;
-  if (i < cnt) isa[off[i]] = rank[i];
-}
-
 // records (offset, rank) as FilteredRanks / the fused round exchange send them
 template <typename P>
 __global__ __launch_bounds__(256) void k_isa_store_rec(const u32 *__restrict__ rec, u64 cnt,
@@ -990,14 +982,6 @@ __global__ __launch_bounds__(256) void k_fuse_answers(FuseTab tab, const u32 *__
   const u32 s = fuse_part(tab.qpre, tab.n, (u32) i);
   const u32 us = tab.upre[s + 1] - tab.upre[s];
   ans[i] = isa[msg[tab.wpre[s] + (u64) us * W + ((u32) i - tab.qpre[s])]];
-}
-
-template <typename P>
-__global__ __launch_bounds__(256) void k_answer(const u32 *__restrict__ q, u64 cnt,
-                                                const P *__restrict__ isa,
-                                                P *__restrict__ ans) {
-  const u64 i = (u64) blockIdx.x * 256 + threadIdx.x;
-  if (i < cnt) ans[i] = isa[q[i]];
 }
 
 template <typename P>
@@ -1973,12 +1957,12 @@ __global__ __launch_bounds__(256) void k_pair_emit(
 // here, the tables get their entries from k_pair_apply, which walks the pairs
 // in TABLE order (in text order its five accesses per pair were five random
 // lines: 18 ms for 170 M pairs)
-constexpr int PR_LINE_MAX = 16; // records a thread loads at once at most (a chunk is a multiple of it)
-template <int BITS, typename P, int PR_LINE>
+constexpr int PR_LINE = 16;     // records a thread loads at once (a chunk is a multiple of it)
+template <int BITS, typename P>
 __global__ __launch_bounds__(256) void k_pair_resolve(
     Text t, const P *__restrict__ pkey, const u64 *__restrict__ pval, u64 nrec, u64 np,
     const u32 *__restrict__ pidx, P *__restrict__ sa, u32 *__restrict__ res, Stats *stats,
-    int chunk, int longext) {
+    int chunk) {
   // records with ordinal < np are pairs (their LCP is a table entry: counted in
   // the statistics); the others are pairs of members of small groups
   __shared__ unsigned long long s_sum[4], s_large[4];
@@ -2056,18 +2040,7 @@ __global__ __launch_bounds__(256) void k_pair_resolve(
           }
         }
       }
-      if (!known) {
-        if (longext) {
-          l = lcp_extend_long<BITS, 4>(t, a, b, (u64) Key<BITS>::KNOWN, &a_first);
-        } else {                                     // (A/B: GTAMD_PAIR_LONG=0)
-          l = lcp_extend<BITS>(t, a, b, (u64) Key<BITS>::KNOWN);
-          // the first difference decides: a special is larger than every letter,
-          // two specials compare by position
-          const bool spa = is_special(t, a + l), spb = is_special(t, b + l);
-          a_first = (spa || spb) ? ((spa && spb) ? a < b : spb)
-                                 : Sym<BITS>::at(t, a + l) < Sym<BITS>::at(t, b + l);
-        }
-      }
+      if (!known) l = lcp_extend_long<BITS, 4>(t, a, b, (u64) Key<BITS>::KNOWN, &a_first);
 #pragma unroll
       for (int k = RING - 1; k > 0; k--) { ra[k] = ra[k - 1]; rb[k] = rb[k - 1]; rl[k] = rl[k - 1]; rf[k] = rf[k - 1]; }
       ra[0] = a; rb[0] = b; rl[0] = l; rf[0] = a_first;
@@ -2802,12 +2775,129 @@ __global__ __launch_bounds__(256) void k_llv_emit(
 static inline u32 stride_grid(u64 tiles) {
   // (3 Gbp, 2048 / 4096 / 8192 / 16384 workgroups alternating in one process:
   // 140.4 / 139.4 / 139.15 / 139.2 ms)
-  u64 cap = 256 * 32;
-  if (const char *e = getenv("GTAMD_STRIDE_WGS")) { const long v = atol(e); if (v >= 256 && v <= (1 << 20)) cap = (u64) v; }
+  const u64 cap = 256 * 32;
   return (u32) (tiles < cap ? (tiles ? tiles : 1) : cap);
 }
 
 #include "esa_msd.h"
+
+// ---------------------------------------------------------------------------
+// Switches of a build run, read from the environment once per gtamd_esa_run (tests
+// change them between runs on one context).  They force, at small sizes, paths the
+// default selection takes only at large n or on particular inputs; an unset or
+// out-of-range value leaves the default.  [who sets them: tests/test_*.py, tools/*.py]
+//   GTAMD_MSD               1: the MSD first sort at any size, other values: the LSD
+//                           sort (whole table); 0: tile keygen + exchange + LSD sort
+//                           (DNA parts)  [test_msd_gpu, fuzz_gpu]
+//   GTAMD_MSD_CBITS         depth of level C, 0..8  [test_msd_gpu, fuzz_gpu, skew_probe]
+//   GTAMD_MSD_BIG_MAX       largest run one workgroup sorts alone: the giant path
+//                           [test_msd_gpu, fuzz_gpu]
+//   GTAMD_MSD_RADIX         1: every level-D run through the LDS radix passes
+//                           [test_msd_gpu, fuzz_gpu]
+//   GTAMD_MSD_PACK          0: level-D tiles cut by the stride rule, not packed
+//                           [test_msd_gpu, fuzz_gpu, exact_probe]
+//   GTAMD_MSD_PACK_CAP      size limit of a packed level-D tile  [fuzz_gpu]
+//   GTAMD_MSD_BIN_LIMIT     crowded-bin limit of k_msd_local  [fuzz_gpu, exact_probe]
+//   GTAMD_FUSED_PASS0       0: plain DNA keygen + all LSD passes  [test_esa_gpu]
+//   GTAMD_FORCE_WIDE        1: 64-bit positions and the part machinery at any size
+//                           [test_esa_gpu, test_parts_gpu, test_dist_nccl_gpu, fuzz_gpu]
+//   GTAMD_NO_PAIRS          1: no pair path, everything through the rounds
+//                           [test_esa_gpu, fuzz_gpu]
+//   GTAMD_NO_SMALL_GROUPS   1: no small groups in the pair list
+//                           [test_esa_gpu, fuzz_gpu, exact_probe]
+//   GTAMD_APPLY_EARLY       0 / 1 / 2: where the pairs' table entries are written
+//                           (out of range: 0)  [test_esa_gpu, fuzz_gpu, exact_probe,
+//                           pairs_probe]
+//   GTAMD_APPLY_WGS         grid of those entries beside the rounds  [test_esa_gpu]
+//   GTAMD_RANK_WINDOW_BITS  smaller rank-table windows: every window shape
+//                           [test_esa_gpu, test_parts_gpu, fuzz_gpu]
+//   GTAMD_RANK_ALL_WINDOWS  1: the whole rank table, not only the windows needed
+//                           [test_esa_gpu, fuzz_gpu, exact_probe]
+//   GTAMD_WIN_FILTER_LDS    0: k_win_filter's bitmap in global memory, as for texts
+//                           of more than 3.9 G symbols  [test_esa_gpu, fuzz_gpu,
+//                           exact_probe]
+//   GTAMD_PAIR_CHUNK        pairs per thread of k_pair_resolve  [fuzz_gpu, exact_probe]
+//   GTAMD_ROUND_STRIDE      distance of the round tiles' starts  [fuzz_gpu, exact_probe]
+//   GTAMD_DEBUG             set: what the run chose, on stderr
+// ---------------------------------------------------------------------------
+struct Switches {
+  int msd = -1;                  // whole table: 1 / 0, -1: by size
+  bool msd_part_off = false;     // parts: GTAMD_MSD=0
+  int msd_cbits = -1;            // -1: chosen per build
+  u32 msd_big_max = MSD_BIG_MAX;
+  bool msd_radix = false;
+  bool msd_pack = true;
+  u32 msd_pack_cap = MD_CAP;
+  u32 msd_bin_limit = MD_BIN_LIMIT_DEFAULT;
+  bool fused_pass0 = true;
+  bool force_wide = false;
+  bool no_pairs = false;
+  bool no_small_groups = false;
+  int apply_early = 2;
+  u64 apply_wgs = 0;             // 0: one workgroup per CU
+  bool apply_wgs_given = false;  // (also when out of range: see launch_apply)
+  int rank_window_bits = RW_BITS;
+  bool rank_all_windows = false;
+  bool win_filter_global = false;
+  int pair_chunk = 0;            // 0: by the number of records
+  u32 round_stride = 1536;
+  bool debug = false;
+};
+
+static Switches read_switches() {
+  Switches sw;
+  auto flag = [](const char *name, char c) {
+    const char *e = getenv(name);
+    return e != nullptr && e[0] == c;
+  };
+  if (const char *e = getenv("GTAMD_MSD")) sw.msd = e[0] == '1';
+  sw.msd_part_off = flag("GTAMD_MSD", '0');
+  if (const char *e = getenv("GTAMD_MSD_CBITS")) {
+    const int v = atoi(e);
+    if (v >= 0 && v <= 8) sw.msd_cbits = v;
+  }
+  if (const char *e = getenv("GTAMD_MSD_BIG_MAX")) {
+    const long v = atol(e);
+    if (v >= MS_TILE && v <= (long) MSD_BIG_MAX) sw.msd_big_max = (u32) v;
+  }
+  sw.msd_radix = flag("GTAMD_MSD_RADIX", '1');
+  if (const char *e = getenv("GTAMD_MSD_PACK")) sw.msd_pack = atoi(e) != 0;
+  if (const char *e = getenv("GTAMD_MSD_PACK_CAP")) {
+    const long v = atol(e);
+    if (v >= 1024 && v <= (long) MD_CAP) sw.msd_pack_cap = (u32) v;
+  }
+  if (const char *e = getenv("GTAMD_MSD_BIN_LIMIT")) {
+    const long v = atol(e);
+    if (v >= 2 && v <= 4096) sw.msd_bin_limit = (u32) v;
+  }
+  sw.fused_pass0 = !flag("GTAMD_FUSED_PASS0", '0');
+  sw.force_wide = flag("GTAMD_FORCE_WIDE", '1');
+  sw.no_pairs = flag("GTAMD_NO_PAIRS", '1');
+  sw.no_small_groups = flag("GTAMD_NO_SMALL_GROUPS", '1');
+  if (const char *e = getenv("GTAMD_APPLY_EARLY")) sw.apply_early = atoi(e);
+  if (sw.apply_early < 0 || sw.apply_early > 2) sw.apply_early = 0;
+  if (const char *e = getenv("GTAMD_APPLY_WGS")) {
+    const long v = atol(e);
+    if (v >= 64 && v <= (1 << 22)) sw.apply_wgs = (u64) v;
+    sw.apply_wgs_given = true;
+  }
+  if (const char *e = getenv("GTAMD_RANK_WINDOW_BITS")) {
+    const int v = atoi(e);
+    if (v >= 2 && v <= RW_BITS) sw.rank_window_bits = v;
+  }
+  sw.rank_all_windows = flag("GTAMD_RANK_ALL_WINDOWS", '1');
+  sw.win_filter_global = flag("GTAMD_WIN_FILTER_LDS", '0');
+  if (const char *e = getenv("GTAMD_PAIR_CHUNK")) {
+    const int v = atoi(e);
+    if (v >= 4 && v <= 1024) sw.pair_chunk = v;
+  }
+  if (const char *e = getenv("GTAMD_ROUND_STRIDE")) {
+    const int v = atoi(e);
+    if (v >= RT_STRIDE_MIN && v <= RT_TILE) sw.round_stride = (u32) v;
+  }
+  sw.debug = getenv("GTAMD_DEBUG") != nullptr;
+  return sw;
+}
 
 // ---------------------------------------------------------------------------
 // context
@@ -2838,7 +2928,6 @@ struct gtamd_esa_ctx {
                            // bucketing scratch and 64-bit positions of a part build
   DevBuf rws;              // radix / scan workspace
   DevBuf msd;              // tables of the most-significant-digit-first sort (esa_msd.h)
-  DevBuf dig0, dig1;       // digit side arrays of the first sort (experiment)
   DevBuf suf, lcp, bwt;    // outputs at on-disk width
   DevBuf tiebits, tiebits2;
   DevBuf arena;            // unresolved list, round buffers
@@ -2921,7 +3010,7 @@ extern "C" void gtamd_esa_destroy(gtamd_esa_ctx *c) {
   if (c->st != nullptr) (void) hipStreamSynchronize(c->st);
   if (c->st2 != nullptr) (void) hipStreamSynchronize(c->st2);
   DevBuf *bufs[] = {&c->tb_own, &c->sp_own, &c->k0, &c->k1, &c->v0, &c->v1, &c->isa_tmp,
-                    &c->rws, &c->dig0, &c->dig1, &c->suf, &c->lcp, &c->bwt, &c->tiebits,
+                    &c->rws, &c->suf, &c->lcp, &c->bwt, &c->tiebits,
                     &c->tiebits2, &c->arena, &c->arena_p, &c->xrecv, &c->winbuf, &c->msd,
                     &c->lcpfull_buf, &c->partws, &c->posw};
   for (DevBuf *b : bufs) free_buf(*b);
@@ -3332,14 +3421,6 @@ static int ensure_workspace(gtamd_esa_ctx *c, u64 cap, u32 want, bool dist) {
   if (want & GTAMD_WANT_LCP) TRY(ensure_buf(c, c->lcp, pad, "the lcp table"));
   if (want & GTAMD_WANT_BWT) TRY(ensure_buf(c, c->bwt, pad, "the bwt table"));
   if (dist) TRY(ensure_buf(c, c->isa_tmp, pad * 8, "the exchange scratch"));
-  {
-    // digit-byte side arrays of the sort: an experiment switch (esa_prims.hip)
-    const char *db = getenv("GTAMD_DIGBYTES");
-    if (db != nullptr && db[0] == '1') {
-      TRY(ensure_buf(c, c->dig0, pad, "digit bytes"));
-      TRY(ensure_buf(c, c->dig1, pad, "digit bytes"));
-    }
-  }
   return 0;
 }
 
@@ -3360,14 +3441,6 @@ static int msd_cbits_max(u64 N) {
   const int c = bits_for(N > 1 ? N - 1 : 1) - 24;
   return c < 0 ? 0 : (c > 8 ? 8 : c);
 }
-// forced depth (tests: every depth at small N), or -1
-static int msd_cbits_forced() {
-  if (const char *e = getenv("GTAMD_MSD_CBITS")) {
-    const int v = atoi(e);
-    if (v >= 0 && v <= 8) return v;
-  }
-  return -1;
-}
 // penalty[k]: what level D pays with cmax - 2 + k bits, summed over the entries
 // (k_msd_skew, ms per 10^9 entries).  Per 10^9 entries one bit less than the
 // deepest is worth ~0.17 ms, two ~0.57 ms (3 Gbp, alternating in one process).
@@ -3384,13 +3457,6 @@ static int msd_choose_cbits(u64 N, int cmax, const float *penalty) {
     if (cost < best_cost) { best = c; best_cost = cost; }
   }
   return best;
-}
-static u32 msd_big_max() {
-  if (const char *e = getenv("GTAMD_MSD_BIG_MAX")) {   // tests: the giant path at small N
-    const long v = atol(e);
-    if (v >= MS_TILE && v <= (long) MSD_BIG_MAX) return (u32) v;
-  }
-  return MSD_BIG_MAX;
 }
 struct MsdWs {
   u32 *hist, *scanws, *tcnt, *tfirst, *dtcnt, *dtfirst, *startA, *startB, *F, *scan2, *counters,
@@ -3470,12 +3536,12 @@ struct MsdPartSrc {
   int has_prev;
 };
 template <int FMT>
-static int msd_sort_emit(gtamd_esa_ctx *c, u32 want, u32 prefixlength, u64 N, u64 density_n,
-                         const MsdPartSrc *src, u32 **sa_out,
+static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 prefixlength, u64 N,
+                         u64 density_n, const MsdPartSrc *src, u32 **sa_out,
                          u64 **fkey, u32 **fval, u64 *local_entries) {
   hipStream_t st = c->st;
   const int cmax = msd_cbits_max(density_n);
-  int cb = msd_cbits_forced() >= 0 ? msd_cbits_forced() : cmax;
+  int cb = sw.msd_cbits >= 0 ? sw.msd_cbits : cmax;
   MsdWs w;
   const u64 bytes = msd_carve(N, cb > cmax ? cb : cmax, nullptr, &w);    // room for the deepest level C
   TRY(ensure_buf(c, c->msd, bytes, "the tables of the first sort"));
@@ -3515,7 +3581,7 @@ static int msd_sort_emit(gtamd_esa_ctx *c, u32 want, u32 prefixlength, u64 N, u6
   k_msd_scatter_lvl<1><<<((w.tilesB_ub + 7u) >> 3) * 8u, MS_THREADS, 0, st>>>(
       ka, xa, pa, w.desc, w.tilesB_ub, w.hist, w.tfirst, w.startB, 8, 24, kb, pb);
   HIP_TRY(hipGetLastError());
-  if (msd_cbits_forced() < 0 && cmax >= 1) {
+  if (sw.msd_cbits < 0 && cmax >= 1) {
     // how deep level C has to cut, from the ranges level B leaves (the host
     // waits here while the device moves the entries of level B)
     float *d_exp = reinterpret_cast<float *>(w.counters);
@@ -3540,18 +3606,15 @@ static int msd_sort_emit(gtamd_esa_ctx *c, u32 want, u32 prefixlength, u64 N, u6
   HIP_TRY(hipMemsetAsync(w.counters, 0, 64, st));
   // tiles of whole ranges: packed (default), or cut by the stride rule
   // (GTAMD_MSD_PACK=0, kept for comparison)
-  const char *pk = getenv("GTAMD_MSD_PACK");
-  const bool packed = pk == nullptr || atoi(pk) != 0;
-  u32 pack_cap = MD_CAP;
-  if (const char *e = getenv("GTAMD_MSD_PACK_CAP")) { const long v = atol(e); if (v >= 1024 && v <= (long) MD_CAP) pack_cap = (u32) v; }
-  if (packed) {
+  const u32 pack_cap = sw.msd_pack_cap;
+  if (sw.msd_pack) {
     k_msd_pack<false><<<(MSD_PARENTS + 1 + 255) / 256, 256, 0, st>>>(F, cb, nullptr, pack_cap, w.dtcnt, nullptr,
                                                                 nullptr, nullptr, nullptr, 0);
     HIP_TRY(hipGetLastError());
     TRY(scan_u32(SCAN_SUM, w.dtcnt, w.dtfirst, (u64) MSD_PARENTS + 1, false, w.scan2, st));
     k_msd_pack<true><<<(MSD_PARENTS + 1 + 255) / 256, 256, 0, st>>>(F, cb, w.dtfirst, pack_cap, nullptr, w.dtiles,
                                                                w.biglist, w.giantlist, w.counters,
-                                                               msd_big_max());
+                                                               sw.msd_big_max);
     HIP_TRY(hipGetLastError());
   } else {
   k_msd_tilecount<<<(MSD_PARENTS + 1 + 255) / 256, 256, 0, st>>>(F, cb, MSD_PARENTS, MSD_STRIDE,
@@ -3560,7 +3623,7 @@ static int msd_sort_emit(gtamd_esa_ctx *c, u32 want, u32 prefixlength, u64 N, u6
   TRY(scan_u32(SCAN_SUM, w.dtcnt, w.dtfirst, (u64) MSD_PARENTS + 1, false, w.scan2, st));
   k_msd_dtiles<<<(w.tilesD_ub + 255) / 256, 256, 0, st>>>(F, cb, w.dtfirst, w.tilesD_ub, w.dtiles,
                                                         w.biglist, w.giantlist, w.crowdlist,
-                                                        w.counters, msd_big_max());
+                                                        w.counters, sw.msd_big_max);
   HIP_TRY(hipGetLastError());
   }
   u32 *hc = c->h_counts;
@@ -3568,7 +3631,7 @@ static int msd_sort_emit(gtamd_esa_ctx *c, u32 want, u32 prefixlength, u64 N, u6
   HIP_TRY(hipMemcpyAsync(hc + 4, w.dtfirst + MSD_PARENTS, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const u32 nbig = hc[0], maxrun = hc[1], nbigentries = hc[2], ngiant = hc[3], ntD = hc[4];
-  if (getenv("GTAMD_DEBUG") != nullptr)
+  if (sw.debug)
     fprintf(stderr, "gtamd: msd sort: %d bits at level C, %u runs, %u big (largest %u, %u entries "
             "in all), %u giant\n", cb, ntD, nbig, maxrun, nbigentries, ngiant);
   std::vector<MdTile> giants(ngiant);
@@ -3602,12 +3665,9 @@ static int msd_sort_emit(gtamd_esa_ctx *c, u32 want, u32 prefixlength, u64 N, u6
   if (ntD > 0) {
     // (GTAMD_MSD_RADIX=1: every run takes the LSD passes a run with a crowded
     // bin of the counting pass is left to; tests)
-    const char *fr = getenv("GTAMD_MSD_RADIX");
     HIP_TRY(hipEventRecord(c->ev_scatter[0], st));
-    u32 bin_limit = MD_BIN_LIMIT_DEFAULT;
-    if (const char *e = getenv("GTAMD_MSD_BIN_LIMIT")) { const long v = atol(e); if (v >= 2 && v <= 4096) bin_limit = (u32) v; }
     k_msd_local<FMT><<<stride_grid(ntD), MS_THREADS, 0, st>>>(kf, pf, w.dtiles, ntD, cb,
-                                                        fr != nullptr && fr[0] == '1', bin_limit,
+                                                        sw.msd_radix, sw.msd_bin_limit,
                                                         w.crowdlist, w.counters, o);
     HIP_TRY(hipEventRecord(c->ev_scatter[1], st));
     HIP_TRY(hipGetLastError());
@@ -3651,7 +3711,8 @@ static int msd_sort_emit(gtamd_esa_ctx *c, u32 want, u32 prefixlength, u64 N, u6
 
 // BITS: symbol width; WIDE: positions and ranks are 64-bit (part builds of
 // sequences with n >= 2^32)
-template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, bool dist) {
+template <int BITS, bool WIDE>
+static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
   using K = Key<BITS>;
   using P = typename std::conditional<WIDE, u64, u32>::type;
   const u64 N = c->N, n = c->n;
@@ -3682,7 +3743,7 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
   memset(&c->stats, 0, sizeof c->stats);
   c->alloc_ms = 0;
   c->llv_pairs = 0;
-  const bool debug = getenv("GTAMD_DEBUG") != nullptr;
+  const bool debug = sw.debug;
 
   // ---- keygen (whole table, or the pairs of this part's key range)
   u64 NL = N, index_offset = 0;
@@ -3704,8 +3765,7 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
   // (the 5-bit alphabets: by the 40-bit code of nine symbols, esa_msd.h FMT 1; the
   // statistics mask with prefixlength, which the code must be able to tell: <= 9)
   if (!dist && !WIDE && !(want & GTAMD_WANT_BCK) && N >= 64 && (BITS == 2 || (prefixlength <= 9 && c->sigma <= 20))) {
-    const char *e = getenv("GTAMD_MSD");
-    msd = e != nullptr ? e[0] == '1' : N >= (1ull << 25);
+    msd = sw.msd >= 0 ? sw.msd == 1 : N >= (1ull << 25);
   }
   // DNA part builds: the part's suffixes are filtered from the replicated text by
   // their key range and sorted most significant digit first -- no pair is
@@ -3714,20 +3774,16 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
   bool msd_part = false;
   u64 prev_key = 0;
   int has_prev = 0;
-  if (dist && BITS == 2) {
-    const char *e = getenv("GTAMD_MSD");
-    msd_part = !(e != nullptr && e[0] == '0');
-  }
+  if (dist && BITS == 2) msd_part = !sw.msd_part_off;
   if (!dist) {
     TRY(ensure_workspace(c, N, want, false));
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, sizeof(Stats), st));
     HIP_TRY(hipEventRecord(c->ev[0], st));
-    const char *fz = getenv("GTAMD_FUSED_PASS0");
     if (msd) {
-      TRY(msd_sort_emit<BITS == 5 ? 1 : 0>(c, want, prefixlength, N, N, nullptr, &msd_sa, &msd_fkey, &msd_fval,
+      TRY(msd_sort_emit<BITS == 5 ? 1 : 0>(c, sw, want, prefixlength, N, N, nullptr, &msd_sa, &msd_fkey, &msd_fval,
                                            &msd_local));
       HIP_TRY(hipEventRecord(c->ev_emitted, st));   // (what the joins below wait for)
-    } else if (BITS == 2 && !(fz != nullptr && fz[0] == '0')) {
+    } else if (BITS == 2 && sw.fused_pass0) {
       const u32 ntiles = (u32) div_up(N, KP_TILE);
       k_dc_hist_dna<<<ntiles, KP_THREADS, 0, st>>>(c->text, N, c->rws.as<u32>());
       HIP_TRY(hipGetLastError());
@@ -3836,7 +3892,7 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
       src.index_offset = index_offset;
       src.prev_key = acc + 3;
       src.has_prev = has_prev;
-      TRY(msd_sort_emit<0>(c, want, prefixlength, NL, N, &src, &msd_sa, &msd_fkey, &msd_fval, &msd_local));
+      TRY(msd_sort_emit<0>(c, sw, want, prefixlength, NL, N, &src, &msd_sa, &msd_fkey, &msd_fval, &msd_local));
       return 0;
     };
     fail = part_sort() != 0;
@@ -3998,8 +4054,7 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
       *vb = pass0_done ? c->v0.as<u32>() : c->v1.as<u32>();
   if (!msd)
     TRY(radix_sort_pairs<u64, u32>(ka, va, kb, vb, NL, shifts, widths, np,
-                              c->rws.as<u32>(), st, c->ev_scatter, &nev, c->dig0.as<u8>(),
-                              c->dig1.as<u8>()));
+                              c->rws.as<u32>(), st, c->ev_scatter, &nev));
   u64 *skey = (np & 1) ? kb : ka;   // sorted keys
   u32 *sa32 = (np & 1) ? vb : va;   // positions in suffix order (low half)
   u64 *fkey = (np & 1) ? ka : kb;   // free key-sized buffer
@@ -4169,10 +4224,8 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
     // prefix doubling
     TRY(ensure_buf(c, c->tiebits2, (nwords + 2) * 8, "the tie bitmap"));
     u64 *tiebits2 = c->tiebits2.as<u64>();
-    const char *np_env = getenv("GTAMD_NO_PAIRS");                // A/B switches
-    const bool no_pairs = np_env != nullptr && np_env[0] == '1';
-    const char *ns_env = getenv("GTAMD_NO_SMALL_GROUPS");
-    const bool no_small = no_pairs || (ns_env != nullptr && ns_env[0] == '1');
+    const bool no_pairs = sw.no_pairs;
+    const bool no_small = no_pairs || sw.no_small_groups;
     u64 nsmall = 0, nsrec = 0;
     if (NL > 0) {
       if (no_pairs) {
@@ -4217,9 +4270,7 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
     // (GTAMD_APPLY_EARLY, see below: the table entries of the pairs beside the
     // rounds need a buffer of their own for the LCP values beyond the byte; both
     // buffers of this step are agreed on in one exchange)
-    int apply_early = 2;
-    if (const char *e = getenv("GTAMD_APPLY_EARLY")) apply_early = atoi(e);
-    if (apply_early < 0 || apply_early > 2) apply_early = 0;
+    int apply_early = sw.apply_early;
     {
       Bump sz = {nullptr, 0};
       layout_p(sz);
@@ -4269,23 +4320,10 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
       // part of eight has an eighth of the records (3 Gbp, 43 M records a part, 8 /
       // 32 / 128 / 512 pairs per thread: 4.7 / 4.7 / 5.6 / 11.5 ms)
       int pair_chunk = (int) (nrec >> 20 < 16 ? 16 : (nrec >> 20 > 128 ? 128 : nrec >> 20));
-      if (const char *e = getenv("GTAMD_PAIR_CHUNK")) { const int v = atoi(e); if (v >= 4 && v <= 1024) pair_chunk = v; }
-      pair_chunk = (pair_chunk + PR_LINE_MAX - 1) / PR_LINE_MAX * PR_LINE_MAX;    // (whole lines of records per thread)
-      {
-        int line = PR_LINE_MAX, longext = 1;
-        if (const char *e = getenv("GTAMD_PAIR_LONG")) longext = e[0] != '0';
-        if (const char *e = getenv("GTAMD_PAIR_LINE")) { const int v = atoi(e); if (v == 4 || v == 8 || v == 16) line = v; }
-        const u32 grid = stride_grid(div_up(div_up(nrec, (u64) pair_chunk), 256));
-        if (line == 4)
-          k_pair_resolve<BITS, P, 4><<<grid, 256, 0, st>>>(
-              c->text, pk_sorted, pv_sorted, nrec, npairs, pidx, sa, pres, c->d_stats, pair_chunk, longext);
-        else if (line == 8)
-          k_pair_resolve<BITS, P, 8><<<grid, 256, 0, st>>>(
-              c->text, pk_sorted, pv_sorted, nrec, npairs, pidx, sa, pres, c->d_stats, pair_chunk, longext);
-        else
-          k_pair_resolve<BITS, P, 16><<<grid, 256, 0, st>>>(
-              c->text, pk_sorted, pv_sorted, nrec, npairs, pidx, sa, pres, c->d_stats, pair_chunk, longext);
-      }
+      if (sw.pair_chunk > 0) pair_chunk = sw.pair_chunk;
+      pair_chunk = (pair_chunk + PR_LINE - 1) / PR_LINE * PR_LINE;    // (whole lines of records per thread)
+      k_pair_resolve<BITS, P><<<stride_grid(div_up(div_up(nrec, (u64) pair_chunk), 256)), 256, 0, st>>>(
+          c->text, pk_sorted, pv_sorted, nrec, npairs, pidx, sa, pres, c->d_stats, pair_chunk);
       HIP_TRY(hipGetLastError());
       if (nsmall > 0) {
         k_small_combine<P><<<(u32) div_up(nsmall, 256), 256, 0, st>>>(
@@ -4321,8 +4359,8 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
       if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && cus > 0)
         apply_wgs = (u64) cus;
     }
-    if (const char *e = getenv("GTAMD_APPLY_WGS")) { const long v = atol(e); if (v >= 64 && v <= (1 << 22)) apply_wgs = (u64) v; }
-    const bool apply_wgs_given = getenv("GTAMD_APPLY_WGS") != nullptr;
+    if (sw.apply_wgs > 0) apply_wgs = sw.apply_wgs;
+    const bool apply_wgs_given = sw.apply_wgs_given;
     auto launch_apply = [&](hipStream_t s) -> int {
       // One workgroup per CU is right while the rounds last as long as the
       // entries take that way (3 Gbp human-like: 13 + 1.6 ms of entries under
@@ -4501,8 +4539,7 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
     u64 rk_nwin = 0, rk_h0 = 0;
     // (tests: the window bitmap of k_win_filter read from global memory, as a text of more
     // than 3.9 G symbols has it)
-    const char *wfe = getenv("GTAMD_WIN_FILTER_LDS");
-    const bool wf_global = wfe != nullptr && wfe[0] == '0';
+    const bool wf_global = sw.win_filter_global;
     bool rk_windows = false;          // only some windows are built
     u32 *w_need = nullptr, *w_built = nullptr, *w_sel = nullptr, *w_list = nullptr;
     // builds the windows that are needed and not built (all == the whole table)
@@ -4515,11 +4552,7 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
       u32 *ppos = c->isa_tmp.as<u32>(), *phead = ppos + ((NL + 3) & ~3ull);  // (skey is still
                                                            // being read by the emission)
       u32 *qhead = heads, *qpos = heads + ((NL + 3) & ~3ull);
-      int wmax = RW_BITS;
-      if (const char *e = getenv("GTAMD_RANK_WINDOW_BITS")) {
-        const int v = atoi(e);
-        if (v >= 2 && v <= RW_BITS) wmax = v;
-      }
+      const int wmax = sw.rank_window_bits;
       const u32 *spos = reinterpret_cast<const u32 *>(sa);
       const bool heads_array = bits_for(N - 1) <= wmax;
       // Partition down to windows that fit the LDS (one or two passes), then
@@ -4541,8 +4574,7 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
       rk_wb = fb;
       rk_nwin = div_up(N, 1ull << fb);
       const u64 nww = rk_nwin / 32 + 2;
-      const char *we = getenv("GTAMD_RANK_ALL_WINDOWS");           // A/B switch
-      const bool all_windows = (we != nullptr && we[0] == '1') || pb == 0;
+      const bool all_windows = sw.rank_all_windows || pb == 0;
       u32 *w_pref = nullptr;
       if (!all_windows) {
         TRY(ensure_buf(c, c->winbuf, (4 * nww + rk_nwin + 16) * 4, "the rank windows"));
@@ -4666,8 +4698,7 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
       rk_wb = 16;
       rk_nwin = div_up(N, 1ull << rk_wb);
       dw_nww = rk_nwin / 32 + 2;
-      const char *we = getenv("GTAMD_RANK_ALL_WINDOWS");           // A/B switch
-      rk_windows = !(we != nullptr && we[0] == '1');
+      rk_windows = !sw.rank_all_windows;
       // (a part that cannot get the buffers of this step says so in the first
       // allgather of send_ranks)
       fail |= ensure_buf(c, c->winbuf, (3 * dw_nww + 16) * 4, "the rank windows") != 0;
@@ -4818,11 +4849,7 @@ template <int BITS, bool WIDE> static int run_impl(gtamd_esa_ctx *c, u32 want, b
     // nominal distance of the round tiles' starts: the rest of a tile is the
     // slack for the group that lies across (a group larger than the slack goes
     // through the global path, forty launches per round)
-    u32 rt_stride = 1536;
-    if (const char *e = getenv("GTAMD_ROUND_STRIDE")) {
-      const int v = atoi(e);
-      if (v >= RT_STRIDE_MIN && v <= RT_TILE) rt_stride = (u32) v;
-    }
+    const u32 rt_stride = sw.round_stride;
     // part builds: the queries of the coming round and the rank updates of the
     // last one are bucketed by owner before the parts agree on the counts
     RankQueries<P> rq;
@@ -5184,11 +5211,10 @@ extern "C" int gtamd_esa_run(gtamd_esa_ctx *c, uint32_t want) {
   if (!c->have_text) { gtamd_set_error("no sequence set"); return -1; }
   if ((want & 15u) == 0) { gtamd_set_error("nothing requested"); return -1; }
   HIP_TRY(hipSetDevice(c->device));
+  const Switches sw = read_switches();
   // 64-bit positions: whenever the sequence needs them; GTAMD_FORCE_WIDE=1
   // takes that path (and the exchange machinery of a part build) at any size
-  const char *fw = getenv("GTAMD_FORCE_WIDE");
-  const bool force_wide = fw != nullptr && fw[0] == '1';
-  const bool wide = force_wide || c->N >= SINGLE_LIMIT;
+  const bool wide = sw.force_wide || c->N >= SINGLE_LIMIT;
   const bool dist = c->numparts > 1 || wide;
   if (c->numparts == 1 && c->N >= SINGLE_LIMIT) {
     gtamd_set_error("sequence of %llu symbols exceeds the 32-bit index range of a "
@@ -5198,9 +5224,9 @@ extern "C" int gtamd_esa_run(gtamd_esa_ctx *c, uint32_t want) {
   }
   int rc;
   if (c->bits == 2)
-    rc = wide ? run_impl<2, true>(c, want, dist) : run_impl<2, false>(c, want, dist);
+    rc = wide ? run_impl<2, true>(c, sw, want, dist) : run_impl<2, false>(c, sw, want, dist);
   else
-    rc = wide ? run_impl<5, true>(c, want, dist) : run_impl<5, false>(c, want, dist);
+    rc = wide ? run_impl<5, true>(c, sw, want, dist) : run_impl<5, false>(c, sw, want, dist);
   guard.ok = rc == 0;
   return rc;
   GTAMD_ABI_END(-1)

@@ -4,8 +4,6 @@
 // wavefront ballot ranking.  No rocPRIM/hipCUB.
 #include "esa_prims.h"
 #include "esa_devutil.h"
-#include <stdlib.h>
-#include <vector>
 
 // ===========================================================================
 // scans
@@ -112,8 +110,6 @@ constexpr int RS_ITEMS = 8;
 constexpr int RS_TILE = RS_THREADS * RS_ITEMS;       // 4096 pairs per block
 constexpr int RS_WAVE_CHUNK = RS_ITEMS * 64;         // 1024 consecutive pairs
 constexpr int RADIX = 256;
-constexpr int OS_MAXPASS = 8;
-constexpr u64 OS_AUX_WORDS = 2 * OS_MAXPASS * RADIX + 64;  // totals, bases, flag
 
 // Per-tile digit histogram, tile-major: hist[tile * 256 + d] (one coalesced
 // 1 KB row per tile, for this kernel's store and the scatter kernel's load).
@@ -255,43 +251,13 @@ __global__ __launch_bounds__(RADIX) void k_cs_rows(u32 *__restrict__ hist, u32 n
   }
 }
 
-// the same histogram from the digit bytes the previous scatter pass left
-// behind (1 B per pair instead of the 8-byte key)
-__global__ __launch_bounds__(RS_THREADS) void k_rs_hist_bytes(
-    const u8 *__restrict__ dig, u64 n, u32 *__restrict__ hist, u32 ntiles) {
-  __shared__ u32 h[RS_WAVES][RADIX];
-  const int tid = threadIdx.x, w = tid >> 6;
-  for (int i = tid; i < RS_WAVES * RADIX; i += RS_THREADS) (&h[0][0])[i] = 0;
-  __syncthreads();
-  const u64 base = (u64) blockIdx.x * RS_TILE + (u64) tid * RS_ITEMS;
-  if (base + RS_ITEMS <= n) {
-    static_assert(RS_ITEMS == 8, "one 8-byte load per thread");
-    const u64 v = *reinterpret_cast<const u64 *>(dig + base);
-#pragma unroll
-    for (int j = 0; j < 8; j++) atomicAdd(&h[w][(u32) (v >> (8 * j)) & 255u], 1u);
-  } else {
-    for (int j = 0; j < RS_ITEMS; j++)
-      if (base + j < n) atomicAdd(&h[w][dig[base + j]], 1u);
-  }
-  __syncthreads();
-  if (tid < RADIX) {
-    u32 c = 0;
-#pragma unroll
-    for (int i = 0; i < RS_WAVES; i++) c += h[i][tid];
-    hist[(u64) blockIdx.x * RADIX + tid] = c;
-  }
-}
-
-// lanes of this wave that hold the same 8-bit digit (all 64 lanes active)
-__device__ __forceinline__ u64 match_digit(u32 d) {
-  u64 m = ~0ull;
-#pragma unroll
-  for (int b = 0; b < 8; b++) {
-    const bool bit = (d >> b) & 1u;
-    const u64 bal = __ballot(bit);
-    m &= bit ? bal : ~bal;
-  }
-  return m;
+// XCD-aware tile order: workgroups b, b+8, b+16, ... share an XCD (and its L2),
+// so they take CONSECUTIVE tiles; the output runs of consecutive tiles are
+// adjacent in every digit region, and the cache line two runs share is then
+// completed inside one L2 instead of leaving two XCDs as two partial writes.
+__device__ __forceinline__ u32 xcd_tile(u32 b, u32 ntiles) {
+  const u32 per = (ntiles + 7u) >> 3;
+  return (b & 7u) * per + (b >> 3);
 }
 
 // Stable scatter of one tile.  Wave w owns the 1024 consecutive pairs
@@ -305,25 +271,7 @@ __device__ __forceinline__ u64 match_digit(u32 d) {
 // 3 Gbp -- register ballots + pipelined LDS counter adds: 122 ms per 6 passes;
 // lane masks through LDS atomic-or: 110 ms; this one: 106.5 ms -- so ranking
 // is not what limits the kernel.)
-constexpr u32 OS_CHUNK = 8;
-constexpr u32 OS_AGG = 1u << 30, OS_INCL = 2u << 30, OS_VAL = (1u << 30) - 1u;
-constexpr u32 OS_SPIN_LIMIT = 1u << 21;
-constexpr int OS_WIN = 8;
-
-__device__ __forceinline__ u32 os_tile(u32 b) {
-  const u32 x = b & 7u, q = b >> 3;
-  return (q / OS_CHUNK) * (8u * OS_CHUNK) + x * OS_CHUNK + (q % OS_CHUNK);
-}
-
-// XCD-aware tile order: workgroups b, b+8, b+16, ... share an XCD (and its L2),
-// so they take CONSECUTIVE tiles; the output runs of consecutive tiles are
-// adjacent in every digit region, and the cache line two runs share is then
-// completed inside one L2 instead of leaving two XCDs as two partial writes.
-__device__ __forceinline__ u32 xcd_tile(u32 b, u32 ntiles) {
-  const u32 per = (ntiles + 7u) >> 3;
-  return (b & 7u) * per + (b >> 3);
-}
-
+//
 // The kernel is VALU-bound (a wave64 instruction occupies its 16-lane SIMD for
 // four cycles; ISA count x 4 cycles accounts for the measured time), so the
 // ranking is written for instruction count:
@@ -372,12 +320,11 @@ struct MakeGroupHeads {
   }
 };
 
-template <bool FULL, bool DIG, typename K, typename V, typename VG = ReadValues>
+template <bool FULL, typename K, typename V, typename VG = ReadValues>
 __device__ __forceinline__ void rs_scatter_tile(
     const K *__restrict__ keys_in, const V *__restrict__ vals_in,
     K *__restrict__ keys_out, V *__restrict__ vals_out, const u32 valid, int shift,
-    u32 mask, u32 gbase, u8 *__restrict__ dig_out, int next_shift, u32 next_mask,
-    K *s_key, V *s_val, u16 *s_cnt_generic /* [RS_WAVES][RADIX] */, u32 *s_obase,
+    u32 mask, u32 gbase, K *s_key, V *s_val, u16 *s_cnt_generic /* [RS_WAVES][RADIX] */, u32 *s_obase,
     const VG vg = VG(), u64 first = 0 /* index of the tile's first pair */) {
   // volatile: lanes read counters that other lanes of the wave have updated
   lds_vu16 *s_cnt = (lds_vu16 *) s_cnt_generic;
@@ -472,19 +419,19 @@ __device__ __forceinline__ void rs_scatter_tile(
       const u32 g = s_obase[d] + e;
       keys_out[g] = k;
       vals_out[g] = s_val[e];
-      if (DIG) dig_out[g] = (u8) ((u32) (k >> next_shift) & next_mask);
     }
   }
 }
 
-template <typename K, typename V, int XCD>
+// last_valid: pairs of the last tile, from the host -- the in-kernel form
+// min(n - tile_base, 4096) was miscompiled in a kernel of this shape (hipcc 7.2:
+// the s_cselect that follows the 64-bit compare read a stale SCC, the partial
+// tile ran as a full one; tests/test_isa_audit.py looks for the pattern)
+template <typename K, typename V>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(
     const K *__restrict__ keys_in, const V *__restrict__ vals_in,
     K *__restrict__ keys_out, V *__restrict__ vals_out, u32 last_valid, int shift,
-    u32 mask, const u32 *__restrict__ hist_scanned, u32 ntiles,
-    u8 *__restrict__ dig_out, int next_shift, u32 next_mask) {
-  // last_valid: pairs of the last tile, from the host (not min(n - tile_base,
-  // 4096) in here: see the note at k_rs_scatter_gen)
+    u32 mask, const u32 *__restrict__ hist_scanned, u32 ntiles) {
   // 53 KB of LDS in all, so that three workgroups (24 waves) share a CU:
   // 16-bit counters (a tile has 4096 pairs) and the scan scratch laid over
   // the key staging area, which is not written before the scan is done
@@ -497,8 +444,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(
                 "three workgroups per CU");
 
   const int tid = threadIdx.x;
-  const u32 tile = XCD == 2 ? os_tile(blockIdx.x)
-                            : (XCD ? xcd_tile(blockIdx.x, ntiles) : blockIdx.x);
+  const u32 tile = xcd_tile(blockIdx.x, ntiles);
   if (tile >= ntiles) return;   // whole block leaves together
   const u64 tile_base = (u64) tile * RS_TILE;
   const u32 valid = tile + 1u == ntiles ? last_valid : (u32) RS_TILE;
@@ -508,221 +454,12 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(
   // issued first so that it is back long before it is needed
   u32 gbase = 0;
   if (tid < RADIX) gbase = hist_scanned[(u64) tile * RADIX + tid];
-  // (the digit-byte side output is an experiment switch, off by default: it
-  // takes the checked variant so that the two hot variants stay branch-free)
-  if (dig_out != nullptr)
-    rs_scatter_tile<false, true, K, V>(keys_in + tile_base, vals_in + tile_base, keys_out,
-                                       vals_out, valid, shift, mask, gbase, dig_out,
-                                       next_shift, next_mask, s_key, s_val, s_cnt, s_obase);
-  else if (valid == (u32) RS_TILE)
-    rs_scatter_tile<true, false, K, V>(keys_in + tile_base, vals_in + tile_base, keys_out,
-                                       vals_out, valid, shift, mask, gbase, dig_out,
-                                       next_shift, next_mask, s_key, s_val, s_cnt, s_obase);
+  if (valid == (u32) RS_TILE)
+    rs_scatter_tile<true, K, V>(keys_in + tile_base, vals_in + tile_base, keys_out, vals_out,
+                                valid, shift, mask, gbase, s_key, s_val, s_cnt, s_obase);
   else
-    rs_scatter_tile<false, false, K, V>(keys_in + tile_base, vals_in + tile_base, keys_out,
-                                        vals_out, valid, shift, mask, gbase, dig_out,
-                                        next_shift, next_mask, s_key, s_val, s_cnt, s_obase);
-}
-
-// ---------------------------------------------------------------------------
-// chained-scan scatter ("onesweep"): no per-tile histogram pass and no scan.
-// Every tile publishes its digit counts in a status word per digit
-// (flag | value in ONE 32-bit word, so no fence is needed), looks back over the
-// status words of the preceding tiles until it meets an inclusive prefix, and
-// publishes its own inclusive prefix.  Tiles are dealt to workgroups in a
-// chunk-permuted order (workgroups b, b+8, ... share an XCD and take
-// OS_CHUNK consecutive tiles at a time) so that neighbouring output runs are
-// still completed inside one L2.  Every spin is bounded; a pass that times out
-// (*errflag) is redone by the caller with the histogram/scan/scatter path.
-// ---------------------------------------------------------------------------
-// digit totals of all passes in one read of the keys
-template <typename K>
-__global__ __launch_bounds__(256) void k_os_totals(
-    const K *__restrict__ keys, u64 n, const int *__restrict__ shifts,
-    const int *__restrict__ widths, int npasses, u32 *__restrict__ totals) {
-  __shared__ u32 h[OS_MAXPASS][RADIX];
-  for (int i = threadIdx.x; i < OS_MAXPASS * RADIX; i += 256) (&h[0][0])[i] = 0;
-  __syncthreads();
-  int sh[OS_MAXPASS];
-  u32 mk[OS_MAXPASS];
-#pragma unroll
-  for (int p = 0; p < OS_MAXPASS; p++) {
-    sh[p] = p < npasses ? shifts[p] : 0;
-    mk[p] = p < npasses ? (1u << widths[p]) - 1u : 0u;
-  }
-  for (u64 i = (u64) blockIdx.x * 256 + threadIdx.x; i < n; i += (u64) gridDim.x * 256) {
-    const K k = keys[i];
-#pragma unroll
-    for (int p = 0; p < OS_MAXPASS; p++)
-      if (p < npasses) atomicAdd(&h[p][(u32) (k >> sh[p]) & mk[p]], 1u);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < npasses * RADIX; i += 256)
-    if ((&h[0][0])[i]) atomicAdd(&totals[i], (&h[0][0])[i]);
-}
-
-// per pass: exclusive scan of the 256 digit totals (one block of 256 threads)
-__global__ __launch_bounds__(256) void k_os_bases(const u32 *__restrict__ totals,
-                                                  u32 *__restrict__ bases) {
-  __shared__ u32 s_scan[4];
-  const u32 v = totals[blockIdx.x * RADIX + threadIdx.x];
-  u32 tot;
-  bases[blockIdx.x * RADIX + threadIdx.x] = block_scan_excl<SCAN_SUM>(v, &tot, s_scan);
-}
-
-template <typename K, typename V>
-__global__ __launch_bounds__(RS_THREADS) void k_os_scatter(
-    const K *__restrict__ keys_in, const V *__restrict__ vals_in,
-    K *__restrict__ keys_out, V *__restrict__ vals_out, u64 n, int shift,
-    u32 mask, const u32 *__restrict__ digit_base, u32 *__restrict__ status,
-    u32 ntiles, u32 *__restrict__ errflag) {
-  __shared__ K s_key[RS_TILE];
-  __shared__ V s_val[RS_TILE];
-  __shared__ u32 s_cnt[RS_WAVES][RADIX];
-  __shared__ u32 s_dbase[RADIX];
-  __shared__ u32 s_obase[RADIX];
-  __shared__ u32 s_tot[RADIX];
-  __shared__ u32 s_scan[RS_WAVES];
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const u32 tile = os_tile(blockIdx.x);
-  if (tile >= ntiles) return;   // whole block leaves together
-  const u64 tile_base = (u64) tile * RS_TILE;
-  const u32 valid = (u32) ((n - tile_base) < (u64) RS_TILE ? (n - tile_base)
-                                                            : (u64) RS_TILE);
-  for (int i = tid; i < RS_WAVES * RADIX; i += RS_THREADS)
-    (&s_cnt[0][0])[i] = 0;
-  u32 gbase = 0;
-  if (tid < RADIX) gbase = digit_base[tid];
-
-  K key[RS_ITEMS];
-  V val[RS_ITEMS];
-  u32 rk[RS_ITEMS];
-#pragma unroll
-  for (int j = 0; j < RS_ITEMS; j++) {
-    const u32 e = (u32) w * RS_WAVE_CHUNK + (u32) j * 64 + lane;
-    if (e < valid) {
-      key[j] = keys_in[tile_base + e];
-      val[j] = vals_in[tile_base + e];
-    } else {
-      key[j] = (K) ~(K) 0;
-      val[j] = 0;
-    }
-  }
-  __syncthreads();
-  const u64 lt = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int j = 0; j < RS_ITEMS; j++) {
-    const u32 e = (u32) w * RS_WAVE_CHUNK + (u32) j * 64 + lane;
-    const u32 d = e < valid ? ((u32) (key[j] >> shift) & mask) : (RADIX - 1);
-    const u64 m = match_digit(d);
-    const u32 intra = (u32) __popcll(m & lt);
-    const int leader = __ffsll((unsigned long long) m) - 1;
-    u32 old = 0;
-    if (lane == leader) {
-      old = s_cnt[w][d];
-      s_cnt[w][d] = old + (u32) __popcll(m);
-    }
-    old = __shfl(old, leader, 64);
-    rk[j] = ((old + intra) << 8) | d;
-  }
-  __syncthreads();
-  {
-    u32 tot = 0;
-    if (tid < RADIX) {
-#pragma unroll
-      for (int i = 0; i < RS_WAVES; i++) {
-        const u32 c = s_cnt[i][tid];
-        s_cnt[i][tid] = tot;
-        tot += c;
-      }
-      // the padding of a short last tile was counted under the last digit
-      if (tid == RADIX - 1) tot -= (u32) RS_TILE - valid;
-    }
-    u32 blocktot;
-    u32 padded = tot + ((tid == RADIX - 1) ? (u32) RS_TILE - valid : 0u);
-    u32 dbase = block_scan_excl<SCAN_SUM, RS_THREADS>(tid < RADIX ? padded : 0u,
-                                                      &blocktot, s_scan);
-    if (tid < RADIX) {
-      s_tot[tid] = tot;
-      s_dbase[tid] = dbase;
-      s_obase[tid] = gbase;
-    }
-  }
-  __syncthreads();
-  // publish this tile's digit counts as early as possible: two digits per
-  // 8-byte store (each 32-bit half is a complete flag|value word)
-  u64 *status64 = reinterpret_cast<u64 *>(status);
-  if (tid < RADIX / 2) {
-    const u32 fl = tile == 0 ? OS_INCL : OS_AGG;
-    const u64 pack = (u64) (fl | s_tot[2 * tid]) | ((u64) (fl | s_tot[2 * tid + 1]) << 32);
-    __hip_atomic_store(status64 + (u64) tile * (RADIX / 2) + tid, pack,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  // stage the tile in LDS in digit order: needs tile-local offsets only, and
-  // gives the preceding tiles time to publish theirs
-#pragma unroll
-  for (int j = 0; j < RS_ITEMS; j++) {
-    const u32 d = rk[j] & 255u;
-    const u32 pos = s_dbase[d] + s_cnt[w][d] + (rk[j] >> 8);
-    s_key[pos] = key[j];
-    s_val[pos] = val[j];
-  }
-  if (tid < RADIX / 2) {
-    // ---- chained scan over the tiles, one thread per digit pair
-    u32 excl0 = 0, excl1 = 0;
-    if (tile > 0) {
-      // walk back OS_WIN tiles at a time: the loads of one window are
-      // independent and in flight together, so a hop costs a fraction of a
-      // memory round trip
-      u32 t = tile, spins = 0, hops = 0;
-      bool done = false;
-      while (!done) {
-        u64 v[OS_WIN];
-#pragma unroll
-        for (int k = 0; k < OS_WIN; k++) {
-          const u32 tt = t > (u32) k ? t - 1 - k : 0u;
-          v[k] = __hip_atomic_load(status64 + (u64) tt * (RADIX / 2) + tid,
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int k = 0; k < OS_WIN; k++) {
-          if (done) break;
-          const u32 lo = (u32) v[k], hi = (u32) (v[k] >> 32);
-          const u32 f = lo >> 30;   // both halves always carry the same flag
-          if (f == 0) {             // not published yet: re-read from here
-            if (++spins > OS_SPIN_LIMIT) { *errflag = 1; done = true; }
-            __builtin_amdgcn_s_sleep(1);
-            break;
-          }
-          excl0 += lo & OS_VAL;
-          excl1 += hi & OS_VAL;
-          t--;
-          hops++;
-          if (f == 2) done = true;  // tile 0 always publishes an inclusive prefix
-        }
-      }
-      if (tid == 0 && errflag[1] != 0) atomicAdd(&errflag[2], hops);
-      const u64 pack = (u64) (OS_INCL | (excl0 + s_tot[2 * tid])) |
-                       ((u64) (OS_INCL | (excl1 + s_tot[2 * tid + 1])) << 32);
-      __hip_atomic_store(status64 + (u64) tile * (RADIX / 2) + tid, pack,
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    s_obase[2 * tid] += excl0 - s_dbase[2 * tid];
-    s_obase[2 * tid + 1] += excl1 - s_dbase[2 * tid + 1];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < RS_ITEMS; j++) {
-    const u32 e = (u32) j * RS_THREADS + tid;
-    if (e < valid) {
-      const K k = s_key[e];
-      const u32 d = (u32) (k >> shift) & mask;
-      const u32 g = s_obase[d] + e;
-      keys_out[g] = k;
-      vals_out[g] = s_val[e];
-    }
-  }
+    rs_scatter_tile<false, K, V>(keys_in + tile_base, vals_in + tile_base, keys_out, vals_out,
+                                 valid, shift, mask, gbase, s_key, s_val, s_cnt, s_obase);
 }
 
 // ---------------------------------------------------------------------------
@@ -847,38 +584,14 @@ static u64 cs_workspace_words(u64 ntiles) {
 u64 radix_workspace_words(u64 n) {
   u64 ntiles = div_up(n, RS_TILE);
   u64 hist = ntiles * RADIX;
-  return hist + cs_workspace_words(ntiles) + 64 + OS_AUX_WORDS;
+  return hist + cs_workspace_words(ntiles) + 64;
 }
-
-// tuning switch (A/B measurements): GTAMD_XCD_REMAP=0 disables the remap
-static bool g_xcd_remap = true;
-static int g_xcd_mode = 1;
-// digit side arrays: opt-in (GTAMD_DIGBYTES=1).  Measured at 3 Gbp: the
-// histogram passes get 17 ms cheaper, but the byte stores cost the scatter
-// kernel 2 ms per pass, net -4.6 ms (1 %): not worth 2 B/pair of memory.
-static bool g_no_digbytes = true;
-// chained-scan scatter: opt-in (GTAMD_ONESWEEP=1).  Measured at 3 Gbp: the
-// look-back walks 39 tiles on average (status hop latency across XCDs x tile
-// rate), which eats most of what the saved histogram pass gives back: sort
-// 151.7 ms vs 158.7 ms.  Correct, but not worth a spin loop by default.
-static bool g_onesweep = false;
 
 template <typename K, typename V>
 int radix_sort_pairs(K *keys_a, V *vals_a, K *keys_b, V *vals_b, u64 n,
                      const int *shifts, const int *widths, int npasses,
-                     u32 *ws, hipStream_t st, hipEvent_t *ev_pairs,
-                     int *n_ev, u8 *dig_a, u8 *dig_b) {
+                     u32 *ws, hipStream_t st, hipEvent_t *ev_pairs, int *n_ev) {
   if (n == 0) return 0;
-  {
-    const char *e = getenv("GTAMD_XCD_REMAP");
-    g_xcd_remap = !(e != nullptr && e[0] == '0');
-    g_xcd_mode = (e != nullptr && e[0] == '2') ? 2 : 1;
-    const char *db = getenv("GTAMD_DIGBYTES");
-    g_no_digbytes = !(db != nullptr && db[0] == '1');
-    const char *o = getenv("GTAMD_ONESWEEP");
-    g_onesweep = o != nullptr && o[0] == '1';
-    if (g_onesweep) g_no_digbytes = true;   // the chained kernel writes no digit bytes
-  }
   if (n >= (1ull << 32)) {
     gtamd_set_error("radix_sort_pairs: %llu pairs exceed the 32-bit index "
                     "range of one sort", (unsigned long long) n);
@@ -890,94 +603,14 @@ int radix_sort_pairs(K *keys_a, V *vals_a, K *keys_b, V *vals_b, u64 n,
   u32 *scanws = ws + (u64) ntiles * RADIX;
   K *kin = keys_a, *kout = keys_b;
   V *vin = vals_a, *vout = vals_b;
-  // ---- chained-scan path for big sorts
-  bool chained[OS_MAXPASS] = {false};
-  u32 *aux = scanws + cs_workspace_words(ntiles) + 32;
-  u32 *d_totals = aux, *d_bases = aux + OS_MAXPASS * RADIX,
-      *d_flag = aux + 2 * OS_MAXPASS * RADIX;
-  int *d_shifts = reinterpret_cast<int *>(d_flag + 8), *d_widths = d_shifts + OS_MAXPASS;
-  if (g_onesweep && n >= (1u << 20) && npasses <= OS_MAXPASS) {
-    HIP_TRY(hipMemsetAsync(d_totals, 0, OS_MAXPASS * RADIX * 4, st));
-    HIP_TRY(hipMemcpyAsync(d_shifts, shifts, npasses * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_widths, widths, npasses * sizeof(int), hipMemcpyHostToDevice, st));
-    k_os_totals<K><<<2048, 256, 0, st>>>(kin, n, d_shifts, d_widths, npasses, d_totals);
-    HIP_TRY(hipGetLastError());
-    k_os_bases<<<npasses, 256, 0, st>>>(d_totals, d_bases);
-    HIP_TRY(hipGetLastError());
-    std::vector<u32> h_tot((size_t) npasses * RADIX);
-    HIP_TRY(hipMemcpyAsync(h_tot.data(), d_totals, h_tot.size() * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int p = 0; p < npasses; p++) {
-      u32 mx = 0;
-      for (int d = 0; d < RADIX; d++) mx = h_tot[(size_t) p * RADIX + d] > mx ? h_tot[(size_t) p * RADIX + d] : mx;
-      chained[p] = mx < (1u << 30);   // status words carry 30-bit prefixes
-    }
-  }
   for (int p = 0; p < npasses; p++) {
     const u32 mask = (1u << widths[p]) - 1u;
-    if (chained[p]) {
-      HIP_TRY(hipMemsetAsync(hist, 0, (u64) ntiles * RADIX * 4, st));
-      HIP_TRY(hipMemsetAsync(d_flag, 0, 12, st));
-      if (getenv("GTAMD_OS_STATS") != nullptr) {
-        const u32 one = 1;
-        HIP_TRY(hipMemcpyAsync(d_flag + 1, &one, 4, hipMemcpyHostToDevice, st));
-      }
-      if (ev_pairs != nullptr) HIP_TRY(hipEventRecord(ev_pairs[2 * *n_ev], st));
-      const u32 groups = (ntiles + 8u * OS_CHUNK - 1u) / (8u * OS_CHUNK);
-      k_os_scatter<K, V><<<groups * 8u * OS_CHUNK, RS_THREADS, 0, st>>>(
-          kin, vin, kout, vout, n, shifts[p], mask, d_bases + p * RADIX, hist,
-          ntiles, d_flag);
-      HIP_TRY(hipGetLastError());
-      if (ev_pairs != nullptr) HIP_TRY(hipEventRecord(ev_pairs[2 * *n_ev + 1], st));
-      u32 h_flags[3] = {0, 0, 0};
-      HIP_TRY(hipMemcpyAsync(h_flags, d_flag, 12, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      const u32 h_flag = h_flags[0];
-      if (h_flags[1])
-        fprintf(stderr, "gtamd: chained scan pass %d: %.2f look-back hops per tile\n", p,
-                (double) h_flags[2] / ntiles);
-      if (h_flag == 0) {
-        if (ev_pairs != nullptr) (*n_ev)++;
-        K *tk = kin; kin = kout; kout = tk;
-        V *tv = vin; vin = vout; vout = tv;
-        continue;
-      }
-      // a look-back timed out (the dispatch order assumption did not hold):
-      // the input of this pass is untouched, redo it the classic way
-      fprintf(stderr, "gtamd: chained scan timed out in pass %d, falling back\n", p);
-    }
-    // digit bytes: written by the previous pass into din, this pass leaves the
-    // next pass's digits in dout
-    const bool have_dig = dig_a != nullptr && p > 0 && !g_no_digbytes;
-    u8 *din = (p & 1) ? dig_a : dig_b, *dout = (p & 1) ? dig_b : dig_a;
-    if (dig_a == nullptr || p + 1 >= npasses || g_no_digbytes) dout = nullptr;
-    const int nsh = p + 1 < npasses ? shifts[p + 1] : 0;
-    const u32 nmk = p + 1 < npasses ? (1u << widths[p + 1]) - 1u : 0u;
-    if (have_dig)
-      k_rs_hist_bytes<<<ntiles, RS_THREADS, 0, st>>>(din, n, hist, ntiles);
-    else
-      k_rs_hist<K><<<ntiles, RS_THREADS, 0, st>>>(kin, n, shifts[p], mask, hist,
-                                               ntiles);
+    k_rs_hist<K><<<ntiles, RS_THREADS, 0, st>>>(kin, n, shifts[p], mask, hist, ntiles);
     HIP_TRY(hipGetLastError());
-    {
-      const u32 nchunks = (ntiles + CS_ROWS - 1) / CS_ROWS;
-      k_cs_chunksum<<<nchunks, RADIX, 0, st>>>(hist, ntiles, scanws);
-      HIP_TRY(hipGetLastError());
-      k_cs_chunkbase<<<1, RADIX * CB_PARTS, 0, st>>>(scanws, nchunks);
-      HIP_TRY(hipGetLastError());
-      k_cs_rows<<<nchunks, RADIX, 0, st>>>(hist, ntiles, scanws);
-      HIP_TRY(hipGetLastError());
-    }
+    TRY(radix_scan_tile_rows(hist, ntiles, scanws, st));
     if (ev_pairs != nullptr) HIP_TRY(hipEventRecord(ev_pairs[2 * *n_ev], st));
-    if (g_xcd_mode == 2)
-      k_rs_scatter<K, V, 2><<<((ntiles + 8u * OS_CHUNK - 1u) / (8u * OS_CHUNK)) * 8u * OS_CHUNK, RS_THREADS, 0, st>>>(
-          kin, vin, kout, vout, last_valid, shifts[p], mask, hist, ntiles, dout, nsh, nmk);
-    else if (!g_xcd_remap)
-      k_rs_scatter<K, V, 0><<<ntiles, RS_THREADS, 0, st>>>(
-          kin, vin, kout, vout, last_valid, shifts[p], mask, hist, ntiles, dout, nsh, nmk);
-    else
-      k_rs_scatter<K, V, 1><<<((ntiles + 7u) >> 3) * 8u, RS_THREADS, 0, st>>>(
-          kin, vin, kout, vout, last_valid, shifts[p], mask, hist, ntiles, dout, nsh, nmk);
+    k_rs_scatter<K, V><<<((ntiles + 7u) >> 3) * 8u, RS_THREADS, 0, st>>>(
+        kin, vin, kout, vout, last_valid, shifts[p], mask, hist, ntiles);
     HIP_TRY(hipGetLastError());
     if (ev_pairs != nullptr) {
       HIP_TRY(hipEventRecord(ev_pairs[2 * *n_ev + 1], st));
@@ -987,38 +620,6 @@ int radix_sort_pairs(K *keys_a, V *vals_a, K *keys_b, V *vals_b, u64 n,
     V *tv = vin; vin = vout; vout = tv;
   }
   return 0;
-}
-
-// scatter pass with generated values (XCD-aware tile order).  last_valid: pairs
-// of the last tile, from the host -- the in-kernel form  min(n - tile_base, 4096)
-// was miscompiled in this kernel (hipcc 7.2: the s_cselect that follows the
-// 64-bit compare read a stale SCC, the partial tile ran as a full one).
-template <typename K, typename VG>
-__global__ __launch_bounds__(RS_THREADS) void k_rs_scatter_gen(
-    const K *__restrict__ keys_in, const VG vg, K *__restrict__ keys_out,
-    u32 *__restrict__ vals_out, u32 last_valid, int shift, u32 mask,
-    const u32 *__restrict__ hist_scanned, u32 ntiles) {
-  __shared__ K s_key[RS_TILE];
-  __shared__ u32 s_val[RS_TILE];
-  __shared__ u16 s_cnt[RS_WAVES * RADIX];
-  __shared__ u32 s_obase[RADIX];
-  const int tid = threadIdx.x;
-  const u32 tile = xcd_tile(blockIdx.x, ntiles);
-  if (tile >= ntiles) return;
-  const u64 tile_base = (u64) tile * RS_TILE;
-  const bool last = tile + 1u == ntiles;
-  for (int i = tid; i < RS_WAVES * RADIX / 2; i += RS_THREADS)
-    reinterpret_cast<u32 *>(s_cnt)[i] = 0;
-  u32 gbase = 0;
-  if (tid < RADIX) gbase = hist_scanned[(u64) tile * RADIX + tid];
-  if (!last || last_valid == (u32) RS_TILE)
-    rs_scatter_tile<true, false, K, u32, VG>(keys_in + tile_base, nullptr, keys_out, vals_out,
-                                             (u32) RS_TILE, shift, mask, gbase, nullptr, 0, 0u,
-                                             s_key, s_val, s_cnt, s_obase, vg, tile_base);
-  else
-    rs_scatter_tile<false, false, K, u32, VG>(keys_in + tile_base, nullptr, keys_out, vals_out,
-                                              last_valid, shift, mask, gbase, nullptr, 0, 0u,
-                                              s_key, s_val, s_cnt, s_obase, vg, tile_base);
 }
 
 int radix_pass_group_heads(const u32 *keys_a, GroupHeadValues gen, u32 *keys_b,
@@ -1038,13 +639,8 @@ int radix_pass_group_heads(const u32 *keys_a, GroupHeadValues gen, u32 *keys_b,
   if (radix_scan_tile_hist(ws, n, st) != 0) return -1;
   MakeGroupHeads mg;
   mg.g = gen;
-  const char *e = getenv("GTAMD_STABLE_PARTITION");   // A/B switch: the sort's own kernel
-  if (e != nullptr && e[0] == '1')
-    k_rs_scatter_gen<u32, MakeGroupHeads><<<((ntiles + 7u) >> 3) * 8u, RS_THREADS, 0, st>>>(
-        keys_a, mg, keys_b, vals_b, last_valid, shift, mask, ws, ntiles);
-  else
-    k_rs_partition<u32, u32, MakeGroupHeads><<<((ntiles + 7u) >> 3) * 8u, RS_THREADS, 0, st>>>(
-        keys_a, nullptr, mg, keys_b, vals_b, last_valid, shift, mask, ws, ntiles);
+  k_rs_partition<u32, u32, MakeGroupHeads><<<((ntiles + 7u) >> 3) * 8u, RS_THREADS, 0, st>>>(
+      keys_a, nullptr, mg, keys_b, vals_b, last_valid, shift, mask, ws, ntiles);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1057,10 +653,6 @@ int radix_partition_u32(const u32 *keys_a, const u32 *vals_a, u32 *keys_b, u32 *
                     (unsigned long long) n);
     return -1;
   }
-  const char *e = getenv("GTAMD_STABLE_PARTITION");
-  if (e != nullptr && e[0] == '1')
-    return radix_sort_pairs<u32, u32>(const_cast<u32 *>(keys_a), const_cast<u32 *>(vals_a), keys_b,
-                                      vals_b, n, &shift, &width, 1, ws, st, nullptr, nullptr);
   const u32 ntiles = (u32) div_up(n, RS_TILE);
   const u32 mask = (1u << width) - 1u;
   const u32 last_valid = (u32) (n - (u64) (ntiles - 1) * RS_TILE);
@@ -1092,19 +684,15 @@ int radix_scan_tile_rows(u32 *hist, u32 ntiles, u32 *scanws, hipStream_t st) {
   return 0;
 }
 
-template int radix_sort_pairs<u64, u32>(u64 *, u32 *, u64 *, u32 *, u64,
-                                        const int *, const int *, int, u32 *,
-                                        hipStream_t, hipEvent_t *, int *, u8 *,
-                                        u8 *);
-template int radix_sort_pairs<u32, u32>(u32 *, u32 *, u32 *, u32 *, u64,
-                                        const int *, const int *, int, u32 *,
-                                        hipStream_t, hipEvent_t *, int *, u8 *,
-                                        u8 *);
-template int radix_sort_pairs<u32, u64>(u32 *, u64 *, u32 *, u64 *, u64,
-                                        const int *, const int *, int, u32 *,
-                                        hipStream_t, hipEvent_t *, int *, u8 *,
-                                        u8 *);
-template int radix_sort_pairs<u64, u64>(u64 *, u64 *, u64 *, u64 *, u64,
-                                        const int *, const int *, int, u32 *,
-                                        hipStream_t, hipEvent_t *, int *, u8 *,
-                                        u8 *);
+template int radix_sort_pairs<u64, u32>(u64 *, u32 *, u64 *, u32 *, u64, const int *,
+                                        const int *, int, u32 *, hipStream_t, hipEvent_t *,
+                                        int *);
+template int radix_sort_pairs<u32, u32>(u32 *, u32 *, u32 *, u32 *, u64, const int *,
+                                        const int *, int, u32 *, hipStream_t, hipEvent_t *,
+                                        int *);
+template int radix_sort_pairs<u32, u64>(u32 *, u64 *, u32 *, u64 *, u64, const int *,
+                                        const int *, int, u32 *, hipStream_t, hipEvent_t *,
+                                        int *);
+template int radix_sort_pairs<u64, u64>(u64 *, u64 *, u64 *, u64 *, u64, const int *,
+                                        const int *, int, u32 *, hipStream_t, hipEvent_t *,
+                                        int *);

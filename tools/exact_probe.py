@@ -42,8 +42,7 @@ def fuzz(seconds, seed, nmin=2 ** 25):
     switches = {"GTAMD_RANK_ALL_WINDOWS": ["0", "0", "1"], "GTAMD_WIN_FILTER_LDS": ["1", "1", "0"],
                 "GTAMD_PAIR_CHUNK": ["16", "32", "128"], "GTAMD_APPLY_EARLY": ["0", "1", "2"],
                 "GTAMD_MSD_PACK": ["0", "1"], "GTAMD_ROUND_STRIDE": ["1024", "1536", "2048"],
-                "GTAMD_NO_SMALL_GROUPS": ["0", "0", "1"], "GTAMD_PAIR_LONG": ["0", "1"],
-                "GTAMD_STABLE_PARTITION": ["0", "1"], "GTAMD_MSD_BIN_LIMIT": ["32", "128", "512"]}
+                "GTAMD_NO_SMALL_GROUPS": ["0", "0", "1"], "GTAMD_MSD_BIN_LIMIT": ["32", "128", "512"]}
     while time.time() - t0 < seconds:
         model = int(rng.choice([0, 1, 1, 2, 3]))
         top = 1.2e9 if model == 2 else 3.1e9

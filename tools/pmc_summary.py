@@ -69,7 +69,7 @@ def main():
             out.write(text + "\n")
     # the dominant kernel of the first sort (bench.py's roofline kernel): k_msd_local
     # in a DNA whole-table build (one launch per build), else the full passes of
-    # k_rs_scatter<unsigned long, unsigned int, 1> (the largest launches)
+    # k_rs_scatter<unsigned long, unsigned int> (the largest launches)
     def sha(name):
         with open(os.path.join(ROOT, "genometools_amd", "csrc", name), "rb") as f:
             return hashlib.sha256(f.read()).hexdigest()
