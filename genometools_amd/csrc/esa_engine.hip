@@ -759,6 +759,16 @@ struct OwnerOfKey {
   }
 };
 
+// the head of entry i once the pairs in the wrong order have changed places:
+// head is i's head in the bitmap without the pairs (a pair's entries are heads
+// of their own), swp the bitmaps of k_pair_swapbits (nullptr: no pairs)
+__device__ __forceinline__ u32 swap_head(const u64 *swp, u64 i, u32 head) {
+  if (swp == nullptr) return head;
+  const ulonglong2 s = *reinterpret_cast<const ulonglong2 *>(swp + 2 * (i >> 6));
+  const int b = (int) (i & 63);
+  return head + (u32) ((s.x >> b) & 1ull) - (u32) ((s.y >> b) & 1ull);
+}
+
 // first ranks of the suffixes [c0, c0 + m) of this part's slice to the owners
 // of their text positions: rank = slice offset + head of the entry's tie group
 template <typename P> struct InitialRanks {
@@ -771,6 +781,7 @@ template <typename P> struct InitialRanks {
   u32 *srec;           // records: offset in the owner's tile, rank (one or two words)
   const u32 *sel;      // windows of 2^wb positions whose ranks travel (nullptr: all)
   int wb;
+  const u64 *swp;      // pairs in the wrong order (swap_head; nullptr: none)
   __device__ __forceinline__ u32 dest(u64 j) const {
     u64 off;
     const u64 p = (u64) sa[c0 + j];
@@ -787,7 +798,7 @@ template <typename P> struct InitialRanks {
     const u64 below = b == 63 ? ~0ull : ((2ull << b) - 1ull);
     const u64 z = ~tiebits[w] & below;
     const u64 head = z ? w * 64 + (u64) (63 - __clzll((long long) z)) : (u64) carry[w];
-    return (P) (index_offset + head);
+    return (P) (index_offset + swap_head(swp, i, (u32) head));
   }
   __device__ __forceinline__ void local(u64 j) const {
     u64 off;
@@ -1352,10 +1363,10 @@ __global__ __launch_bounds__(256) void k_unres_emit(
 // for 12 GB of payload).  So: (1) heads in suffix order, streaming;
 // (2) one radix pass partitions the (position, head) pairs by the leading
 // position bits; (3) the scatter then walks one position window after the
-// other and its stores meet in cache before they reach HBM.
+// other and its stores meet in cache before they reach HBM.  swp: see swap_head.
 __global__ __launch_bounds__(256) void k_heads(
     const u64 *__restrict__ tiebits, const u32 *__restrict__ carry, u64 N,
-    u32 rank_offset, u32 *__restrict__ heads) {
+    u32 rank_offset, const u64 *__restrict__ swp, u32 *__restrict__ heads) {
   // four consecutive entries per thread (one 16-byte store): they share their
   // bitmap word, the head of an entry is the head of the one before it unless
   // it starts a group itself
@@ -1367,6 +1378,15 @@ __global__ __launch_bounds__(256) void k_heads(
 #pragma unroll
   for (int g = 1; g < 4; g++)
     h[g] = ((t >> ((i0 + g) & 63)) & 1ull) ? h[g - 1] : (u32) (i0 + g);
+  if (swp != nullptr) {
+    // (a swapped pair's entries are not tied: the chain above never passes one on)
+    const ulonglong2 sw = *reinterpret_cast<const ulonglong2 *>(swp + 2 * (i0 >> 6));
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+      const int b = (int) ((i0 + g) & 63);
+      h[g] += (u32) ((sw.x >> b) & 1ull) - (u32) ((sw.y >> b) & 1ull);
+    }
+  }
   if (i0 + 4 <= N) {
     *reinterpret_cast<uint4 *>(heads + i0) =
         make_uint4(rank_offset + h[0], rank_offset + h[1], rank_offset + h[2],
@@ -1556,7 +1576,9 @@ __global__ __launch_bounds__(1024) void k_win_select(const u32 *__restrict__ nee
 // P: positions of 32 bits, or of 64 (part builds of n >= 2^32); cap: room in the
 // list -- a workgroup that would write behind it stops and sets stats->count2 (the
 // caller takes another way then); pref != nullptr: the list gets compact positions
-// (see k_rank_window) instead of positions.
+// (see k_rank_window) instead of positions; swp != nullptr: the heads of the pairs'
+// entries follow the pairs' resolved order (swap_head) -- read for the selected
+// entries only, in table order.
 constexpr int WF_THREADS = 1024;
 constexpr int WF_Q = 4;                                   // uint4 loads per thread
 constexpr u64 WF_SPAN = (u64) WF_THREADS * 4 * WF_Q;      // 16384 entries
@@ -1590,7 +1612,8 @@ template <typename P, bool LSEL>
 __global__ __launch_bounds__(WF_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_win_filter(
     const P *__restrict__ sa, u64 NL, int wb, const u32 *__restrict__ sel, u32 nww,
     const u32 *__restrict__ pref, const u64 *__restrict__ tiebits, const u32 *__restrict__ carry,
-    P *__restrict__ fpos, u32 *__restrict__ fhead, u64 cap, Stats *stats) {
+    const u64 *__restrict__ swp, P *__restrict__ fpos, u32 *__restrict__ fhead, u64 cap,
+    Stats *stats) {
   extern __shared__ __attribute__((aligned(16))) u32 s_dyn[];
   __shared__ u32 s_scan[WF_THREADS / 64];
   __shared__ u32 s_base;
@@ -1667,7 +1690,8 @@ __global__ __launch_bounds__(WF_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
           v = (P) (((u64) d << wb) | ((u64) v & ((1ull << wb) - 1ull)));
         }
         fpos[base + j] = v;
-        fhead[base + j] = group_head(tiebits, carry, first + s_qidx[j]);
+        const u64 i = first + s_qidx[j];
+        fhead[base + j] = swap_head(swp, i, group_head(tiebits, carry, i));
       }
       __syncthreads();
     }
@@ -1953,16 +1977,24 @@ __global__ __launch_bounds__(256) void k_pair_emit(
 }
 
 // order and LCP of every pair, LCP_CHUNK consecutive pairs (by text position)
-// per thread; a pair in the wrong order changes places in the suffix array
-// here, the tables get their entries from k_pair_apply, which walks the pairs
-// in TABLE order (in text order its five accesses per pair were five random
-// lines: 18 ms for 170 M pairs)
+// per thread: res[ordinal] = LCP | PAIR_SWAP, nothing else.  A pair in the
+// wrong order is NOT swapped in the suffix array here: in text order that is a
+// random look-up of the table index and two random stores per swapped pair,
+// and those overlapped the comparisons and the result stores only in part
+// (§10: 6.7 ms of the kernel's 11.2; as a kernel of its own, walking the table,
+// the swap was 5.4 ms of read-modify-write over nearly every line of it).  The
+// walks that come after already visit the pairs' entries in TABLE order and
+// touch their lines anyway: k_pair_swapbits turns the results into a bitmap by
+// table index (streaming), the rank table's walks give a pair's members the
+// ranks of their resolved places from it (swap_head), and k_pair_apply, which
+// writes the pairs' table entries beside the rounds, swaps their .suf / .bwt
+// entries (in text order its five accesses per pair were five random lines:
+// 18 ms for 170 M pairs).  The suffix array keeps the old order to the end.
 constexpr int PR_LINE = 16;     // records a thread loads at once (a chunk is a multiple of it)
 template <int BITS, typename P>
 __global__ __launch_bounds__(256) void k_pair_resolve(
     Text t, const P *__restrict__ pkey, const u64 *__restrict__ pval, u64 nrec, u64 np,
-    const u32 *__restrict__ pidx, P *__restrict__ sa, u32 *__restrict__ res, Stats *stats,
-    int chunk) {
+    const P *__restrict__ sa, u32 *__restrict__ res, Stats *stats, int chunk) {
   // records with ordinal < np are pairs (their LCP is a table entry: counted in
   // the statistics); the others are pairs of members of small groups
   __shared__ unsigned long long s_sum[4], s_large[4];
@@ -2048,15 +2080,6 @@ __global__ __launch_bounds__(256) void k_pair_resolve(
       const u32 lv = l < 0x7FFFFFFFull ? (u32) l : 0x7FFFFFFFu;
       res[j] = lv | (a_first ? 0u : PAIR_SWAP);   // by ordinal: the later steps walk the table
       if (j < np) {
-        // a pair in the wrong order changes places here (both positions are at
-        // hand; this kernel waits for memory anyway -- as a kernel of its own
-        // the swap was 5.4 ms of read-modify-write); the small groups are
-        // sorted by k_small_combine
-        if (!a_first) {
-          const u64 i = sizeof(P) == 4 ? (u64) pidx[j] : (iv & 0xFFFFFFFFull);
-          sa[i] = (P) b;
-          sa[i + 1] = (P) a;
-        }
         sum += lv;     // tied suffixes have >= KEY_SYMS >= prefixlength letters
         nlarge += lv >= GTAMD_LCPOVERFLOW;
         mx = lv > mx ? lv : mx;
@@ -2085,10 +2108,42 @@ __global__ __launch_bounds__(256) void k_pair_resolve(
   }
 }
 
+// the pairs in the wrong order by table index, one thread per bitmap word (the
+// pairs' ordinals are in table order: the same counts as k_pair_emit):
+// swp[2w] has the first entry of every swapped pair of word w (its rank is its
+// index + 1), swp[2w + 1] the second entry (index - 1) -- 16 bytes per 64
+// entries, read in one piece next to the tie bitmap
+__global__ __launch_bounds__(256) void k_pair_swapbits(
+    const u64 *__restrict__ tiebits, u64 nwords, const u32 *__restrict__ off,
+    const u32 *__restrict__ res, u64 *__restrict__ swp) {
+  __shared__ u32 s_scan[4];
+  const u64 w = (u64) blockIdx.x * 256 + threadIdx.x;
+  u64 t = 0, ph = 0;
+  if (w < nwords) {
+    t = tiebits[w];
+    const u64 nx = w + 1 < nwords ? tiebits[w + 1] : 0ull;
+    ph = pair_heads(t, nx);
+  }
+  u32 tot;
+  const u32 j0 = off[blockIdx.x] + block_scan_excl_sum((u32) __popcll(ph), &tot, s_scan);
+  if (w >= nwords) return;
+  u64 up = 0, down = 0;
+  // a pair head in bit 63 of the word before: its second entry is this word's
+  // bit 0, its ordinal the one before this word's first
+  if (w > 0 && (pair_heads(tiebits[w - 1], t) >> 63) && (res[j0 - 1] & PAIR_SWAP)) down = 1;
+  u32 j = j0;
+  for (u64 h = ph; h; h &= h - 1) {
+    const int b = __ffsll((unsigned long long) h) - 1;
+    if (res[j++] & PAIR_SWAP) up |= 1ull << b;
+  }
+  down |= up << 1;
+  *reinterpret_cast<ulonglong2 *>(swp + 2 * w) = make_ulonglong2(up, down);
+}
+
 // table entries of the pairs (after the emission of the other entries), pair by
-// pair in table order: the LCP of the second entry; .suf and .bwt of both
-// change places with the suffixes (the emission wrote the BWT symbols of the
-// keys, in key order)
+// pair in table order: the LCP of the second entry; .suf and .bwt of a swapped
+// pair change places (the suffix array has both in the old order, the emission
+// wrote the BWT symbols of the keys, in key order)
 template <typename P>
 __global__ __launch_bounds__(256) void k_pair_apply(
     const u32 *__restrict__ pidx, const u32 *__restrict__ res, u64 np,
@@ -2103,11 +2158,12 @@ __global__ __launch_bounds__(256) void k_pair_apply(
       if (lv >= GTAMD_LCPOVERFLOW) lcpfull[i + 1] = lv;
     }
     // (a pair in its old order has its .suf / .bwt entries from the emission;
-    // suffix 0, whose place the statistics want, is always the first of its pair)
+    // suffix 0, whose place the statistics want, is always the first of its
+    // pair in the old order: the smaller position)
     if (r & PAIR_SWAP) {
       const u64 x = sa[i], y = sa[i + 1];
-      if (y == 0) stats->longest = index_offset + i + 1;
-      if (suf != nullptr) { suf[i] = x; suf[i + 1] = y; }
+      if (x == 0) stats->longest = index_offset + i + 1;
+      if (suf != nullptr) { suf[i] = y; suf[i + 1] = x; }
       if (bwt != nullptr) {
         const u8 b0 = bwt[i], b1 = bwt[i + 1];
         bwt[i] = b1;
@@ -4258,6 +4314,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
     u32 *pidx = nullptr, *pres = nullptr, *prws = nullptr, *sidx = nullptr, *sres = nullptr,
         *slcp = nullptr, *srec = nullptr;
     u8 *ssize = nullptr;
+    u64 *swp = nullptr;     // the pairs in the wrong order by table index (k_pair_swapbits)
     auto layout_p = [&](Bump &a) {
       pk_a = a.take<P>(pp); pk_b = a.take<P>(pp);
       pv_a = a.take<u64>(pp); pv_b = a.take<u64>(pp);
@@ -4266,6 +4323,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       sidx = a.take<u32>(sp); sres = a.take<u32>(sp); slcp = a.take<u32>(3 * sp);
       srec = a.take<u32>(sp);
       ssize = a.take<u8>(sp);
+      swp = a.take<u64>(npairs > 0 ? 2 * nwords + 8 : 0);
     };
     // (GTAMD_APPLY_EARLY, see below: the table entries of the pairs beside the
     // rounds need a buffer of their own for the LCP values beyond the byte; both
@@ -4323,8 +4381,12 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       if (sw.pair_chunk > 0) pair_chunk = sw.pair_chunk;
       pair_chunk = (pair_chunk + PR_LINE - 1) / PR_LINE * PR_LINE;    // (whole lines of records per thread)
       k_pair_resolve<BITS, P><<<stride_grid(div_up(div_up(nrec, (u64) pair_chunk), 256)), 256, 0, st>>>(
-          c->text, pk_sorted, pv_sorted, nrec, npairs, pidx, sa, pres, c->d_stats, pair_chunk);
+          c->text, pk_sorted, pv_sorted, nrec, npairs, sa, pres, c->d_stats, pair_chunk);
       HIP_TRY(hipGetLastError());
+      if (npairs > 0) {
+        k_pair_swapbits<<<(u32) nwb, 256, 0, st>>>(tiebits, nwords, poff, pres, swp);
+        HIP_TRY(hipGetLastError());
+      }
       if (nsmall > 0) {
         k_small_combine<P><<<(u32) div_up(nsmall, 256), 256, 0, st>>>(
             sidx, ssize, srec, pres, nsmall, sa, tiebits2, sres, slcp, c->d_stats);
@@ -4394,6 +4456,13 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       }
       return 0;
     };
+    // The pairs in the wrong order never change places in the suffix array: it
+    // is the build's working copy, and behind the pair path only the walks that
+    // rank the table's entries by their index read a pair's entries there --
+    // they take the resolved order from swp (swap_head).  (Swapped by
+    // k_pair_apply beside the rounds, the stores into the suffix array's lines
+    // cost the rounds 0.9 ms at 3 Gbp.)
+    const u64 *pair_swp = npairs > 0 ? swp : nullptr;
     auto apply_beside = [&]() -> int {
       // (ev_sorted is free: the emission, if it is a kernel of its own, has been
       // launched by the pair path; st2 runs the entries behind it)
@@ -4592,7 +4661,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
         }
         rk_windows = true;
       }
-      const GroupHeadValues headgen = {tiebits2, carry, nwords, 0u};
+      const GroupHeadValues headgen = {tiebits2, carry, nwords, 0u, pair_swp};
       build_rank = [=, &rk_windows, &rank_built](bool first) -> int {
         u64 nsel = 0;
         if (rk_windows) {
@@ -4609,7 +4678,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
         }
         if (!rk_windows) {
           if (heads_array) {
-            k_heads<<<(u32) div_up(NL, 1024), 256, 0, st>>>(tiebits2, carry, NL, 0u, heads);
+            k_heads<<<(u32) div_up(NL, 1024), 256, 0, st>>>(tiebits2, carry, NL, 0u, pair_swp, heads);
             HIP_TRY(hipGetLastError());
           }
           const u32 *wpos = spos, *whead = heads;
@@ -4648,10 +4717,12 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
                                       hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int) wf_lds_bytes<u32>(nww, true)));
           k_win_filter<u32, true><<<(u32) div_up(NL, WF_SPAN * WF_ITER), WF_THREADS, wf_lds_bytes<u32>(nww, true), st>>>(
-              spos, NL, fb, w_sel, (u32) nww, w_pref, tiebits2, carry, ppos, phead, ~0ull, c->d_stats);
+              spos, NL, fb, w_sel, (u32) nww, w_pref, tiebits2, carry, pair_swp, ppos, phead, ~0ull,
+              c->d_stats);
         } else
           k_win_filter<u32, false><<<(u32) div_up(NL, WF_SPAN * WF_ITER), WF_THREADS, wf_lds_bytes<u32>(nww, false), st>>>(
-              spos, NL, fb, w_sel, (u32) nww, w_pref, tiebits2, carry, ppos, phead, ~0ull, c->d_stats);
+              spos, NL, fb, w_sel, (u32) nww, w_pref, tiebits2, carry, pair_swp, ppos, phead, ~0ull,
+              c->d_stats);
         HIP_TRY(hipGetLastError());
         TRY(fetch_stats(c));
         const u64 M = c->h_stats->count;   // nsel windows (the last one of the text is short)
@@ -4773,10 +4844,12 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
                                         hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int) wf_lds_bytes<P>(dw_nww, true)));
             k_win_filter<P, true><<<(u32) div_up(NL, WF_SPAN * WF_ITER), WF_THREADS, wf_lds_bytes<P>(dw_nww, true), st>>>(
-                sa, NL, rk_wb, d_sel, (u32) dw_nww, nullptr, tiebits2, carry, fpos, fhead, list_cap, c->d_stats);
+                sa, NL, rk_wb, d_sel, (u32) dw_nww, nullptr, tiebits2, carry, pair_swp, fpos, fhead,
+                list_cap, c->d_stats);
           } else
             k_win_filter<P, false><<<(u32) div_up(NL, WF_SPAN * WF_ITER), WF_THREADS, wf_lds_bytes<P>(0, false), st>>>(
-                sa, NL, rk_wb, d_sel, 0u, nullptr, tiebits2, carry, fpos, fhead, list_cap, c->d_stats);
+                sa, NL, rk_wb, d_sel, 0u, nullptr, tiebits2, carry, pair_swp, fpos, fhead, list_cap,
+                c->d_stats);
           HIP_TRY(hipGetLastError());
           TRY(fetch_stats(c));
           listed = c->h_stats->count2 == 0;
@@ -4804,7 +4877,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
             InitialRanks<P> ir;
             ir.sa = sa; ir.tiebits = tiebits2; ir.carry = carry; ir.c0 = c0;
             ir.index_offset = index_offset; ir.tl = tl; ir.isa = isa; ir.srec = xmsg;
-            ir.sel = d_sel; ir.wb = rk_wb;
+            ir.sel = d_sel; ir.wb = rk_wb; ir.swp = pair_swp;
             TRY(dest_count(c, ir, cm, xdest_q, xbc_q, xbo_q, scanws2, 0));
             HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, DEST_MAXPARTS * 4,
                                    hipMemcpyDeviceToHost, st));

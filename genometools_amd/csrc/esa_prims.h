@@ -47,6 +47,9 @@ struct GroupHeadValues {
   const u32 *carry;
   u64 nwords;     // words of the bitmap (and entries of carry)
   u32 offset;
+  // pairs of entries that change places (nullptr: none): 2 words per bitmap
+  // word, the first entries of such pairs (head + 1) and the second (head - 1)
+  const u64 *swp;
 };
 int radix_pass_group_heads(const u32 *keys_a, GroupHeadValues gen, u32 *keys_b,
                            u32 *vals_b, u64 n, int shift, int width, u32 *ws,

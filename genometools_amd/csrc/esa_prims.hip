@@ -316,7 +316,13 @@ struct MakeGroupHeads {
     const int b = (int) (i & 63);
     const u64 below = b == 63 ? ~0ull : ((2ull << b) - 1ull);
     const u64 z = ~t & below;
-    return g.offset + (z ? ((u32) i & ~63u) + (63u - (u32) __clzll((long long) z)) : c);
+    u32 h = g.offset + (z ? ((u32) i & ~63u) + (63u - (u32) __clzll((long long) z)) : c);
+    if (g.swp != nullptr) {
+      // (the lanes of a wave read the same 16 bytes for an item: one request)
+      const ulonglong2 s = *reinterpret_cast<const ulonglong2 *>(g.swp + 2 * (i >> 6));
+      h += (u32) ((s.x >> b) & 1ull) - (u32) ((s.y >> b) & 1ull);
+    }
+    return h;
   }
 };
 
