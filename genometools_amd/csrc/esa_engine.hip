@@ -2870,7 +2870,7 @@ static inline u32 stride_grid(u64 tiles) {
 //   GTAMD_RANK_ALL_WINDOWS  1: the whole rank table, not only the windows needed
 //                           [test_esa_gpu, fuzz_gpu, exact_probe]
 //   GTAMD_WIN_FILTER_LDS    0: k_win_filter's bitmap in global memory, as for texts
-//                           of more than 3.9 G symbols  [test_esa_gpu, fuzz_gpu,
+//                           of more than 3.22 G symbols  [test_esa_gpu, fuzz_gpu,
 //                           exact_probe]
 //   GTAMD_PAIR_CHUNK        pairs per thread of k_pair_resolve  [fuzz_gpu, exact_probe]
 //   GTAMD_ROUND_STRIDE      distance of the round tiles' starts  [fuzz_gpu, exact_probe]
@@ -4607,7 +4607,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
     int rk_wb = 0;
     u64 rk_nwin = 0, rk_h0 = 0;
     // (tests: the window bitmap of k_win_filter read from global memory, as a text of more
-    // than 3.9 G symbols has it)
+    // than 3.22 G symbols has it: (N / 2^13 / 32 + 6) * 5 > WF_LDS_MAX)
     const bool wf_global = sw.win_filter_global;
     bool rk_windows = false;          // only some windows are built
     u32 *w_need = nullptr, *w_built = nullptr, *w_sel = nullptr, *w_list = nullptr;

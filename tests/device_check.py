@@ -1,11 +1,13 @@
 """Exact checks of tables that are too large for the CPU oracle, with torch on the
-device that holds them.  TEST INFRASTRUCTURE (the checker, never the thing
-checked): a restatement of the reference's own linear-time checkers
+device that holds them (or on the CPU: tests/test_device_check.py).  TEST
+INFRASTRUCTURE (the checker, never the thing checked): a restatement of the
+reference's own linear-time checkers
 
   gt_suftab_lightweightcheck   src/match/sfx-lwcheck.c:181-337
   gt_lcptab_lightweightcheck   src/match/sfx-linlcp.c:548
 
-for tables in device memory.  Sortedness of a suffix array is a LOCAL property
+for tables in device memory; check_lcp_exact turns Kasai's inheritance argument
+into a check of every .lcp and .llv entry.  Sortedness of a suffix array is a LOCAL property
 once it is a permutation: with rank = its inverse,
 
     suffix SA[i-1] < suffix SA[i]   for all i
@@ -27,23 +29,35 @@ def _chunks(n, step=CHUNK):
         yield a, min(n, a + step)
 
 
-def check_suffix_array_exact(sa, enc):
-    """sa: int64 device tensor, N = n + 1 entries; enc: uint8 device tensor, n
-    encoded symbols.  Returns (ok, message)."""
+def suffix_ranks(sa):
+    """the inverse of a suffix table that is a permutation of [0, n]: (rank, "") with
+    rank an int64 tensor of N entries on the table's device, or (None, message)"""
     N = sa.numel()
     n = N - 1
     dev = sa.device
-    # ---- permutation: the inverse exists and inverts
     rank = torch.empty(N, dtype=torch.int64, device=dev)
     rank.fill_(-1)
     for a, b in _chunks(N):
         p = sa[a:b]
         if int(p.min()) < 0 or int(p.max()) > n:
-            return False, "entry outside [0, n] in [%d, %d)" % (a, b)
+            return None, "entry outside [0, n] in [%d, %d)" % (a, b)
         rank[p] = torch.arange(a, b, dtype=torch.int64, device=dev)
     for a, b in _chunks(N):
         if not bool((sa[rank[a:b]] == torch.arange(a, b, dtype=torch.int64, device=dev)).all()):
-            return False, "not a permutation (positions [%d, %d))" % (a, b)
+            return None, "not a permutation (positions [%d, %d))" % (a, b)
+    return rank, ""
+
+
+def check_suffix_array_exact(sa, enc, rank=None):
+    """sa: int64 device tensor, N = n + 1 entries; enc: uint8 device tensor, n
+    encoded symbols; rank: suffix_ranks(sa) when the caller keeps it for
+    check_lcp_exact.  Returns (ok, message)."""
+    N = sa.numel()
+    n = N - 1
+    if rank is None:
+        rank, msg = suffix_ranks(sa)
+        if rank is None:
+            return False, msg
     # ---- order of every pair of neighbours
     def c_of(p):
         sym = torch.where(p < n, enc[torch.clamp(p, max=n - 1)].to(torch.int64),
@@ -58,36 +72,7 @@ def check_suffix_array_exact(sa, enc):
         if not bool(ok.all()):
             i = int(torch.nonzero(~ok)[0].item()) + a + 1
             return False, "suffixes out of order at table index %d" % i
-    del rank
     return True, ""
-
-
-def lcp_of_pairs(enc, p, q, cap=None):
-    """longest common prefix of the suffixes p[k], q[k] (int64 device tensors):
-    equal letters count, a special on either side ends the match"""
-    n = enc.numel()
-    m = p.numel()
-    l = torch.zeros(m, dtype=torch.int64, device=p.device)
-    active = torch.arange(m, dtype=torch.int64, device=p.device)
-    step = 0
-    while active.numel() > 0:
-        pa, qa, la = p[active], q[active], l[active]
-        # 16 symbols per sweep: the first mismatch inside them
-        off = torch.arange(16, dtype=torch.int64, device=p.device)
-        ia = pa[:, None] + la[:, None] + off[None, :]
-        ib = qa[:, None] + la[:, None] + off[None, :]
-        va = torch.where(ia < n, enc[torch.clamp(ia, max=n - 1)], torch.full_like(ia, 255, dtype=torch.uint8))
-        vb = torch.where(ib < n, enc[torch.clamp(ib, max=n - 1)], torch.full_like(ib, 255, dtype=torch.uint8))
-        stop = (va != vb) | (va >= 254)
-        first = torch.where(stop.any(dim=1), stop.to(torch.int8).argmax(dim=1),
-                            torch.full((active.numel(),), 16, dtype=torch.int64, device=p.device))
-        l[active] = la + first
-        keep = first == 16
-        if cap is not None:
-            keep &= (la + first) < cap
-        active = active[keep]
-        step += 1
-    return l
 
 
 def check_bwt_exact(sa, enc, bwt):
@@ -101,24 +86,107 @@ def check_bwt_exact(sa, enc, bwt):
     return True, ""
 
 
-def check_lcp_samples(sa, enc, lcp, llv_idx, llv_val, idx):
-    """idx: int64 device tensor of table indices >= 1; the LCP byte of each, and
-    for bytes of 255 the entry of .llv, against the symbols themselves"""
-    p, q = sa[idx - 1], sa[idx]
-    l = lcp_of_pairs(enc, p, q)
-    byte = lcp[idx].to(torch.int64)
-    if not bool((byte == torch.clamp(l, max=255)).all()):
-        k = int(torch.nonzero(byte != torch.clamp(l, max=255))[0].item())
-        return False, "lcp byte at table index %d is %d, the suffixes share %d" % (
-            int(idx[k]), int(byte[k]), int(l[k]))
-    big = l >= 255
-    if bool(big.any()):
-        bi = idx[big]
-        pos = torch.searchsorted(llv_idx, bi)
-        if int(pos.max()) >= llv_idx.numel() or not bool((llv_idx[pos] == bi).all()):
-            return False, "an lcp >= 255 has no .llv entry"
-        if not bool((llv_val[pos] == l[big]).all()):
-            return False, "a .llv value differs from the symbols"
+LCP_CHUNK = 1 << 21          # text positions per step of check_lcp_exact
+SWEEP = 1 << 25              # symbol pairs per sweep of its part (b)
+
+
+def _sym(enc, i):
+    """the symbols at positions i (int64), 255 (a special) at and beyond the end"""
+    n = enc.numel()
+    return torch.where(i < n, enc[torch.clamp(i, max=n - 1)],
+                       torch.full_like(i, 255, dtype=torch.uint8))
+
+
+def check_lcp_exact(sa, enc, lcp, llv_idx, llv_val, rank=None):
+    """EVERY entry of .lcp and .llv, in time linear in n: Kasai's inheritance
+    argument (the reference's src/match/sfx-linlcp.c) turned into a check.  Only
+    for a suffix table that check_suffix_array_exact has accepted; rank: its
+    suffix_ranks(sa) if the caller has it.
+
+    C[i] is the claimed LCP of table index i (the byte, the .llv value where the
+    byte is 255), PLCP[p] = C[rank[p]], phi(p) = sa[rank[p] - 1].  For every
+    position p with rank[p] >= 1:
+      (a) suffixes p and phi(p) differ at offset PLCP[p] (different symbols, a
+          special or the end on either side): true LCP <= claim;
+      (b) they hold equal letters at every offset in [s, PLCP[p]), with
+          s = max(PLCP[p-1] - 1, 0) (0 for p = 0 or rank[p-1] = 0): suffixes
+          phi(p-1)+1 and p share PLCP[p-1] - 1 symbols and phi(p) lies between
+          them in the table, so by induction over p the offsets below s agree:
+          true LCP >= claim.
+    (b) compares sum(max(0, PLCP[p] - PLCP[p-1] + 1)) <= 2N symbol pairs."""
+    N = sa.numel()
+    n = N - 1
+    dev = sa.device
+    # ---- .llv: exactly the table indices whose byte is 255, ascending
+    m = llv_idx.numel()
+    if int(lcp[0].item()) != 0:
+        return False, "lcp byte at table index 0 is %d" % int(lcp[0].item())
+    overflows = count_lcp_overflows(lcp)
+    if overflows != m:
+        return False, "%d lcp bytes of 255, %d .llv entries" % (overflows, m)
+    if m > 0:
+        if not bool((llv_idx[1:] > llv_idx[:-1]).all()):
+            return False, ".llv indices not ascending"
+        if int(llv_idx[0].item()) < 1 or int(llv_idx[-1].item()) > n:
+            return False, ".llv index outside [1, n]"
+        for a, b in _chunks(m):
+            i, v = llv_idx[a:b], llv_val[a:b]
+            if not bool((lcp[i] == 255).all()):
+                return False, ".llv entry where the lcp byte is not 255"
+            if int(v.min().item()) < 255 or int(v.max().item()) > n:
+                return False, ".llv value outside [255, n]"
+    if rank is None:
+        rank, msg = suffix_ranks(sa)
+        if rank is None:
+            return False, msg
+
+    def claims(r):
+        c = lcp[r].to(torch.int64)
+        big = c == 255
+        c[big] = llv_val[torch.searchsorted(llv_idx, r[big])]
+        return c
+
+    def report(p, q, r, claim, at, what):
+        return False, "lcp at table index %d (suffixes %d, %d) is %d, %s at offset %d" % (
+            r, q, p, claim, what, at)
+
+    for a, b in _chunks(N, LCP_CHUNK):
+        lo = max(a - 1, 0)              # (PLCP[a - 1] gives the start of (b) at a)
+        r = rank[lo:b]
+        has = r >= 1
+        rc = torch.clamp(r, min=1)
+        plcp = torch.where(has, claims(rc), torch.zeros_like(r))
+        phi = sa[rc - 1]
+        s = torch.zeros_like(plcp)
+        s[1:] = torch.where(has[:-1], torch.clamp(plcp[:-1] - 1, min=0), s[1:])
+        k = a - lo
+        p = torch.arange(a, b, dtype=torch.int64, device=dev)
+        r, has, plcp, phi, s = r[k:], has[k:], plcp[k:], phi[k:], s[k:]
+        # (a) the first offset where the two differ is the claim
+        va, vb = _sym(enc, p + plcp), _sym(enc, phi + plcp)
+        bad = has & (va == vb) & (va < 254)
+        if bool(bad.any()):
+            j = int(torch.nonzero(bad)[0].item())
+            return report(a + j, int(phi[j]), int(r[j]), int(plcp[j]), int(plcp[j]), "they agree")
+        # (b) equal letters in [s, claim), sweeps of 16 symbols that double, up to
+        # 16 K, while the positions still open fit SWEEP
+        act = torch.nonzero(has & (plcp > s)).flatten()
+        cur, end, pa, qa = s[act], plcp[act], p[act], phi[act]
+        w = 16
+        while act.numel() > 0:
+            o = cur[:, None] + torch.arange(w, dtype=torch.int64, device=dev)[None, :]
+            xa, xb = _sym(enc, pa[:, None] + o), _sym(enc, qa[:, None] + o)
+            bad = (o < end[:, None]) & ((xa != xb) | (xa >= 254))
+            if bool(bad.any()):
+                j, t = (int(x) for x in torch.nonzero(bad)[0])
+                return report(int(pa[j]), int(qa[j]), int(rank[pa[j]]), int(end[j]), int(o[j, t]),
+                              "they differ")
+            cur = cur + w
+            keep = cur < end
+            act, cur, end, pa, qa = act[keep], cur[keep], end[keep], pa[keep], qa[keep]
+            w = min(2 * w, 1 << 14)
+            while w > 16 and act.numel() * w > SWEEP:
+                w //= 2
     return True, ""
 
 

@@ -1,0 +1,210 @@
+"""The device checkers (tests/device_check.py) on the CPU: they accept the oracle's
+tables and the reference's own, and reject every seeded mutation of the table each
+of them checks -- an .lcp byte or .llv value off by one, a byte of 254 raised to
+255 with an .llv entry, a dropped .llv entry, two neighbours of .suf swapped, a
+duplicated .suf entry, a changed .bwt byte -- at table index 1, in the special
+tail, at the entry of position n and at random indices.  The full-size GPU tests
+rely on these checkers to be exact, not sampled."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import device_check as dc
+import oracle_util as ou
+from genometools_amd import synth
+
+
+def _special_heavy(seed, n):
+    """uniform DNA with a third of its positions special: runs and single
+    wildcards and separators, a run at both ends"""
+    rng = np.random.default_rng(seed)
+    enc = rng.integers(0, 4, n).astype(np.uint8)
+    enc[rng.random(n) < 0.2] = 254
+    for start in rng.integers(0, n - 40, n // 200):
+        enc[start:start + rng.integers(1, 40)] = 254
+    enc[rng.random(n) < 0.02] = 255
+    enc[:7] = 254
+    enc[-5:] = 255
+    return enc
+
+
+def _runs(n):
+    """long homopolymer and period-3 runs between specials: LCPs up to
+    thousands, every byte from 0 to 255 in .lcp"""
+    parts = [np.zeros(6000, np.uint8), [254], np.tile(np.array([1, 2, 3], np.uint8), 3000), [255],
+             np.zeros(2500, np.uint8), [254], synth.generate(synth.MODEL_UNIFORM_DNA, 5, n - 17503)]
+    return np.concatenate([np.asarray(p, np.uint8) for p in parts])
+
+
+def _text(name):
+    """(encoded symbols, tables {suf, lcp, llv, bwt} as numpy)"""
+    if name.startswith("fixture:"):
+        fx = name.split(":", 1)[1]
+        protein = ou.golden()[fx]["alphabet"] == "protein"
+        enc = ou.encode_fasta(ou.fixture_path(fx), protein)
+        t = {ext: ou.golden_table(fx, ext) for ext in ("suf", "lcp", "llv", "bwt")}
+        t["llv"] = t["llv"].reshape(-1, 2)
+        return enc, t
+    model_of = {"uniform": synth.MODEL_UNIFORM_DNA, "humanlike": synth.MODEL_HUMANLIKE_DNA,
+                "repeatheavy": synth.MODEL_REPEAT_HEAVY, "protein": synth.MODEL_PROTEIN}
+    if name in model_of:
+        enc = synth.generate(model_of[name], 43, 120_000)
+        sigma = synth.numofchars(model_of[name])
+    elif name == "specialheavy":
+        enc, sigma = _special_heavy(32, 100_000), 4
+    else:
+        enc, sigma = _runs(60_000), 4
+    return enc, ou.esa(enc, sigma)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    enc, t = _text(name)
+    return {"enc": torch.from_numpy(np.ascontiguousarray(enc)),
+            "suf": torch.from_numpy(t["suf"].astype(np.int64)),
+            "lcp": torch.from_numpy(np.array(t["lcp"])),
+            "llv": torch.from_numpy(t["llv"].astype(np.int64).reshape(-1, 2)),
+            "bwt": torch.from_numpy(np.array(t["bwt"])),
+            "N": enc.size + 1, "specials": int(np.count_nonzero(enc >= 254))}
+
+
+def _rng(name, what):
+    return np.random.default_rng([sum(map(ord, name)), sum(map(ord, what))])
+
+
+TEXTS = ["uniform", "humanlike", "repeatheavy", "protein", "specialheavy", "runs",
+         "fixture:Atinsert.fna", "fixture:Duplicate.fna", "fixture:sw100K1.fsa"]
+# the texts with LCPs of 254 and above (.llv entries)
+LLV_TEXTS = ["humanlike", "repeatheavy", "runs", "fixture:Duplicate.fna"]
+
+
+def _lcp_check(c, lcp=None, llv=None):
+    llv = c["llv"] if llv is None else llv
+    return dc.check_lcp_exact(c["suf"], c["enc"], c["lcp"] if lcp is None else lcp,
+                              llv[:, 0].contiguous(), llv[:, 1].contiguous())
+
+
+def _indices(c, rng, count):
+    """table index 1, the first entry of the special tail and its last special,
+    the entry of position n (N - 1), and `count` random indices >= 1"""
+    N, sp = c["N"], c["specials"]
+    edge = [1, N - 1] + ([N - 1 - sp, N - 2] if sp else [])
+    return sorted(set(edge) | set(int(x) for x in rng.integers(1, N, count)))
+
+
+@pytest.mark.parametrize("name", TEXTS)
+def test_checkers_accept_the_tables(name):
+    c = _case(name)
+    rank, msg = dc.suffix_ranks(c["suf"])
+    assert rank is not None, msg
+    assert dc.check_suffix_array_exact(c["suf"], c["enc"], rank) == (True, "")
+    assert dc.check_bwt_exact(c["suf"], c["enc"], c["bwt"]) == (True, "")
+    idx, val = c["llv"][:, 0].contiguous(), c["llv"][:, 1].contiguous()
+    assert dc.check_lcp_exact(c["suf"], c["enc"], c["lcp"], idx, val, rank) == (True, "")
+    assert dc.check_llv_all(c["suf"], c["enc"], c["lcp"], idx, val) == (True, "")
+    assert (c["llv"].shape[0] > 0) == (name in LLV_TEXTS)
+
+
+@pytest.mark.parametrize("name", TEXTS)
+def test_lcp_byte_off_by_one_is_rejected(name):
+    c = _case(name)
+    accepted, tried = [], 0
+    for i in _indices(c, _rng(name, "lcp"), 40):
+        b = int(c["lcp"][i])
+        for d in (1, -1):
+            if b == 255 or b + d < 0:
+                continue
+            lcp = c["lcp"].clone()
+            lcp[i] = b + d
+            tried += 1
+            if _lcp_check(c, lcp=lcp)[0]:
+                accepted.append((i, b, d))
+    assert tried >= 40 and not accepted
+
+
+@pytest.mark.parametrize("name", LLV_TEXTS)
+def test_llv_value_off_by_one_is_rejected(name):
+    c = _case(name)
+    m = c["llv"].shape[0]
+    accepted = []
+    for k in sorted({0, m - 1} | set(int(x) for x in _rng(name, "llv").integers(0, m, 30))):
+        for d in (1, -1):
+            llv = c["llv"].clone()
+            llv[k, 1] += d
+            ok = _lcp_check(c, llv=llv)[0]
+            ok_all = dc.check_llv_all(c["suf"], c["enc"], c["lcp"], llv[:, 0].contiguous(),
+                                      llv[:, 1].contiguous())[0]
+            if ok or ok_all:
+                accepted.append((k, d, ok, ok_all))
+    assert not accepted
+
+
+@pytest.mark.parametrize("name", LLV_TEXTS)
+def test_lcp_254_raised_with_an_llv_entry_is_rejected(name):
+    c = _case(name)
+    at = np.flatnonzero(c["lcp"].numpy() == 254)
+    assert at.size > 0
+    accepted = []
+    for i in at[:20]:
+        i = int(i)
+        lcp = c["lcp"].clone()
+        lcp[i] = 255
+        k = int(torch.searchsorted(c["llv"][:, 0].contiguous(), torch.tensor(i)))
+        llv = torch.cat([c["llv"][:k], torch.tensor([[i, 255]]), c["llv"][k:]])
+        if _lcp_check(c, lcp=lcp, llv=llv)[0]:
+            accepted.append(i)
+    assert not accepted
+
+
+@pytest.mark.parametrize("name", LLV_TEXTS)
+def test_dropped_llv_entry_is_rejected(name):
+    c = _case(name)
+    m = c["llv"].shape[0]
+    accepted = []
+    for k in sorted({0, m - 1} | set(int(x) for x in _rng(name, "drop").integers(0, m, 10))):
+        llv = torch.cat([c["llv"][:k], c["llv"][k + 1:]])
+        if _lcp_check(c, llv=llv)[0]:
+            accepted.append(k)
+    assert not accepted
+
+
+@pytest.mark.parametrize("name", TEXTS)
+def test_swapped_suf_neighbours_are_rejected(name):
+    c = _case(name)
+    accepted = []
+    for i in _indices(c, _rng(name, "swap"), 40):
+        sa = c["suf"].clone()
+        sa[i - 1], sa[i] = c["suf"][i], c["suf"][i - 1]
+        if dc.check_suffix_array_exact(sa, c["enc"])[0]:
+            accepted.append(i)
+    assert not accepted
+
+
+@pytest.mark.parametrize("name", TEXTS)
+def test_duplicated_suf_entry_is_rejected(name):
+    c = _case(name)
+    accepted = []
+    for i in _indices(c, _rng(name, "dup"), 20):
+        for src in (i - 1, i):               # the entry before over this one, and back
+            sa = c["suf"].clone()
+            sa[2 * i - 1 - src] = c["suf"][src]
+            if dc.check_suffix_array_exact(sa, c["enc"])[0]:
+                accepted.append((i, src))
+    assert not accepted
+
+
+@pytest.mark.parametrize("name", TEXTS)
+def test_changed_bwt_byte_is_rejected(name):
+    c = _case(name)
+    sigma = 20 if name in ("protein", "fixture:sw100K1.fsa") else 4
+    accepted = []
+    for i in [0] + _indices(c, _rng(name, "bwt"), 40):
+        b = int(c["bwt"][i])
+        for v in {(b + 1) % sigma if b < sigma else 0, 254 if b != 254 else 1}:
+            bwt = c["bwt"].clone()
+            bwt[i] = v
+            if dc.check_bwt_exact(c["suf"], c["enc"], bwt)[0]:
+                accepted.append((i, b, v))
+    assert not accepted

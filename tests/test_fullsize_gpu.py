@@ -5,15 +5,19 @@ oracle's comparison sort cannot run at these sizes):
   checker (permutation + sortedness, oracle/esa_oracle.c ora_check_suffix_array)
   and LCP/BWT equal the tables the oracle derives from that suffix array
   (Kasai).  Together that is bit-exactness of all three tables.
-* configs[2], 3 Gbp human-like DNA (the bench workload): the suffix table
-  EXACTLY -- permutation + every neighbour pair ordered by (first symbol, rank of
-  the successor), the reference's lightweight check restated on the device
-  (tests/device_check.py) --, .bwt for every entry, .lcp on 2 * 10^7 samples,
-  every .llv entry, the tail layout (specials in text order, then n).
-* configs[4], 10^9 protein residues: the same properties on the 5-bit path.
+* configs[2], 3 Gbp human-like DNA (the bench workload), and the repeat-heavy
+  model at 3 Gbp: every table EXACTLY on the device (tests/device_check.py) --
+  the suffix table as a permutation whose every neighbour pair is ordered by
+  (first symbol, rank of the successor), .lcp with .llv by Kasai's inheritance
+  argument, .bwt entry by entry --, every .llv entry probed once more, the tail
+  layout (specials in text order, then n) and the .prj statistics.
+* configs[4], 10^9 protein residues: the same exact checks on the 5-bit path.
 * the position range of configs[3] (n >= 2^32; the 24 Gbp input itself needs
   the 8 GPUs it is defined on): 2^32 + 4 M bases of uniform DNA built in two
-  parts on the one GPU, 64-bit positions and ranks.
+  parts on the one GPU, 64-bit positions and ranks; both slices put together
+  and checked exactly.
+* the largest single build, SINGLE_LIMIT - 1 entries (k_win_filter's window
+  bitmap in global memory), exactly; one entry more is refused.
 """
 import numpy as np
 import pytest
@@ -60,16 +64,86 @@ def test_config1_256mbp_uniform_bit_exact(gpu):
     assert np.array_equal(enc[:1 << 20], synth.generate(synth.MODEL_UNIFORM_DNA, 42, n, 0, 1 << 20))
 
 
+def _check_tables(sa, enc, lcp, bwt, llv_idx, llv_val):
+    """the four exact checks of tests/device_check.py, one rank table for two of them"""
+    import device_check as dc
+    rank, msg = dc.suffix_ranks(sa)
+    assert rank is not None, msg
+    ok, msg = dc.check_suffix_array_exact(sa, enc, rank)
+    assert ok, msg
+    ok, msg = dc.check_lcp_exact(sa, enc, lcp, llv_idx, llv_val, rank)
+    assert ok, msg
+    del rank
+    ok, msg = dc.check_bwt_exact(sa, enc, bwt)
+    assert ok, msg
+    ok, msg = dc.check_llv_all(sa, enc, lcp, llv_idx, llv_val)
+    assert ok, msg
+    torch.cuda.empty_cache()        # (the next engine allocates outside torch)
+
+
+def _check_tail_and_prj(sa, enc, lcp, llv_val, st):
+    """the special tail (every suffix that starts with a special, in text order,
+    then n) and the statistics of .prj that follow from the tables"""
+    import device_check as dc
+    N = sa.numel()
+    n = N - 1
+    assert int(sa[st["longest"]].item()) == 0
+    specials = int((enc >= 254).sum().item())
+    tail = sa[N - 1 - specials:]
+    assert int(tail[-1].item()) == n
+    assert bool((enc[tail[:-1]] >= 254).all()) and bool((tail[1:] > tail[:-1]).all())
+    assert int(enc[sa[N - 2 - specials]].item()) < 254
+    assert bool((lcp[N - specials:] == 0).all())
+    nl = llv_val.numel()
+    assert nl == st["largelcpvalues"] == dc.count_lcp_overflows(lcp)
+    assert nl == 0 or int(llv_val.max().item()) == st["maxbranchdepth"]
+
+
+def _device_tables(eng, N):
+    import device_check as dc
+    nl = eng.entries(esa.TAB_LLV)
+    llv = (dc.as_tensor(eng.device_pointer(esa.TAB_LLV), 2 * nl, "<i8") if nl else
+           torch.empty(0, dtype=torch.int64, device="cuda:0")).view(-1, 2)
+    return (dc.as_tensor(eng.device_pointer(esa.TAB_SUF), N, "<i8"),
+            dc.as_tensor(eng.device_pointer(esa.TAB_LCP), N, "|u1"),
+            dc.as_tensor(eng.device_pointer(esa.TAB_BWT), N, "|u1"),
+            llv[:, 0].contiguous(), llv[:, 1].contiguous())
+
+
+def _tables_to_host(engines):
+    """the slices of .suf, .lcp, .bwt and .llv of `engines` (the parts of one
+    build, or one whole build) in host memory, so that the engines can be closed
+    before the tables return to the device for the checks: the engine's workspace
+    and the checks' rank table do not fit the device together at these sizes"""
+    return [(eng.table_offset(), eng.table(esa.TAB_SUF).view(np.int64), eng.table(esa.TAB_LCP),
+             eng.table(esa.TAB_BWT), eng.table(esa.TAB_LLV).view(np.int64)) for eng in engines]
+
+
+def _tables_to_device(slices, N):
+    """whole-table device tensors (sa, lcp, bwt, llv_idx, llv_val) from the
+    slices of _tables_to_host; .llv indices count from the start of the whole
+    table (k_llv_emit adds the slice's table offset)"""
+    dev = "cuda:0"
+    sa = torch.empty(N, dtype=torch.int64, device=dev)
+    lcp = torch.empty(N, dtype=torch.uint8, device=dev)
+    bwt = torch.empty(N, dtype=torch.uint8, device=dev)
+    for off, suf, lc, bw, _ in slices:
+        sa[off:off + suf.size].copy_(torch.from_numpy(suf))
+        lcp[off:off + suf.size].copy_(torch.from_numpy(lc))
+        bwt[off:off + suf.size].copy_(torch.from_numpy(bw))
+    llv = torch.from_numpy(np.concatenate([sl[4] for sl in slices])).to(dev)
+    return sa, lcp, bwt, llv[:, 0].contiguous(), llv[:, 1].contiguous()
+
+
 def test_config2_3gbp_humanlike_exact(gpu):
     """BASELINE.json configs[2], the bench workload, with the switches the bench
-    runs with (none).  The suffix table is checked EXACTLY, on the device
-    (tests/device_check.py: the reference's lightweight check restated -- a
+    runs with (none).  Every table EXACTLY, on the device (tests/device_check.py):
+    the suffix table by the reference's lightweight check restated -- a
     permutation whose every neighbour pair is ordered by (first symbol, rank of the
-    successor) is the sorted table); .bwt for every entry; .lcp on 2 * 10^7 sampled
-    entries against the symbols; every one of the 117 M .llv entries (position,
-    mismatch right behind its value, agreement at its last and at 16 random
-    offsets); the statistics of .prj from the tables."""
-    import device_check as dc
+    successor) is the sorted table --, .lcp and .llv by Kasai's inheritance
+    argument turned into a check, .bwt for every entry, and every one of the 117 M
+    .llv entries once more (mismatch right behind its value, agreement at its last
+    and at 16 random offsets); the tail; the statistics of .prj from the tables."""
     n = 3 * 1000 * 1000 * 1000
     N = n + 1
     buf = _device_sequence(synth.MODEL_HUMANLIKE_DNA, 43, n)
@@ -78,39 +152,27 @@ def test_config2_3gbp_humanlike_exact(gpu):
         eng.run()
         st = eng.stats()
         assert st["msd_big_entries"] > 0 and st["pair_suffixes"] > 3e8 and st["refine_rounds"] >= 9
-        sa = dc.as_tensor(eng.device_pointer(esa.TAB_SUF), N, "<i8")
-        lcp = dc.as_tensor(eng.device_pointer(esa.TAB_LCP), N, "|u1")
-        bwt = dc.as_tensor(eng.device_pointer(esa.TAB_BWT), N, "|u1")
-        ok, msg = dc.check_suffix_array_exact(sa, buf)
-        assert ok, msg
-        assert int(sa[st["longest"]].item()) == 0
-        ok, msg = dc.check_bwt_exact(sa, buf, bwt)
-        assert ok, msg
-        # the special tail: every suffix that starts with a special, in text order, then n
-        specials = int((buf >= 254).sum().item())
-        tail = sa[N - 1 - specials:]
-        assert int(tail[-1].item()) == n
-        assert bool((buf[tail[:-1]] >= 254).all()) and bool((tail[1:] > tail[:-1]).all())
-        assert int(buf[sa[N - 2 - specials]].item()) < 254
-        assert bool((lcp[N - specials:] == 0).all())
-        # .llv: all of it
-        nl = eng.entries(esa.TAB_LLV)
-        assert nl == st["largelcpvalues"] > 10 ** 8
-        llv = dc.as_tensor(eng.device_pointer(esa.TAB_LLV), 2 * nl, "<i8").view(-1, 2)
-        llv_idx, llv_val = llv[:, 0].contiguous(), llv[:, 1].contiguous()
-        assert dc.count_lcp_overflows(lcp) == nl
-        assert int(llv_val.max().item()) == st["maxbranchdepth"]
-        ok, msg = dc.check_llv_all(sa, buf, lcp, llv_idx, llv_val)
-        assert ok, msg
-        # .lcp on samples (2 * 10^7 entries, a tenth of them where the LCP is large)
-        g = torch.Generator(device="cuda:0")
-        g.manual_seed(2026)
-        idx = torch.randint(1, N - specials, (18_000_000,), device="cuda:0", generator=g)
-        pick = llv_idx[torch.randint(0, nl, (2_000_000,), device="cuda:0", generator=g)]
-        for part in (idx, pick, torch.clamp(pick + 1, max=N - 1)):
-            for a in range(0, part.numel(), 1 << 22):
-                ok, msg = dc.check_lcp_samples(sa, buf, lcp, llv_idx, llv_val, part[a:a + (1 << 22)])
-                assert ok, msg
+        sa, lcp, bwt, llv_idx, llv_val = _device_tables(eng, N)
+        assert llv_idx.numel() > 10 ** 8
+        _check_tables(sa, buf, lcp, bwt, llv_idx, llv_val)
+        _check_tail_and_prj(sa, buf, lcp, llv_val, st)
+
+
+def test_repeatheavy_3gbp_exact(gpu):
+    """MODEL_REPEAT_HEAVY at 3 Gbp: the hard case of prefix doubling (14 rounds,
+    393 M .llv entries, LCPs up to 255 865), every table exact"""
+    n = 3 * 1000 * 1000 * 1000
+    N = n + 1
+    buf = _device_sequence(synth.MODEL_REPEAT_HEAVY, 43, n)
+    with esa.EsaEngine(n, 4) as eng:
+        eng.set_sequence_device(buf.data_ptr(), n)
+        eng.run()
+        st = eng.stats()
+        assert st["refine_rounds"] >= 12
+        sa, lcp, bwt, llv_idx, llv_val = _device_tables(eng, N)
+        assert llv_idx.numel() > 3 * 10 ** 8 and st["maxbranchdepth"] > 10 ** 5
+        _check_tables(sa, buf, lcp, bwt, llv_idx, llv_val)
+        _check_tail_and_prj(sa, buf, lcp, llv_val, st)
 
 
 def _sampled_neighbours(eng, enc_of, n, lo, hi, rng, samples, index_offset=0, wildcard_ok=True):
@@ -141,10 +203,10 @@ def _sampled_neighbours(eng, enc_of, n, lo, hi, rng, samples, index_offset=0, wi
     return bad
 
 
-def test_config4_protein_1g_properties(gpu):
+def test_config4_protein_1g_exact(gpu):
     """BASELINE.json configs[4]: 10^9 residues over the 20-letter alphabet
     (src/core/alphabet.c:488-503), -suf -lcp (+ -bwt): the 5-bit symbol path at
-    full size (7 sort passes, N/12 word indexing)"""
+    full size (7 sort passes, N/12 word indexing), every table exact on the device"""
     n = 1000 * 1000 * 1000
     N = n + 1
     buf = _device_sequence(synth.MODEL_PROTEIN, 44, n)
@@ -153,10 +215,8 @@ def test_config4_protein_1g_properties(gpu):
         eng.run()
         st = eng.stats()
         assert st["prefixlength"] == 5
-        sa = torch.as_tensor(_Wrap(eng.device_pointer(esa.TAB_SUF), N, "<i8"), device="cuda:0")
-        assert int(sa.sum().item()) == N * (N - 1) // 2
-        sq = int((sa * sa).sum().item()) % (1 << 64)
-        assert sq == ((N - 1) * N * (2 * N - 1) // 6) % (1 << 64)
+        sa, lcp, bwt, llv_idx, llv_val = _device_tables(eng, N)
+        _check_tables(sa, buf, lcp, bwt, llv_idx, llv_val)
         assert int(sa[st["longest"]].item()) == 0
         del sa
         enc = buf.cpu().numpy()
@@ -171,9 +231,6 @@ def test_config4_protein_1g_properties(gpu):
         assert np.all(np.diff(tail[:-1].astype(np.int64)) > 0)
         before_tail = eng.table(esa.TAB_SUF, N - 2 - specials, 1)[0]
         assert enc[int(before_tail)] < 254
-        rng = np.random.default_rng(44)
-        bad = _sampled_neighbours(eng, lambda a, b: enc[a:b], n, 1, N - specials - 1, rng, 4000)
-        assert bad == 0
         # i.i.d. residues: no LCP near the byte limit
         assert st["largelcpvalues"] == 0 and st["maxbranchdepth"] < 64
         lcp = eng.table(esa.TAB_LCP)
@@ -187,7 +244,8 @@ def test_config4_protein_1g_properties(gpu):
 def test_positions_beyond_2p32_in_two_parts(gpu):
     """n just above 2^32 (the position range BASELINE.json configs[3], 24 Gbp
     on 8 GPUs, needs): two parts as threads on the one GPU, 64-bit positions
-    and ranks, the slices of both parts checked on the device and by samples"""
+    and ranks; the slices of both parts checked on the device and by samples,
+    then put together and every table checked exactly"""
     import threading
     from thread_comm import ThreadComm
     n = (1 << 32) + (1 << 22) + 12345
@@ -248,9 +306,57 @@ def test_positions_beyond_2p32_in_two_parts(gpu):
         d = int(np.nonzero(a[:m] != b[:m])[0][0])
         assert a[d] < b[d]
         assert int(engines[1].table(esa.TAB_LCP, 0, 1)[0]) == d
+        # every entry: both slices as one table, checked once the engines are closed
+        slices = _tables_to_host(engines)
+        for eng in engines:
+            eng.close()
+        tables = _tables_to_device(slices, N)
+        del slices
+        buf = _device_sequence(synth.MODEL_UNIFORM_DNA, seed, n)
+        _check_tables(tables[0], buf, *tables[1:])
     finally:
         for eng in engines:
             eng.close()
+
+
+SINGLE_LIMIT = (1 << 32) - 4096     # table entries of a single build (esa_engine.hip)
+
+
+def test_single_build_at_the_32bit_limit(gpu):
+    """the largest single build, N = SINGLE_LIMIT - 1 entries of human-like DNA:
+    32-bit ranks and compact positions at their largest, and the window bitmap
+    of k_win_filter too large for the LDS, read from global memory.  Every table
+    exact.  One symbol more is refused with the advice to build in parts."""
+    import device_check as dc
+    n = SINGLE_LIMIT - 2
+    N = n + 1
+    with esa.EsaEngine(n + 1, 4) as eng:
+        buf = _device_sequence(synth.MODEL_HUMANLIKE_DNA, 46, n + 1)
+        eng.set_sequence_device(buf.data_ptr(), n + 1)
+        with pytest.raises(esa.EsaError, match="build it in parts"):
+            eng.run()
+        del buf
+        torch.cuda.empty_cache()
+        buf = _device_sequence(synth.MODEL_HUMANLIKE_DNA, 46, n)
+        eng.set_sequence_device(buf.data_ptr(), n)
+        eng.run()
+        st = eng.stats()
+        free, total = torch.cuda.mem_get_info()
+        print("after the build: %.1f of %.1f GB free" % (free / 1e9, total / 1e9))
+        assert eng.table_offset() == 0 and eng.entries(esa.TAB_SUF) == N
+        # k_win_filter keeps the bitmap of the selected rank windows (2^13
+        # positions each) in LDS while (words + 4) * 5 <= 60 KB; this build is past
+        # that, and it built only the selected windows, so the filter ran on the
+        # bitmap in global memory
+        words = -(-N // (1 << 13)) // 32 + 2
+        assert (words + 4) * 5 > 60 * 1024
+        assert 0 < st["rank_entries_built"] < N
+        slices = _tables_to_host([eng])
+    tables = _tables_to_device(slices, N)
+    del slices
+    _check_tables(tables[0], buf, *tables[1:])
+    _check_tail_and_prj(tables[0], buf, tables[1], tables[4], st)
+    assert tables[4].numel() > 10 ** 7
 
 
 # ---- the packed index at a size the oracle cannot reach --------------------------
