@@ -1017,10 +1017,12 @@ __global__ __launch_bounds__(256) void k_wide_positions(const u64 *__restrict__ 
 // bucket table (.bck): bcktab.c:55-81,519-577, sfx-suffixer.c:379-383,476-516
 // ---------------------------------------------------------------------------
 // code of the first k symbols in base sigma; a prefix shorter than k letters is
-// padded with the largest letter (the key pads with 1-bits)
+// padded with the largest letter (the key pads with 1-bits).  The 2-bit key is
+// the base-4 code itself only for sigma 4: a 2- or 3-letter alphabet needs the
+// base-sigma code, and its 1-bit padding (digit 3) clamped to sigma - 1.
 template <int BITS>
 __device__ __forceinline__ u64 bck_code(u64 key, u32 k, u32 sigma) {
-  if (BITS == 2) return k == 0 ? 0 : key >> (64 - 2 * k);
+  if (BITS == 2 && sigma == 4) return k == 0 ? 0 : key >> (64 - 2 * k);
   u64 code = 0;
   for (u32 j = 0; j < k; j++) {
     u32 d = (u32) (key >> (64 - BITS * (j + 1))) & ((1u << BITS) - 1u);
@@ -1029,16 +1031,33 @@ __device__ __forceinline__ u64 bck_code(u64 key, u32 k, u32 sigma) {
   }
   return code;
 }
+// k > KEY_SYMS (2 letters from 2^26 symbols): the digits after the key from the
+// text at p + KEY_SYMS, up to the first special, then padded; a key that
+// already ends in a special is padded all the way
+template <int BITS>
+__device__ __forceinline__ u64 bck_code_long(const Text &t, u64 key, u64 p, u32 k,
+                                             u32 sigma) {
+  using K = Key<BITS>;
+  if (k <= (u32) K::SYMS) return bck_code<BITS>(key, k, sigma);
+  u64 code = bck_code<BITS>(key, K::SYMS, sigma);
+  const u64 sp = K::dcode(key) == 0 ? sp_window(t, p + K::SYMS) : ~0ull;
+  const u32 more = sp ? (u32) __ffsll((unsigned long long) sp) - 1u : 64u;
+  for (u32 j = 0; j < k - (u32) K::SYMS; j++)
+    code = code * sigma + (j < more ? Sym<BITS>::at(t, p + K::SYMS + j) : sigma - 1);
+  return code;
+}
 
 // hist[c] = entries whose padded k-code is c (suffixes that start with a
 // special are not in any bucket); the keys are sorted, so a wave adds one count
 // per run of equal codes.  Suffixes with fewer than k letters in front of a
 // special are counted per padded (k-1)-prefix and, for 1..k-2 letters, per
 // prefix of exactly that length.
+//   pos (k > KEY_SYMS only): the sorted positions' low halves, beside the keys
 template <int BITS>
 __global__ __launch_bounds__(256) void k_bck_count(
     const u64 *__restrict__ keys, u64 N, u32 k, u32 sigma, u32 *__restrict__ hist,
-    u32 *__restrict__ countspecial, u32 *__restrict__ distpfx) {
+    u32 *__restrict__ countspecial, u32 *__restrict__ distpfx, Text t,
+    const u32 *__restrict__ pos) {
   using K = Key<BITS>;
   const u64 i = (u64) blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
@@ -1046,7 +1065,11 @@ __global__ __launch_bounds__(256) void k_bck_count(
   const u64 key = valid ? keys[i] : ~0ull;
   const u32 dc = K::dcode(key);
   const bool inbucket = valid && dc != K::DMAX;
-  const u64 code = inbucket ? bck_code<BITS>(key, k, sigma) : ~0ull;
+  const bool longk = k > (u32) K::SYMS;
+  const u64 p = longk && inbucket ? (K::poshi(key) << 32) | pos[i] : 0;
+  const u64 code = !inbucket ? ~0ull
+                   : longk ? bck_code_long<BITS>(t, key, p, k, sigma)
+                           : bck_code<BITS>(key, k, sigma);
   const u64 prev = __shfl_up(code, 1, 64);
   const bool head = inbucket && (lane == 0 || prev != code);
   const u64 heads = __ballot(head), live = __ballot(inbucket);
@@ -1058,14 +1081,18 @@ __global__ __launch_bounds__(256) void k_bck_count(
     mask &= ~((1ull << lane) - 1ull);
     atomicAdd(&hist[code], (u32) __popcll(live & mask));
   }
-  if (inbucket && dc != 0) {
-    const u32 letters = K::letters(key);
+  if (inbucket && (dc != 0 || longk)) {
+    u32 letters = K::letters(key);
+    if (dc == 0) {   // (longk) letters past the key
+      const u64 sp = sp_window(t, p + K::SYMS);
+      letters += sp ? (u32) __ffsll((unsigned long long) sp) - 1u : 64u;
+    }
     if (letters < k) {
-      atomicAdd(&countspecial[bck_code<BITS>(key, k - 1, sigma)], 1u);
+      atomicAdd(&countspecial[bck_code_long<BITS>(t, key, p, k - 1, sigma)], 1u);
       if (letters >= 1 && letters + 2 <= k) {
         u64 off = 0, pw = sigma;
         for (u32 l = 1; l < letters; l++) { off += pw; pw *= sigma; }
-        atomicAdd(&distpfx[off + bck_code<BITS>(key, letters, sigma)], 1u);
+        atomicAdd(&distpfx[off + bck_code_long<BITS>(t, key, p, letters, sigma)], 1u);
       }
     }
   }
@@ -1089,6 +1116,7 @@ struct Stats {          // device-side accumulators
   unsigned long long smalldone;   // entries of the small groups settled directly
   unsigned long long crowded;     // MSD sort: entries of the runs k_msd_local read and left to
                                   // k_msd_local_radix (a crowded bin): read, not written by it
+  unsigned long long msum;        // lcp sum from the finished tables (prefixlength > KEY_SYMS)
 };
 
 constexpr int FIN_THREADS = 256;
@@ -2825,6 +2853,38 @@ __global__ __launch_bounds__(256) void k_llv_emit(
   }
 }
 
+// lcptabsum when the prefix length exceeds the key width (2 letters from 2^26
+// symbols): the sums of finalize and of the tie paths count an entry by the
+// letters its key shows, at most KEY_SYMS.  Here every entry of the finished
+// tables counts if its suffix has prefixlength letters in front of the first
+// special (the bitmap's bit n stands for the end): bytes below 255 from .lcp,
+// the rest from .llv.  prefixlength < 64: one window of the bitmap.
+__device__ __forceinline__ bool has_letters(const Text &t, u64 p, u32 k) {
+  return (sp_window(t, p) & ((1ull << k) - 1ull)) == 0;
+}
+__device__ __forceinline__ void add_msum(unsigned long long sum, Stats *stats) {
+  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+  if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&stats->msum, sum);
+}
+__global__ __launch_bounds__(256) void k_masked_lcpsum(
+    Text t, const u64 *__restrict__ suf, const u8 *__restrict__ lcp, u64 N, u32 k,
+    Stats *stats) {
+  unsigned long long sum = 0;
+  for (u64 i = (u64) blockIdx.x * 256 + threadIdx.x; i < N; i += (u64) gridDim.x * 256) {
+    const u32 l = lcp[i];
+    if (l != 255 && l != 0 && has_letters(t, suf[i], k)) sum += l;
+  }
+  add_msum(sum, stats);
+}
+__global__ __launch_bounds__(256) void k_masked_llvsum(
+    Text t, const u64 *__restrict__ suf, const u64 *__restrict__ llv, u64 m,
+    u64 index_offset, u32 k, Stats *stats) {
+  unsigned long long sum = 0;
+  for (u64 j = (u64) blockIdx.x * 256 + threadIdx.x; j < m; j += (u64) gridDim.x * 256)
+    if (has_letters(t, suf[llv[2 * j] - index_offset], k)) sum += llv[2 * j + 1];
+  add_msum(sum, stats);
+}
+
 // grid of a kernel whose workgroups stride over `tiles` tiles: enough
 // workgroups to fill the 256 CUs several times over, few enough that their
 // closing atomics do not queue up on one address
@@ -3421,7 +3481,7 @@ static u64 dest_words(u32 R, u64 m) { return (u64) R * div_up(m ? m : 1, 256) + 
 
 // the three sections of the bucket table from the sorted keys
 template <int BITS>
-static int build_bcktab(gtamd_esa_ctx *c, const u64 *skey, u64 NL, u32 k,
+static int build_bcktab(gtamd_esa_ctx *c, const u64 *skey, const u32 *spos, u64 NL, u32 k,
                         hipStream_t st) {
   u64 codes = 1, special = 1, dist = 0, pw = 1;
   for (u32 j = 0; j < k; j++) {
@@ -3442,7 +3502,7 @@ static int build_bcktab(gtamd_esa_ctx *c, const u64 *skey, u64 NL, u32 k,
   if (NL > 0) {
     k_bck_count<BITS><<<(u32) div_up(NL, 256), 256, 0, st>>>(
         skey, NL, k, c->sigma, c->bck, c->bck + codes + 1,
-        c->bck + codes + 1 + special);
+        c->bck + codes + 1 + special, c->text, spos);
     HIP_TRY(hipGetLastError());
   }
   // left borders: exclusive prefix sums; the last entry becomes the number of
@@ -3774,16 +3834,19 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
   const u64 N = c->N, n = c->n;
   const u32 R = c->numparts;
   hipStream_t st = c->st;
-  const bool want_suf = want & GTAMD_WANT_SUF, want_lcp = want & GTAMD_WANT_LCP,
-             want_bwt = want & GTAMD_WANT_BWT;
+  // (a user-given prefix length is capped at the key width by
+  // gtamd_esa_set_prefixlength; the recommended one exceeds it from 2^26 symbols
+  // over 2 letters, 5^13 over 5)
   const u32 prefixlength = c->user_prefixlength
                                ? c->user_prefixlength
                                : gtamd_recommended_prefixlength(c->sigma, n);
-  if (prefixlength > (u32) K::SYMS) {
-    gtamd_set_error("prefixlength %u exceeds the key width %d", prefixlength,
-                    K::SYMS);
-    return -1;
-  }
+  // beyond the key width the sums of finalize and of the tie paths cannot tell
+  // an entry's letters from its key: lcptabsum is taken from the finished tables
+  // (k_masked_lcpsum), which needs the suffix table
+  const bool long_prefix = prefixlength > (u32) K::SYMS;
+  if (long_prefix && (want & GTAMD_WANT_LCP)) want |= GTAMD_WANT_SUF;
+  const bool want_suf = want & GTAMD_WANT_SUF, want_lcp = want & GTAMD_WANT_LCP,
+             want_bwt = want & GTAMD_WANT_BWT;
   if (dist && (want & GTAMD_WANT_BCK)) {
     // as the reference: no bucket table from a run in parts
     // (gt_Sfxiterator_bcktab2file, src/match/sfx-suffixer.c:2206-2217)
@@ -4123,7 +4186,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
   }
   HIP_TRY(hipEventRecord(c->ev[2], st));
 
-  if (want & GTAMD_WANT_BCK) TRY(build_bcktab<BITS>(c, skey, NL, prefixlength, st));
+  if (want & GTAMD_WANT_BCK) TRY(build_bcktab<BITS>(c, skey, sa32, NL, prefixlength, st));
 
   // positions at the width the refinement works with
   P *sa;
@@ -5229,6 +5292,22 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       want_lcp ? (c->h_stats->maxlcp > c->h_stats->dmax ? c->h_stats->maxlcp
                                                          : c->h_stats->dmax) : 0;
   c->stats.lcptabsum = want_lcp ? c->h_stats->lcpsum + c->h_stats->dsum : 0;
+  if (long_prefix && want_lcp) {
+    HIP_TRY(hipMemsetAsync(&c->d_stats->msum, 0, 8, st));
+    if (c->NL > 0) {
+      k_masked_lcpsum<<<stride_grid(div_up(c->NL, 256)), 256, 0, st>>>(
+          c->text, c->suf.as<u64>(), c->lcp.as<u8>(), c->NL, prefixlength, c->d_stats);
+      HIP_TRY(hipGetLastError());
+    }
+    if (c->llv_pairs > 0) {
+      k_masked_llvsum<<<stride_grid(div_up(c->llv_pairs, 256)), 256, 0, st>>>(
+          c->text, c->suf.as<u64>(), c->llv, c->llv_pairs, c->index_offset, prefixlength,
+          c->d_stats);
+      HIP_TRY(hipGetLastError());
+    }
+    TRY(fetch_stats(c));
+    c->stats.lcptabsum = c->h_stats->msum;
+  }
   c->stats.prefixlength = prefixlength;
   c->stats.refine_rounds = rounds;
   c->stats.tied_suffixes = (m0_tied_all ? m0_tied_all : m0) + 2 * npairs + c->h_stats->smalldone;

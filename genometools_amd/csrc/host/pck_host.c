@@ -82,7 +82,7 @@ static int uint_option(int argc, const char **argv, int *i, uint32_t *out, char 
 int gtamd_packedindex_trsuftab(int argc, const char **argv, char *err, size_t errlen)
 {
   gtamd_pck_params pp = { 8, 8, 16, 0, 0 };
-  int locbitmap = -1, verbose = 0, rc = -1, protein = 0, sprank = 0, ctxilog = -2;
+  int locbitmap = -1, verbose = 0, rc = -1, sprank = 0, ctxilog = -2;
   const char *index = NULL;
   char path[4096];
   unsigned long long totallength, longest, integersize = 64;
@@ -136,8 +136,13 @@ int gtamd_packedindex_trsuftab(int argc, const char **argv, char *err, size_t er
   (void) prj_value(path, "integersize", &integersize);
   if (integersize != 64)
     return pfail(err, errlen, "file '%s' describes tables of another integer size", path);
-  /* the alphabet comes with the encoded sequence (the reference maps INDEX.esq) */
-  if (gtamd_read_esq(index, &enc, &n, &protein, &ss, err, errlen) != 0) return -1;
+  /* the alphabet comes with the encoded sequence (the reference maps INDEX.esq):
+     DNA, protein or a symbol map, only its size matters here */
+  {
+    gtamd_alphabet alpha;
+    if (gtamd_read_esq_alpha(index, &enc, &n, &alpha, &ss, err, errlen) != 0) return -1;
+    gtamd_alphabet_free(&alpha);
+  }
   free(enc);
   if (n != totallength) return pfail(err, errlen, "INDEX.esq and INDEX.prj of '%s' disagree on the total length", index);
   snprintf(path, sizeof path, "%s.bwt", index);

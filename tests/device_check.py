@@ -220,6 +220,50 @@ def check_llv_all(sa, enc, lcp, llv_idx, llv_val, rng_seed=1, probes=16):
     return True, ""
 
 
+def check_esastats_exact(sa, enc, lcp, llv_idx, llv_val, prefixlength, stats):
+    """the .prj numbers that depend on the tables, by the oracle's definition
+    (oracle/esa_oracle.c, ora_esastats_compute): `longest` is the table index of
+    suffix 0, `largelcpvalues` the entries of LCP >= 255, `maxbranchdepth` the
+    largest LCP, `lcptabsum` the sum of the LCPs of the entries whose suffix has
+    at least `prefixlength` letters in front of the first special or the end.
+    Only for tables the other checkers have accepted; stats: the engine's dict.
+    Returns (ok, message)."""
+    N = sa.numel()
+    n = N - 1
+    dev = sa.device
+    # letters in front of the next special: the next special's position from a
+    # reverse cumulative minimum, chunk by chunk from the end of the text
+    enough = torch.empty(N, dtype=torch.bool, device=dev)
+    enough[n] = prefixlength == 0
+    carry = n
+    for a, b in reversed(list(_chunks(n))):
+        p = torch.arange(a, b, dtype=torch.int64, device=dev)
+        nxt = torch.where(enc[a:b] >= 254, p, torch.full_like(p, carry))
+        nxt = torch.flip(torch.cummin(torch.flip(nxt, [0]), 0).values, [0])
+        enough[a:b] = nxt - p >= prefixlength
+        carry = int(nxt[0].item())
+    longest, large, depth, total = -1, 0, 0, 0
+    for a, b in _chunks(N):
+        p = sa[a:b]
+        at = torch.nonzero(p == 0).flatten()
+        if at.numel() > 0:
+            longest = a + int(at[0].item())
+        c = lcp[a:b].to(torch.int64)
+        big = c == 255
+        if bool(big.any()):
+            r = torch.nonzero(big).flatten() + a
+            c[big] = llv_val[torch.searchsorted(llv_idx, r)]
+        large += int(big.sum().item())
+        depth = max(depth, int(c.max().item()))
+        total += int((c * enough[p]).sum().item())
+    want = {"longest": longest, "largelcpvalues": large, "maxbranchdepth": depth,
+            "lcptabsum": total}
+    for name, v in want.items():
+        if int(stats[name]) != v:
+            return False, "%s is %d, the tables give %d" % (name, int(stats[name]), v)
+    return True, ""
+
+
 def count_lcp_overflows(lcp):
     total = 0
     for a, b in _chunks(lcp.numel()):

@@ -75,6 +75,14 @@ SMAP_CASES = [("trans_dna.map", "Atinsert.fna"), ("trans_dna.map", "Duplicate.fn
               ("trans_dna.map", "extra/lowercase_iupac.fna"),
               ("prot5.map", "sw100K1.fsa"), ("prot5.map", "extra/protein_specials.faa"),
               ("prot5.map", "extra/protein_long_x.faa")]
+# the reference's own maps of 2..22 letters (gtdata/trans) on both protein inputs,
+# where the map covers the input's characters (Transab: a, b and *; TransMass has
+# no U, which protein_specials.faa holds)
+SMAP_CASES += [(m, f) for m in ("TransProt2", "TransProt3", "TransProt4", "TransProt8",
+                                "TransProt12", "TransMass")
+               for f in ("sw100K1.fsa", "extra/protein_specials.faa")
+               if (m, f) != ("TransMass", "extra/protein_specials.faa")]
+SMAP_CASES += [("Transab", "extra/ab_wildcards.fa")]
 LOSSLESS_FILES = ["Atinsert.fna", "Duplicate.fna", "RandomN.fna", "TTTN.fna", "Reads1.fna",
                   "extra/lowercase_iupac.fna", "extra/lowercase_across_records.fna",
                   "extra/long_runs.fna", "extra/protein_specials.faa", "sw100K1.fsa",

@@ -61,14 +61,16 @@ def key(name, opts, mkindex=False, sprank=False, direction=None):
         ("|dir=" + direction if direction else "")
 
 
-def run_case(tmp, name, protein, opts, mkindex=False, sprank=False, direction=None):
+def run_case(tmp, name, protein, opts, mkindex=False, sprank=False, direction=None, smap=None):
     src = os.path.join(OUT, "fixtures", name) if not name.startswith("extra/") \
         else os.path.join(OUT, name)
     idx = os.path.join(tmp, "idx")
     for f in os.listdir(tmp):
         os.unlink(os.path.join(tmp, f))
     # (a mkindex run takes the direction itself: the encoded sequence is stored forward)
-    subprocess.run([SFX, "-protein" if protein else "-dna", "-suf", "-bwt", "-db", src,
+    alpha = ["-smap", os.path.join(OUT, "extra", smap)] if smap else \
+        ["-protein" if protein else "-dna"]
+    subprocess.run([SFX] + alpha + ["-suf", "-bwt", "-db", src,
                     "-indexname", idx] + (["-dir", direction] if direction and not mkindex else []),
                    check=True, stdout=subprocess.DEVNULL)
     b, k, f, bm = opts
@@ -180,6 +182,27 @@ def main():
     with open(os.path.join(OUT, "golden_pck.json"), "w") as f:
         json.dump(golden, f, indent=1, sort_keys=True)
     print("%d packed-index goldens" % len(golden))
+    smap_main()
+
+
+# symbol maps (-smap, tests/golden/extra/): alphabets of 2 and 8 letters, in a file
+# of their own -- the readers of golden_pck.json encode every key without a map.
+# Keys "map|" + the key of golden_pck.json.
+SMAP_PCK = [("TransProt2", "sw100K1.fsa"), ("TransProt8", "sw100K1.fsa")]
+SMAP_PCK_SETS = [((8, 8, 16, None), False), ((3, 5, 7, True), False), ((8, 8, 16, None), True),
+                 ((10, 8, 32, None), True)]
+
+
+def smap_main():
+    golden = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for smap, name in SMAP_PCK:
+            for opts, sp in SMAP_PCK_SETS:
+                golden[smap + "|" + key(name, opts, False, sp)] = \
+                    run_case(tmp, name, True, opts, False, sp, smap=smap)
+    with open(os.path.join(OUT, "golden_pck_smap.json"), "w") as f:
+        json.dump(golden, f, indent=1, sort_keys=True)
+    print("%d packed-index goldens over symbol maps" % len(golden))
 
 
 if __name__ == "__main__":

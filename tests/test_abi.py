@@ -57,11 +57,18 @@ def test_prefixlength_matches_reference_values():
 def test_prefixlength_matches_oracle_on_a_sweep():
     import oracle_util as ou
     lib, ora = _lib.load(), ou.lib()
-    for sigma in (4, 20):
+    for sigma in range(2, 29):
         for e in range(0, 36):
             for n in (1 << e, (1 << e) + 1, 3 * (1 << e) - 1):
                 assert lib.gtamd_recommended_prefixlength(sigma, n) == \
                     ora.ora_recommended_prefixlength(sigma, n), (sigma, n)
+    # where the recommended length crosses the key width (20 symbols of the 2-bit
+    # keys, 10 of the 5-bit ones) and the 5-bit MSD sort's limit of 9
+    for sigma, n, k in ((2, 67_108_847, 20), (2, 67_108_848, 21), (3, 1 << 28, 14),
+                        (5, 195_312_495, 9), (5, 195_312_496, 10),
+                        (5, 976_562_495, 10), (5, 976_562_496, 11), (28, 300_000_000, 5)):
+        assert ora.ora_recommended_prefixlength(sigma, n) == k, (sigma, n)
+        assert lib.gtamd_recommended_prefixlength(sigma, n) == k, (sigma, n)
 
 
 def test_no_cpu_fallback():

@@ -259,7 +259,7 @@ SMAP = __import__("json").load(open(os.path.join(ou.GOLDEN_DIR, "golden_smap.jso
 @pytest.mark.parametrize("key", sorted(SMAP))
 @pytest.mark.parametrize("encoder", ["device", "host"])
 def test_cli_symbol_map_alphabets(cli, key, encoder, tmp_path):
-    """-smap FILE (5- and 4-letter alphabets from tests/golden/extra/*.map): all
+    """-smap FILE (2- to 22-letter alphabets from tests/golden/extra/): all
     tables, the bucket table and the sequence-side files"""
     mapname, name = key.split("|")
     e = SMAP[key]
@@ -276,6 +276,15 @@ def test_cli_symbol_map_alphabets(cli, key, encoder, tmp_path):
     for ext, v in e["seqfiles"].items():
         with open(idx + "." + ext, "rb") as f:
             assert hashlib.md5(f.read()).hexdigest() == v["md5"], ext
+
+
+def test_cli_symbol_map_of_more_than_28_letters(cli, tmp_path):
+    """the reference's 36-letter map (gtdata/trans/TransAnum): exit status 1"""
+    anum = os.path.join(ou.GOLDEN_DIR, "extra", "TransAnum")
+    r = subprocess.run([cli, "-smap", anum, "-suf", "-indexname", str(tmp_path / "idx"), "-db",
+                        ou.fixture_path("sw100K1.fsa")], capture_output=True, text=True)
+    assert r.returncode == 1
+    assert "symbol map '%s' defines more than 28 letters" % anum in r.stderr
 
 
 REF_CHECK = os.path.join(os.path.dirname(_lib.HERE), "oracle", "_ref", "gt_ref_check")
@@ -395,6 +404,36 @@ def test_mergeesa_equals_suffixerator_over_all_files(cli, files, tmp_path):
     r = subprocess.run([cli, "mergeesa", "-indexname", str(tmp_path / "x"), "-ii"] + idx,
                        capture_output=True, text=True)
     assert r.returncode == 1 and "gt dev mergeesa: error: cannot open file" in r.stderr
+
+
+PCK_SMAP = __import__("json").load(open(os.path.join(ou.GOLDEN_DIR, "golden_pck_smap.json")))
+
+
+@pytest.mark.parametrize("mapname", sorted({k.split("|")[0] for k in PCK_SMAP}))
+def test_packedindex_trsuftab_over_a_symbol_map(cli, mapname, tmp_path):
+    """-smap (2 and 8 letters) -suf -bwt, then `gt packedindex trsuftab`: INDEX.bdx
+    equals the file the reference wrote (tests/golden/golden_pck_smap.json)"""
+    idx = str(tmp_path / "pidx")
+    keys = sorted(k for k in PCK_SMAP if k.split("|")[0] == mapname)
+    name = keys[0].split("|")[1]
+    subprocess.run([cli, "-smap", os.path.join(ou.GOLDEN_DIR, "extra", mapname), "-suf", "-bwt",
+                    "-indexname", idx, "-db", ou.fixture_path(name)], check=True)
+    for key in keys:
+        _, kw = ou.parse_pck_key(key.split("|", 1)[1])
+        args = ["-bsize", str(kw["bsize"]), "-blbuck", str(kw["blbuck"]), "-locfreq", str(kw["locfreq"])]
+        if kw["locbitmap"] is not None:
+            args += ["-locbitmap", "yes" if kw["locbitmap"] else "no"]
+        if kw.get("sprank"):
+            args += ["-sprank"]
+        if os.path.exists(idx + ".bdx"):
+            os.remove(idx + ".bdx")
+        r = subprocess.run([cli, "packedindex", "trsuftab"] + args + [idx],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, (key, r.stderr)
+        with open(idx + ".bdx", "rb") as f:
+            raw = f.read()
+        assert len(raw) == PCK_SMAP[key]["size"], key
+        assert hashlib.md5(raw).hexdigest() == PCK_SMAP[key]["md5"], key
 
 
 @pytest.mark.parametrize("name", ["Atinsert.fna", "Duplicate.fna", "sw100K2.fsa"])

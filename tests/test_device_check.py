@@ -5,6 +5,7 @@ of them checks -- an .lcp byte or .llv value off by one, a byte of 254 raised to
 duplicated .suf entry, a changed .bwt byte -- at table index 1, in the special
 tail, at the entry of position n and at random indices.  The full-size GPU tests
 rely on these checkers to be exact, not sampled."""
+import ctypes
 import functools
 
 import numpy as np
@@ -208,3 +209,73 @@ def test_changed_bwt_byte_is_rejected(name):
             if dc.check_bwt_exact(c["suf"], c["enc"], bwt)[0]:
                 accepted.append((i, b, v))
     assert not accepted
+
+
+# ---- check_esastats_exact: the .prj numbers at other alphabet sizes and prefix
+# lengths, beyond the key width (20 symbols of the 2-bit keys) included
+def _stats_text(sigma, seed):
+    """letters with dense wildcard runs and separators (many suffixes with fewer
+    letters than the prefix length in front of a special), long copies (.llv)"""
+    rng = np.random.default_rng(seed)
+    enc = rng.integers(0, sigma, 40_000).astype(np.uint8)
+    enc[rng.random(enc.size) < 0.01] = 254
+    for start in rng.integers(0, enc.size - 30, 60):
+        enc[start:start + rng.integers(1, 30)] = 254
+    enc[rng.random(enc.size) < 0.002] = 255
+    enc[20_000:21_000] = enc[5_000:6_000]
+    enc[30_000:30_600] = sigma - 1
+    return enc
+
+
+def _oracle_stats(enc, sigma, prefixlength):
+    t = ou.esa(enc, sigma)
+    st = ou.EsaStats()
+    ou.lib().ora_esastats_compute(ou._p(enc), enc.size, ou._p(t["suf"]), ou._p(t["lcpfull"]),
+                                  prefixlength, ctypes.byref(st))
+    return t, {name: int(getattr(st, name)) for name, _ in st._fields_}
+
+
+STATS_CASES = [(2, 0), (2, 1), (2, 20), (2, 21), (2, 40), (3, 14), (3, 21), (5, 9), (5, 11),
+               (12, 4), (28, 5), (28, 12)]
+
+
+@functools.lru_cache(maxsize=None)
+def _stats_case(sigma, prefixlength):
+    enc = _stats_text(sigma, 100 + sigma)
+    t, st = _oracle_stats(enc, sigma, prefixlength)
+    llv = torch.from_numpy(t["llv"].astype(np.int64).reshape(-1, 2))
+    args = (torch.from_numpy(t["suf"].astype(np.int64)), torch.from_numpy(enc),
+            torch.from_numpy(np.array(t["lcp"])), llv[:, 0].contiguous(), llv[:, 1].contiguous(),
+            prefixlength)
+    return args, st, t
+
+
+@pytest.mark.parametrize("sigma,prefixlength", STATS_CASES)
+def test_esastats_checker_accepts_the_oracle(sigma, prefixlength):
+    args, st, t = _stats_case(sigma, prefixlength)
+    assert st["largelcpvalues"] > 0
+    assert dc.check_esastats_exact(*args, st) == (True, "")
+
+
+@pytest.mark.parametrize("sigma,prefixlength", STATS_CASES)
+def test_esastats_off_by_one_is_rejected(sigma, prefixlength):
+    args, st, _ = _stats_case(sigma, prefixlength)
+    for name in ("longest", "largelcpvalues", "maxbranchdepth", "lcptabsum"):
+        for d in (1, -1):
+            bad = dict(st)
+            bad[name] += d
+            ok, msg = dc.check_esastats_exact(*args, bad)
+            assert not ok and msg.startswith(name), (name, d)
+
+
+@pytest.mark.parametrize("sigma,prefixlength", [c for c in STATS_CASES if c[1] > 1])
+def test_esastats_unmasked_sum_is_rejected(sigma, prefixlength):
+    """a sum that also counts entries with fewer than prefixlength letters in
+    front of a special -- all of them, or those one letter short (at prefix length
+    1 the two agree: a suffix that starts with a special has LCP 0)"""
+    args, st, t = _stats_case(sigma, prefixlength)
+    for k in (0, prefixlength - 1):
+        _, loose = _oracle_stats(args[1].numpy(), sigma, k)
+        assert loose["lcptabsum"] > st["lcptabsum"], k
+        ok, msg = dc.check_esastats_exact(*args, dict(st, lcptabsum=loose["lcptabsum"]))
+        assert not ok and msg.startswith("lcptabsum"), k

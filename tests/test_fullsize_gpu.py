@@ -540,3 +540,94 @@ def test_packed_index_beyond_2p32_positions(gpu):
             lambda first, count: suf[first:first + count].cpu().numpy().astype(np.uint64),
             nspecial, sample, count_prefix_below=10 ** 7)
         assert inf["var_bits"] > 1 << 32
+
+
+# ---------------------------------------------------------------------------
+# alphabets other than DNA and protein at the sizes where the prefix length, and
+# with it the path, changes: 2 and 3 letters through the DNA kernels, 5 letters on
+# either side of the 5-bit MSD sort's limit (prefixlength 9), 28 letters (largest
+# codes, LSD sort), and 2 and 5 letters on either side of the key width (20 and 10
+# symbols): beyond it lcptabsum and .bck read the text past the key
+# ---------------------------------------------------------------------------
+def _alphabet_text(sigma, n, seed, copies=False):
+    """i.i.d. letters (numpy, fixed seed) with wildcard runs, single wildcards and
+    separators; `copies`: 5 kb blocks copied elsewhere, ties far past the key"""
+    rng = np.random.default_rng(seed)
+    enc = rng.integers(0, sigma, n, dtype=np.uint8)
+    for p in rng.integers(0, n - 1000, n // 100_000):
+        enc[p:p + int(rng.integers(1, 1000))] = 254
+    enc[rng.integers(0, n, n // 50_000)] = 254
+    enc[rng.integers(0, n, n // 200_000)] = 255
+    if copies:
+        for src, dst in rng.integers(0, n - 5000, (400, 2)):
+            enc[dst:dst + 5000] = enc[src:src + 5000]
+    return torch.from_numpy(enc).to("cuda:0")
+
+
+ALPHABET_SIZES = [(2, 67_108_847, 20, True), (2, 67_108_848, 21, True), (3, 1 << 28, 14, False),
+                  (5, 195_312_495, 9, False), (5, 195_312_496, 10, False),
+                  (5, 976_562_496, 11, False), (28, 300_000_000, 5, False)]
+
+
+@pytest.mark.parametrize("sigma,n,prefixlength,copies", ALPHABET_SIZES,
+                         ids=["sigma%d_n%d" % (c[0], c[1]) for c in ALPHABET_SIZES])
+def test_alphabet_at_size_exact(gpu, monkeypatch, capfd, sigma, n, prefixlength, copies):
+    """every table and the .prj statistics exact on the device, the prefix length
+    the reference recommends, the first sort the size selects"""
+    import device_check as dc
+    assert ou.lib().ora_recommended_prefixlength(sigma, n) == prefixlength
+    N = n + 1
+    buf = _alphabet_text(sigma, n, 60 + sigma, copies)
+    monkeypatch.setenv("GTAMD_DEBUG", "1")
+    capfd.readouterr()
+    with esa.EsaEngine(n, sigma) as eng:
+        eng.set_sequence_device(buf.data_ptr(), n)
+        eng.run()
+        st = eng.stats()
+        msd = "msd sort" in capfd.readouterr().err
+        assert st["prefixlength"] == prefixlength
+        # the 5-bit MSD sort tells the prefix length from nine symbols' codes
+        assert msd == (sigma <= 4 or (sigma <= 20 and prefixlength <= 9))
+        sa, lcp, bwt, llv_idx, llv_val = _device_tables(eng, N)
+        if copies:
+            assert llv_idx.numel() > 0 and st["maxbranchdepth"] >= 5000
+        _check_tables(sa, buf, lcp, bwt, llv_idx, llv_val)
+        _check_tail_and_prj(sa, buf, lcp, llv_val, st)
+        ok, msg = dc.check_esastats_exact(sa, buf, lcp, llv_idx, llv_val, prefixlength, st)
+        assert ok, msg
+
+
+@pytest.mark.parametrize("sigma,n,k", [(2, 67_108_847, 20), (2, 67_108_848, 21),
+                                       (5, 976_562_496, 11)])
+def test_alphabet_bucket_table_at_size(gpu, sigma, n, k):
+    """-bck at the recommended prefix length on either side of the 2-bit key width
+    (20 symbols) and past the 5-bit one (10): base-sigma codes with clamped
+    padding, digits past the key from the text; left borders against counts of
+    the suffixes' padded k-codes on the device; the LSD sort's suffix table
+    (WANT_BCK turns the MSD sort off) exact"""
+    import device_check as dc
+    buf = _alphabet_text(sigma, n, 62, sigma == 2)
+    with esa.EsaEngine(n, sigma) as eng:
+        eng.set_sequence_device(buf.data_ptr(), n)
+        eng.run(esa.WANT_SUF | esa.WANT_BCK)
+        assert eng.stats()["prefixlength"] == k
+        leftborder = torch.from_numpy(eng.bcktab()[0].astype(np.int64)).to("cuda:0")
+        sa = dc.as_tensor(eng.device_pointer(esa.TAB_SUF), n + 1, "<i8")
+        rank, msg = dc.suffix_ranks(sa)
+        assert rank is not None, msg
+        ok, msg = dc.check_suffix_array_exact(sa, buf, rank)
+        assert ok, msg
+        del rank
+    # padded k-code of every suffix that starts with a letter
+    code = torch.zeros(n, dtype=torch.int64, device="cuda:0")
+    live = torch.ones(n, dtype=torch.bool, device="cuda:0")
+    for j in range(k):
+        d = torch.full((n,), 254, dtype=torch.uint8, device="cuda:0")
+        d[:n - j] = buf[j:]
+        live &= d < sigma
+        code = code * sigma + torch.where(live, d.to(torch.int64), torch.full_like(code, sigma - 1))
+    counts = torch.bincount(code[buf < sigma], minlength=sigma ** k)
+    want = torch.zeros(sigma ** k + 1, dtype=torch.int64, device="cuda:0")
+    want[1:] = torch.cumsum(counts, 0)
+    assert leftborder.numel() == want.numel()
+    assert bool((leftborder == want).all())

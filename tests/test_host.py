@@ -594,6 +594,10 @@ def test_symbol_map_errors(host, tmp_path):
     rc, msg = _run_tool(host, "-smap", os.path.join(ou.GOLDEN_DIR, "extra", "prot5.map"), "-dir",
                         "rcl", "-indexname", idx, "-db", ou.fixture_path("extra/protein_specials.faa"))
     assert rc == -1 and msg == "option -rcl only can be used for DNA alphabets"
+    # the reference's 36-letter map (gtdata/trans/TransAnum): more than the engine takes
+    anum = os.path.join(ou.GOLDEN_DIR, "extra", "TransAnum")
+    rc, msg = _run_tool(host, "-smap", anum, "-indexname", idx, "-db", src)
+    assert rc == -1 and msg == "symbol map '%s' defines more than 28 letters" % anum
 
 
 LOSSLESS = __import__("json").load(open(os.path.join(ou.GOLDEN_DIR, "golden_lossless.json")))

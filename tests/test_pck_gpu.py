@@ -81,6 +81,28 @@ def test_device_bdx_equals_oracle_on_synthetic(model, sigma, n, builder):
         _against_oracle(enc, sigma, builder, **kw)
 
 
+@pytest.mark.parametrize("sigma", [2, 3, 5, 8, 12, 21, 28])
+def test_device_bdx_equals_oracle_on_other_alphabets(sigma, builder):
+    """alphabet sizes of -smap maps (the reference's files pin 4 and 20 only):
+    2 and 3 letters sorted with the DNA keys, 21..28 without the MSD sort"""
+    rng = np.random.default_rng(40 + sigma)
+    enc = rng.integers(0, sigma, 120_000, dtype=np.uint8)
+    enc[rng.integers(0, enc.size, 600)] = 254
+    enc[rng.integers(0, enc.size, 40)] = 255
+    enc[5000:5070] = 254
+    enc[9000:9400] = sigma - 1
+    enc[20000:22000] = enc[30000:32000]
+    sets = [dict(), dict(bsize=3, locbitmap=True), dict(sprank=True)]
+    if sigma > 20:
+        # blocks of 8 over more than 20 letters: composition indices wider than the
+        # device builder packs (18 bits); 5 is the largest block size up to 28
+        with pytest.raises(esa.EsaError, match="needs wider indices"):
+            _against_oracle(enc, sigma, builder)
+        sets = [dict(bsize=5), dict(bsize=3, locbitmap=True), dict(bsize=5, sprank=True)]
+    for kw in sets:
+        _against_oracle(enc, sigma, builder, **kw)
+
+
 def test_geometries_and_bucket_borders(builder):
     """block sizes and bucket lengths that do not divide the tile, sequences
     that end on / just before / just behind a bucket border, buckets longer
