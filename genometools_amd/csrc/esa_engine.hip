@@ -3576,7 +3576,7 @@ static int msd_choose_cbits(u64 N, int cmax, const float *penalty) {
 }
 struct MsdWs {
   u32 *hist, *scanws, *tcnt, *tfirst, *dtcnt, *dtfirst, *startA, *startB, *F, *scan2, *counters,
-      *biglist, *giantlist, *crowdlist;
+      *biglist, *giantlist, *crowdlist, *bndA;
   MsTile *desc;
   MdTile *dtiles;
   u64 *firstkey, *lastkey;
@@ -3602,6 +3602,7 @@ static u64 msd_carve(u64 N, int cb, u8 *base, MsdWs *w) {
   w->dtcnt = b.take<u32>(MSD_PARENTS + 8);
   w->dtfirst = b.take<u32>(MSD_PARENTS + 8);
   w->startA = b.take<u32>(256 + 8);
+  w->bndA = b.take<u32>(256 * MSD_BLOCKS);
   w->startB = b.take<u32>(MSD_PARENTS + 8);
   w->F = b.take<u32>(w->nf + 8);
   w->scan2 = b.take<u32>(scan_workspace_words(w->nf + 1) + 64);
@@ -3616,17 +3617,20 @@ static u64 msd_carve(u64 N, int cb, u8 *base, MsdWs *w) {
 }
 
 // One level below A: parents pstart[0 .. np], digit = the top `cb` bits of the
-// key word.  prepare: tiles, histogram, scan, child starts (cstart, (np << cb)
-// + 1 entries); scatter: the move.
+// key word (kin, or the upper word of level A's u64 entries ein).  prepare: tiles,
+// histogram, scan, child starts (cstart, (np << cb) + 1 entries); scatter: the move.
 static int msd_level_prepare(gtamd_esa_ctx *c, const MsdWs &w, const u32 *pstart, u32 np, int cb,
-                             u32 tiles_ub, const u32 *kin, u32 *cstart) {
+                             u32 tiles_ub, const u32 *kin, const u64 *ein, u32 *cstart) {
   hipStream_t st = c->st;
   k_msd_tilecount<<<(np + 1 + 255) / 256, 256, 0, st>>>(pstart, 0, np, (u32) MS_TILE, w.tcnt);
   HIP_TRY(hipGetLastError());
   TRY(scan_u32(SCAN_SUM, w.tcnt, w.tfirst, (u64) np + 1, false, w.scan2, st));
   k_msd_tiledesc<<<(tiles_ub + 255) / 256, 256, 0, st>>>(pstart, w.tfirst, np, tiles_ub, w.desc);
   HIP_TRY(hipGetLastError());
-  k_msd_hist_lvl<<<tiles_ub + 1, MS_THREADS, 0, st>>>(kin, w.desc, tiles_ub, 32 - cb, w.hist);
+  if (ein != nullptr)
+    k_msd_hist_lvl<u64><<<tiles_ub + 1, MS_THREADS, 0, st>>>(ein, w.desc, tiles_ub, 32 - cb, w.hist);
+  else
+    k_msd_hist_lvl<u32><<<tiles_ub + 1, MS_THREADS, 0, st>>>(kin, w.desc, tiles_ub, 32 - cb, w.hist);
   HIP_TRY(hipGetLastError());
   TRY(radix_scan_tile_rows(w.hist, tiles_ub + 1, w.scanws, st));
   const u64 nchild = (u64) np << cb;
@@ -3665,11 +3669,15 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
   const u32 ntA = (u32) div_up(N, MS_TILE);
   const u32 last_valid = (u32) (N - (u64) (ntA - 1) * MS_TILE);
   const u64 pad = N + 8;
-  // buffer pairs: (k0, v0) and (k1, v1) as 32-bit keys and positions; the bytes
-  // of level A in the upper half of k1
+  // buffer pairs: (k0, v0) and (k1, v1) as 32-bit keys and positions.  Level A
+  // writes one u64 per entry to k0 (whole-table builds, esa_msd_blocks.h) or three
+  // arrays (part builds: ka, pa and the bytes in the upper half of k1)
   u32 *ka = c->k0.as<u32>(), *pa = c->v0.as<u32>();
   u32 *kb = c->k1.as<u32>(), *pb = c->v1.as<u32>();
   u8 *xa = c->k1.as<u8>() + pad * 4;
+  u64 *ea = c->k0.as<u64>();
+  const bool wide = src == nullptr;
+  const int lbits = msd_block_bits(N);
   // ---- level A
   if (src != nullptr)
     k_msd_hist_a_keys<<<ntA, MS_THREADS, 0, st>>>(src->ck, N, w.hist);
@@ -3679,23 +3687,30 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
     k_msd_hist_a<<<ntA, MS_THREADS, 0, st>>>(c->text, N, w.hist);
   HIP_TRY(hipGetLastError());
   TRY(radix_scan_tile_rows(w.hist, ntA, w.scanws, st));
-  k_msd_starts_a<<<1, 256, 0, st>>>(w.hist, (u32) N, w.startA);
+  k_msd_starts_a<<<wide ? MSD_BLOCKS : 1, 256, 0, st>>>(w.hist, (u32) N, ntA, lbits, w.startA,
+                                                         wide ? w.bndA : nullptr);
   HIP_TRY(hipGetLastError());
   if (src != nullptr)
     k_msd_scatter_a<1><<<((ntA + 7u) >> 3) * 8u, MS_THREADS, 0, st>>>(
-        c->text, N, last_valid, w.hist, ntA, src->ck, src->cp32, ka, xa, pa);
+        c->text, N, last_valid, w.hist, ntA, src->ck, src->cp32, ka, xa, pa, nullptr);
   else if (FMT == 1)
     k_msd_scatter_a<2><<<((ntA + 7u) >> 3) * 8u, MS_THREADS, 0, st>>>(
-        c->text, N, last_valid, w.hist, ntA, nullptr, nullptr, ka, xa, pa);
+        c->text, N, last_valid, w.hist, ntA, nullptr, nullptr, nullptr, nullptr, nullptr, ea);
   else
     k_msd_scatter_a<0><<<((ntA + 7u) >> 3) * 8u, MS_THREADS, 0, st>>>(
-        c->text, N, last_valid, w.hist, ntA, nullptr, nullptr, ka, xa, pa);
+        c->text, N, last_valid, w.hist, ntA, nullptr, nullptr, nullptr, nullptr, nullptr, ea);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev[1], st));
-  // ---- level B: (ka, xa, pa) -> (kb, pb)
-  TRY(msd_level_prepare(c, w, w.startA, 256, 8, w.tilesB_ub, ka, w.startB));
-  k_msd_scatter_lvl<1><<<((w.tilesB_ub + 7u) >> 3) * 8u, MS_THREADS, 0, st>>>(
-      ka, xa, pa, w.desc, w.tilesB_ub, w.hist, w.tfirst, w.startB, 8, 24, kb, pb);
+  // ---- level B: ea, or (ka, xa, pa) -> (kb, pb)
+  TRY(msd_level_prepare(c, w, w.startA, 256, 8, w.tilesB_ub, ka, wide ? ea : nullptr, w.startB));
+  if (wide)
+    k_msd_scatter_lvl<1, true><<<((w.tilesB_ub + 7u) >> 3) * 8u, MS_THREADS, 0, st>>>(
+        nullptr, nullptr, nullptr, ea, w.bndA, lbits, w.desc, w.tilesB_ub, w.hist, w.tfirst,
+        w.startB, 8, 24, kb, pb);
+  else
+    k_msd_scatter_lvl<1, false><<<((w.tilesB_ub + 7u) >> 3) * 8u, MS_THREADS, 0, st>>>(
+        ka, xa, pa, nullptr, nullptr, 0, w.desc, w.tilesB_ub, w.hist, w.tfirst, w.startB, 8, 24,
+        kb, pb);
   HIP_TRY(hipGetLastError());
   if (sw.msd_cbits < 0 && cmax >= 1) {
     // how deep level C has to cut, from the ranges level B leaves (the host
@@ -3714,7 +3729,7 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
   u32 *kf = kb, *pf = pb, *ko = ka, *po = pa;   // (kf, pf): where the finest level ends up
   const u32 *F = w.startB;
   if (cb > 0) {
-    TRY(msd_level_prepare(c, w, w.startB, MSD_PARENTS, cb, w.tilesC_ub, kb, w.F));
+    TRY(msd_level_prepare(c, w, w.startB, MSD_PARENTS, cb, w.tilesC_ub, kb, nullptr, w.F));
     F = w.F;
     kf = ka; pf = pa; ko = kb; po = pb;
   }
@@ -3759,8 +3774,9 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
       HIP_TRY(hipMemcpy(&giants[i], w.dtiles + giant_t[i], sizeof(MdTile), hipMemcpyDeviceToHost));
   }
   if (cb > 0) {
-    k_msd_scatter_lvl<2><<<((w.tilesC_ub + 7u) >> 3) * 8u, MS_THREADS, 0, st>>>(
-        kb, nullptr, pb, w.desc, w.tilesC_ub, w.hist, w.tfirst, w.F, cb, 32 - cb, ka, pa);
+    k_msd_scatter_lvl<2, false><<<((w.tilesC_ub + 7u) >> 3) * 8u, MS_THREADS, 0, st>>>(
+        kb, nullptr, pb, nullptr, nullptr, 0, w.desc, w.tilesC_ub, w.hist, w.tfirst, w.F, cb,
+        32 - cb, ka, pa);
     HIP_TRY(hipGetLastError());
   }
   // ---- level D

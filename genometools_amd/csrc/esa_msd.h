@@ -10,17 +10,19 @@
 // implied by where the entry lies, so it need not be carried:
 //
 //   level A  (fused with the keygen, text order)   digit = symbols 0..3
-//            writes  K1 = symbols 4..19 (u32), X = dcode | payload (u8), P (u32)  27 GB
+//            writes  K1 = symbols 4..19, X = dcode | payload, the low 24 bits
+//            of P as one u64 (esa_msd_blocks.h: level B restores the rest)    24 GB
 //   level B  inside each of the 256 ranges         digit = symbols 4..7
-//            writes  K2 = symbols 8..19 | X (u32), P                             12 + 27 + 24 GB
+//            writes  K2 = symbols 8..19 | X (u32), P                             24 + 24 + 24 GB
 //   level C  inside each of the 65536 ranges       digit = the next `cbits` bits
 //            writes  K2, P                                                       12 + 24 + 24 GB
 //   level D  one workgroup per run of whole ranges (<= 4096 entries): stable
 //            LSD sort of the rest of K2 in LDS, then .suf/.lcp/.bwt, the tie
 //            bitmap and the statistics straight from LDS                         24 + 42 GB
 //
-// 216 GB.  Levels A-C are stable partitions (per-tile histogram, column scan,
-// ballot-ranked scatter: the LSD sort's machinery), so entries with equal keys
+// 213 GB.  (Part builds, whose values are not text positions, keep level A's
+// three arrays K1 u32, X u8, P u32.)  Levels A-C are stable partitions (per-tile
+// histogram, column scan, ballot-ranked scatter: the LSD sort's machinery), so entries with equal keys
 // stay in text order, which the order of suffixes that run into a special
 // relies on (esa_common.h).  The levels below A work on ragged tiles: a tile
 // never straddles two parent ranges, a parent range of s entries has
@@ -33,6 +35,7 @@
 // key; poly-A; two-letter texts) by the device-wide LSD sort on the 29 bits that
 // are left, run by run, followed by k_msd_emit_run.
 #pragma once
+#include "esa_msd_blocks.h"
 
 constexpr int MS_TILE = 4096;
 constexpr int MS_THREADS = 512;
@@ -635,29 +638,50 @@ __global__ __launch_bounds__(256) void k_part_positions(const u32 *__restrict__ 
   if (p == 0) stats->longest = index_offset + i;
 }
 
-// starts of the 256 level-A ranges: row 0 of the scanned histogram
-__global__ void k_msd_starts_a(const u32 *__restrict__ scanned, u32 N, u32 *__restrict__ start) {
-  const u32 d = threadIdx.x;
-  if (d < 256) start[d] = scanned[d];
-  if (d == 0) start[256] = N;
+// starts of the 256 level-A ranges: row 0 of the scanned histogram (workgroup 0);
+// bnd != nullptr: also the block boundaries of esa_msd_blocks.h, one workgroup per
+// block k: bnd[d * 256 + k] = row (k << (L - 12)) of the scanned histogram, for the
+// blocks behind the text the end of parent d (a boundary no entry of d reaches).
+// Level B's preparation writes over the histogram, so they are copied out here.
+__global__ __launch_bounds__(256) void k_msd_starts_a(const u32 *__restrict__ scanned, u32 N,
+                                                      u32 ntiles, int L, u32 *__restrict__ start,
+                                                      u32 *__restrict__ bnd) {
+  const u32 d = threadIdx.x, k = blockIdx.x;
+  if (k == 0) {
+    start[d] = scanned[d];
+    if (d == 0) start[256] = N;
+  }
+  if (bnd != nullptr) {
+    const u32 t = k << (L - 12);
+    const u32 end = d < 255u ? scanned[d + 1] : N;
+    bnd[d * MSD_BLOCKS + k] = t < ntiles ? scanned[(u64) t * 256 + d] : end;
+  }
 }
 
 // SRC 0: all suffixes of a 2-bit text; SRC 1 (FROMKEYS): the entries are the keys a
 // part build has filtered from the text (ck, their values cp32 or -- nullptr --
 // their numbers); SRC 2: all suffixes of a 5-bit text, by their FMT 1 codes (as
-// "keys" code << 24 | payload: level-A digit and K1 lie where Key<2> has them)
+// "keys" code << 24 | payload: level-A digit and K1 lie where Key<2> has them).
+// SRC 0 and 2 write one u64 per entry to eout, K1 << 32 | X << 24 | position &
+// 0xFFFFFF (esa_msd_blocks.h); SRC 1 three arrays, K1 to k1out, X to xout, the
+// value to pout.  (What the kernel is bound by: its store requests, a run of ~16
+// entries per digit and tile that starts inside a line, per array.  At 3 Gbp
+// scale: the three arrays' pattern alone 15.8 ms, the one u64 array's 11.3 ms --
+// tools/microbench/levela.hip.)
 template <int SRC>
 __global__ __launch_bounds__(MS_THREADS) void k_msd_scatter_a(
     Text t, u64 N, u32 last_valid, const u32 *__restrict__ scanned, u32 ntiles,
     const u64 *__restrict__ ck, const u32 *__restrict__ cp32,
-    u32 *__restrict__ k1out, u8 *__restrict__ xout, u32 *__restrict__ pout) {
+    u32 *__restrict__ k1out, u8 *__restrict__ xout, u32 *__restrict__ pout,
+    u64 *__restrict__ eout) {
   // 40 KB: first the keys in (suffix of the thread, thread) order, padded
   // against bank conflicts; then the staging area in digit order
   __shared__ u64 s_t[5120];
   __shared__ u16 s_cnt_mem[MS_WAVES * 256];
   __shared__ u32 s_obase[256];
   __shared__ u32 s_scan[MS_WAVES];
-  static_assert(KP_PER * MS_PAD <= 5120 && MS_TILE * 10 <= 5120 * 8, "staging fits");
+  static_assert(KP_PER * MS_PAD <= 5120 && MS_TILE * 10 <= 5120 * 8 && MS_TILE * 9 <= 5120 * 8,
+                "staging fits");
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const u32 tile = ms_xcd_tile(blockIdx.x, ntiles);
   if (tile >= ntiles) return;
@@ -735,6 +759,26 @@ __global__ __launch_bounds__(MS_THREADS) void k_msd_scatter_a(
     }
   }
   __syncthreads();
+  if (!FROMKEYS) {
+    u8 *s_d = reinterpret_cast<u8 *>(s_t + MS_TILE);
+#pragma unroll
+    for (int j = 0; j < MS_ITEMS; j++) {
+      const u32 e = (u32) w * MS_WCHUNK + (u32) j * 64 + lane;
+      const u32 d = rk[j] & 255u;
+      const u32 pos = (u32) cnt_w[d] + (rk[j] >> 8);
+      const u32 x = SRC == 2 ? (u32) key[j] & 63u
+                             : (((u32) (key[j] >> 19) & 31u) << 3) | ((u32) key[j] & 7u);
+      s_t[pos] = ((key[j] >> 24) << 32) | ((u64) x << 24) | (u64) (((u32) tile_base + e) & 0xFFFFFFu);
+      s_d[pos] = (u8) d;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < MS_ITEMS; j++) {
+      const u32 e = (u32) j * MS_THREADS + tid;
+      if (e < valid) eout[s_obase[s_d[e]] + e] = s_t[e];
+    }
+    return;
+  }
   u32 *s_k1 = reinterpret_cast<u32 *>(s_t);
   u32 *s_p = s_k1 + MS_TILE;
   u8 *s_x = reinterpret_cast<u8 *>(s_p + MS_TILE);
@@ -806,10 +850,18 @@ __global__ __launch_bounds__(256) void k_msd_tiledesc(const u32 *__restrict__ ps
   desc[t] = d;
 }
 
-// row t: counts of the digit  key >> dsh  over tile t; rows >= tiles_ub are zero
+// row t: counts of the digit  key >> dsh  over tile t; rows >= tiles_ub are zero.
+// KT u32: the keys; u64: level A's entries, the key their upper word
+template <typename KT>
+__device__ __forceinline__ u32 ms_hist_key(KT k) {
+  return sizeof(KT) == 8 ? (u32) ((u64) k >> 32) : (u32) k;
+}
+template <typename KT>
 __global__ __launch_bounds__(MS_THREADS) void k_msd_hist_lvl(
-    const u32 *__restrict__ keys, const MsTile *__restrict__ desc, u32 tiles_ub, int dsh,
+    const KT *__restrict__ keys, const MsTile *__restrict__ desc, u32 tiles_ub, int dsh,
     u32 *__restrict__ hist) {
+  constexpr u32 PER = 16 / sizeof(KT);                      // entries per 16-byte load
+  constexpr int NLD = MS_TILE / (int) PER / MS_THREADS;     // loads per thread
   __shared__ u32 h[MS_WAVES][256];
   const int tid = threadIdx.x, w = tid >> 6;
   for (int i = tid; i < MS_WAVES * 256; i += MS_THREADS) (&h[0][0])[i] = 0;
@@ -818,28 +870,30 @@ __global__ __launch_bounds__(MS_THREADS) void k_msd_hist_lvl(
   if (t < tiles_ub) {
     const MsTile d = desc[t];
     const u32 valid = d.segvalid & 0x1FFFu;
-    // 16-byte loads from the first entry whose index is a multiple of four (the
-    // order inside the tile does not matter to a histogram); the up to three
-    // entries in front of it and behind the last whole quad one by one
-    u32 head = (4u - (d.start & 3u)) & 3u;
+    // 16-byte loads from the first entry whose index is a multiple of PER (the
+    // order inside the tile does not matter to a histogram); the entries in front
+    // of it and behind the last whole load one by one
+    u32 head = (PER - (d.start & (PER - 1u))) & (PER - 1u);
     head = head < valid ? head : valid;
-    const u32 nq = (valid - head) >> 2, tail = valid - head - 4u * nq;
-    const u32 *kp = keys + d.start;
-    uint4 q[2];
+    const u32 nq = (valid - head) / PER, tail = valid - head - PER * nq;
+    const KT *kp = keys + d.start;
+    uint4 q[NLD];
 #pragma unroll
-    for (int j = 0; j < 2; j++) {
+    for (int j = 0; j < NLD; j++) {
       const u32 i = (u32) j * MS_THREADS + tid;
-      if (i < nq) q[j] = *reinterpret_cast<const uint4 *>(kp + head + 4u * i);
+      if (i < nq) q[j] = *reinterpret_cast<const uint4 *>(kp + head + PER * i);
     }
-    if ((u32) tid < head) atomicAdd(&h[w][kp[tid] >> dsh], 1u);
-    if ((u32) tid < tail) atomicAdd(&h[w][kp[head + 4u * nq + tid] >> dsh], 1u);
+    if ((u32) tid < head) atomicAdd(&h[w][ms_hist_key(kp[tid]) >> dsh], 1u);
+    if ((u32) tid < tail) atomicAdd(&h[w][ms_hist_key(kp[head + PER * nq + tid]) >> dsh], 1u);
 #pragma unroll
-    for (int j = 0; j < 2; j++) {
+    for (int j = 0; j < NLD; j++) {
       const u32 i = (u32) j * MS_THREADS + tid;
       if (i < nq) {
-        atomicAdd(&h[w][q[j].x >> dsh], 1u);
+        if (PER == 4) {
+          atomicAdd(&h[w][q[j].x >> dsh], 1u);
+          atomicAdd(&h[w][q[j].z >> dsh], 1u);
+        }
         atomicAdd(&h[w][q[j].y >> dsh], 1u);
-        atomicAdd(&h[w][q[j].z >> dsh], 1u);
         atomicAdd(&h[w][q[j].w >> dsh], 1u);
       }
     }
@@ -866,20 +920,26 @@ __global__ __launch_bounds__(256) void k_msd_tot(const u32 *__restrict__ scanned
   tot[i] = scanned[(u64) tfirst[s + 1] * 256 + d] - scanned[(u64) tfirst[s] * 256 + d];
 }
 
-// LEVEL 1 (B): (K1, X, P) -> (K2 = K1 << 8 | X, P), digit K1 >> 24
+// LEVEL 1 (B): (K1, X, P) -> (K2 = K1 << 8 | X, P), digit K1 >> 24; WIDE: level A's
+// entries are one u64 each (ein), the position's upper bits come from the block
+// boundaries bnd of esa_msd_blocks.h (blocks of 2^lbits positions)
 // LEVEL 2 (C): (K2, P) -> (K2, P), digit K2 >> dsh
-template <int LEVEL>
+template <int LEVEL, bool WIDE>
 __global__ __launch_bounds__(MS_THREADS) void k_msd_scatter_lvl(
     const u32 *__restrict__ kin, const u8 *__restrict__ xin, const u32 *__restrict__ pin,
+    const u64 *__restrict__ ein, const u32 *__restrict__ bnd, int lbits,
     const MsTile *__restrict__ desc, u32 tiles_ub, const u32 *__restrict__ scanned,
     const u32 *__restrict__ tfirst, const u32 *__restrict__ cstart, int cb, int dsh,
     u32 *__restrict__ kout, u32 *__restrict__ pout) {
+  static_assert(!WIDE || LEVEL == 1, "only level A writes the u64 entries");
   __shared__ u32 s_key[MS_TILE];
   __shared__ u32 s_val[MS_TILE];
   __shared__ u8 s_x[LEVEL == 1 ? MS_TILE : 4];
   __shared__ u16 s_cnt_mem[MS_WAVES * 256];
   __shared__ u32 s_obase[256];
   __shared__ u32 s_scan[MS_WAVES];
+  __shared__ u32 s_in[WIDE ? MSD_BLOCKS : 1];     // block boundaries inside the tile
+  __shared__ u32 s_bcnt[WIDE ? 8 : 1];            // per wave: boundaries before it, inside it
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const u32 tile = ms_xcd_tile(blockIdx.x, tiles_ub);
   if (tile >= tiles_ub) return;
@@ -888,6 +948,9 @@ __global__ __launch_bounds__(MS_THREADS) void k_msd_scatter_lvl(
   if (valid == 0) return;
   for (int i = tid; i < MS_WAVES * 256 / 2; i += MS_THREADS)
     reinterpret_cast<u32 *>(s_cnt_mem)[i] = 0;
+  // WIDE: boundary k of the parent, loaded by thread k (k = 1 .. 255, waves 0-3)
+  u32 bk = 0;
+  if (WIDE && tid >= 1 && tid < MSD_BLOCKS) bk = bnd[seg * MSD_BLOCKS + tid];
   // where this tile's entries of digit d go: start of child (seg, d) + what the
   // tiles of the parent in front of this one hold of d
   u32 gbase = 0;
@@ -895,20 +958,48 @@ __global__ __launch_bounds__(MS_THREADS) void k_msd_scatter_lvl(
     gbase = cstart[((u64) seg << cb) + tid] + scanned[(u64) tile * 256 + tid] -
             scanned[(u64) tfirst[seg] * 256 + tid];
   u32 key[MS_ITEMS], val[MS_ITEMS], xv[MS_ITEMS], rk[MS_ITEMS];
-  const u32 *kp = kin + td.start;
-  const u32 *pp = pin + td.start;
-  const u8 *xp = xin + td.start;
+  if (WIDE) {
+    // (the entries as loaded, taken apart behind the loop: taken apart inside the
+    // branch, each load waits for the one before it)
+    u64 en[MS_ITEMS];
 #pragma unroll
-  for (int j = 0; j < MS_ITEMS; j++) {
-    const u32 e = (u32) w * MS_WCHUNK + (u32) j * 64 + lane;
-    if (e < valid) {
-      key[j] = kp[e];
-      val[j] = pp[e];
-      xv[j] = LEVEL == 1 ? (u32) xp[e] : 0u;
-    } else {
-      key[j] = ~0u;
-      val[j] = 0;
-      xv[j] = 0;
+    for (int j = 0; j < MS_ITEMS; j++) {
+      const u32 e = (u32) w * MS_WCHUNK + (u32) j * 64 + lane;
+      en[j] = e < valid ? ein[td.start + e] : ~0ull << 32;
+    }
+#pragma unroll
+    for (int j = 0; j < MS_ITEMS; j++) {
+      key[j] = (u32) (en[j] >> 32);
+      xv[j] = (u32) (en[j] >> 24) & 255u;
+      val[j] = (u32) en[j] & 0xFFFFFFu;          // the position's low 24 bits, for now
+    }
+  } else {
+    const u32 *kp = kin + td.start;
+    const u32 *pp = pin + td.start;
+    const u8 *xp = xin + td.start;
+#pragma unroll
+    for (int j = 0; j < MS_ITEMS; j++) {
+      const u32 e = (u32) w * MS_WCHUNK + (u32) j * 64 + lane;
+      if (e < valid) {
+        key[j] = kp[e];
+        val[j] = pp[e];
+        xv[j] = LEVEL == 1 ? (u32) xp[e] : 0u;
+      } else {
+        key[j] = ~0u;
+        val[j] = 0;
+        xv[j] = 0;
+      }
+    }
+  }
+  // WIDE: how many boundaries lie at or before the tile's first entry, how many
+  // inside it (looked at once the entries' loads are out)
+  u32 bcls = 0;
+  if (WIDE) {
+    if (tid >= 1 && tid < MSD_BLOCKS) bcls = msd_bound_class(bk, td.start, valid);
+    const u64 b1 = __ballot(bcls == 1u), b2 = __ballot(bcls == 2u);
+    if (lane == 0 && w < MSD_BLOCKS / 64) {
+      s_bcnt[2 * w] = (u32) __popcll(b1);
+      s_bcnt[2 * w + 1] = (u32) __popcll(b2);
     }
   }
   __syncthreads();   // counters are zero
@@ -922,6 +1013,18 @@ __global__ __launch_bounds__(MS_THREADS) void k_msd_scatter_lvl(
     const u32 old = cnt_w[d];
     if (intra == 0) cnt_w[d] = (u16) (old + group);
     rk[j] = ((old + intra) << 8) | d;
+  }
+  // WIDE: the tile's first block (kb0) and the boundaries inside it, to LDS in
+  // order (a row is nondecreasing: boundary k is the (k - 1 - kb0)-th inside)
+  u32 kb0 = 0, nin = 0;
+  if (WIDE) {
+#pragma unroll
+    for (int i = 0; i < MSD_BLOCKS / 64; i++) {
+      kb0 += s_bcnt[2 * i];
+      nin += s_bcnt[2 * i + 1];
+    }
+    const u32 at = (u32) tid - 1u - kb0;
+    if (bcls == 2u && at < (u32) MSD_BLOCKS) s_in[at] = bk - td.start;
   }
   __syncthreads();
   {
@@ -951,6 +1054,11 @@ __global__ __launch_bounds__(MS_THREADS) void k_msd_scatter_lvl(
   for (int j = 0; j < MS_ITEMS; j++) {
     const u32 d = rk[j] & 255u;
     const u32 pos = (u32) cnt_w[d] + (rk[j] >> 8);
+    if (WIDE) {
+      const u32 e = (u32) w * MS_WCHUNK + (u32) j * 64 + lane;
+      const u32 blk = nin == 0 ? kb0 : msd_block_in_tile(kb0, s_in, nin, e);
+      val[j] = msd_position(blk, val[j], lbits);
+    }
     s_key[pos] = key[j];
     s_val[pos] = val[j];
     if (LEVEL == 1) s_x[pos] = (u8) xv[j];

@@ -288,7 +288,8 @@ __global__ void k_checksum(const u32 *k1, const u32 *p, const u8 *x, u64 N, unsi
 
 // ---- the output pattern alone: tiles of TILE entries, every tile a run of TILE/256 entries in
 // each of 256 bins (uniform digits), written as MODE 0: u32 + u32 + u8 arrays, 1: u64 + u8,
-// 2: u32 + u32 only, 3: u64 only
+// 2: u32 + u32 only, 3: u64 only; MODE 4-6 the same as 0, 3 and 2 with every run starting
+// (bin * 7) % 16 entries into its line (what the engine's tiles write)
 template <int TILE, int MODE>
 __global__ __launch_bounds__(512) void k_pattern(u32 ntiles, u32 *__restrict__ a, u32 *__restrict__ b,
                                                  u8 *__restrict__ x, u64 binsize) {
@@ -299,9 +300,9 @@ __global__ __launch_bounds__(512) void k_pattern(u32 ntiles, u32 *__restrict__ a
   for (int j = 0; j < TILE / 512; j++) {
     const u32 e = (u32) j * 512 + threadIdx.x;
     const u64 g = (u64) (e / RUN) * binsize + (u64) tile * RUN + (e % RUN) + (MODE >= 4 ? ((e / RUN) * 7u) % 16u : 0u);
-    if (MODE == 0 || MODE == 2 || MODE == 4) { a[g] = e; b[g] = tile; }
+    if (MODE == 0 || MODE == 2 || MODE == 4 || MODE == 6) { a[g] = e; b[g] = tile; }
     if (MODE == 4) x[g] = (u8) e;
-    if (MODE == 1 || MODE == 3) reinterpret_cast<u64 *>(a)[g] = ((u64) e << 32) | tile;
+    if (MODE == 1 || MODE == 3 || MODE == 5) reinterpret_cast<u64 *>(a)[g] = ((u64) e << 32) | tile;
     if (MODE == 0 || MODE == 1) x[g] = (u8) e;
   }
 }
@@ -714,6 +715,8 @@ int main() {
     auto pat = [&](const char *name, auto &&fn) { timeit(name, false, fn); };
     pat("pattern 4096: u32+u32+u8 (runs of 16)", [&] { k_pattern<4096, 0><<<(u32) (N / 4096), 512>>>((u32) (N / 4096), ab, ab + N, x, N / 256); });
     pat("pattern 4096: u32+u32+u8, runs not aligned", [&] { k_pattern<4096, 4><<<(u32) (N / 4096), 512>>>((u32) (N / 4096), ab, ab + N + 64, x, N / 256); });
+    pat("pattern 4096: u64, runs not aligned", [&] { k_pattern<4096, 5><<<(u32) (N / 4096), 512>>>((u32) (N / 4096), ab, ab + N, x, N / 256); });
+    pat("pattern 4096: u32+u32, runs not aligned", [&] { k_pattern<4096, 6><<<(u32) (N / 4096), 512>>>((u32) (N / 4096), ab, ab + N + 64, x, N / 256); });
     pat("pattern 8192: u32+u32+u8, runs not aligned", [&] { k_pattern<8192, 4><<<(u32) (N / 8192), 512>>>((u32) (N / 8192), ab, ab + N + 64, x, N / 256); });
     pat("write-combining pattern, 4 tiles a workgroup", [&] { k_pattern_wc<4><<<(u32) (N / 4096 / 4), 512>>>((u32) (N / 4096 / 4), ab, ab + N + 64, x, N / 256); });
     pat("write-combining pattern, 8 tiles a workgroup", [&] { k_pattern_wc<8><<<(u32) (N / 4096 / 8), 512>>>((u32) (N / 4096 / 8), ab, ab + N + 64, x, N / 256); });
