@@ -18,6 +18,11 @@ oracle's comparison sort cannot run at these sizes):
   and checked exactly.
 * the largest single build, SINGLE_LIMIT - 1 entries (k_win_filter's window
   bitmap in global memory), exactly; one entry more is refused.
+* the packed index (INDEX.bdx) of 10^9 and 3 * 10^9 human-like bases, of 10^9
+  protein residues in the largest block size the builder takes for 20 letters,
+  in a non-default geometry, and of made-up tables past 2^32 entries whose
+  counters and var offsets pass 2^32: every field of every bucket, the header
+  and the region list exact on the device (check_packed_index_exact).
 """
 import numpy as np
 import pytest
@@ -359,158 +364,109 @@ def test_single_build_at_the_32bit_limit(gpu):
     assert tables[4].numel() > 10 ** 7
 
 
-# ---- the packed index at a size the oracle cannot reach --------------------------
-def _bits(raw, pos, n):
-    """n bits at bit position pos of a byte string, most significant first"""
-    v = 0
-    for b in range(pos, pos + n):
-        v = (v << 1) | ((raw[b >> 3] >> (7 - (b & 7))) & 1)
-    return v
-
-
-def _unrank_block(comp, perm, sigma, B):
-    """the block with composition index `comp` and permutation index `perm`
-    (inverse of gt_block2IndexPair, src/match/eis-seqblocktranslate.c:436-540)"""
-    from math import comb, factorial
-    cnt, left = [], B
-    for i in range(sigma - 1):
-        k = sigma - i - 1
-        v = 0
-        while True:
-            ways = comb(left - v + k - 1, k - 1)
-            if comp < ways:
-                break
-            comp -= ways
-            v += 1
-        cnt.append(v)
-        left -= v
-    cnt.append(left)
-
-    def arrangements(c):
-        r = factorial(sum(c))
-        for x in c:
-            r //= factorial(x)
-        return r
-    out = []
-    for _ in range(B):
-        for s in range(sigma):
-            if cnt[s] == 0:
-                continue
-            cnt[s] -= 1
-            ways = arrangements(cnt)
-            if perm < ways:
-                out.append(s)
-                break
-            perm -= ways
-            cnt[s] += 1
-    return out, arrangements
-
-
-def _check_packed_index(builder, N, get_bwt, get_suf, nspecial, sample, count_prefix_below=0):
-    """header, sizes and sampled buckets of the image in `builder` (default options:
-    block size 8, 8 blocks per bucket, locate interval 16, marks as counts) against
-    the tables it was made from; get_bwt / get_suf(first, count) -> numpy"""
-    import struct
-    from math import comb
+# ---- the packed index at sizes the oracle cannot reach: every field of every bucket
+def _check_packed_index(builder, bwt, suf, sigma, what, **kw):
+    """check_packed_index_exact (tests/device_check.py) of the builder's image,
+    on the device, against the tables it was built from: header, every bucket's
+    counters, var offset, index bits, composition and permutation indices and
+    locate marks, the region list, the size.  Prints what it checked and the
+    time the check took."""
+    import time
+    import device_check as dc
     inf = builder.info()
-    B, K, L, sigma, locfreq = 8, 8, 64, 4, 16
-    assert inf["num_buckets"] == (N + 1 + L - 1) // L
-    header = builder.image(0, 8192).tobytes()
-    assert header[:4] == b"BDX\0"
-    voff, roff, seqlen = (struct.unpack_from("<Q", header, o)[0] for o in (28, 40, 52))
-    assert (voff, roff, seqlen) == (inf["var_data_pos"], inf["range_enc_pos"], N)
-    bits_ulong, vdob = struct.unpack_from("<I", header, 64)[0], struct.unpack_from("<I", header, 72)[0]
-    assert bits_ulong == (N - 1).bit_length()
-    cib = (comb(B + sigma - 1, sigma - 1) - 1).bit_length()
-    cbb = struct.unpack_from("<I", header, 84 + 4 * sigma + 32 + 4)[0]
-    cw_bits = sigma * bits_ulong + vdob + cbb + K * cib
-    assert cw_bits == inf["cw_bits"]
-    assert inf["file_bytes"] == roff + 8 + 16 * inf["num_regions"]
-    assert roff == voff + (inf["var_bits"] + 7) // 8
-    for j in sample:
-        rb = (j * cw_bits) // 8
-        cw = builder.image(inf["cw_data_pos"] + rb, cw_bits // 8 + 2).tobytes()
-        at = j * cw_bits - rb * 8
-        sums = [_bits(cw, at + s * bits_ulong, bits_ulong) for s in range(sigma)]
-        var_off = _bits(cw, at + sigma * bits_ulong, vdob)
-        pbits = _bits(cw, at + sigma * bits_ulong + vdob, cbb)
-        if j * L <= count_prefix_below:
-            before = get_bwt(0, j * L)
-            assert sums == [int(np.count_nonzero(before == s)) for s in range(sigma)], j
-        want = get_bwt(j * L, L)
-        vb = var_off // 8
-        var = builder.image(voff + vb, 1200).tobytes()
-        vat = var_off - vb * 8
-        used = 0
-        for b in range(K):
-            comp = _bits(cw, at + sigma * bits_ulong + vdob + cbb + b * cib, cib)
-            block, arrangements = _unrank_block(comp, 0, sigma, B)
-            ways = arrangements([block.count(s) for s in range(sigma)])
-            pb = (ways - 1).bit_length() if ways > 1 else 0
-            perm = _bits(var, vat + used, pb)
-            used += pb
-            block, _ = _unrank_block(comp, perm, sigma, B)
-            w = want[b * B:(b + 1) * B]
-            assert block == [int(x) if x < 254 else 0 for x in w], (j, b)
-        assert used == pbits, j
-        # locate marks (count mode): number, then (row in bucket, text position)
-        suf = get_suf(j * L, L)
-        nm = _bits(var, vat + used, 7)
-        used += 7
-        rows = np.arange(j * L, (j + 1) * L)
-        marked = [i for i in range(L) if int(suf[i]) % locfreq == 0 or
-                  bool(want[i] >= 254) != bool(rows[i] >= N - nspecial)]
-        assert nm == len(marked), j
-        for i in marked:
-            assert _bits(var, vat + used, 6) == i
-            assert _bits(var, vat + used + 6, bits_ulong) == int(suf[i]), (j, i)
-            used += 6 + bits_ulong
-    return inf, roff
+    img = dc.as_tensor(builder.device_pointer(), inf["file_bytes"], "|u1")
+    rep = {}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ok, msg = dc.check_packed_index_exact(img, bwt, suf, sigma, report=rep, **kw)
+    torch.cuda.synchronize()
+    print("%s: %d buckets checked in %.1f s; largest counter %d, largest var offset %d bits; "
+          "%d regions; image %.2f GB built in %.1f ms" % (
+              what, rep.get("buckets", -1), time.perf_counter() - t0, rep.get("max_counter", -1),
+              rep.get("max_var_offset", -1), rep.get("regions", -1), inf["file_bytes"] / 1e9,
+              inf["build_ms"]))
+    assert ok, msg
+    assert rep["buckets"] == inf["num_buckets"] and rep["regions"] == inf["num_regions"]
+    assert rep["var_bits"] == inf["var_bits"]
+    torch.cuda.empty_cache()
+    return rep
 
 
-def test_packed_index_of_a_1gbp_sequence_decodes_to_the_bwt(gpu):
-    """INDEX.bdx of 10^9 bases (human-like model: wildcard runs, separators), built
-    from the resident tables: sampled buckets decode -- occurrence counters,
-    composition and permutation index of every block, locate marks -- to the .bwt
-    and .suf tables the image was made from; the region list is the list of the
-    runs of specials in the BWT; sizes add up"""
-    import struct
+def _esa_bwt_suf(eng, N):
+    import device_check as dc
+    return (dc.as_tensor(eng.device_pointer(esa.TAB_BWT), N, "|u1"),
+            dc.as_tensor(eng.device_pointer(esa.TAB_SUF), N, "<i8"))
+
+
+def _packed_index_of(model, seed, n, sigma, what, **kw):
+    """INDEX.bdx of n symbols of a model, built from the resident tables and
+    checked exactly; returns the check's report"""
     from genometools_amd import pck
-    n = 1000 * 1000 * 1000
-    buf = _device_sequence(synth.MODEL_HUMANLIKE_DNA, 43, n)
-    with esa.EsaEngine(n, 4) as eng, pck.PackedIndex() as builder:
+    buf = _device_sequence(model, seed, n)
+    with esa.EsaEngine(n, sigma) as eng, pck.PackedIndex() as builder:
         eng.set_sequence_device(buf.data_ptr(), n)
         del buf
         eng.run(esa.WANT_SUF | esa.WANT_BWT)
-        builder.build_from_esa(eng)
-        bwt = eng.table(esa.TAB_BWT)
-        N = n + 1
-        special = bwt >= 254
-        rng = np.random.default_rng(9)
-        nb = (N + 1 + 63) // 64
-        sample = sorted(set(int(x) for x in rng.integers(0, nb - 1, 300)) |
-                        {0, 1, 100, 5000, 200000, nb - 2})
-        inf, roff = _check_packed_index(
-            builder, N, lambda first, count: bwt[first:first + count],
-            lambda first, count: eng.table(esa.TAB_SUF, first, count),
-            int(np.count_nonzero(special)), sample, count_prefix_below=5 * 10 ** 7)
-        # region list == runs of specials in the BWT
-        change = np.flatnonzero(np.diff(bwt.astype(np.int16)) != 0) + 1
-        starts = np.concatenate(([0], change))
-        starts = starts[special[starts]]
-        regions = builder.image(roff, 8 + 16 * inf["num_regions"]).tobytes()
-        assert struct.unpack_from("<Q", regions, 0)[0] == inf["num_regions"] == starts.size + 1
-        rec = np.frombuffer(regions, dtype=np.uint64, offset=8).reshape(-1, 2)
-        assert np.array_equal(rec[:-1, 0], starts.astype(np.uint64))
-        assert int(rec[-1, 0]) == N + 8
+        builder.build_from_esa(eng, **kw)
+        return _check_packed_index(builder, *_esa_bwt_suf(eng, n + 1), sigma, what, **kw)
+
+
+def test_packed_index_of_a_1gbp_sequence_decodes_to_the_bwt(gpu):
+    """INDEX.bdx of 10^9 bases (human-like model: wildcard runs, separators) with
+    the default options, built from the resident tables: every one of the 15.6 M
+    buckets decodes -- occurrence counters, var offset, composition and
+    permutation index of every block, locate marks -- to the .bwt and .suf tables
+    the image was made from; the region list is the list of the runs of specials
+    in the BWT; sizes add up"""
+    rep = _packed_index_of(synth.MODEL_HUMANLIKE_DNA, 43, 10 ** 9, 4, "1 Gbp human-like")
+    assert rep["buckets"] == (10 ** 9 + 2 + 63) // 64
+    assert rep["regions"] > 1000 and rep["max_counter"] > 2 * 10 ** 8
+
+
+def test_packed_index_of_a_1gbp_sequence_in_another_geometry(gpu):
+    """the same 10^9 bases in blocks of 16 (too many for the block table: the
+    indices computed per block), 16 blocks per bucket, a mark every 32 positions
+    as a bitmap, with sequence statistics (mkindex: counters as wide as each
+    letter's total), every field exact"""
+    rep = _packed_index_of(synth.MODEL_HUMANLIKE_DNA, 43, 10 ** 9, 4, "1 Gbp human-like, 16x16/32 bitmap mkindex",
+                           bsize=16, blbuck=16, locfreq=32, locbitmap=True, mkindex=True)
+    assert rep["buckets"] == (10 ** 9 + 2 + 255) // 256
+
+
+def test_packed_index_of_config2_3gbp_exact(gpu):
+    """BASELINE.json configs[2], the 3 Gbp human-like sequence of the bench, with
+    the default options: every field of the 47 M buckets exact"""
+    rep = _packed_index_of(synth.MODEL_HUMANLIKE_DNA, 43, 3 * 10 ** 9, 4, "3 Gbp human-like")
+    assert rep["max_var_offset"] > 1 << 32
+
+
+def test_packed_index_of_config4_protein_1g_exact(gpu):
+    """BASELINE.json configs[4], 10^9 residues over 20 letters, in blocks of 6: the
+    largest block size whose composition indices (C(25, 19) = 177 100 of them) fit
+    the builder's 18 bits -- 7 letters per block is refused --, indices computed
+    per block (20^6 blocks are too many for the table); every field exact"""
+    from genometools_amd import pck
+    n = 10 ** 9
+    buf = _device_sequence(synth.MODEL_PROTEIN, 44, n)
+    with esa.EsaEngine(n, 20) as eng, pck.PackedIndex() as builder:
+        eng.set_sequence_device(buf.data_ptr(), n)
+        del buf
+        eng.run(esa.WANT_SUF | esa.WANT_BWT)
+        with pytest.raises(esa.EsaError, match="needs wider indices"):
+            builder.build_from_esa(eng, bsize=7)
+        builder.build_from_esa(eng, bsize=6)
+        rep = _check_packed_index(builder, *_esa_bwt_suf(eng, n + 1), 20, "1 G protein, blocks of 6",
+                                  bsize=6)
+    assert rep["buckets"] == (n + 2 + 47) // 48 and rep["regions"] > 10 ** 6
 
 
 def test_packed_index_beyond_2p32_positions(gpu):
-    """more than 2^32 table entries (33-bit counters and text positions, var offsets
-    beyond 2^32 bits): tables made up on the device -- the builder takes any .bwt /
-    .suf pair -- and sampled buckets of the image decoded against them"""
+    """more than 2^32 table entries: tables made up on the device (the builder
+    takes any .bwt / .suf pair) with 97 % of the BWT letter 0, so that letter's
+    33-bit counters pass 2^32 in the last sixth of the buckets, and var offsets
+    beyond 2^32 bits; every field of the image exact"""
     from genometools_amd import pck
-    N = (1 << 32) + (1 << 20) + 7
+    N = 5 * (1 << 30) + 7
     dev = "cuda:0"
     g = torch.Generator(device=dev)
     g.manual_seed(11)
@@ -519,27 +475,20 @@ def test_packed_index_beyond_2p32_positions(gpu):
     step = 1 << 28
     for o in range(0, N, step):
         m = min(step, N - o)
-        x = torch.randint(0, 4, (m,), dtype=torch.uint8, device=dev, generator=g)
+        x = torch.randint(1, 4, (m,), dtype=torch.uint8, device=dev, generator=g)
         u = torch.rand(m, device=dev, generator=g)
-        x[u < 0.01] = 254
+        x[u < 0.97] = 0
+        x[u >= 0.99] = 254
+        x[u >= 0.998] = 255
         bwt[o:o + m] = x
         i = torch.arange(o, o + m, dtype=torch.int64, device=dev)
         suf[o:o + m] = (i * 11400714819 + 12345) % N          # any values below N do
         del x, u, i
-    # the tail of the table holds the suffixes that start with a special: as many
-    # rows as the BWT holds specials
-    nspecial = int((bwt >= 254).sum().item())
     with pck.PackedIndex() as builder:
         builder.build(bwt.data_ptr(), suf.data_ptr(), N, 4, 5)
-        rng = np.random.default_rng(3)
-        nb = (N + 1 + 63) // 64
-        sample = sorted(set(int(x) for x in rng.integers(0, nb - 1, 200)) |
-                        {0, 1, (1 << 26) - 1, 1 << 26, (1 << 26) + 1, nb - 2})
-        inf, _ = _check_packed_index(
-            builder, N, lambda first, count: bwt[first:first + count].cpu().numpy(),
-            lambda first, count: suf[first:first + count].cpu().numpy().astype(np.uint64),
-            nspecial, sample, count_prefix_below=10 ** 7)
-        assert inf["var_bits"] > 1 << 32
+        rep = _check_packed_index(builder, bwt, suf, 4, "2^32 + made-up tables", longest=5)
+    assert rep["max_counter"] >= 1 << 32 and rep["max_var_offset"] >= 1 << 32
+    assert rep["var_bits"] > 1 << 32
 
 
 # ---------------------------------------------------------------------------
