@@ -2901,39 +2901,52 @@ static inline u32 stride_grid(u64 tiles) {
 // Switches of a build run, read from the environment once per gtamd_esa_run (tests
 // change them between runs on one context).  They force, at small sizes, paths the
 // default selection takes only at large n or on particular inputs; an unset or
-// out-of-range value leaves the default.  [who sets them: tests/test_*.py, tools/*.py]
+// out-of-range value leaves the default.  GTAMD_DEBUG reports the effective values
+// (a "switches" line) and the paths the run took, read by tests/engine_paths.py;
+// tests/test_switch_coverage.py fails when no test sets a switch.
+// [who sets them: tests/test_*.py (fuzz_cases: the fuzzer's draws), tools/*.py]
 //   GTAMD_MSD               1: the MSD first sort at any size, other values: the LSD
 //                           sort (whole table); 0: tile keygen + exchange + LSD sort
-//                           (DNA parts)  [test_msd_gpu, fuzz_gpu]
-//   GTAMD_MSD_CBITS         depth of level C, 0..8  [test_msd_gpu, fuzz_gpu, skew_probe]
+//                           (DNA parts)  [test_msd_gpu, test_msd_level_a_format_gpu,
+//                           test_alphabets_gpu, test_switches_gpu, fuzz_gpu]
+//   GTAMD_MSD_CBITS         depth of level C, 0..8  [test_msd_gpu, test_switches_gpu,
+//                           fuzz_gpu, skew_probe]
 //   GTAMD_MSD_BIG_MAX       largest run one workgroup sorts alone: the giant path
-//                           [test_msd_gpu, fuzz_gpu]
+//                           [test_msd_gpu, test_switches_gpu, fuzz_gpu]
 //   GTAMD_MSD_RADIX         1: every level-D run through the LDS radix passes
-//                           [test_msd_gpu, fuzz_gpu]
+//                           [test_msd_gpu, test_switches_gpu, fuzz_gpu]
 //   GTAMD_MSD_PACK          0: level-D tiles cut by the stride rule, not packed
-//                           [test_msd_gpu, fuzz_gpu, exact_probe]
-//   GTAMD_MSD_PACK_CAP      size limit of a packed level-D tile  [fuzz_gpu]
-//   GTAMD_MSD_BIN_LIMIT     crowded-bin limit of k_msd_local  [fuzz_gpu, exact_probe]
-//   GTAMD_FUSED_PASS0       0: plain DNA keygen + all LSD passes  [test_esa_gpu]
-//   GTAMD_FORCE_WIDE        1: 64-bit positions and the part machinery at any size
-//                           [test_esa_gpu, test_parts_gpu, test_dist_nccl_gpu, fuzz_gpu]
-//   GTAMD_NO_PAIRS          1: no pair path, everything through the rounds
-//                           [test_esa_gpu, fuzz_gpu]
-//   GTAMD_NO_SMALL_GROUPS   1: no small groups in the pair list
-//                           [test_esa_gpu, fuzz_gpu, exact_probe]
-//   GTAMD_APPLY_EARLY       0 / 1 / 2: where the pairs' table entries are written
-//                           (out of range: 0)  [test_esa_gpu, fuzz_gpu, exact_probe,
-//                           pairs_probe]
-//   GTAMD_APPLY_WGS         grid of those entries beside the rounds  [test_esa_gpu]
-//   GTAMD_RANK_WINDOW_BITS  smaller rank-table windows: every window shape
-//                           [test_esa_gpu, test_parts_gpu, fuzz_gpu]
-//   GTAMD_RANK_ALL_WINDOWS  1: the whole rank table, not only the windows needed
-//                           [test_esa_gpu, fuzz_gpu, exact_probe]
-//   GTAMD_WIN_FILTER_LDS    0: k_win_filter's bitmap in global memory, as for texts
-//                           of more than 3.22 G symbols  [test_esa_gpu, fuzz_gpu,
+//                           [test_msd_gpu, test_switches_gpu, fuzz_gpu, exact_probe]
+//   GTAMD_MSD_PACK_CAP      size limit of a packed level-D tile  [test_switches_gpu, fuzz_gpu]
+//   GTAMD_MSD_BIN_LIMIT     crowded-bin limit of k_msd_local  [test_switches_gpu, fuzz_gpu,
 //                           exact_probe]
-//   GTAMD_PAIR_CHUNK        pairs per thread of k_pair_resolve  [fuzz_gpu, exact_probe]
-//   GTAMD_ROUND_STRIDE      distance of the round tiles' starts  [fuzz_gpu, exact_probe]
+//   GTAMD_FUSED_PASS0       0: plain DNA keygen + all LSD passes  [test_esa_gpu,
+//                           test_switches_gpu]
+//   GTAMD_FORCE_WIDE        1: 64-bit positions and the part machinery at any size
+//                           [test_esa_gpu, test_parts_gpu, test_pair_order_gpu,
+//                           test_alphabets_gpu, test_dist_nccl_gpu, test_switches_gpu, fuzz_gpu]
+//   GTAMD_NO_PAIRS          1: no pair path, everything through the rounds
+//                           [test_esa_gpu, test_alphabets_gpu, test_switches_gpu, fuzz_gpu]
+//   GTAMD_NO_SMALL_GROUPS   1: no small groups in the pair list
+//                           [test_esa_gpu, test_switches_gpu, fuzz_gpu, exact_probe]
+//   GTAMD_APPLY_EARLY       0 / 1 / 2: where the pairs' table entries are written
+//                           (out of range: 0)  [test_esa_gpu, test_pair_order_gpu,
+//                           test_switches_gpu, fuzz_gpu, exact_probe, pairs_probe]
+//   GTAMD_APPLY_WGS         grid of those entries beside the rounds  [test_esa_gpu,
+//                           test_switches_gpu]
+//   GTAMD_RANK_WINDOW_BITS  smaller rank-table windows: every window shape
+//                           [test_esa_gpu, test_parts_gpu, test_pair_order_gpu,
+//                           test_alphabets_gpu, test_switches_gpu, fuzz_gpu]
+//   GTAMD_RANK_ALL_WINDOWS  1: the whole rank table, not only the windows needed
+//                           [test_esa_gpu, test_pair_order_gpu, test_switches_gpu,
+//                           fuzz_gpu, exact_probe]
+//   GTAMD_WIN_FILTER_LDS    0: k_win_filter's bitmap in global memory, as for texts
+//                           of more than 3.22 G symbols  [test_esa_gpu, test_pair_order_gpu,
+//                           test_switches_gpu, fuzz_gpu, exact_probe]
+//   GTAMD_PAIR_CHUNK        pairs per thread of k_pair_resolve (rounded up to whole
+//                           lines of 16)  [test_switches_gpu, fuzz_gpu, exact_probe]
+//   GTAMD_ROUND_STRIDE      distance of the round tiles' starts  [test_switches_gpu,
+//                           fuzz_gpu, exact_probe]
 //   GTAMD_DEBUG             set: what the run chose, on stderr
 // ---------------------------------------------------------------------------
 struct Switches {
@@ -3738,7 +3751,8 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
   // tiles of whole ranges: packed (default), or cut by the stride rule
   // (GTAMD_MSD_PACK=0, kept for comparison)
   const u32 pack_cap = sw.msd_pack_cap;
-  if (sw.msd_pack) {
+  const bool packed = sw.msd_pack;      // (what GTAMD_DEBUG reports is what ran)
+  if (packed) {
     k_msd_pack<false><<<(MSD_PARENTS + 1 + 255) / 256, 256, 0, st>>>(F, cb, nullptr, pack_cap, w.dtcnt, nullptr,
                                                                 nullptr, nullptr, nullptr, 0);
     HIP_TRY(hipGetLastError());
@@ -3762,9 +3776,20 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
   HIP_TRY(hipMemcpyAsync(hc + 4, w.dtfirst + MSD_PARENTS, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const u32 nbig = hc[0], maxrun = hc[1], nbigentries = hc[2], ngiant = hc[3], ntD = hc[4];
-  if (sw.debug)
-    fprintf(stderr, "gtamd: msd sort: %d bits at level C, %u runs, %u big (largest %u, %u entries "
-            "in all), %u giant\n", cb, ntD, nbig, maxrun, nbigentries, ngiant);
+  char dpre[32] = "";     // (part builds: which part says it)
+  if (src != nullptr) snprintf(dpre, sizeof dpre, "part %u: ", c->part);
+  if (sw.debug) {
+    fprintf(stderr, "gtamd: %smsd sort: %d bits at level C, %u runs, %u big (largest %u, %u entries "
+            "in all), %u giant\n", dpre, cb, ntD, nbig, maxrun, nbigentries, ngiant);
+    // the level-D tiles as the host does not otherwise see them
+    std::vector<MdTile> dt(ntD);
+    if (ntD > 0)
+      HIP_TRY(hipMemcpy(dt.data(), w.dtiles, (size_t) ntD * sizeof(MdTile), hipMemcpyDeviceToHost));
+    u32 largest = 0;
+    for (const MdTile &d : dt) largest = d.end - d.begin > largest ? d.end - d.begin : largest;
+    fprintf(stderr, "gtamd: %smsd level D: packed=%d pack_cap=%u tiles=%u largest=%u\n", dpre,
+            (int) packed, pack_cap, ntD, largest);
+  }
   std::vector<MdTile> giants(ngiant);
   std::vector<u32> giant_t(ngiant);
   if (ngiant > 0) {
@@ -3798,8 +3823,9 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
     // (GTAMD_MSD_RADIX=1: every run takes the LSD passes a run with a crowded
     // bin of the counting pass is left to; tests)
     HIP_TRY(hipEventRecord(c->ev_scatter[0], st));
+    const int force_radix = sw.msd_radix ? 1 : 0;
     k_msd_local<FMT><<<stride_grid(ntD), MS_THREADS, 0, st>>>(kf, pf, w.dtiles, ntD, cb,
-                                                        sw.msd_radix, sw.msd_bin_limit,
+                                                        force_radix, sw.msd_bin_limit,
                                                         w.crowdlist, w.counters, o);
     HIP_TRY(hipEventRecord(c->ev_scatter[1], st));
     HIP_TRY(hipGetLastError());
@@ -3807,6 +3833,12 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
                                                                         w.crowdlist, w.counters,
                                                                         cb, o);
     HIP_TRY(hipGetLastError());
+    if (sw.debug) {
+      HIP_TRY(hipMemcpyAsync(hc + 6, w.counters + 4, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      fprintf(stderr, "gtamd: %smsd local: radix_runs=%u force_radix=%d bin_limit=%u\n", dpre, hc[6],
+              force_radix, sw.msd_bin_limit);
+    }
   }
   if (nbig > 0) {
     k_msd_big<FMT><<<nbig < 2048u ? nbig : 2048u, MS_THREADS, 0, st>>>(kf, pf, ko, po, w.dtiles,
@@ -3910,6 +3942,12 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
   u64 prev_key = 0;
   int has_prev = 0;
   if (dist && BITS == 2) msd_part = !sw.msd_part_off;
+  // DNA whole-table builds with the LSD sort: keygen fused with its first pass
+  const bool fused_pass0 = !dist && !msd && BITS == 2 && sw.fused_pass0;
+  if (debug)
+    fprintf(stderr, "gtamd: part %u: run: parts=%u positions=%d first_sort=%s pass0=%s\n", c->part, R,
+            WIDE ? 64 : 32, msd || msd_part ? "msd" : "lsd",
+            dist || msd || BITS != 2 ? "none" : (fused_pass0 ? "fused" : "plain"));
   if (!dist) {
     TRY(ensure_workspace(c, N, want, false));
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, sizeof(Stats), st));
@@ -3918,7 +3956,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       TRY(msd_sort_emit<BITS == 5 ? 1 : 0>(c, sw, want, prefixlength, N, N, nullptr, &msd_sa, &msd_fkey, &msd_fval,
                                            &msd_local));
       HIP_TRY(hipEventRecord(c->ev_emitted, st));   // (what the joins below wait for)
-    } else if (BITS == 2 && sw.fused_pass0) {
+    } else if (fused_pass0) {
       const u32 ntiles = (u32) div_up(N, KP_TILE);
       k_dc_hist_dna<<<ntiles, KP_THREADS, 0, st>>>(c->text, N, c->rws.as<u32>());
       HIP_TRY(hipGetLastError());
@@ -4459,6 +4497,10 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       int pair_chunk = (int) (nrec >> 20 < 16 ? 16 : (nrec >> 20 > 128 ? 128 : nrec >> 20));
       if (sw.pair_chunk > 0) pair_chunk = sw.pair_chunk;
       pair_chunk = (pair_chunk + PR_LINE - 1) / PR_LINE * PR_LINE;    // (whole lines of records per thread)
+      if (debug)
+        fprintf(stderr, "gtamd: part %u: pair resolve: records=%llu chunk=%d grid=%u\n", c->part,
+                (unsigned long long) nrec, pair_chunk,
+                stride_grid(div_up(div_up(nrec, (u64) pair_chunk), 256)));
       k_pair_resolve<BITS, P><<<stride_grid(div_up(div_up(nrec, (u64) pair_chunk), 256)), 256, 0, st>>>(
           c->text, pk_sorted, pv_sorted, nrec, npairs, sa, pres, c->d_stats, pair_chunk);
       HIP_TRY(hipGetLastError());
@@ -4520,6 +4562,12 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
           const double have = 1.25 * 4.0e-7 * (double) m0 + 0.5;
           if (need > have) cap = (u64) ((double) apply_wgs * (need / have));
         }
+      }
+      if (debug) {
+        const u64 gpair = div_up(npairs, 256), gsmall = div_up(nsmall, 256);
+        fprintf(stderr, "gtamd: part %u: apply: placement=%d pair_grid=%llu small_grid=%llu\n", c->part,
+                apply_early, (unsigned long long) (gpair < cap ? gpair : cap),
+                (unsigned long long) (gsmall < cap ? gsmall : cap));
       }
       if (npairs > 0) {
         const u64 g = div_up(npairs, 256);
@@ -4756,6 +4804,9 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
                     rk_windows ? "" : " -> whole table");
         }
         if (!rk_windows) {
+          if (debug)
+            fprintf(stderr, "gtamd: part %u: rank table: whole table of %llu entries\n", c->part,
+                    (unsigned long long) NL);
           if (heads_array) {
             k_heads<<<(u32) div_up(NL, 1024), 256, 0, st>>>(tiebits2, carry, NL, 0u, pair_swp, heads);
             HIP_TRY(hipGetLastError());
@@ -4790,7 +4841,11 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
         // the pairs of the selected windows, with compact positions, partitioned down
         // to the windows the LDS takes
         HIP_TRY(hipMemsetAsync(&c->d_stats->count, 0, 4, st));
-        if ((nww + 4) * 5 <= WF_LDS_MAX && !wf_global) {
+        const bool wf_lds = (nww + 4) * 5 <= WF_LDS_MAX && !wf_global;
+        if (debug)
+          fprintf(stderr, "gtamd: part %u: win filter: bitmap=%s windows=%llu\n", c->part,
+                  wf_lds ? "lds" : "global", (unsigned long long) nsel);
+        if (wf_lds) {
           // (more than the 64 KB a kernel gets without asking)
           HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_win_filter<u32, true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -4882,7 +4937,10 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
         // the windows any part needs and nobody has sent yet (the first allgather of
         // this step also says whether a part could not get its buffers)
         const u32 *d_sel = nullptr;
+        u64 fresh_windows = 0;
         int agreed = 0;
+        if (debug && !rk_windows)
+          fprintf(stderr, "gtamd: part %u: rank exchange: all windows\n", c->part);
         if (rk_windows) {
           if (!fail) {
             HIP_TRY(hipStreamSynchronize(st));
@@ -4905,6 +4963,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
                     "(%llu of %llu so far)\n", c->part, (unsigned long long) fresh, rk_wb,
                     (unsigned long long) all, (unsigned long long) rk_nwin);
           if (fresh == 0) return 0;
+          fresh_windows = fresh;
           HIP_TRY(hipMemcpyAsync(w_sel, h_need.data(), dw_nww * 4, hipMemcpyHostToDevice, st));
           HIP_TRY(hipMemcpyAsync(w_built, h_built.data(), dw_nww * 4, hipMemcpyHostToDevice, st));
           d_sel = w_sel;
@@ -4918,7 +4977,11 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
         if (!fail && d_sel != nullptr && NL > 0 && list_cap > 0) {
           HIP_TRY(hipMemsetAsync(&c->d_stats->count, 0, 8, st));     // count, count2
           // (the bitmap of the windows of 64 K positions: 6 KB for 3 Gbp -- in LDS whenever it fits)
-          if ((dw_nww + 4) * 5 <= WF_LDS_MAX && !wf_global) {
+          const bool wf_lds = (dw_nww + 4) * 5 <= WF_LDS_MAX && !wf_global;
+          if (debug)
+            fprintf(stderr, "gtamd: part %u: win filter: bitmap=%s windows=%llu\n", c->part,
+                    wf_lds ? "lds" : "global", (unsigned long long) fresh_windows);
+          if (wf_lds) {
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_win_filter<P, true>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int) wf_lds_bytes<P>(dw_nww, true)));
@@ -5167,8 +5230,8 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       TRY(fetch_stats(c));
       const u64 nf = c->h_stats->count;
       if (debug)
-        fprintf(stderr, "gtamd: part %u round %u: %llu entries in groups across tile borders\n",
-                c->part, rounds, (unsigned long long) nf);
+        fprintf(stderr, "gtamd: part %u round %u: %llu entries in groups across tile borders "
+                "(%u tiles, stride %u)\n", c->part, rounds, (unsigned long long) nf, ntiles, rt_stride);
       if (nf > 0) {
         // groups crossing a tile border / larger than a tile: ordered by
         // (group, k2) through two stable sorts of an index
@@ -5380,6 +5443,18 @@ extern "C" int gtamd_esa_run(gtamd_esa_ctx *c, uint32_t want) {
   if ((want & 15u) == 0) { gtamd_set_error("nothing requested"); return -1; }
   HIP_TRY(hipSetDevice(c->device));
   const Switches sw = read_switches();
+  if (sw.debug)
+    fprintf(stderr, "gtamd: part %u: switches: msd=%d msd_part_off=%d msd_cbits=%d msd_big_max=%u "
+            "msd_radix=%d msd_pack=%d msd_pack_cap=%u msd_bin_limit=%u fused_pass0=%d "
+            "force_wide=%d no_pairs=%d no_small_groups=%d apply_early=%d apply_wgs=%llu "
+            "apply_wgs_given=%d rank_window_bits=%d rank_all_windows=%d win_filter_global=%d "
+            "pair_chunk=%d round_stride=%u debug=%d\n",
+            c->part, sw.msd, (int) sw.msd_part_off, sw.msd_cbits, sw.msd_big_max, (int) sw.msd_radix,
+            (int) sw.msd_pack, sw.msd_pack_cap, sw.msd_bin_limit, (int) sw.fused_pass0,
+            (int) sw.force_wide, (int) sw.no_pairs, (int) sw.no_small_groups, sw.apply_early,
+            (unsigned long long) sw.apply_wgs, (int) sw.apply_wgs_given, sw.rank_window_bits,
+            (int) sw.rank_all_windows, (int) sw.win_filter_global, sw.pair_chunk, sw.round_stride,
+            (int) sw.debug);
   // 64-bit positions: whenever the sequence needs them; GTAMD_FORCE_WIDE=1
   // takes that path (and the exchange machinery of a part build) at any size
   const bool wide = sw.force_wide || c->N >= SINGLE_LIMIT;

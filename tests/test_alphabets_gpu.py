@@ -6,6 +6,7 @@ and the two ends, are here."""
 import numpy as np
 import pytest
 
+import engine_paths
 import oracle_util as ou
 from genometools_amd import esa
 from thread_comm import build_in_parts
@@ -120,19 +121,33 @@ def test_msd_switch(gpu, monkeypatch, capfd, sigma, msd):
     ora = ou.esa(enc, sigma)
     _assert_same_as_oracle(enc, sigma, res, ora)
     takes_msd = sigma <= 4 or (sigma <= 20 and ora["stats"]["prefixlength"] <= 9)
-    assert ("msd sort" in err) == (msd == "1" and takes_msd), err
+    p = engine_paths.single(err)
+    assert p["switches"]["msd"] == int(msd)
+    assert p["run"]["first_sort"] == ("msd" if msd == "1" and takes_msd else "lsd"), err
+    assert (p["msd"] is not None) == (msd == "1" and takes_msd), err
 
 
 @pytest.mark.parametrize("switch", [("GTAMD_FORCE_WIDE", "1"), ("GTAMD_NO_PAIRS", "1"),
                                     ("GTAMD_RANK_WINDOW_BITS", "4")],
                          ids=lambda s: "%s=%s" % s)
 @pytest.mark.parametrize("sigma", FORCED_SIGMAS)
-def test_forced_paths(gpu, monkeypatch, sigma, switch):
+def test_forced_paths(gpu, monkeypatch, capfd, sigma, switch):
     enc = _mixed(sigma, 300_000, 11 + sigma)
     monkeypatch.setenv(*switch)
     if switch[0] == "GTAMD_RANK_WINDOW_BITS":
         monkeypatch.setenv("GTAMD_NO_PAIRS", "1")   # (pairs would not need the table)
-    _assert_same_as_oracle(enc, sigma, esa.suffixerator_tables(enc, sigma))
+    monkeypatch.setenv("GTAMD_DEBUG", "1")
+    capfd.readouterr()
+    res = esa.suffixerator_tables(enc, sigma)
+    p = engine_paths.single(capfd.readouterr().err)
+    if switch[0] == "GTAMD_FORCE_WIDE":
+        assert p["switches"]["force_wide"] == 1 and p["run"]["positions"] == 64
+    elif switch[0] == "GTAMD_NO_PAIRS":
+        assert p["switches"]["no_pairs"] == 1 and p["pair_resolve"] is None
+        assert res.stats["pair_suffixes"] == 0
+    else:
+        assert p["switches"]["rank_window_bits"] == 4 and (p["rank_whole"] or p["rank_windows"])
+    _assert_same_as_oracle(enc, sigma, res)
 
 
 @pytest.mark.parametrize("parts", [2, 3])

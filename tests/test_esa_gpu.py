@@ -6,11 +6,24 @@ import hashlib
 import numpy as np
 import pytest
 
+import engine_paths
 import oracle_util as ou
 from genometools_amd import esa, synth
 
 pytestmark = pytest.mark.gpu
 GOLDEN = ou.golden()
+
+
+def _forced(monkeypatch, capfd, enc, sigma, **want):
+    """one build with GTAMD_DEBUG on: the result and what the build reports
+    (engine_paths), its effective switches checked against `want`"""
+    monkeypatch.setenv("GTAMD_DEBUG", "1")
+    capfd.readouterr()
+    res = esa.suffixerator_tables(enc, sigma)
+    p = engine_paths.single(capfd.readouterr().err)
+    for k, v in want.items():
+        assert p["switches"][k] == v, (k, p["switches"][k], v)
+    return res, p
 
 
 def _md5(a):
@@ -310,7 +323,7 @@ def test_bucket_table_matches_oracle(gpu, model, n, ks):
     (4, 1_500_000),     # two passes and two workgroups per (twice too large) window
     (15, 1_500_000),    # the shape a build of this size takes by itself
 ])
-def test_rank_table_window_shapes(gpu, monkeypatch, wbits, n):
+def test_rank_table_window_shapes(gpu, monkeypatch, capfd, wbits, n):
     """rank table through LDS windows (k_rank_window): GTAMD_RANK_WINDOW_BITS
     shrinks the window so that the partition shapes of a 3 Gbp build (two
     passes, split windows) are reached at test sizes; repeats make sure the
@@ -320,20 +333,25 @@ def test_rank_table_window_shapes(gpu, monkeypatch, wbits, n):
     enc = synth.generate(synth.MODEL_HUMANLIKE_DNA, 77 + wbits, n)
     if n < 200_000:     # too short for the model's repeats: a tandem repeat instead
         enc = np.resize(synth.generate(synth.MODEL_UNIFORM_DNA, 5, 700), n).astype(np.uint8)
-    res = esa.suffixerator_tables(enc, 4)
-    assert res.stats["refine_rounds"] > 0
+    res, p = _forced(monkeypatch, capfd, enc, 4, rank_window_bits=wbits, no_pairs=1)
+    assert p["rank_whole"] or p["rank_windows"]
+    assert res.stats["refine_rounds"] > 0 and res.stats["pair_suffixes"] == 0
     _assert_same_as_oracle(enc, 4, res)
 
 
 @pytest.mark.parametrize("wbits,n,later", [(15, 3_000_000, False), (8, 600_000, False), (4, 600_000, False),
                                            (10, 900_000, True), (5, 900_000, True)])
 @pytest.mark.parametrize("lds", ["1", "0"])
-def test_rank_table_of_selected_windows(gpu, monkeypatch, wbits, n, later, lds):
+def test_rank_table_of_selected_windows(gpu, monkeypatch, capfd, wbits, n, later, lds):
     """only the windows of positions the rounds can touch are built (k_win_mark,
     k_win_filter with compact positions, k_rank_window per selected window): a random
     text with a few blocks in several copies -- the tied suffixes lie in a small part
-    of the text; `later`: copies longer than the first rounds reach, so that windows
-    are added between rounds (k_win_check); the last window of the text among them"""
+    of the text; `later`: copies longer than the offsets marked at the start
+    (rk_h0), so that the rounds check for windows beyond them (k_win_check); the
+    last window of the text among them.  A round reads at most KNOWN - 1 positions
+    behind the last tied suffix of a copy, inside what the windows built first
+    cover at these window sizes, so none is added between rounds (that takes
+    windows of 2^2 positions: test_parts_gpu.test_deep_groups_reach_new_rank_windows)"""
     monkeypatch.setenv("GTAMD_RANK_WINDOW_BITS", str(wbits))
     monkeypatch.setenv("GTAMD_NO_PAIRS", "1")
     monkeypatch.setenv("GTAMD_WIN_FILTER_LDS", lds)     # (0: the bitmap from global memory)
@@ -344,7 +362,9 @@ def test_rank_table_of_selected_windows(gpu, monkeypatch, wbits, n, later, lds):
     for at in (n // 3, n // 2 + 17, n - blk):        # (the last copy ends the text)
         enc[at:at + blk] = src
     enc[n // 5] = 254
-    res = esa.suffixerator_tables(enc, 4)
+    res, p = _forced(monkeypatch, capfd, enc, 4, rank_window_bits=wbits, win_filter_global=int(lds == "0"))
+    assert p["win_filter"] and p["rank_windows"] and not p["rank_whole"]
+    assert all(w["bitmap"] == ("global" if lds == "0" else "lds") for w in p["win_filter"])
     st = res.stats
     assert st["refine_rounds"] > 0
     assert 0 < st["rank_entries_built"] < (n + 1) // 2
@@ -352,7 +372,7 @@ def test_rank_table_of_selected_windows(gpu, monkeypatch, wbits, n, later, lds):
 
 
 @pytest.mark.parametrize("n,sigma", [(70_337, 4), (70_337 + 512, 4), (70_337, 20), (2948, 20)])
-def test_tie_group_that_reaches_the_last_word_of_the_table(gpu, monkeypatch, n, sigma):
+def test_tie_group_that_reaches_the_last_word_of_the_table(gpu, monkeypatch, capfd, n, sigma):
     """the largest suffixes tied -- a run of the largest letter, and nothing but the
     terminator behind them in the table -- with a table length that leaves the last
     64-entry chunk of the rank-table partition with fewer entries than its item number:
@@ -369,14 +389,15 @@ def test_tie_group_that_reaches_the_last_word_of_the_table(gpu, monkeypatch, n, 
     run = 1219 if n < 5000 else 3000
     at = n // 4
     enc[at:at + run] = sigma - 1                                  # (... but for one long run)
-    res = esa.suffixerator_tables(enc, sigma)
+    res, p = _forced(monkeypatch, capfd, enc, sigma, rank_all_windows=1)
+    assert p["rank_whole"] == [n + 1] and not p["rank_windows"] and not p["win_filter"]
     assert res.stats["refine_rounds"] > 0
     _assert_same_as_oracle(enc, sigma, res)
 
 
 @pytest.mark.parametrize("fused", ["1", "0"])
 @pytest.mark.parametrize("n", [1, 15, 16, 17, 4095, 4096, 4097, 70_001, 1_000_003])
-def test_keygen_with_and_without_fused_first_pass(gpu, monkeypatch, fused, n):
+def test_keygen_with_and_without_fused_first_pass(gpu, monkeypatch, capfd, fused, n):
     """DNA keygen: fused with the sort's dcode pass (k_dc_hist_dna +
     k_keygen_pass0_dna, the default) and plain (k_keygen_dna + all six passes,
     GTAMD_FUSED_PASS0=0, the A/B switch) give the reference's tables; sizes
@@ -394,7 +415,9 @@ def test_keygen_with_and_without_fused_first_pass(gpu, monkeypatch, fused, n):
         enc[0] = 0
     if enc[-1] == 255:
         enc[-1] = 0
-    res = esa.suffixerator_tables(enc, 4)
+    res, p = _forced(monkeypatch, capfd, enc, 4, fused_pass0=int(fused))
+    assert p["run"]["first_sort"] == "lsd"
+    assert p["run"]["pass0"] == ("fused" if fused == "1" else "plain")
     _assert_same_as_oracle(enc, 4, res)
 
 
@@ -444,12 +467,16 @@ def _pair_cases():
 
 @pytest.mark.parametrize("name,enc", list(_pair_cases()), ids=[c[0] for c in _pair_cases()])
 @pytest.mark.parametrize("pairs", ["on", "off"])
-def test_pair_path(gpu, monkeypatch, name, enc, pairs):
+def test_pair_path(gpu, monkeypatch, capfd, name, enc, pairs):
     """with and without the pair path (GTAMD_NO_PAIRS=1: everything through
     prefix doubling) the tables are the oracle's"""
     if pairs == "off":
         monkeypatch.setenv("GTAMD_NO_PAIRS", "1")
-    res = esa.suffixerator_tables(enc, 4)
+    res, p = _forced(monkeypatch, capfd, enc, 4, no_pairs=int(pairs == "off"))
+    if pairs == "off":
+        assert p["pair_resolve"] is None
+    elif res.stats["pair_suffixes"] > 0:
+        assert p["pair_resolve"]["records"] >= res.stats["pair_suffixes"] // 2
     _assert_same_as_oracle(enc, 4, res)
     if pairs == "off":
         assert res.stats["pair_suffixes"] == 0
@@ -474,12 +501,13 @@ def test_pair_path_large(gpu):
 
 @pytest.mark.parametrize("name", ["Atinsert.fna", "Duplicate.fna", "RandomN.fna", "TTTN.fna",
                                   "sw100K1.fsa"])
-def test_wide_positions_reference_fixtures(gpu, monkeypatch, name):
+def test_wide_positions_reference_fixtures(gpu, monkeypatch, capfd, name):
     monkeypatch.setenv("GTAMD_FORCE_WIDE", "1")
     e = GOLDEN[name]
     protein = e["alphabet"] == "protein"
     enc = ou.encode_fasta(ou.fixture_path(name), protein)
-    res = esa.suffixerator_tables(enc, 20 if protein else 4)
+    res, p = _forced(monkeypatch, capfd, enc, 20 if protein else 4, force_wide=1)
+    assert p["run"]["positions"] == 64
     for tab in ("suf", "lcp", "llv", "bwt"):
         assert _md5(getattr(res, tab)) == e["tables"][tab]["md5"], tab
 
@@ -489,18 +517,20 @@ def test_wide_positions_reference_fixtures(gpu, monkeypatch, name):
     (synth.MODEL_HUMANLIKE_DNA, 4, 600000, 3),
     (synth.MODEL_PROTEIN, 20, 200000, 5),
 ])
-def test_wide_positions_synthetic(gpu, monkeypatch, model, sigma, n, seed):
+def test_wide_positions_synthetic(gpu, monkeypatch, capfd, model, sigma, n, seed):
     monkeypatch.setenv("GTAMD_FORCE_WIDE", "1")
     enc = synth.generate(model, seed, n)
-    res = esa.suffixerator_tables(enc, sigma)
+    res, p = _forced(monkeypatch, capfd, enc, sigma, force_wide=1)
+    assert p["run"]["positions"] == 64
     _assert_same_as_oracle(enc, sigma, res)
 
 
 @pytest.mark.parametrize("name,enc", list(_cases()) + list(_pair_cases()),
                          ids=[c[0] for c in _cases()] + [c[0] for c in _pair_cases()])
-def test_wide_positions_edge_cases(gpu, monkeypatch, name, enc):
+def test_wide_positions_edge_cases(gpu, monkeypatch, capfd, name, enc):
     monkeypatch.setenv("GTAMD_FORCE_WIDE", "1")
-    res = esa.suffixerator_tables(enc, 4)
+    res, p = _forced(monkeypatch, capfd, enc, 4, force_wide=1)
+    assert p["run"]["positions"] == 64
     _assert_same_as_oracle(enc, 4, res)
 
 
@@ -530,7 +560,7 @@ def test_repeat_heavy_model_device_equals_numpy(gpu):
     assert np.array_equal(res.bwt, t["bwt"])
 
 
-def test_small_groups(gpu, monkeypatch):
+def test_small_groups(gpu, monkeypatch, capfd):
     """tie groups of three and four (sorted by direct comparisons): a pair with
     a third suffix that shares 20 symbols only, three and four copies; with
     the path switched off (GTAMD_NO_SMALL_GROUPS=1) the same tables"""
@@ -540,11 +570,17 @@ def test_small_groups(gpu, monkeypatch):
     enc = np.concatenate([a, [255], a, [254], third, [255], a[:2000], [255], a[100:1900], [255],
                           rng.integers(0, 4, 4000, dtype=np.uint8)]).astype(np.uint8)
     enc = np.concatenate([enc, enc[::-1][:3000]]).astype(np.uint8)
+    # (a random tail: the small groups' records stay below an eighth of the table,
+    # else the path leaves them to the rounds)
+    enc = np.concatenate([enc, rng.integers(0, 4, 200000, dtype=np.uint8)]).astype(np.uint8)
     ora = ou.esa(enc, 4)
-    res = esa.suffixerator_tables(enc, 4)
+    res, p = _forced(monkeypatch, capfd, enc, 4, no_small_groups=0)
+    assert p["ties"]["small_groups"] > 0
     _assert_same_as_oracle(enc, 4, res, ora)
     monkeypatch.setenv("GTAMD_NO_SMALL_GROUPS", "1")
-    _assert_same_as_oracle(enc, 4, esa.suffixerator_tables(enc, 4), ora)
+    res, p = _forced(monkeypatch, capfd, enc, 4, no_small_groups=1)
+    assert p["ties"]["small_groups"] == 0
+    _assert_same_as_oracle(enc, 4, res, ora)
 
 
 def test_small_groups_too_deep_fall_back(gpu):
@@ -564,7 +600,7 @@ def test_small_groups_too_deep_fall_back(gpu):
 
 
 @pytest.mark.parametrize("mode,wgs", [("0", None), ("1", None), ("2", None), ("2", "64"), ("1", "100000")])
-def test_table_entries_of_the_pairs_beside_the_rounds(gpu, monkeypatch, mode, wgs):
+def test_table_entries_of_the_pairs_beside_the_rounds(gpu, monkeypatch, capfd, mode, wgs):
     """the table entries of the pairs and small groups are written on the second
     stream beside the doubling rounds (GTAMD_APPLY_EARLY=2, the default), from
     the pair path on (1) or behind the rounds on the main stream (0), by a
@@ -579,7 +615,13 @@ def test_table_entries_of_the_pairs_beside_the_rounds(gpu, monkeypatch, mode, wg
     monkeypatch.setenv("GTAMD_APPLY_EARLY", mode)
     if wgs is not None:
         monkeypatch.setenv("GTAMD_APPLY_WGS", wgs)
-    res = esa.suffixerator_tables(enc, 4)
+    res, p = _forced(monkeypatch, capfd, enc, 4, apply_early=int(mode),
+                     apply_wgs=int(wgs or 0), apply_wgs_given=int(wgs is not None))
+    assert len(p["apply"]) == 1
+    a = p["apply"][0]
+    assert a["placement"] == int(mode) and a["pair_grid"] > 0
+    if wgs is not None:         # (a given grid caps both kernels beside the rounds)
+        assert a["pair_grid"] <= int(wgs) and a["small_grid"] <= int(wgs)
     assert res.stats["pair_suffixes"] > 0 and res.stats["refine_rounds"] > 0
     assert res.stats["largelcpvalues"] > 0
     _assert_same_as_oracle(enc, 4, res, ora)

@@ -28,6 +28,7 @@ import numpy as np
 import pytest
 import torch
 
+import engine_paths
 import oracle_util as ou
 from genometools_amd import _lib, esa, synth
 
@@ -533,7 +534,9 @@ def test_alphabet_at_size_exact(gpu, monkeypatch, capfd, sigma, n, prefixlength,
         eng.set_sequence_device(buf.data_ptr(), n)
         eng.run()
         st = eng.stats()
-        msd = "msd sort" in capfd.readouterr().err
+        p = engine_paths.single(capfd.readouterr().err)
+        msd = p["run"]["first_sort"] == "msd"
+        assert msd == (p["msd"] is not None)
         assert st["prefixlength"] == prefixlength
         # the 5-bit MSD sort tells the prefix length from nine symbols' codes
         assert msd == (sigma <= 4 or (sigma <= 20 and prefixlength <= 9))

@@ -8,6 +8,7 @@ block holds, and for the 5-bit alphabet."""
 import numpy as np
 import pytest
 
+import engine_paths
 import oracle_util as ou
 from genometools_amd import esa, synth
 
@@ -33,9 +34,15 @@ def _block_bits(n):
 
 
 @pytest.fixture
-def msd(monkeypatch):
+def msd(monkeypatch, capfd):
+    """GTAMD_MSD=1, and at the end of the test: the MSD sort ran"""
     monkeypatch.setenv("GTAMD_MSD", "1")
-    return monkeypatch
+    monkeypatch.setenv("GTAMD_DEBUG", "1")
+    capfd.readouterr()
+    yield monkeypatch
+    parts = engine_paths.parse(capfd.readouterr().err)
+    assert sorted(parts) == [0] and parts[0]["switches"]["msd"] == 1
+    assert parts[0]["run"]["first_sort"] == "msd" and parts[0]["msd"] is not None
 
 
 # L = 12 (one block up to 4096, then 2..256), 13 at 2^20 + 1, 14 at 2^21 + 1, 15 at 3 * 2^20

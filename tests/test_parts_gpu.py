@@ -6,6 +6,7 @@ produce, slice by slice, exactly the tables of the single build."""
 import numpy as np
 import pytest
 
+import engine_paths
 import oracle_util as ou
 from genometools_amd import synth
 from thread_comm import build_in_parts, build_sequences_in_parts
@@ -59,16 +60,24 @@ def test_degenerate_inputs_in_parts(gpu):
 
 
 @pytest.mark.parametrize("parts", [2, 3, 8])
-def test_wide_positions_in_parts(gpu, monkeypatch, parts):
+def test_wide_positions_in_parts(gpu, monkeypatch, capfd, parts):
     """the 64-bit position / rank kernels of a build with n >= 2^32, forced at
     oracle sizes (GTAMD_FORCE_WIDE=1)"""
     monkeypatch.setenv("GTAMD_FORCE_WIDE", "1")
-    _check(synth.generate(synth.MODEL_HUMANLIKE_DNA, 5, 400000), 4, parts)
-    _check(synth.generate(synth.MODEL_PROTEIN, 7, 150000), 20, parts)
-    _check(np.zeros(3000, dtype=np.uint8), 4, parts)
+    monkeypatch.setenv("GTAMD_DEBUG", "1")
     rng = np.random.default_rng(3)
     a = rng.integers(0, 4, 3000, dtype=np.uint8)
-    _check(np.concatenate([a, [255], a, [254], a]).astype(np.uint8), 4, parts)
+    for enc, sigma in ((synth.generate(synth.MODEL_HUMANLIKE_DNA, 5, 400000), 4),
+                       (synth.generate(synth.MODEL_PROTEIN, 7, 150000), 20),
+                       (np.zeros(3000, dtype=np.uint8), 4),
+                       (np.concatenate([a, [255], a, [254], a]).astype(np.uint8), 4)):
+        capfd.readouterr()
+        _check(enc, sigma, parts)
+        per_part = engine_paths.parse(capfd.readouterr().err)
+        assert sorted(per_part) == list(range(parts))
+        for p in per_part.values():
+            assert p["switches"]["force_wide"] == 1
+            assert p["run"]["positions"] == 64 and p["run"]["parts"] == parts
 
 
 def test_part_contexts_are_reusable(gpu):
@@ -102,19 +111,30 @@ def test_many_parts(gpu):
 
 
 @pytest.mark.parametrize("parts", [1, 3])
-def test_deep_groups_reach_new_rank_windows(gpu, monkeypatch, parts):
-    """five copies of 30 000 bases: groups of five stay tied for 11 rounds and
-    the offsets of the late rounds (h > 10 240) reach windows of the rank table
-    that were not built / sent at first -- the lazy extension, in a single
-    build (small windows forced) and in a part build"""
+def test_deep_groups_reach_new_rank_windows(gpu, monkeypatch, capfd, parts):
+    """five copies of 15 000 bases: groups of five stay tied for 10 rounds.  A
+    round at offset h reads the rank of p + h, which lies at most KNOWN - 1 = 19
+    positions behind the last tied suffix of its copy (what lies further was
+    settled before, and settled it ends the group).  The windows built first cover
+    rk_h0 = min(KNOWN << 9, 3 << window bits) positions behind every tied suffix,
+    so only windows of 2^2 positions (rk_h0 = 12, a text below 2^18 symbols) leave
+    windows for the rounds to add -- the lazy extension of the single build.  A
+    part build covers 10 240 positions: its first exchange sends every window the
+    rounds reach."""
     rng = np.random.default_rng(31)
-    a = rng.integers(0, 4, 30000, dtype=np.uint8)
+    a = rng.integers(0, 4, 15000, dtype=np.uint8)
     enc = np.concatenate([a, [255], a, [254], a, [255], a, [255], a,
-                          rng.integers(0, 4, 200000, dtype=np.uint8)]).astype(np.uint8)
+                          rng.integers(0, 4, 165000, dtype=np.uint8)]).astype(np.uint8)
     if parts == 1:
         from genometools_amd import esa
-        monkeypatch.setenv("GTAMD_RANK_WINDOW_BITS", "8")
+        monkeypatch.setenv("GTAMD_RANK_WINDOW_BITS", "2")
+        monkeypatch.setenv("GTAMD_DEBUG", "1")
+        capfd.readouterr()
         res = esa.suffixerator_tables(enc, 4)
+        p = engine_paths.single(capfd.readouterr().err)
+        assert p["switches"]["rank_window_bits"] == 2
+        # (windows selected at first, more added by the late rounds)
+        assert len(p["rank_windows"]) >= 2 and not p["rank_windows"][0]["whole"]
         tabs = {"suf": res.suf, "lcp": res.lcp, "llv": res.llv, "bwt": res.bwt}
         rounds = res.stats["refine_rounds"]
     else:
