@@ -29,8 +29,8 @@
 #include <stdarg.h>
 #include <stdlib.h>
 #include <chrono>
-#include <functional>
 #include <type_traits>
+#include <utility>
 #include <vector>
 #include "../../include/gtamd_esa.h"
 #include "esa_prims.h"
@@ -739,6 +739,14 @@ struct Tiles {
     const u64 d = q / T;
     *off = q - d * T;
     return (u32) d;
+  }
+  // host side: positions per tile for R parts (a multiple of the keygen tile),
+  // where the tile of part q starts and how many positions it has
+  static u64 size_for(u64 N, u32 R) { return div_up(div_up(N, R), 4096) * 4096; }
+  u64 first(u32 q, u64 N) const { return (u64) q * T < N ? (u64) q * T : N; }
+  u64 count(u32 q, u64 N) const {
+    const u64 f = first(q, N);
+    return f + T < N ? T : N - f;
   }
 };
 
@@ -3096,9 +3104,21 @@ struct gtamd_esa_ctx {
   gtamd_esa_timing timing;
   u64 alloc_bytes;         // device memory held by the context
   float alloc_ms;          // host time of the allocations since the last run started
-  // events
+  // events: ev[] by TimingEvent
   hipEvent_t ev[8];
   hipEvent_t ev_scatter[2 * 16];
+};
+
+// what the timing events c->ev[] mark on the first stream (gtamd_esa_timing is made of
+// the times between them)
+enum TimingEvent {
+  EV_START,          // the run begins
+  EV_KEYS,           // keys are made (the MSD sort: after its level A)
+  EV_SORTED,         // the first sort is done
+  EV_TIEBITS,        // tie bitmap (LSD sort) and the count of the ties
+  EV_REFINE_BEGIN,   // the parts have agreed on whether there are ties
+  EV_REFINE_END,     // behind the last round (without ties: where it began)
+  EV_DONE            // tables final, emission joined
 };
 
 static void free_dev(void *p) { if (p != nullptr) (void) hipFree(p); }
@@ -3713,7 +3733,7 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
     k_msd_scatter_a<0><<<((ntA + 7u) >> 3) * 8u, MS_THREADS, 0, st>>>(
         c->text, N, last_valid, w.hist, ntA, nullptr, nullptr, nullptr, nullptr, nullptr, ea);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev[1], st));
+  HIP_TRY(hipEventRecord(c->ev[EV_KEYS], st));
   // ---- level B: ea, or (ka, xa, pa) -> (kb, pb)
   TRY(msd_level_prepare(c, w, w.startA, 256, 8, w.tilesB_ub, ka, wide ? ea : nullptr, w.startB));
   if (wide)
@@ -3873,85 +3893,507 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
   return 0;
 }
 
-// BITS: symbol width; WIDE: positions and ranks are 64-bit (part builds of
-// sequences with n >= 2^32)
+// ---------------------------------------------------------------------------
+// the build driver: what gtamd_esa_run does on the host, phase by phase
+// ---------------------------------------------------------------------------
+// shifts and widths of the 8-bit radix passes over the bits [from, to), least
+// significant first
+static int passes_for(int from, int to, int *ps, int *pw) {
+  int cnt = 0;
+  for (int b = from; b < to; b += 8) {
+    ps[cnt] = b;
+    pw[cnt] = to - b < 8 ? to - b : 8;
+    cnt++;
+  }
+  return cnt;
+}
+
+// range cuts of a part build from the counts of the PART_BINS key bins: cut[r]
+// is the smallest bin with r / R of everything counted in the bins below it;
+// part r owns the bins cut[r] .. cut[r + 1] - 1
+template <typename T>
+static std::vector<u32> range_cuts(const T *bins, u32 R) {
+  u64 nsamp = 0;
+  for (int b = 0; b < PART_BINS; b++) nsamp += bins[b];
+  std::vector<u32> cut(R + 1);
+  cut[0] = 0;
+  cut[R] = PART_BINS;
+  u64 run = 0;
+  u32 b = 0;
+  for (u32 r = 1; r < R; r++) {
+    const u64 target = (u64) (((unsigned __int128) nsamp * r) / R);
+    while (b < (u32) PART_BINS && run < target) run += bins[b++];
+    cut[r] = b;
+  }
+  return cut;
+}
+
+// one word of every part, reduced: *word goes out and the result comes back.
+// `failed` is the status this part reports with it (see comm_allgather)
+enum Reduce { RED_SUM, RED_AND, RED_OR, RED_MAX };
+static int allgather_word(gtamd_esa_ctx *c, int failed, Reduce op, u64 *word) {
+  std::vector<u64> all(c->numparts);
+  TRY(comm_allgather(c, failed, word, all.data(), 8));
+  u64 v = all[0];
+  for (u32 r = 1; r < c->numparts; r++)
+    switch (op) {
+      case RED_SUM: v += all[r]; break;
+      case RED_AND: v &= all[r]; break;
+      case RED_OR: v |= all[r]; break;
+      case RED_MAX: v = all[r] > v ? all[r] : v; break;
+    }
+  *word = v;
+  return 0;
+}
+
+static void set_slice_error(u64 NL) {
+  gtamd_set_error("slice of %llu entries exceeds the 32-bit index range of one "
+                  "part: use more parts", (unsigned long long) NL);
+}
+
+// k_win_filter over the NL positions of sa: the entries of the windows of 2^wb
+// positions selected in sel (nww bitmap words) go to (fpos, fhead), at most cap of
+// them.  The bitmap goes to LDS whenever it fits (the bitmap of the windows of 64 K
+// positions: 6 KB for 3 Gbp); otherwise, and with GTAMD_WIN_FILTER_LDS=0, the
+// kernel reads it from global memory and is told nww_global words (each site's own)
+struct WinFilterTies {
+  const u64 *tiebits2;
+  const u32 *carry;
+  const u64 *swp;
+};
+template <typename Q>
+static int launch_win_filter(gtamd_esa_ctx *c, const Switches &sw, const Q *sa, u64 NL, int wb,
+                             const u32 *sel, u64 nww, u32 nww_global, const u32 *pref,
+                             const WinFilterTies &t, Q *fpos, u32 *fhead, u64 cap, u64 windows) {
+  hipStream_t st = c->st;
+  const bool wf_lds = (nww + 4) * 5 <= WF_LDS_MAX && !sw.win_filter_global;
+  if (sw.debug)
+    fprintf(stderr, "gtamd: part %u: win filter: bitmap=%s windows=%llu\n", c->part,
+            wf_lds ? "lds" : "global", (unsigned long long) windows);
+  const u32 grid = (u32) div_up(NL, WF_SPAN * WF_ITER);
+  if (wf_lds) {
+    // (more than the 64 KB a kernel gets without asking)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_win_filter<Q, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int) wf_lds_bytes<Q>(nww, true)));
+    k_win_filter<Q, true><<<grid, WF_THREADS, wf_lds_bytes<Q>(nww, true), st>>>(
+        sa, NL, wb, sel, (u32) nww, pref, t.tiebits2, t.carry, t.swp, fpos, fhead, cap, c->d_stats);
+  } else
+    k_win_filter<Q, false><<<grid, WF_THREADS, wf_lds_bytes<Q>(0, false), st>>>(
+        sa, NL, wb, sel, nww_global, pref, t.tiebits2, t.carry, t.swp, fpos, fhead, cap, c->d_stats);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// One run of the engine.  BITS: symbol width; WIDE: positions and ranks are 64-bit
+// (part builds of sequences with n >= 2^32).  The members are what outlives a
+// phase, grouped by the buffer they live in; the member functions are the phases,
+// in the order run() calls them.
 template <int BITS, bool WIDE>
-static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
+struct Build {
   using K = Key<BITS>;
   using P = typename std::conditional<WIDE, u64, u32>::type;
-  const u64 N = c->N, n = c->n;
-  const u32 R = c->numparts;
-  hipStream_t st = c->st;
-  // (a user-given prefix length is capped at the key width by
-  // gtamd_esa_set_prefixlength; the recommended one exceeds it from 2^26 symbols
-  // over 2 letters, 5^13 over 5)
-  const u32 prefixlength = c->user_prefixlength
-                               ? c->user_prefixlength
-                               : gtamd_recommended_prefixlength(c->sigma, n);
-  // beyond the key width the sums of finalize and of the tie paths cannot tell
-  // an entry's letters from its key: lcptabsum is taken from the finished tables
-  // (k_masked_lcpsum), which needs the suffix table
-  const bool long_prefix = prefixlength > (u32) K::SYMS;
-  if (long_prefix && (want & GTAMD_WANT_LCP)) want |= GTAMD_WANT_SUF;
-  const bool want_suf = want & GTAMD_WANT_SUF, want_lcp = want & GTAMD_WANT_LCP,
-             want_bwt = want & GTAMD_WANT_BWT;
-  if (dist && (want & GTAMD_WANT_BCK)) {
-    // as the reference: no bucket table from a run in parts
-    // (gt_Sfxiterator_bcktab2file, src/match/sfx-suffixer.c:2206-2217)
-    gtamd_set_error("the bucket table is not available from a part build");
-    return -1;
-  }
-  if (R > 1 && (c->comm_allgather == nullptr || c->comm_alltoallv == nullptr)) {
-    gtamd_set_error("a part build needs the collective callbacks "
-                    "(gtamd_esa_set_comm)");
-    return -1;
-  }
-  memset(&c->timing, 0, sizeof c->timing);
-  memset(&c->stats, 0, sizeof c->stats);
-  c->alloc_ms = 0;
-  c->llv_pairs = 0;
-  const bool debug = sw.debug;
+  static constexpr u64 RANKREC = 1 + sizeof(P) / 4;     // words of an (offset, rank) record
+  static constexpr u64 ISA_CHUNK = 1ull << 27;          // first ranks bucketed at a time
 
-  // ---- keygen (whole table, or the pairs of this part's key range)
-  u64 NL = N, index_offset = 0;
-  Tiles tl;
-  tl.T = N;
-  tl.self = c->part;
-  u64 Tn = N;                       // positions of the own text tile
-  int fail = 0;                     // local failure, reported in the next allgather
-  // DNA whole-table builds: the keygen also does the sort's first pass (the
-  // dcode digit); GTAMD_FUSED_PASS0=0 takes the plain keygen + full sort
-  bool pass0_done = false;
-  // DNA whole-table builds with 32-bit positions: keygen, sort and emission
-  // most significant digit first (esa_msd.h).  GTAMD_MSD=0 takes the LSD sort,
-  // GTAMD_MSD=1 the MSD sort at any size (tests; by default from 2^25 entries,
-  // where it starts to win: 2.3 against 2.6 ms at 50 M, 1.8 against 1.2 ms at 20 M)
-  bool msd = false;
-  u32 *msd_sa = nullptr, *msd_fval = nullptr;
-  u64 *msd_fkey = nullptr, msd_local = 0;
-  // (the 5-bit alphabets: by the 40-bit code of nine symbols, esa_msd.h FMT 1; the
-  // statistics mask with prefixlength, which the code must be able to tell: <= 9)
-  if (!dist && !WIDE && !(want & GTAMD_WANT_BCK) && N >= 64 && (BITS == 2 || (prefixlength <= 9 && c->sigma <= 20))) {
-    msd = sw.msd >= 0 ? sw.msd == 1 : N >= (1ull << 25);
-  }
-  // DNA part builds: the part's suffixes are filtered from the replicated text by
-  // their key range and sorted most significant digit first -- no pair is
-  // exchanged (GTAMD_MSD=0: tile keygen + alltoallv of the pairs + LSD sort, which
-  // is what the 5-bit alphabets still take)
-  bool msd_part = false;
-  u64 prev_key = 0;
+  // ---- fixed for the run
+  gtamd_esa_ctx *const c;
+  const Switches &sw;
+  u32 want;
+  const bool dist;                  // part build, or the part machinery with one part
+  const u64 N, n;
+  const u32 R;
+  const hipStream_t st;
+  const bool debug;
+
+  // ---- what the checks decide
+  u32 prefixlength = 0;
+  bool long_prefix = false, want_suf = false, want_lcp = false, want_bwt = false;
+  bool msd = false;          // the first sort is the MSD sort: the tables are out after it
+  bool msd_part = false;     // ... of a part that filters its suffixes from the text
+  bool fused_pass0 = false;
+
+  // A part that has failed locally (out of memory, a HIP error) says so in the NEXT
+  // allgather, where all parts leave together (comm_allgather): until then it goes
+  // on without launching anything on the buffers it did not get.  One flag, set by
+  // the step that failed and handed to the allgather that follows it: the first
+  // sort of a part, the arena of the pairs, the arena of the rounds, the buffers
+  // of the rank exchange.
+  int fail = 0;
+
+  // ---- the slice of this part (whole table: all of it)
+  u64 NL, index_offset = 0;
+  Tiles tl;                  // text tiles of the parts: who owns the rank of a position
+  u64 Tn;                    // positions of the own text tile
+  u64 prev_key = 0;          // largest key of the ranges below
   int has_prev = 0;
-  if (dist && BITS == 2) msd_part = !sw.msd_part_off;
-  // DNA whole-table builds with the LSD sort: keygen fused with its first pass
-  const bool fused_pass0 = !dist && !msd && BITS == 2 && sw.fused_pass0;
-  if (debug)
-    fprintf(stderr, "gtamd: part %u: run: parts=%u positions=%d first_sort=%s pass0=%s\n", c->part, R,
-            WIDE ? 64 : 32, msd || msd_part ? "msd" : "lsd",
-            dist || msd || BITS != 2 ? "none" : (fused_pass0 ? "fused" : "plain"));
-  if (!dist) {
+
+  // ---- what the first sort hands on.  (k0, v0) and (k1, v1) of the context are its
+  // ping-pong pairs; after it one pair holds the sorted slice and the other is free.
+  bool pass0_done = false;   // the keygen has done the first LSD pass
+  u32 *msd_sa = nullptr, *msd_fval = nullptr;   // MSD sort: where it left positions and
+  u64 *msd_fkey = nullptr, msd_local = 0;       // free buffers; entries k_msd_local saw
+  int nev = 0;               // scatter launches of the LSD sort timed in c->ev_scatter
+  u64 *skey = nullptr;       // sorted keys (nullptr behind the MSD sort); read by the
+                             // emission until c->ev_emitted
+  P *sa = nullptr;           // positions in suffix order, the build's working copy
+                             // (WIDE: in isa_tmp, whose bucketing scratch / kept keys are dead)
+  u64 *fkey = nullptr;       // free key-sized buffer: group heads of the rank table
+                             // build; WIDE part builds: the ranks of the own tile
+  u32 *fval = nullptr;       // free value-sized buffer: the rank table (single build) /
+                             // the ranks of the own tile (32-bit part build); behind the
+                             // rounds the LCP values beyond the byte (lcpfull)
+  u64 *d_suf = nullptr;      // outputs at on-disk width, nullptr: not wanted
+  u8 *d_lcp = nullptr, *d_bwt = nullptr;
+  bool emitted = false;      // the table emission has been launched
+
+  // ---- ties
+  u64 *tiebits = nullptr;    // bit i: entry i is tied with entry i - 1
+  u64 *tiebits2 = nullptr;   // ... without the pairs and the small groups
+  u64 numties = 0, anyties = 0;     // of this part, of all parts
+  u64 nwords = 0, nwb = 0;          // bitmap words, workgroups of 256 of them
+  u64 m0 = 0;                // tied suffixes on the unresolved list
+  u64 m0_tied_all = 0;       // ... before the direct settle emptied it (statistics)
+  u64 anyleft = 0;           // ... of all parts
+  u64 npairs = 0, nsmall = 0, nrec = 0;   // pairs, small groups, records of the pair list
+  u64 rank_built = 0;
+  u32 rounds = 0;
+  int nb = 0, nbl = 0;       // bits of a position / of an index into the slice
+  int ps[8], pw[8], pn = 0;  // radix passes over a position
+
+  // Per-word arrays of the tie bitmaps (nwords + 16 words each) in c->rws: the
+  // radix workspace is idle from the count of the ties to the end of the run.
+  // cntw / offw are reused by the .llv walk; pws is what is left of the workspace.
+  struct Words {
+    u32 *cntw, *headw, *offw, *carry;
+    u32 *pcnt, *poff;        // pair heads per word, and their scan
+    u32 *scnt, *soff;        // small-group heads per word, and their scan
+    u32 *rcnt, *roff;        // pairs of members of the small groups per word
+    u32 *scanws;
+    u32 *pws;                // radix workspace (NL pairs)
+    void carve(u32 *base, u64 nw) {
+      cntw = base;
+      headw = cntw + nw + 16;
+      offw = headw + nw + 16;
+      carry = offw + nw + 16;
+      pcnt = carry + nw + 16;
+      poff = pcnt + nw + 16;
+      scnt = poff + nw + 16;
+      soff = scnt + nw + 16;
+      rcnt = soff + nw + 16;
+      roff = rcnt + nw + 16;
+      scanws = roff + nw + 16;
+      pws = scanws + scan_workspace_words(nw) + 64;
+    }
+  } wd;
+
+  // Lists of the pairs and of the small groups, in c->arena_p from the pair path
+  // until their table entries are written (launch_apply: beside the rounds on the
+  // second stream, or behind them).
+  struct PairLists {
+    P *pk_a, *pk_b;
+    u64 *pv_a, *pv_b;
+    u32 *pidx, *pres, *prws, *sidx, *sres, *slcp, *srec;
+    u8 *ssize;
+    u64 *swp;     // the pairs in the wrong order by table index (k_pair_swapbits)
+    void carve(Bump &a, u64 records, u64 pairs, u64 groups, u64 nw) {
+      const u64 pp = (records + 64 + 3) & ~3ull;
+      const u64 sp = (groups + 64 + 3) & ~3ull;
+      pk_a = a.take<P>(pp); pk_b = a.take<P>(pp);
+      pv_a = a.take<u64>(pp); pv_b = a.take<u64>(pp);
+      pidx = a.take<u32>(pp); pres = a.take<u32>(pp);
+      prws = a.take<u32>(radix_workspace_words(records));
+      sidx = a.take<u32>(sp); sres = a.take<u32>(sp); slcp = a.take<u32>(3 * sp);
+      srec = a.take<u32>(sp);
+      ssize = a.take<u8>(sp);
+      swp = a.take<u64>(pairs > 0 ? 2 * nw + 8 : 0);
+    }
+  } pl;
+  // The pairs in the wrong order never change places in the suffix array: it
+  // is the build's working copy, and behind the pair path only the walks that
+  // rank the table's entries by their index read a pair's entries there --
+  // they take the resolved order from swp (swap_head).  (Swapped by
+  // k_pair_apply beside the rounds, the stores into the suffix array's lines
+  // cost the rounds 0.9 ms at 3 Gbp.)
+  const u64 *pair_swp = nullptr;    // pl.swp, or nullptr: no pairs
+  int apply_early = 0;       // GTAMD_APPLY_EARLY as it applies to this build
+  u64 apply_wgs = 256;
+  u32 *lcpfull = nullptr;    // LCP values beyond the byte, by table index: in
+                             // c->lcpfull_buf when the pairs' entries are written beside
+                             // the rounds, else in a buffer that has done its work (tie_fix)
+
+  // Unresolved list, round buffers and exchange buffers, in c->arena from
+  // carve_rounds to the end of the tie fix (the direct settle of few ties carves
+  // an unresolved list of its own there and ends the refinement).
+  struct Rounds {
+    u32 *uidx0, *uidx, *ugrp, *uidx2, *ugrp2;
+    P *upos, *upos2;
+    P *cvo;                  // positions in the round's new order
+    u32 *hv;                 // head values -> new group ids
+    u64 *keep;               // 1 bit per slot
+    u32 *koff;               // per-block survivor counts and their scan; tile counts of
+                             // a round until its apply step; counts of the tie fix
+    P *k2;                   // rank of the suffix h further on
+    u32 *flagbits;           // deferred to the global path (1 bit per slot)
+    u32 *tstart;             // where the tiles of a round start
+    // global path of a round (groups across tile borders)
+    P *fk2, *fk2s_a, *fk2s_b, *fpos, *cvs;
+    u32 *fgrp, *fj, *perm_a, *perm_b, *gk_a, *gk_b, *fhv;
+    // LCP pairs of the tie fix
+    P *lk_a, *lk_b;
+    u32 *lv_a, *lv_b;
+    u32 *rws2, *scanws2;     // radix + scan workspace for the rounds
+    // part builds: bucketing by owner and the messages of the exchanges
+    u32 *xoff, *xorder, *xqoff, *xmsg, *xbc_q, *xbo_q, *xbc_u, *xbo_u;
+    P *xrank, *xans;
+    u8 *xdest_q, *xdest_u;
+    void carve(Bump &a, u64 mp, u64 tied, u64 items, u32 parts, bool exchange) {
+      uidx0 = a.take<u32>(mp); uidx = a.take<u32>(mp); ugrp = a.take<u32>(mp);
+      uidx2 = a.take<u32>(mp); ugrp2 = a.take<u32>(mp);
+      upos = a.take<P>(mp); upos2 = a.take<P>(mp);
+      cvo = a.take<P>(mp);
+      hv = a.take<u32>(mp);
+      keep = a.take<u64>(mp / 64 + 4);
+      koff = a.take<u32>(mp);
+      k2 = a.take<P>(mp);
+      flagbits = a.take<u32>(mp / 32 + RT_TILE / 32 + 64);
+      tstart = a.take<u32>(mp / RT_STRIDE_MIN + 64);
+      fk2 = a.take<P>(mp); fk2s_a = a.take<P>(mp); fk2s_b = a.take<P>(mp);
+      fpos = a.take<P>(mp); cvs = a.take<P>(mp);
+      fgrp = a.take<u32>(mp); fj = a.take<u32>(mp);
+      perm_a = a.take<u32>(mp); perm_b = a.take<u32>(mp);
+      gk_a = a.take<u32>(mp); gk_b = a.take<u32>(mp);
+      fhv = a.take<u32>(mp);
+      lk_a = a.take<P>(mp); lk_b = a.take<P>(mp);
+      lv_a = a.take<u32>(mp); lv_b = a.take<u32>(mp);
+      rws2 = a.take<u32>(radix_workspace_words(tied));
+      scanws2 = a.take<u32>(scan_workspace_words(mp > dest_words(parts, items) ? mp : dest_words(parts, items)));
+      xoff = xorder = xqoff = xmsg = xbc_q = xbo_q = xbc_u = xbo_u = nullptr;
+      xrank = xans = nullptr;
+      xdest_q = xdest_u = nullptr;
+      if (exchange) {
+        xoff = a.take<u32>(items + 64); xorder = a.take<u32>(items + 64);
+        xrank = a.take<P>(items + 64); xans = a.take<P>(items + 64);
+        xqoff = a.take<u32>(items + 64);
+        // one message per exchange: the first ranks as records; a round's new
+        // ranks (records) and queries (offsets) together
+        xmsg = a.take<u32>((items + 64) * (RANKREC + 1));
+        xdest_q = a.take<u8>(items + 64); xdest_u = a.take<u8>(items + 64);
+        xbc_q = a.take<u32>(dest_words(parts, items)); xbo_q = a.take<u32>(dest_words(parts, items));
+        xbc_u = a.take<u32>(dest_words(parts, items)); xbo_u = a.take<u32>(dest_words(parts, items));
+      }
+    }
+  } ar;
+  u64 xm = 0;                // part builds: items bucketed at a time
+  u64 xrecv_n = 0;           // what one exchange can bring in
+  // received, in c->xrecv: a message of up to xrecv_n records and xrecv_n offsets,
+  // and behind it the answers to the offsets
+  u32 *xrecv_msg = nullptr;
+  P *xrecv_ans = nullptr;
+  P *rank = nullptr;         // whole table (single build), in fval ...
+  P *isa = nullptr;          // ... or the ranks of the own text tile (part build), in
+                             // fkey (WIDE) / fval
+
+  // Windows of positions whose ranks the rounds can reach: only those are built
+  // (single build) or travel (part build).  The bitmaps and the list live in
+  // c->winbuf from prepare_rank_table / prepare_rank_exchange to the last round.
+  struct RankWindows {
+    int wb = 0;              // a window is 2^wb positions
+    u64 nwin = 0, nww = 0;   // windows, words of a bitmap of them
+    u64 h0 = 0;              // offsets of the first rounds, marked before the first build
+    bool windows = false;    // only some windows are built / travel
+    u32 *w_need = nullptr, *w_built = nullptr, *w_sel = nullptr, *w_pref = nullptr,
+        *w_list = nullptr;
+    // part builds: the bitmaps on the host, own and of all parts
+    std::vector<u32> h_need, h_built, h_all;
+    // part builds: where the entries of the windows that travel are listed: a buffer
+    // that has done its work (isa_tmp: the keys the part filtered from the text;
+    // WIDE: posw, their positions)
+    P *lpos = nullptr;
+    u32 *lhead = nullptr;
+    u64 list_cap = 0;
+  } rk;
+
+  // Buffers and shape of the rank table build of a single build, constant from
+  // prepare_rank_table on.  heads / (qhead, qpos) are the free key buffer (fkey),
+  // (ppos, phead) the two halves of isa_tmp (skey is still being read by the
+  // emission), rank32 is fval.
+  struct RankTable {
+    u32 *rank32, *heads, *ppos, *phead, *qhead, *qpos;
+    const u32 *spos;         // sa
+    bool heads_array;
+    int wmax, pb, wb, split;
+    int fb;                  // the windows that are selected are finer than the windows the LDS takes
+    GroupHeadValues headgen;
+  } rt;
+
+  Build(gtamd_esa_ctx *ctx, const Switches &switches, u32 want_, bool dist_)
+      : c(ctx), sw(switches), want(want_), dist(dist_), N(ctx->N), n(ctx->n), R(ctx->numparts),
+        st(ctx->st), debug(switches.debug), NL(ctx->N), Tn(ctx->N) {
+    tl.T = N;
+    tl.self = c->part;
+  }
+
+  int run() {
+    TRY(plan());
+    if (!dist) TRY(first_sort_whole());
+    else if (msd_part) TRY(first_sort_filtered());
+    else TRY(first_sort_exchanged());
+    TRY(finish_first_sort());
+    TRY(count_ties());
+    if (anyties > 0) {
+      TRY(count_tied_words());
+      bool settled = false;
+      TRY(settle_few_ties(&settled));
+      if (!settled) {
+        TRY(pair_path());
+        TRY(place_apply());
+        if (apply_early == 1) TRY(apply_beside());
+        TRY(count_left());
+        TRY(carve_rounds());
+        TRY(settle_few_left());
+        if (anyleft > 0 && !dist) {
+          TRY(prepare_rank_table());
+          TRY(build_rank(true));
+        }
+        if (anyleft > 0 && dist) {
+          TRY(prepare_rank_exchange());
+          TRY(send_ranks());
+        }
+        TRY(launch_emission());   // (if the pair path has not started it)
+        if (apply_early == 2) TRY(apply_beside());
+        TRY(doubling_rounds());
+        TRY(tie_fix());
+      }
+    }
+    return report();
+  }
+
+  // ---- small steps several phases share ------------------------------------------
+  // what follows on the second stream starts behind everything launched on the
+  // first so far (c->ev_sorted is free again as soon as the wait is enqueued)
+  int fork_second_stream() {
+    HIP_TRY(hipEventRecord(c->ev_sorted, st));
+    HIP_TRY(hipStreamWaitEvent(c->st2, c->ev_sorted, 0));
+    return 0;
+  }
+
+  // Table emission (k_finalize, bandwidth-bound) runs on the second stream.
+  // It is started where the first stream turns latency-bound (the comparisons
+  // of the pair path, the rounds), so that the two actually overlap; whatever
+  // it writes for tied entries is provisional and overwritten after the join.
+  int launch_emission() {
+    if (emitted) return 0;
+    emitted = true;
+    TRY(fork_second_stream());
+    if (NL > 0) {
+      k_finalize<BITS, P><<<stride_grid(div_up(NL, FIN_TILE)), FIN_THREADS, 0, c->st2>>>(
+          skey, sa, NL, prefixlength, d_suf, d_lcp, d_bwt, nullptr,
+          c->d_stats, prev_key, has_prev, index_offset);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(c->ev_emitted, c->st2));
+    return 0;
+  }
+
+  // counts per word of a tie bitmap and their scans; the number of tied
+  // suffixes comes back in c->h_stats->count
+  int tie_words(const u64 *bits) {
+    if (NL > 0) {
+      k_tie_words<<<(u32) nwb, 256, 0, st>>>(bits, nwords, wd.cntw, wd.headw);
+      HIP_TRY(hipGetLastError());
+      TRY(scan_u32(SCAN_SUM, wd.cntw, wd.offw, nwb, false, wd.scanws, st));
+      TRY(scan_u32(SCAN_MAX, wd.headw, wd.carry, nwords, false, wd.scanws, st));
+    }
+    k_total<<<1, 1, 0, st>>>(wd.offw, wd.cntw, NL > 0 ? nwb : 0, c->d_stats);
+    HIP_TRY(hipGetLastError());
+    TRY(fetch_stats(c));
+    return 0;
+  }
+
+  // the m0 suffixes of an unresolved list settled by direct comparison, behind the
+  // emission; c->h_stats->dfallback != 0: a deep or a big group, not settled
+  u64 direct_limit() const { return NL / 512 > 4096 ? NL / 512 : 4096; }
+  int direct_ties(const u32 *uidx0, const u32 *ugrp, bool clear_fallback) {
+    TRY(launch_emission());
+    HIP_TRY(hipStreamWaitEvent(st, c->ev_emitted, 0));   // join the emission
+    if (clear_fallback) HIP_TRY(hipMemsetAsync(&c->d_stats->dfallback, 0, 4, st));
+    if (m0 > 0) {
+      k_direct_ties<BITS, P><<<(u32) div_up(m0, 256), 256, 0, st>>>(
+          c->text, uidx0, ugrp, m0, sa, d_suf, d_lcp, d_bwt, want_lcp,
+          index_offset, c->d_stats);
+      HIP_TRY(hipGetLastError());
+    }
+    TRY(fetch_stats(c));
+    return 0;
+  }
+  // discard the partial statistics of a direct attempt that gave up
+  int drop_direct_stats() {
+    HIP_TRY(hipMemsetAsync(&c->d_stats->dsum, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(&c->d_stats->dmax, 0, 4, st));
+    return 0;
+  }
+
+  // ---- checks, prefix length, which first sort --------------------------------------
+  int plan() {
+    // (a user-given prefix length is capped at the key width by
+    // gtamd_esa_set_prefixlength; the recommended one exceeds it from 2^26 symbols
+    // over 2 letters, 5^13 over 5)
+    prefixlength = c->user_prefixlength ? c->user_prefixlength
+                                        : gtamd_recommended_prefixlength(c->sigma, n);
+    // beyond the key width the sums of finalize and of the tie paths cannot tell
+    // an entry's letters from its key: lcptabsum is taken from the finished tables
+    // (k_masked_lcpsum), which needs the suffix table
+    long_prefix = prefixlength > (u32) K::SYMS;
+    if (long_prefix && (want & GTAMD_WANT_LCP)) want |= GTAMD_WANT_SUF;
+    want_suf = want & GTAMD_WANT_SUF;
+    want_lcp = want & GTAMD_WANT_LCP;
+    want_bwt = want & GTAMD_WANT_BWT;
+    if (dist && (want & GTAMD_WANT_BCK)) {
+      // as the reference: no bucket table from a run in parts
+      // (gt_Sfxiterator_bcktab2file, src/match/sfx-suffixer.c:2206-2217)
+      gtamd_set_error("the bucket table is not available from a part build");
+      return -1;
+    }
+    if (R > 1 && (c->comm_allgather == nullptr || c->comm_alltoallv == nullptr)) {
+      gtamd_set_error("a part build needs the collective callbacks "
+                      "(gtamd_esa_set_comm)");
+      return -1;
+    }
+    memset(&c->timing, 0, sizeof c->timing);
+    memset(&c->stats, 0, sizeof c->stats);
+    c->alloc_ms = 0;
+    c->llv_pairs = 0;
+    // DNA whole-table builds with 32-bit positions: keygen, sort and emission
+    // most significant digit first (esa_msd.h).  GTAMD_MSD=0 takes the LSD sort,
+    // GTAMD_MSD=1 the MSD sort at any size (tests; by default from 2^25 entries,
+    // where it starts to win: 2.3 against 2.6 ms at 50 M, 1.8 against 1.2 ms at 20 M)
+    // (the 5-bit alphabets: by the 40-bit code of nine symbols, esa_msd.h FMT 1; the
+    // statistics mask with prefixlength, which the code must be able to tell: <= 9)
+    if (!dist && !WIDE && !(want & GTAMD_WANT_BCK) && N >= 64 && (BITS == 2 || (prefixlength <= 9 && c->sigma <= 20))) {
+      msd = sw.msd >= 0 ? sw.msd == 1 : N >= (1ull << 25);
+    }
+    // DNA part builds: the part's suffixes are filtered from the replicated text by
+    // their key range and sorted most significant digit first -- no pair is
+    // exchanged (GTAMD_MSD=0: tile keygen + alltoallv of the pairs + LSD sort, which
+    // is what the 5-bit alphabets still take)
+    if (dist && BITS == 2) msd_part = !sw.msd_part_off;
+    // DNA whole-table builds with the LSD sort: the keygen also does the sort's
+    // first pass (the dcode digit); GTAMD_FUSED_PASS0=0 takes the plain keygen +
+    // full sort
+    fused_pass0 = !dist && !msd && BITS == 2 && sw.fused_pass0;
+    if (debug)
+      fprintf(stderr, "gtamd: part %u: run: parts=%u positions=%d first_sort=%s pass0=%s\n", c->part, R,
+              WIDE ? 64 : 32, msd || msd_part ? "msd" : "lsd",
+              dist || msd || BITS != 2 ? "none" : (fused_pass0 ? "fused" : "plain"));
+    return 0;
+  }
+
+  // ---- first sort, whole table: MSD sort / keygen fused with pass 0 / plain keygen ----
+  int first_sort_whole() {
     TRY(ensure_workspace(c, N, want, false));
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, sizeof(Stats), st));
-    HIP_TRY(hipEventRecord(c->ev[0], st));
+    HIP_TRY(hipEventRecord(c->ev[EV_START], st));
     if (msd) {
       TRY(msd_sort_emit<BITS == 5 ? 1 : 0>(c, sw, want, prefixlength, N, N, nullptr, &msd_sa, &msd_fkey, &msd_fval,
                                            &msd_local));
@@ -3973,109 +4415,101 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       k_keygen<BITS><<<(u32) div_up(N, 1024), 256, 0, st>>>(c->text, 0, N, c->k0.as<u64>(),
                                                             c->v0.as<u32>());
     HIP_TRY(hipGetLastError());
-  } else if (msd_part) {
+    return 0;
+  }
+
+  // ---- first sort of a part that filters its suffixes from the text -------------------
+  // a failure in it is local: it is reported with the count of the ties (count_ties)
+  int first_sort_filtered() {
     msd = true;
     // tile geometry of the rank table (cut by text position, see below)
-    tl.T = div_up(div_up(N, R), 4096) * 4096;
-    {
-      const u64 first = (u64) c->part * tl.T < N ? (u64) c->part * tl.T : N;
-      const u64 end = first + tl.T < N ? first + tl.T : N;
-      Tn = end - first;
-    }
-    auto part_sort = [&]() -> int {
-      HIP_TRY(hipMemsetAsync(c->d_stats, 0, sizeof(Stats), st));
-      HIP_TRY(hipEventRecord(c->ev[0], st));
-      // ---- range cuts from a histogram of the key bins over every stride-th
-      // suffix of the WHOLE text: every part computes the same counts (integer
-      // sums) and so the same cuts -- nothing to agree on
-      u32 *hist = c->h_hist;
-      // (a sample of 10^7 suffixes puts the cuts within 0.1 % of where all of them
-      // would; every workgroup flushes its 16 K counters with atomics: few workgroups)
-      const u64 stride = N > (1ull << 30) ? 256 : (N > (1u << 24) ? 16 : 1);
-      HIP_TRY(hipMemsetAsync(c->d_parthist, 0, PART_BINS * 4, st));
-      k_key_hist<BITS><<<N > (1ull << 30) ? 512 : 1024, 256, 0, st>>>(c->text, 0, N, stride, c->d_parthist);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(hist, c->d_parthist, PART_BINS * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      u64 nsamp = 0;
-      for (int b = 0; b < PART_BINS; b++) nsamp += hist[b];
-      std::vector<u32> cut(R + 1);
-      cut[0] = 0;
-      cut[R] = PART_BINS;
-      {
-        u64 run = 0;
-        u32 b = 0;
-        for (u32 r = 1; r < R; r++) {
-          const u64 target = (u64) (((unsigned __int128) nsamp * r) / R);
-          while (b < (u32) PART_BINS && run < target) run += hist[b++];
-          cut[r] = b;
-        }
-      }
-      const u32 lo = cut[c->part], hi = cut[c->part + 1];
-      // ---- what the part keeps: per text tile, below its range, in all
-      const u64 ntT64 = div_up(N, MS_TILE);
-      if (ntT64 >= (1ull << 31)) { gtamd_set_error("text of %llu tiles", (unsigned long long) ntT64); return -1; }
-      const u32 ntT = (u32) ntT64;
-      TRY(ensure_buf(c, c->partws, ((u64) ntT + 64 + scan_workspace_words(ntT)) * 4, "the tile counts of the part"));
-      u32 *tkeep = c->partws.as<u32>(), *tscan = tkeep + ntT + 32;
-      unsigned long long *acc = reinterpret_cast<unsigned long long *>(c->d_counts);
-      unsigned long long *hacc = reinterpret_cast<unsigned long long *>(c->h_counts);
-      HIP_TRY(hipMemsetAsync(acc, 0, 32, st));
-      HIP_TRY(hipMemsetAsync(tkeep, 0, (u64) ntT * 4, st));
-      k_part_count<<<ntT < 4096u ? ntT : 4096u, MS_THREADS, 0, st>>>(c->text, N, ntT, lo, hi, tkeep, acc);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(hacc, acc, 24, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      index_offset = hacc[0];
-      const u32 binbelow = hacc[0] > 0 ? (u32) hacc[1] : (u32) PART_BINS;
-      has_prev = hacc[0] > 0;
-      NL = hacc[2];
-      if (NL >= SINGLE_LIMIT) {
-        gtamd_set_error("slice of %llu entries exceeds the 32-bit index range of one "
-                        "part: use more parts", (unsigned long long) NL);
-        return -1;
-      }
-      // (everything behind the sort is sized for the slice or the text tile,
-      // whichever is larger: the rank table of the tile lives in the sort's buffers)
-      const u64 cap = NL > Tn ? NL : Tn;
-      TRY(ensure_workspace(c, cap, want, true));
-      if (WIDE) TRY(ensure_buf(c, c->posw, (NL + 8) * 8, "the positions of the part's suffixes"));
-      msd_sa = c->v0.as<u32>();
-      msd_fkey = c->k1.as<u64>();
-      msd_fval = c->v1.as<u32>();
-      if (NL == 0) {
-        HIP_TRY(hipMemsetAsync(c->tiebits.p, 0, 16, st));
-        HIP_TRY(hipEventRecord(c->ev[1], st));
-        return 0;
-      }
-      // ---- its keys and positions, in text order
-      TRY(scan_u32(SCAN_SUM, tkeep, tkeep, ntT, false, tscan, st));
-      u64 *ck = c->isa_tmp.as<u64>();
-      HIP_TRY(hipMemsetAsync(acc + 3, 0, 8, st));     // (the largest key below, made beside the filter)
-      if (WIDE)
-        k_part_filter<u64><<<ntT, MS_THREADS, 0, st>>>(c->text, N, lo, hi, binbelow, tkeep, ck,
-                                                      c->posw.as<u64>(), acc + 3);
-      else
-        k_part_filter<u32><<<ntT, MS_THREADS, 0, st>>>(c->text, N, lo, hi, binbelow, tkeep, ck,
-                                                      c->v1.as<u32>(), acc + 3);
-      HIP_TRY(hipGetLastError());
-      MsdPartSrc src;
-      src.ck = ck;
-      src.cp32 = WIDE ? nullptr : c->v1.as<u32>();
-      src.index_offset = index_offset;
-      src.prev_key = acc + 3;
-      src.has_prev = has_prev;
-      TRY(msd_sort_emit<0>(c, sw, want, prefixlength, NL, N, &src, &msd_sa, &msd_fkey, &msd_fval, &msd_local));
-      return 0;
-    };
-    fail = part_sort() != 0;
+    tl.T = Tiles::size_for(N, R);
+    Tn = tl.count(c->part, N);
+    fail = filter_and_sort() != 0;
     HIP_TRY(hipEventRecord(c->ev_emitted, st));
-  } else {
+    return 0;
+  }
+  int filter_and_sort() {
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, sizeof(Stats), st));
+    HIP_TRY(hipEventRecord(c->ev[EV_START], st));
+    // ---- range cuts from a histogram of the key bins over every stride-th
+    // suffix of the WHOLE text: every part computes the same counts (integer
+    // sums) and so the same cuts -- nothing to agree on
+    u32 *hist = c->h_hist;
+    // (a sample of 10^7 suffixes puts the cuts within 0.1 % of where all of them
+    // would; every workgroup flushes its 16 K counters with atomics: few workgroups)
+    const u64 stride = N > (1ull << 30) ? 256 : (N > (1u << 24) ? 16 : 1);
+    HIP_TRY(hipMemsetAsync(c->d_parthist, 0, PART_BINS * 4, st));
+    k_key_hist<BITS><<<N > (1ull << 30) ? 512 : 1024, 256, 0, st>>>(c->text, 0, N, stride, c->d_parthist);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hist, c->d_parthist, PART_BINS * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const std::vector<u32> cut = range_cuts(hist, R);
+    const u32 lo = cut[c->part], hi = cut[c->part + 1];
+    // ---- what the part keeps: per text tile, below its range, in all
+    const u64 ntT64 = div_up(N, MS_TILE);
+    if (ntT64 >= (1ull << 31)) { gtamd_set_error("text of %llu tiles", (unsigned long long) ntT64); return -1; }
+    const u32 ntT = (u32) ntT64;
+    TRY(ensure_buf(c, c->partws, ((u64) ntT + 64 + scan_workspace_words(ntT)) * 4, "the tile counts of the part"));
+    u32 *tkeep = c->partws.as<u32>(), *tscan = tkeep + ntT + 32;
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(c->d_counts);
+    unsigned long long *hacc = reinterpret_cast<unsigned long long *>(c->h_counts);
+    HIP_TRY(hipMemsetAsync(acc, 0, 32, st));
+    HIP_TRY(hipMemsetAsync(tkeep, 0, (u64) ntT * 4, st));
+    k_part_count<<<ntT < 4096u ? ntT : 4096u, MS_THREADS, 0, st>>>(c->text, N, ntT, lo, hi, tkeep, acc);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hacc, acc, 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    index_offset = hacc[0];
+    const u32 binbelow = hacc[0] > 0 ? (u32) hacc[1] : (u32) PART_BINS;
+    has_prev = hacc[0] > 0;
+    NL = hacc[2];
+    if (NL >= SINGLE_LIMIT) {
+      set_slice_error(NL);
+      return -1;
+    }
+    // (everything behind the sort is sized for the slice or the text tile,
+    // whichever is larger: the rank table of the tile lives in the sort's buffers)
+    const u64 cap = NL > Tn ? NL : Tn;
+    TRY(ensure_workspace(c, cap, want, true));
+    if (WIDE) TRY(ensure_buf(c, c->posw, (NL + 8) * 8, "the positions of the part's suffixes"));
+    msd_sa = c->v0.as<u32>();
+    msd_fkey = c->k1.as<u64>();
+    msd_fval = c->v1.as<u32>();
+    if (NL == 0) {
+      HIP_TRY(hipMemsetAsync(c->tiebits.p, 0, 16, st));
+      HIP_TRY(hipEventRecord(c->ev[EV_KEYS], st));
+      return 0;
+    }
+    // ---- its keys and positions, in text order
+    TRY(scan_u32(SCAN_SUM, tkeep, tkeep, ntT, false, tscan, st));
+    u64 *ck = c->isa_tmp.as<u64>();
+    HIP_TRY(hipMemsetAsync(acc + 3, 0, 8, st));     // (the largest key below, made beside the filter)
+    if (WIDE)
+      k_part_filter<u64><<<ntT, MS_THREADS, 0, st>>>(c->text, N, lo, hi, binbelow, tkeep, ck,
+                                                    c->posw.as<u64>(), acc + 3);
+    else
+      k_part_filter<u32><<<ntT, MS_THREADS, 0, st>>>(c->text, N, lo, hi, binbelow, tkeep, ck,
+                                                    c->v1.as<u32>(), acc + 3);
+    HIP_TRY(hipGetLastError());
+    MsdPartSrc src;
+    src.ck = ck;
+    src.cp32 = WIDE ? nullptr : c->v1.as<u32>();
+    src.index_offset = index_offset;
+    src.prev_key = acc + 3;
+    src.has_prev = has_prev;
+    TRY(msd_sort_emit<0>(c, sw, want, prefixlength, NL, N, &src, &msd_sa, &msd_fkey, &msd_fval, &msd_local));
+    return 0;
+  }
+
+  // ---- first sort of a part, keys of the own text tile: keygen, exchange of the pairs ----
+  // (the LSD passes over what arrives: finish_first_sort)
+  int first_sort_exchanged() {
     // the own text tile: T positions per part, a multiple of the keygen tile
-    tl.T = div_up(div_up(N, R), 4096) * 4096;
-    const u64 first = (u64) c->part * tl.T < N ? (u64) c->part * tl.T : N;
-    const u64 end = first + tl.T < N ? first + tl.T : N;
-    Tn = end - first;
+    tl.T = Tiles::size_for(N, R);
+    const u64 first = tl.first(c->part, N);
+    Tn = tl.count(c->part, N);
+    const u64 end = first + Tn;
     // room for the slice: the tile plus a margin for uneven ranges (grown
     // below, once the real slice size is known, if that is not enough)
     u64 cap = Tn + Tn / 8 + 65536;
@@ -4083,7 +4517,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
     fail |= ensure_workspace(c, cap, want, true) != 0;
     if (!fail) {
       HIP_TRY(hipMemsetAsync(c->d_stats, 0, sizeof(Stats), st));
-      HIP_TRY(hipEventRecord(c->ev[0], st));
+      HIP_TRY(hipEventRecord(c->ev[EV_START], st));
     }
     // range cuts from a histogram of the key bins over every 16th suffix: every
     // part counts its own tile, the sum is the same on every part
@@ -4111,24 +4545,11 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       HIP_TRY(hipStreamSynchronize(st));
     }
     TRY(comm_allgather(c, fail, hist, allhist.data(), PART_BINS * 4));
-    std::vector<u64> start(PART_BINS + 1);
-    start[0] = 0;
-    for (int b = 0; b < PART_BINS; b++) {
-      u64 s = 0;
-      for (u32 r = 0; r < R; r++) s += allhist[(size_t) r * PART_BINS + b];
-      start[b + 1] = start[b] + s;
-    }
-    const u64 nsamp = start[PART_BINS];
-    std::vector<u32> cut(R + 1);
+    std::vector<u64> bins(PART_BINS, 0);
+    for (int b = 0; b < PART_BINS; b++)
+      for (u32 r = 0; r < R; r++) bins[b] += allhist[(size_t) r * PART_BINS + b];
+    const std::vector<u32> cut = range_cuts(bins.data(), R);
     std::vector<u8> owner(PART_BINS);
-    cut[0] = 0;
-    cut[R] = PART_BINS;
-    for (u32 r = 1; r < R; r++) {
-      const u64 target = (u64) (((unsigned __int128) nsamp * r) / R);
-      u32 b = cut[r - 1];
-      while (b < (u32) PART_BINS && start[b] < target) b++;
-      cut[r] = b;
-    }
     for (u32 r = 0; r < R; r++)
       for (u32 b = cut[r]; b < cut[r + 1]; b++) owner[b] = (u8) r;
     HIP_TRY(hipMemcpyAsync(c->d_owner, owner.data(), PART_BINS,
@@ -4172,8 +4593,7 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       fail = 1;
     }
     if (NL >= SINGLE_LIMIT) {
-      gtamd_set_error("slice of %llu entries exceeds the 32-bit index range of one "
-                      "part: use more parts", (unsigned long long) NL);
+      set_slice_error(NL);
       fail = 1;
     }
     // the receive side first (its old contents -- the unbucketed pairs -- are
@@ -4191,227 +4611,161 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
       HIP_TRY(hipStreamSynchronize(st));   // k1/v1 have been sent
       fail |= ensure_workspace(c, NL, want, true) != 0;
       // (a failure here is reported by the next allgather; nothing is launched
-      // on the missing buffers, see `fail` below)
+      // on the missing buffers, see `fail` in finish_first_sort)
     }
-  }
-  c->NL = NL;
-  c->index_offset = index_offset;
-  if (debug)
-    fprintf(stderr, "gtamd: part %u/%u: tile %llu positions, slice %llu entries at %llu%s\n",
-            c->part, R, (unsigned long long) Tn, (unsigned long long) NL,
-            (unsigned long long) index_offset, WIDE ? " (64-bit positions)" : "");
-  // (a part that filters its suffixes from the text reports a failure with the
-  // count of its ties, further down: no exchange of its own for it)
-  if (dist && !msd_part) TRY(comm_allgather(c, fail, nullptr, nullptr, 0));
-  if (!msd) HIP_TRY(hipEventRecord(c->ev[1], st));   // (the MSD sort: after its level A)
-
-  // ---- first sort: all key bits above the payload
-  int shifts[16], widths[16], np = 0;
-  if (pass0_done) {   // the dcode digit is sorted: the prefix bits are left
-    static_assert((64 - Key<2>::LOW_BITS) % 8 == 0, "whole passes over the DNA prefix");
-    for (int b = K::LOW_BITS; b < 64; b += 8) {
-      shifts[np] = b;
-      widths[np] = 64 - b < 8 ? 64 - b : 8;
-      np++;
-    }
-  } else
-  for (int b = K::DSHIFT; b < 64; b += 8) {   // dcode and prefix, contiguous
-    shifts[np] = b;
-    widths[np] = 64 - b < 8 ? 64 - b : 8;
-    np++;
-  }
-  int nev = 0;
-  u64 *ka = pass0_done ? c->k1.as<u64>() : c->k0.as<u64>(),
-      *kb = pass0_done ? c->k0.as<u64>() : c->k1.as<u64>();
-  u32 *va = pass0_done ? c->v1.as<u32>() : c->v0.as<u32>(),
-      *vb = pass0_done ? c->v0.as<u32>() : c->v1.as<u32>();
-  if (!msd)
-    TRY(radix_sort_pairs<u64, u32>(ka, va, kb, vb, NL, shifts, widths, np,
-                              c->rws.as<u32>(), st, c->ev_scatter, &nev));
-  u64 *skey = (np & 1) ? kb : ka;   // sorted keys
-  u32 *sa32 = (np & 1) ? vb : va;   // positions in suffix order (low half)
-  u64 *fkey = (np & 1) ? ka : kb;   // free key-sized buffer
-  u32 *fval = (np & 1) ? va : vb;   // free value-sized buffer
-  if (msd) {
-    skey = nullptr;                 // (no sorted keys: the tables are out already)
-    sa32 = msd_sa;
-    fkey = msd_fkey;
-    fval = msd_fval;
-  }
-  HIP_TRY(hipEventRecord(c->ev[2], st));
-
-  if (want & GTAMD_WANT_BCK) TRY(build_bcktab<BITS>(c, skey, sa32, NL, prefixlength, st));
-
-  // positions at the width the refinement works with
-  P *sa;
-  if (WIDE) {
-    u64 *sa64 = c->isa_tmp.as<u64>();   // (the bucketing scratch / the kept keys are dead)
-    if (NL > 0 && msd_part && !fail) {
-      k_part_positions<<<(u32) div_up(NL, 256), 256, 0, st>>>(
-          sa32, c->posw.as<u64>(), NL, index_offset, sa64, want_suf ? c->suf.as<u64>() : nullptr,
-          c->d_stats);
-      HIP_TRY(hipGetLastError());
-    } else if (NL > 0 && !msd_part) {
-      k_wide_positions<BITS><<<(u32) div_up(NL, 256), 256, 0, st>>>(skey, sa32, NL, sa64);
-      HIP_TRY(hipGetLastError());
-    }
-    sa = reinterpret_cast<P *>(sa64);
-  } else
-    sa = reinterpret_cast<P *>(sa32);
-  u64 *d_suf = want_suf ? c->suf.as<u64>() : nullptr;
-  u8 *d_lcp = want_lcp ? c->lcp.as<u8>() : nullptr;
-  u8 *d_bwt = want_bwt ? c->bwt.as<u8>() : nullptr;
-
-  // ---- finalize; a part needs the last key of the preceding range (the MSD
-  // sort of a part has it from its count of the text)
-  if (R > 1 && !msd_part) {
-    u64 mine[2] = {NL, 0};
-    HIP_TRY(hipStreamSynchronize(st));
-    if (NL > 0)   // (blocking copy: the destination is on this stack frame)
-      HIP_TRY(hipMemcpy(&mine[1], skey + (NL - 1), 8, hipMemcpyDeviceToHost));
-    std::vector<u64> all(2 * (size_t) R);
-    TRY(comm_allgather(c, 0, mine, all.data(), 16));
-    for (u32 r = 0; r < c->part; r++)
-      if (all[2 * r] > 0) { prev_key = all[2 * r + 1]; has_prev = 1; }
-  }
-  // Table emission (k_finalize, bandwidth-bound) runs on the second stream.
-  // It is started where the first stream turns latency-bound (the comparisons
-  // of the pair path, the rounds), so that the two actually overlap; whatever
-  // it writes for tied entries is provisional and overwritten after the join.
-  bool emitted = msd;
-  auto launch_emission = [&]() -> int {
-    if (emitted) return 0;
-    emitted = true;
-    HIP_TRY(hipEventRecord(c->ev_sorted, st));
-    HIP_TRY(hipStreamWaitEvent(c->st2, c->ev_sorted, 0));
-    if (NL > 0) {
-      k_finalize<BITS, P><<<stride_grid(div_up(NL, FIN_TILE)), FIN_THREADS, 0, c->st2>>>(
-          skey, sa, NL, prefixlength, d_suf, d_lcp, d_bwt, nullptr,
-          c->d_stats, prev_key, has_prev, index_offset);
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(c->ev_emitted, c->st2));
     return 0;
-  };
-  u64 *tiebits = c->tiebits.as<u64>();
-  if (NL > 0 && !msd) {
-    k_tiebits<BITS><<<stride_grid(div_up(NL, 4096)), 256, 0, st>>>(skey, NL, tiebits,
-                                                                   c->d_stats);
-    HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(c->ev[3], st));
-  if (!(msd_part && fail)) TRY(fetch_stats(c));
-  const u64 numties = (msd_part && fail) ? 0 : c->h_stats->numties;
-  u64 anyties = numties;
-  if (msd_part && fail && R == 1) return -1;
-  if (R > 1) {
-    std::vector<u64> all(R);
-    TRY(comm_allgather(c, msd_part ? fail : 0, &numties, all.data(), 8));
-    anyties = 0;
-    for (u32 r = 0; r < R; r++) anyties += all[r];
-  }
-  u32 rounds = 0;
-  u64 m0 = 0, npairs = 0, m0_tied_all = 0, rank_built = 0;
-  HIP_TRY(hipEventRecord(c->ev[4], st));
-  HIP_TRY(hipEventRecord(c->ev[5], st));
-  if (anyties > 0) {
-    // ---- how many suffixes are tied with a neighbour
-    const u64 nwords = div_up(NL, 64);
-    u32 *cntw = c->rws.as<u32>();          // radix workspace is idle now
-    u32 *headw = cntw + nwords + 16;
-    u32 *offw = headw + nwords + 16;
-    u32 *carry = offw + nwords + 16;
-    u32 *pcnt = carry + nwords + 16;       // pair heads per word, and their scan
-    u32 *poff = pcnt + nwords + 16;
-    u32 *scnt = poff + nwords + 16;        // small-group heads per word, and their scan
-    u32 *soff = scnt + nwords + 16;
-    u32 *rcnt = soff + nwords + 16;        // pairs of members of the small groups per word
-    u32 *roff = rcnt + nwords + 16;
-    u32 *scanws = roff + nwords + 16;
-    u32 *pws = scanws + scan_workspace_words(nwords) + 64;   // radix workspace (NL pairs)
-    const u64 nwb = div_up(nwords, 256);   // workgroups of 256 bitmap words
-    auto tie_words = [&](const u64 *bits) -> int {
-      if (NL > 0) {
-        k_tie_words<<<(u32) nwb, 256, 0, st>>>(bits, nwords, cntw, headw);
+
+  // ---- LSD passes, bucket table, positions at width P, the previous part's last key ----
+  int finish_first_sort() {
+    c->NL = NL;
+    c->index_offset = index_offset;
+    if (debug)
+      fprintf(stderr, "gtamd: part %u/%u: tile %llu positions, slice %llu entries at %llu%s\n",
+              c->part, R, (unsigned long long) Tn, (unsigned long long) NL,
+              (unsigned long long) index_offset, WIDE ? " (64-bit positions)" : "");
+    // (a part that filters its suffixes from the text reports a failure with the
+    // count of its ties, further down: no exchange of its own for it)
+    if (dist && !msd_part) TRY(comm_allgather(c, fail, nullptr, nullptr, 0));
+    if (!msd) HIP_TRY(hipEventRecord(c->ev[EV_KEYS], st));   // (the MSD sort: after its level A)
+
+    // ---- first sort: all key bits above the payload (the dcode digit is sorted by
+    // a fused keygen: the prefix bits are left; else dcode and prefix, contiguous)
+    static_assert((64 - Key<2>::LOW_BITS) % 8 == 0, "whole passes over the DNA prefix");
+    int shifts[16], widths[16];
+    const int np = passes_for(pass0_done ? K::LOW_BITS : K::DSHIFT, 64, shifts, widths);
+    u64 *ka = pass0_done ? c->k1.as<u64>() : c->k0.as<u64>(),
+        *kb = pass0_done ? c->k0.as<u64>() : c->k1.as<u64>();
+    u32 *va = pass0_done ? c->v1.as<u32>() : c->v0.as<u32>(),
+        *vb = pass0_done ? c->v0.as<u32>() : c->v1.as<u32>();
+    if (!msd)
+      TRY(radix_sort_pairs<u64, u32>(ka, va, kb, vb, NL, shifts, widths, np,
+                                c->rws.as<u32>(), st, c->ev_scatter, &nev));
+    skey = (np & 1) ? kb : ka;        // sorted keys
+    u32 *sa32 = (np & 1) ? vb : va;   // positions in suffix order (low half)
+    fkey = (np & 1) ? ka : kb;        // free key-sized buffer
+    fval = (np & 1) ? va : vb;        // free value-sized buffer
+    if (msd) {
+      skey = nullptr;                 // (no sorted keys: the tables are out already)
+      sa32 = msd_sa;
+      fkey = msd_fkey;
+      fval = msd_fval;
+    }
+    HIP_TRY(hipEventRecord(c->ev[EV_SORTED], st));
+
+    if (want & GTAMD_WANT_BCK) TRY(build_bcktab<BITS>(c, skey, sa32, NL, prefixlength, st));
+
+    // positions at the width the refinement works with
+    if (WIDE) {
+      u64 *sa64 = c->isa_tmp.as<u64>();   // (the bucketing scratch / the kept keys are dead)
+      if (NL > 0 && msd_part && !fail) {
+        k_part_positions<<<(u32) div_up(NL, 256), 256, 0, st>>>(
+            sa32, c->posw.as<u64>(), NL, index_offset, sa64, want_suf ? c->suf.as<u64>() : nullptr,
+            c->d_stats);
         HIP_TRY(hipGetLastError());
-        TRY(scan_u32(SCAN_SUM, cntw, offw, nwb, false, scanws, st));
-        TRY(scan_u32(SCAN_MAX, headw, carry, nwords, false, scanws, st));
+      } else if (NL > 0 && !msd_part) {
+        k_wide_positions<BITS><<<(u32) div_up(NL, 256), 256, 0, st>>>(skey, sa32, NL, sa64);
+        HIP_TRY(hipGetLastError());
       }
-      k_total<<<1, 1, 0, st>>>(offw, cntw, NL > 0 ? nwb : 0, c->d_stats);
+      sa = reinterpret_cast<P *>(sa64);
+    } else
+      sa = reinterpret_cast<P *>(sa32);
+    d_suf = want_suf ? c->suf.as<u64>() : nullptr;
+    d_lcp = want_lcp ? c->lcp.as<u8>() : nullptr;
+    d_bwt = want_bwt ? c->bwt.as<u8>() : nullptr;
+
+    // ---- finalize; a part needs the last key of the preceding range (the MSD
+    // sort of a part has it from its count of the text)
+    if (R > 1 && !msd_part) {
+      u64 mine[2] = {NL, 0};
+      HIP_TRY(hipStreamSynchronize(st));
+      if (NL > 0)   // (blocking copy: the destination is on this stack frame)
+        HIP_TRY(hipMemcpy(&mine[1], skey + (NL - 1), 8, hipMemcpyDeviceToHost));
+      std::vector<u64> all(2 * (size_t) R);
+      TRY(comm_allgather(c, 0, mine, all.data(), 16));
+      for (u32 r = 0; r < c->part; r++)
+        if (all[2 * r] > 0) { prev_key = all[2 * r + 1]; has_prev = 1; }
+    }
+    emitted = msd;
+    return 0;
+  }
+
+  // ---- tie bitmap, the number of ties, whether any part has some ----------------------
+  int count_ties() {
+    tiebits = c->tiebits.as<u64>();
+    if (NL > 0 && !msd) {
+      k_tiebits<BITS><<<stride_grid(div_up(NL, 4096)), 256, 0, st>>>(skey, NL, tiebits,
+                                                                     c->d_stats);
       HIP_TRY(hipGetLastError());
-      TRY(fetch_stats(c));
-      return 0;
-    };
+    }
+    HIP_TRY(hipEventRecord(c->ev[EV_TIEBITS], st));
+    if (!(msd_part && fail)) TRY(fetch_stats(c));
+    numties = (msd_part && fail) ? 0 : c->h_stats->numties;
+    anyties = numties;
+    if (msd_part && fail && R == 1) return -1;
+    if (R > 1) TRY(allgather_word(c, msd_part ? fail : 0, RED_SUM, &anyties));
+    HIP_TRY(hipEventRecord(c->ev[EV_REFINE_BEGIN], st));
+    HIP_TRY(hipEventRecord(c->ev[EV_REFINE_END], st));
+    return 0;
+  }
+
+  // ---- how many suffixes are tied with a neighbour: the counts per word ---------------
+  int count_tied_words() {
+    nwords = div_up(NL, 64);
+    nwb = div_up(nwords, 256);
+    wd.carve(c->rws.as<u32>(), nwords);    // radix workspace is idle now
     TRY(tie_words(tiebits));
     m0 = c->h_stats->count;
-    // few shallow ties: settle them by direct comparison, no rank table
-    bool settled = false;
-    {
-      const u64 thresh = NL / 512 > 4096 ? NL / 512 : 4096;
-      u64 small = m0 <= thresh;
-      if (R > 1) {
-        std::vector<u64> all(R);
-        TRY(comm_allgather(c, 0, &small, all.data(), 8));
-        for (u32 r = 0; r < R; r++) small &= all[r];
+    return 0;
+  }
+
+  // ---- few shallow ties: settle them by direct comparison, no rank table -------------
+  int settle_few_ties(bool *settled) {
+    *settled = false;
+    u64 small = m0 <= direct_limit();
+    if (R > 1) TRY(allgather_word(c, 0, RED_AND, &small));
+    if (!small) return 0;
+    const u64 mp = (m0 + 64 + 3) & ~3ull;
+    const int bad = ensure_buf(c, c->arena, mp * (12 + sizeof(P)) + 4096, "the tied suffixes") != 0;
+    if (!bad) {
+      Bump a = {c->arena.as<u8>(), 0};
+      u32 *uidx0 = a.take<u32>(mp), *uidx = a.take<u32>(mp), *ugrp = a.take<u32>(mp);
+      P *upos = a.take<P>(mp);
+      if (m0 > 0) {
+        k_unres_emit<P><<<(u32) div_up(nwords, 256), 256, 0, st>>>(
+            tiebits, nwords, wd.offw, wd.carry, sa, uidx0, uidx, upos, ugrp);
+        HIP_TRY(hipGetLastError());
       }
-      if (small) {
-        const u64 mp = (m0 + 64 + 3) & ~3ull;
-        int bad = ensure_buf(c, c->arena, mp * (12 + sizeof(P)) + 4096, "the tied suffixes") != 0;
-        if (!bad) {
-          Bump a = {c->arena.as<u8>(), 0};
-          u32 *uidx0 = a.take<u32>(mp), *uidx = a.take<u32>(mp), *ugrp = a.take<u32>(mp);
-          P *upos = a.take<P>(mp);
-          if (m0 > 0) {
-            k_unres_emit<P><<<(u32) div_up(nwords, 256), 256, 0, st>>>(
-                tiebits, nwords, offw, carry, sa, uidx0, uidx, upos, ugrp);
-            HIP_TRY(hipGetLastError());
-          }
-          TRY(launch_emission());
-          HIP_TRY(hipStreamWaitEvent(st, c->ev_emitted, 0));   // join the emission
-          if (m0 > 0) {
-            k_direct_ties<BITS, P><<<(u32) div_up(m0, 256), 256, 0, st>>>(
-                c->text, uidx0, ugrp, m0, sa, d_suf, d_lcp, d_bwt, want_lcp,
-                index_offset, c->d_stats);
-            HIP_TRY(hipGetLastError());
-          }
-          TRY(fetch_stats(c));
-        }
-        u64 gaveup = bad ? 1 : c->h_stats->dfallback;
-        if (R > 1) {
-          std::vector<u64> all(R);
-          TRY(comm_allgather(c, bad, &gaveup, all.data(), 8));
-          gaveup = 0;
-          for (u32 r = 0; r < R; r++) gaveup |= all[r];
-        } else if (bad)
-          return -1;
-        settled = gaveup == 0;
-        if (!settled) {
-          // discard the partial statistics of the direct attempt
-          HIP_TRY(hipMemsetAsync(&c->d_stats->dsum, 0, 8, st));
-          HIP_TRY(hipMemsetAsync(&c->d_stats->dmax, 0, 4, st));
-        }
-      }
+      TRY(direct_ties(uidx0, ugrp, false));
     }
-    if (!settled) {
-    // ---- pairs and small groups leave the bitmap; what is left goes through
-    // prefix doubling
+    u64 gaveup = bad ? 1 : c->h_stats->dfallback;
+    if (R > 1) TRY(allgather_word(c, bad, RED_OR, &gaveup));
+    else if (bad) return -1;
+    *settled = gaveup == 0;
+    if (!*settled) TRY(drop_direct_stats());
+    return 0;
+  }
+
+  // ---- pairs and small groups leave the bitmap; what is left goes through
+  // prefix doubling
+  int pair_path() {
     TRY(ensure_buf(c, c->tiebits2, (nwords + 2) * 8, "the tie bitmap"));
-    u64 *tiebits2 = c->tiebits2.as<u64>();
+    tiebits2 = c->tiebits2.as<u64>();
     const bool no_pairs = sw.no_pairs;
     const bool no_small = no_pairs || sw.no_small_groups;
-    u64 nsmall = 0, nsrec = 0;
+    u64 nsrec = 0;
     if (NL > 0) {
       if (no_pairs) {
         HIP_TRY(hipMemcpyAsync(tiebits2, tiebits, nwords * 8, hipMemcpyDeviceToDevice, st));
       } else {
-        k_pair_words<<<(u32) nwb, 256, 0, st>>>(tiebits, nwords, pcnt, scnt, rcnt, tiebits2);
+        k_pair_words<<<(u32) nwb, 256, 0, st>>>(tiebits, nwords, wd.pcnt, wd.scnt, wd.rcnt, tiebits2);
         HIP_TRY(hipGetLastError());
-        TRY(scan_u32(SCAN_SUM, pcnt, poff, nwb, false, scanws, st));
-        TRY(scan_u32(SCAN_SUM, scnt, soff, nwb, false, scanws, st));
-        TRY(scan_u32(SCAN_SUM, rcnt, roff, nwb, false, scanws, st));
-        k_total2<<<1, 1, 0, st>>>(poff, pcnt, nwb, c->d_stats);
-        k_total3<<<1, 1, 0, st>>>(soff, scnt, nwb, c->d_stats);
-        k_total<<<1, 1, 0, st>>>(roff, rcnt, nwb, c->d_stats);
+        TRY(scan_u32(SCAN_SUM, wd.pcnt, wd.poff, nwb, false, wd.scanws, st));
+        TRY(scan_u32(SCAN_SUM, wd.scnt, wd.soff, nwb, false, wd.scanws, st));
+        TRY(scan_u32(SCAN_SUM, wd.rcnt, wd.roff, nwb, false, wd.scanws, st));
+        k_total2<<<1, 1, 0, st>>>(wd.poff, wd.pcnt, nwb, c->d_stats);
+        k_total3<<<1, 1, 0, st>>>(wd.soff, wd.scnt, nwb, c->d_stats);
+        k_total<<<1, 1, 0, st>>>(wd.roff, wd.rcnt, nwb, c->d_stats);
         HIP_TRY(hipGetLastError());
         TRY(fetch_stats(c));
         npairs = c->h_stats->count2;
@@ -4423,111 +4777,86 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
     // small part of the table (a sequence set with three or four near-identical
     // members has them everywhere: prefix doubling is the better tool then)
     if (no_small || nsrec > NL / 8 || npairs + nsrec >= SINGLE_LIMIT) { nsmall = 0; nsrec = 0; }
-    const u64 nrec = npairs + nsrec;          // records of the pair list
-    const u64 pp = (nrec + 64 + 3) & ~3ull;
-    const u64 sp = (nsmall + 64 + 3) & ~3ull;
-    P *pk_a = nullptr, *pk_b = nullptr;
-    u64 *pv_a = nullptr, *pv_b = nullptr;
-    u32 *pidx = nullptr, *pres = nullptr, *prws = nullptr, *sidx = nullptr, *sres = nullptr,
-        *slcp = nullptr, *srec = nullptr;
-    u8 *ssize = nullptr;
-    u64 *swp = nullptr;     // the pairs in the wrong order by table index (k_pair_swapbits)
-    auto layout_p = [&](Bump &a) {
-      pk_a = a.take<P>(pp); pk_b = a.take<P>(pp);
-      pv_a = a.take<u64>(pp); pv_b = a.take<u64>(pp);
-      pidx = a.take<u32>(pp); pres = a.take<u32>(pp);
-      prws = a.take<u32>(radix_workspace_words(nrec));
-      sidx = a.take<u32>(sp); sres = a.take<u32>(sp); slcp = a.take<u32>(3 * sp);
-      srec = a.take<u32>(sp);
-      ssize = a.take<u8>(sp);
-      swp = a.take<u64>(npairs > 0 ? 2 * nwords + 8 : 0);
-    };
-    // (GTAMD_APPLY_EARLY, see below: the table entries of the pairs beside the
+    nrec = npairs + nsrec;          // records of the pair list
+    // (GTAMD_APPLY_EARLY, see place_apply: the table entries of the pairs beside the
     // rounds need a buffer of their own for the LCP values beyond the byte; both
     // buffers of this step are agreed on in one exchange)
-    int apply_early = sw.apply_early;
+    apply_early = sw.apply_early;
     {
       Bump sz = {nullptr, 0};
-      layout_p(sz);
+      pl.carve(sz, nrec, npairs, nsmall, nwords);
       fail = ensure_buf(c, c->arena_p, sz.off + 4096, "the pairs of tied suffixes") != 0;
       if (!fail && want_lcp && apply_early && nrec > 0)
         fail = ensure_buf(c, c->lcpfull_buf, (NL + 8) * 4, "the LCP values beyond the byte") != 0;
       if (R > 1) TRY(comm_allgather(c, fail, nullptr, nullptr, 0));
       else if (fail) return -1;
       Bump a = {c->arena_p.as<u8>(), 0};
-      layout_p(a);
+      pl.carve(a, nrec, npairs, nsmall, nwords);
     }
-    const int nb = bits_for(N - 1);      // bits of a position / of a rank
-    const int nbl = bits_for(NL ? NL - 1 : 0);   // bits of an index into the slice
-    auto passes_for = [](int bits, int *ps, int *pw) -> int {
-      int cnt = 0;
-      for (int b = 0; b < bits; b += 8) {
-        ps[cnt] = b;
-        pw[cnt] = bits - b < 8 ? bits - b : 8;
-        cnt++;
-      }
-      return cnt;
-    };
-    int ps[8], pw[8];
-    const int pn = passes_for(nb, ps, pw);
+    nb = bits_for(N - 1);
+    nbl = bits_for(NL ? NL - 1 : 0);
+    pn = passes_for(0, nb, ps, pw);
+    pair_swp = npairs > 0 ? pl.swp : nullptr;
+    if (nrec == 0) return 0;
     // ---- the pairs (and the pairs of members of the small groups): sorted by
     // text position, compared
-    if (nrec > 0) {
-      if (npairs > 0) {
-        k_pair_emit<P><<<(u32) div_up(nwords, 256), 256, 0, st>>>(tiebits, nwords, poff, sa, pk_a,
-                                                                 pv_a, pidx);
-        HIP_TRY(hipGetLastError());
-      }
-      if (nsmall > 0) {
-        k_small_emit<P><<<(u32) div_up(nwords, 256), 256, 0, st>>>(
-            tiebits, nwords, soff, roff, sa, npairs, sidx, ssize, srec, pk_a, pv_a);
-        HIP_TRY(hipGetLastError());
-      }
-      TRY(radix_sort_pairs<P, u64>(pk_a, pv_a, pk_b, pv_b, nrec, ps, pw, pn, prws, st,
-                                   nullptr, nullptr));
-      const P *pk_sorted = (pn & 1) ? pk_b : pk_a;
-      const u64 *pv_sorted = (pn & 1) ? pv_b : pv_a;
-      TRY(launch_emission());   // bandwidth-bound, beside the comparisons
-      // pairs per thread: a chunk's first pair pays its whole comparison, the
-      // others ride on the diagonal (3 Gbp, alternating in one process, 16 / 32 /
-      // 64 / 128 pairs: 145.0 / 144.4 / 144.0 / 143.6 ms)
-      // -- with a million threads at least: the kernel waits for its loads, and a
-      // part of eight has an eighth of the records (3 Gbp, 43 M records a part, 8 /
-      // 32 / 128 / 512 pairs per thread: 4.7 / 4.7 / 5.6 / 11.5 ms)
-      int pair_chunk = (int) (nrec >> 20 < 16 ? 16 : (nrec >> 20 > 128 ? 128 : nrec >> 20));
-      if (sw.pair_chunk > 0) pair_chunk = sw.pair_chunk;
-      pair_chunk = (pair_chunk + PR_LINE - 1) / PR_LINE * PR_LINE;    // (whole lines of records per thread)
-      if (debug)
-        fprintf(stderr, "gtamd: part %u: pair resolve: records=%llu chunk=%d grid=%u\n", c->part,
-                (unsigned long long) nrec, pair_chunk,
-                stride_grid(div_up(div_up(nrec, (u64) pair_chunk), 256)));
-      k_pair_resolve<BITS, P><<<stride_grid(div_up(div_up(nrec, (u64) pair_chunk), 256)), 256, 0, st>>>(
-          c->text, pk_sorted, pv_sorted, nrec, npairs, sa, pres, c->d_stats, pair_chunk);
+    if (npairs > 0) {
+      k_pair_emit<P><<<(u32) div_up(nwords, 256), 256, 0, st>>>(tiebits, nwords, wd.poff, sa, pl.pk_a,
+                                                               pl.pv_a, pl.pidx);
       HIP_TRY(hipGetLastError());
-      if (npairs > 0) {
-        k_pair_swapbits<<<(u32) nwb, 256, 0, st>>>(tiebits, nwords, poff, pres, swp);
-        HIP_TRY(hipGetLastError());
-      }
-      if (nsmall > 0) {
-        k_small_combine<P><<<(u32) div_up(nsmall, 256), 256, 0, st>>>(
-            sidx, ssize, srec, pres, nsmall, sa, tiebits2, sres, slcp, c->d_stats);
-        HIP_TRY(hipGetLastError());
-      }
     }
-    // ---- table entries of the pairs and of the small groups (random lines,
-    // 11 ms at 3 Gbp): on the second stream, beside the rank table and the
-    // doubling rounds (streaming kernels, then short ones that leave most of
-    // the device idle).  Nothing on this stream touches those entries or the
-    // pair lists until the join before the walk over the LCP table; the LCP
-    // values beyond the byte need a buffer of their own for that -- behind the
-    // rounds they went where the rank table had been.  GTAMD_APPLY_EARLY: 0 =
-    // behind the rounds on this stream, 1 = from here on, 2 = from the first
-    // round on.  The rank table's kernels are bound by HBM bandwidth, where every
-    // byte of the entries costs its time again (k_win_filter 7.8 -> 13 ms beside
-    // them); the rounds wait for latency and launches, and there the entries
-    // are nearly free (3 Gbp, one process: 142.5 / 137.5 / 133.0 ms).
-    u32 *lcpfull = nullptr;
-    if (want_lcp && apply_early && nrec > 0) lcpfull = c->lcpfull_buf.as<u32>();   // (allocated above)
+    if (nsmall > 0) {
+      k_small_emit<P><<<(u32) div_up(nwords, 256), 256, 0, st>>>(
+          tiebits, nwords, wd.soff, wd.roff, sa, npairs, pl.sidx, pl.ssize, pl.srec, pl.pk_a, pl.pv_a);
+      HIP_TRY(hipGetLastError());
+    }
+    TRY(radix_sort_pairs<P, u64>(pl.pk_a, pl.pv_a, pl.pk_b, pl.pv_b, nrec, ps, pw, pn, pl.prws, st,
+                                 nullptr, nullptr));
+    const P *pk_sorted = (pn & 1) ? pl.pk_b : pl.pk_a;
+    const u64 *pv_sorted = (pn & 1) ? pl.pv_b : pl.pv_a;
+    TRY(launch_emission());   // bandwidth-bound, beside the comparisons
+    // pairs per thread: a chunk's first pair pays its whole comparison, the
+    // others ride on the diagonal (3 Gbp, alternating in one process, 16 / 32 /
+    // 64 / 128 pairs: 145.0 / 144.4 / 144.0 / 143.6 ms)
+    // -- with a million threads at least: the kernel waits for its loads, and a
+    // part of eight has an eighth of the records (3 Gbp, 43 M records a part, 8 /
+    // 32 / 128 / 512 pairs per thread: 4.7 / 4.7 / 5.6 / 11.5 ms)
+    int pair_chunk = (int) (nrec >> 20 < 16 ? 16 : (nrec >> 20 > 128 ? 128 : nrec >> 20));
+    if (sw.pair_chunk > 0) pair_chunk = sw.pair_chunk;
+    pair_chunk = (pair_chunk + PR_LINE - 1) / PR_LINE * PR_LINE;    // (whole lines of records per thread)
+    if (debug)
+      fprintf(stderr, "gtamd: part %u: pair resolve: records=%llu chunk=%d grid=%u\n", c->part,
+              (unsigned long long) nrec, pair_chunk,
+              stride_grid(div_up(div_up(nrec, (u64) pair_chunk), 256)));
+    k_pair_resolve<BITS, P><<<stride_grid(div_up(div_up(nrec, (u64) pair_chunk), 256)), 256, 0, st>>>(
+        c->text, pk_sorted, pv_sorted, nrec, npairs, sa, pl.pres, c->d_stats, pair_chunk);
+    HIP_TRY(hipGetLastError());
+    if (npairs > 0) {
+      k_pair_swapbits<<<(u32) nwb, 256, 0, st>>>(tiebits, nwords, wd.poff, pl.pres, pl.swp);
+      HIP_TRY(hipGetLastError());
+    }
+    if (nsmall > 0) {
+      k_small_combine<P><<<(u32) div_up(nsmall, 256), 256, 0, st>>>(
+          pl.sidx, pl.ssize, pl.srec, pl.pres, nsmall, sa, tiebits2, pl.sres, pl.slcp, c->d_stats);
+      HIP_TRY(hipGetLastError());
+    }
+    return 0;
+  }
+
+  // ---- table entries of the pairs and of the small groups (random lines,
+  // 11 ms at 3 Gbp): on the second stream, beside the rank table and the
+  // doubling rounds (streaming kernels, then short ones that leave most of
+  // the device idle).  Nothing on this stream touches those entries or the
+  // pair lists until the join before the walk over the LCP table; the LCP
+  // values beyond the byte need a buffer of their own for that -- behind the
+  // rounds they went where the rank table had been.  GTAMD_APPLY_EARLY: 0 =
+  // behind the rounds on this stream, 1 = from here on, 2 = from the first
+  // round on.  The rank table's kernels are bound by HBM bandwidth, where every
+  // byte of the entries costs its time again (k_win_filter 7.8 -> 13 ms beside
+  // them); the rounds wait for latency and launches, and there the entries
+  // are nearly free (3 Gbp, one process: 142.5 / 137.5 / 133.0 ms).
+  int place_apply() {
+    if (want_lcp && apply_early && nrec > 0) lcpfull = c->lcpfull_buf.as<u32>();   // (allocated by pair_path)
     if (nrec == 0) apply_early = 0;
     // Beside the refinement the two kernels get a grid of one workgroup per CU:
     // with a workgroup per 256 pairs the dispatcher kept every wave slot filled
@@ -4536,755 +4865,671 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
     // for milliseconds (kernel trace: a 6 ms copy).  64 / 128 / 192 / 256 /
     // 320 / 384 / 512 / 1024 workgroups: 146.0 / 135.5 / 133.3 / 133.0 / 133.8 /
     // 134.3 / 136.4 / 138.0 ms -- fewer do not finish before the join.
-    u64 apply_wgs = 256;
-    {
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && cus > 0)
-        apply_wgs = (u64) cus;
-    }
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && cus > 0)
+      apply_wgs = (u64) cus;
     if (sw.apply_wgs > 0) apply_wgs = sw.apply_wgs;
-    const bool apply_wgs_given = sw.apply_wgs_given;
-    auto launch_apply = [&](hipStream_t s) -> int {
-      // One workgroup per CU is right while the rounds last as long as the
-      // entries take that way (3 Gbp human-like: 13 + 1.6 ms of entries under
-      // 12 ms of rounds; repeat-heavy: 35 under 195).  Many pairs and few
-      // suffixes left for the rounds -- low-copy repeats only -- would leave the
-      // small grid working alone behind the last round: the grid grows with what
-      // the entries need over what the rounds give (measured rates: 77 ns per
-      // 1000 pairs and 285 ns per 1000 small groups with one workgroup per CU,
-      // 400 ns per 1000 suffixes in the rounds), up to the full one.
-      u64 cap = ~0ull;
-      if (apply_early == 1) cap = apply_wgs;
-      else if (apply_early == 2 && m0 > 0) {
-        cap = apply_wgs;
-        if (!apply_wgs_given) {
-          const double need = 7.7e-8 * (double) npairs + 2.85e-7 * (double) nsmall;   // ms
-          const double have = 1.25 * 4.0e-7 * (double) m0 + 0.5;
-          if (need > have) cap = (u64) ((double) apply_wgs * (need / have));
-        }
+    return 0;
+  }
+  int launch_apply(hipStream_t s) {
+    // One workgroup per CU is right while the rounds last as long as the
+    // entries take that way (3 Gbp human-like: 13 + 1.6 ms of entries under
+    // 12 ms of rounds; repeat-heavy: 35 under 195).  Many pairs and few
+    // suffixes left for the rounds -- low-copy repeats only -- would leave the
+    // small grid working alone behind the last round: the grid grows with what
+    // the entries need over what the rounds give (measured rates: 77 ns per
+    // 1000 pairs and 285 ns per 1000 small groups with one workgroup per CU,
+    // 400 ns per 1000 suffixes in the rounds), up to the full one.
+    u64 cap = ~0ull;
+    if (apply_early == 1) cap = apply_wgs;
+    else if (apply_early == 2 && m0 > 0) {
+      cap = apply_wgs;
+      if (!sw.apply_wgs_given) {
+        const double need = 7.7e-8 * (double) npairs + 2.85e-7 * (double) nsmall;   // ms
+        const double have = 1.25 * 4.0e-7 * (double) m0 + 0.5;
+        if (need > have) cap = (u64) ((double) apply_wgs * (need / have));
       }
-      if (debug) {
-        const u64 gpair = div_up(npairs, 256), gsmall = div_up(nsmall, 256);
-        fprintf(stderr, "gtamd: part %u: apply: placement=%d pair_grid=%llu small_grid=%llu\n", c->part,
-                apply_early, (unsigned long long) (gpair < cap ? gpair : cap),
-                (unsigned long long) (gsmall < cap ? gsmall : cap));
-      }
-      if (npairs > 0) {
-        const u64 g = div_up(npairs, 256);
-        k_pair_apply<P><<<(u32) (g < cap ? g : cap), 256, 0, s>>>(
-            pidx, pres, npairs, sa, d_suf, d_lcp, d_bwt, lcpfull, index_offset, c->d_stats);
-        HIP_TRY(hipGetLastError());
-      }
-      if (nsmall > 0) {
-        const u64 g = div_up(nsmall, 256);
-        k_small_apply<P><<<(u32) (g < cap ? g : cap), 256, 0, s>>>(
-            sidx, sres, slcp, nsmall, sa, d_suf, d_lcp, d_bwt, lcpfull, index_offset, c->d_stats);
-        HIP_TRY(hipGetLastError());
-      }
-      return 0;
-    };
-    // The pairs in the wrong order never change places in the suffix array: it
-    // is the build's working copy, and behind the pair path only the walks that
-    // rank the table's entries by their index read a pair's entries there --
-    // they take the resolved order from swp (swap_head).  (Swapped by
-    // k_pair_apply beside the rounds, the stores into the suffix array's lines
-    // cost the rounds 0.9 ms at 3 Gbp.)
-    const u64 *pair_swp = npairs > 0 ? swp : nullptr;
-    auto apply_beside = [&]() -> int {
-      // (ev_sorted is free: the emission, if it is a kernel of its own, has been
-      // launched by the pair path; st2 runs the entries behind it)
-      // (a stream of the lowest priority for them changes nothing: 137.6 ms
-      // against 136.9 -- the rounds lose 5 ms to the memory system, not to the
-      // dispatcher)
-      HIP_TRY(hipEventRecord(c->ev_sorted, st));
-      HIP_TRY(hipStreamWaitEvent(c->st2, c->ev_sorted, 0));
-      TRY(launch_apply(c->st2));
-      HIP_TRY(hipEventRecord(c->ev_applied, c->st2));
-      return 0;
-    };
-    if (apply_early == 1) TRY(apply_beside());
+    }
+    if (debug) {
+      const u64 gpair = div_up(npairs, 256), gsmall = div_up(nsmall, 256);
+      fprintf(stderr, "gtamd: part %u: apply: placement=%d pair_grid=%llu small_grid=%llu\n", c->part,
+              apply_early, (unsigned long long) (gpair < cap ? gpair : cap),
+              (unsigned long long) (gsmall < cap ? gsmall : cap));
+    }
+    if (npairs > 0) {
+      const u64 g = div_up(npairs, 256);
+      k_pair_apply<P><<<(u32) (g < cap ? g : cap), 256, 0, s>>>(
+          pl.pidx, pl.pres, npairs, sa, d_suf, d_lcp, d_bwt, lcpfull, index_offset, c->d_stats);
+      HIP_TRY(hipGetLastError());
+    }
+    if (nsmall > 0) {
+      const u64 g = div_up(nsmall, 256);
+      k_small_apply<P><<<(u32) (g < cap ? g : cap), 256, 0, s>>>(
+          pl.sidx, pl.sres, pl.slcp, nsmall, sa, d_suf, d_lcp, d_bwt, lcpfull, index_offset, c->d_stats);
+      HIP_TRY(hipGetLastError());
+    }
+    return 0;
+  }
+  int apply_beside() {
+    // (ev_sorted is free: the emission, if it is a kernel of its own, has been
+    // launched by the pair path; st2 runs the entries behind it)
+    // (a stream of the lowest priority for them changes nothing: 137.6 ms
+    // against 136.9 -- the rounds lose 5 ms to the memory system, not to the
+    // dispatcher)
+    TRY(fork_second_stream());
+    TRY(launch_apply(c->st2));
+    HIP_TRY(hipEventRecord(c->ev_applied, c->st2));
+    return 0;
+  }
+
+  // ---- what the pair path has left, here and on all parts ----------------------------
+  int count_left() {
     TRY(tie_words(tiebits2));
     m0 = c->h_stats->count;
     const u64 smalldone = c->h_stats->smalldone;
-    u64 anyleft = m0;
-    if (R > 1) {
-      std::vector<u64> all(R);
-      TRY(comm_allgather(c, 0, &m0, all.data(), 8));
-      anyleft = 0;
-      for (u32 r = 0; r < R; r++) anyleft += all[r];
-    }
+    anyleft = m0;
+    if (R > 1) TRY(allgather_word(c, 0, RED_SUM, &anyleft));
     if (debug)
       fprintf(stderr, "gtamd: part %u: %llu tied with a neighbour, %llu pairs, %llu small groups "
               "(%llu entries settled), %llu left\n",
               c->part, (unsigned long long) numties, (unsigned long long) npairs,
               (unsigned long long) nsmall, (unsigned long long) smalldone,
               (unsigned long long) m0);
-    // arena: unresolved list and round buffers | exchange buffers
+    return 0;
+  }
+
+  // ---- arena: unresolved list and round buffers | exchange buffers; the
+  // unresolved list of what is left
+  int carve_rounds() {
     const u64 mp = (m0 + 64 + 3) & ~3ull;   // every array of the arena 16-byte aligned
-    const u64 ISA_CHUNK = 1ull << 27;
     const u64 ichunk = NL < ISA_CHUNK ? NL : ISA_CHUNK;
-    const u64 xm = dist ? (ichunk > mp ? ichunk : mp) : 0;   // items bucketed at a time
+    xm = dist ? (ichunk > mp ? ichunk : mp) : 0;
     // what one exchange can bring in: a position of the own tile is asked for /
     // updated at most once per round and no part sends more than it has tied
     // suffixes (or one chunk of first ranks)
-    u64 xrecv_n = (u64) R * ISA_CHUNK > anyleft ? (u64) R * ISA_CHUNK : anyleft;
+    xrecv_n = (u64) R * ISA_CHUNK > anyleft ? (u64) R * ISA_CHUNK : anyleft;
     if (xrecv_n > Tn) xrecv_n = Tn;
     xrecv_n += 64;
-    P *upos = nullptr, *upos2 = nullptr, *cvo = nullptr,
-      *k2 = nullptr, *fk2 = nullptr, *fk2s_a = nullptr, *fk2s_b = nullptr, *fpos = nullptr,
-      *cvs = nullptr, *lk_a = nullptr, *lk_b = nullptr, *xrank = nullptr, *xans = nullptr;
-    u32 *uidx0 = nullptr,
-        *uidx = nullptr, *ugrp = nullptr, *uidx2 = nullptr, *ugrp2 = nullptr, *hv = nullptr,
-        *koff = nullptr, *fgrp = nullptr, *fj = nullptr, *perm_a = nullptr, *perm_b = nullptr,
-        *gk_a = nullptr, *gk_b = nullptr, *fhv = nullptr, *lv_a = nullptr, *lv_b = nullptr,
-        *rws2 = nullptr, *scanws2 = nullptr, *xoff = nullptr, *xorder = nullptr,
-        *xbc_q = nullptr, *xbo_q = nullptr, *xbc_u = nullptr, *xbo_u = nullptr, *xqoff = nullptr,
-        *xmsg = nullptr;
-    constexpr u64 RANKREC = 1 + sizeof(P) / 4;     // words of an (offset, rank) record
-    u64 *keep = nullptr;
-    u8 *xdest_q = nullptr, *xdest_u = nullptr;
-    u32 *flagbits = nullptr, *tstart = nullptr;
-    auto layout = [&](Bump &a) {
-      uidx0 = a.take<u32>(mp); uidx = a.take<u32>(mp); ugrp = a.take<u32>(mp);
-      uidx2 = a.take<u32>(mp); ugrp2 = a.take<u32>(mp);
-      upos = a.take<P>(mp); upos2 = a.take<P>(mp);
-      cvo = a.take<P>(mp);           // positions in the round's new order
-      hv = a.take<u32>(mp);          // head values -> new group ids
-      keep = a.take<u64>(mp / 64 + 4);   // 1 bit per slot
-      koff = a.take<u32>(mp);
-      k2 = a.take<P>(mp);            // rank of the suffix h further on
-      flagbits = a.take<u32>(mp / 32 + RT_TILE / 32 + 64);   // deferred to the global path (1 bit per slot)
-      tstart = a.take<u32>(mp / RT_STRIDE_MIN + 64);          // where the tiles of a round start
-      // global path of a round (groups across tile borders)
-      fk2 = a.take<P>(mp); fk2s_a = a.take<P>(mp); fk2s_b = a.take<P>(mp);
-      fpos = a.take<P>(mp); cvs = a.take<P>(mp);
-      fgrp = a.take<u32>(mp); fj = a.take<u32>(mp);
-      perm_a = a.take<u32>(mp); perm_b = a.take<u32>(mp);
-      gk_a = a.take<u32>(mp); gk_b = a.take<u32>(mp);
-      fhv = a.take<u32>(mp);
-      // LCP pairs of the tie fix
-      lk_a = a.take<P>(mp); lk_b = a.take<P>(mp);
-      lv_a = a.take<u32>(mp); lv_b = a.take<u32>(mp);
-      rws2 = a.take<u32>(radix_workspace_words(m0));   // radix + scan workspace for the rounds
-      scanws2 = a.take<u32>(scan_workspace_words(mp > dest_words(R, xm) ? mp : dest_words(R, xm)));
-      if (dist) {
-        xoff = a.take<u32>(xm + 64); xorder = a.take<u32>(xm + 64);
-        xrank = a.take<P>(xm + 64); xans = a.take<P>(xm + 64);
-        xqoff = a.take<u32>(xm + 64);
-        // one message per exchange: the first ranks as records; a round's new
-        // ranks (records) and queries (offsets) together
-        xmsg = a.take<u32>((xm + 64) * (RANKREC + 1));
-        xdest_q = a.take<u8>(xm + 64); xdest_u = a.take<u8>(xm + 64);
-        xbc_q = a.take<u32>(dest_words(R, xm)); xbo_q = a.take<u32>(dest_words(R, xm));
-        xbc_u = a.take<u32>(dest_words(R, xm)); xbo_u = a.take<u32>(dest_words(R, xm));
-      }
-    };
     {
       Bump sz = {nullptr, 0};
-      layout(sz);
+      ar.carve(sz, mp, m0, xm, R, dist);
       fail = ensure_buf(c, c->arena, sz.off + 4096, "the refinement of tied suffixes") != 0;
       if (dist && !fail)
         fail = ensure_buf(c, c->xrecv, xrecv_n * (8 + 2 * sizeof(P)) + 1024,
                           "the exchange of ranks") != 0;
-      if (dist && !fail)      // (bitmaps of the windows of 2^16 positions, see below)
+      if (dist && !fail)      // (bitmaps of the windows of 2^16 positions, see prepare_rank_exchange)
         fail = ensure_buf(c, c->winbuf, (3 * (div_up(N, 1ull << 16) / 32 + 2) + 16) * 4,
                           "the rank windows") != 0;
       if (R > 1) TRY(comm_allgather(c, fail, nullptr, nullptr, 0));
       else if (fail) return -1;
       Bump a = {c->arena.as<u8>(), 0};
-      layout(a);
+      ar.carve(a, mp, m0, xm, R, dist);
     }
-    // received: a message of up to xrecv_n records and xrecv_n offsets, and behind
-    // it the answers to the offsets
-    u32 *xrecv_msg = c->xrecv.as<u32>();
-    P *xrecv_ans = reinterpret_cast<P *>(c->xrecv.as<u8>() + ((xrecv_n * (4 + 4 * RANKREC) + 255) & ~255ull));
-    P *rank = nullptr;       // whole table (single build) ...
-    P *isa = nullptr;        // ... or the ranks of the own text tile (part build)
-    // ---- unresolved list of what is left
+    xrecv_msg = c->xrecv.as<u32>();
+    xrecv_ans = reinterpret_cast<P *>(c->xrecv.as<u8>() + ((xrecv_n * (4 + 4 * RANKREC) + 255) & ~255ull));
     if (m0 > 0) {
       k_unres_emit<P><<<(u32) div_up(nwords, 256), 256, 0, st>>>(
-          tiebits2, nwords, offw, carry, sa, uidx0, uidx, upos, ugrp);
+          tiebits2, nwords, wd.offw, wd.carry, sa, ar.uidx0, ar.uidx, ar.upos, ar.ugrp);
       HIP_TRY(hipGetLastError());
     }
-    // ---- few suffixes left behind the pair path (random coincidences of three or
-    // more: a protein set, a uniform text -- 410 K of 10^9 residues): settled by
-    // direct comparison like the few ties of a small input; no rank table (its
-    // filter alone walks the whole suffix array: 2 ms at 10^9), no round
+    return 0;
+  }
+
+  // ---- few suffixes left behind the pair path (random coincidences of three or
+  // more: a protein set, a uniform text -- 410 K of 10^9 residues): settled by
+  // direct comparison like the few ties of a small input; no rank table (its
+  // filter alone walks the whole suffix array: 2 ms at 10^9), no round
+  int settle_few_left() {
     m0_tied_all = m0;                        // (what the statistics report)
-    if (!dist && m0 > 0 && m0 <= (NL / 512 > 4096 ? NL / 512 : 4096)) {
-      TRY(launch_emission());
-      HIP_TRY(hipStreamWaitEvent(st, c->ev_emitted, 0));
-      HIP_TRY(hipMemsetAsync(&c->d_stats->dfallback, 0, 4, st));
-      k_direct_ties<BITS, P><<<(u32) div_up(m0, 256), 256, 0, st>>>(
-          c->text, uidx0, ugrp, m0, sa, d_suf, d_lcp, d_bwt, want_lcp, index_offset, c->d_stats);
+    if (dist || m0 == 0 || m0 > direct_limit()) return 0;
+    TRY(direct_ties(ar.uidx0, ar.ugrp, true));
+    if (c->h_stats->dfallback == 0) {
+      m0 = 0;
+      anyleft = 0;
+    } else {
+      // (a deep or a big group: the rounds take them all)
+      TRY(drop_direct_stats());
+    }
+    return 0;
+  }
+
+  // ---- rank table of a single build: the windows of positions the rounds can
+  // touch (all of them when that is most of the text)
+  int prepare_rank_table() {
+    TRY(ensure_buf(c, c->isa_tmp, (NL + 8) * 8, "the rank table build"));
+    rt.rank32 = fval;
+    rank = reinterpret_cast<P *>(rt.rank32);
+    rt.heads = reinterpret_cast<u32 *>(fkey);
+    rt.ppos = c->isa_tmp.as<u32>(); rt.phead = rt.ppos + ((NL + 3) & ~3ull);
+    rt.qhead = rt.heads; rt.qpos = rt.heads + ((NL + 3) & ~3ull);
+    rt.wmax = sw.rank_window_bits;
+    rt.spos = reinterpret_cast<const u32 *>(sa);
+    rt.heads_array = bits_for(N - 1) <= rt.wmax;
+    // Partition down to windows that fit the LDS (one or two passes), then
+    // k_rank_window.  (Measured at 3 Gbp: direct scatter 120 ms; one 8-bit
+    // pass + global scatter 84 ms; two passes + LDS window 30 ms.)
+    // GTAMD_RANK_WINDOW_BITS shrinks the window so that tests reach every
+    // shape at small N.
+    rt.pb = nb > rt.wmax ? nb - rt.wmax : 0;
+    if (rt.pb > 16) rt.pb = 16;
+    rt.wb = nb - rt.pb;             // wmax, or wmax + 1 with two halves
+    if (rt.wb > rt.wmax + 1) {
+      gtamd_set_error("rank table: %d position bits do not fit two passes and a "
+                      "%d-bit window", nb, rt.wmax);
+      return -1;
+    }
+    rt.split = rt.wb > rt.wmax ? 2 : 1;
+    rt.fb = rt.wmax < RW_FINE ? rt.wmax : RW_FINE;
+    rk.wb = rt.fb;
+    rk.nwin = div_up(N, 1ull << rt.fb);
+    rk.nww = rk.nwin / 32 + 2;
+    const bool all_windows = sw.rank_all_windows || rt.pb == 0;
+    if (!all_windows) {
+      TRY(ensure_buf(c, c->winbuf, (4 * rk.nww + rk.nwin + 16) * 4, "the rank windows"));
+      rk.w_need = c->winbuf.as<u32>(); rk.w_built = rk.w_need + rk.nww; rk.w_sel = rk.w_built + rk.nww;
+      rk.w_pref = rk.w_sel + rk.nww;
+      rk.w_list = rk.w_pref + rk.nww;
+      HIP_TRY(hipMemsetAsync(rk.w_need, 0, 2 * rk.nww * 4, st));
+      // offsets of the first rounds
+      rk.h0 = (u64) K::KNOWN << 9;
+      if (rk.h0 > (3ull << rt.wb)) rk.h0 = 3ull << rt.wb;
+      if (m0 > 0) {
+        k_win_mark<P><<<(u32) div_up(m0, 256), 256, 0, st>>>(ar.upos, m0, 0, rk.h0, rt.fb, rk.nwin,
+                                                            rk.w_need);
+        HIP_TRY(hipGetLastError());
+      }
+      rk.windows = true;
+    }
+    rt.headgen = {tiebits2, wd.carry, nwords, 0u, pair_swp};
+    return 0;
+  }
+
+  // `count` (position, head) pairs partitioned by the top pb of `bits` position bits
+  // (pb > 8: two passes, the second has to keep the first one's grouping: the
+  // sort's stable pass), then k_rank_window over windows of 2^(bits - pb) positions.
+  // The pairs start in (in_pos, in_head) -- in_head == nullptr: the heads come
+  // from rt.headgen -- and go to (a_pos, a_head), with two passes on to (b_pos, b_head).
+  int rank_windows(const u32 *in_pos, const u32 *in_head, u32 *a_pos, u32 *a_head, u32 *b_pos,
+                   u32 *b_head, u64 count, int bits, int pb, int split, u64 span, const u32 *list,
+                   int fb, u32 nsel, u64 M) {
+    const u32 *wpos = in_pos, *whead = in_head;
+    if (pb > 0) {
+      const int s0 = bits - pb, w0 = pb > 8 ? pb - 8 : pb;
+      if (in_head != nullptr)
+        TRY(radix_partition_u32(in_pos, in_head, a_pos, a_head, count, s0, w0, wd.pws, st));
+      else
+        TRY(radix_pass_group_heads(in_pos, rt.headgen, a_pos, a_head, count, s0, w0, wd.pws, st));
+      wpos = a_pos; whead = a_head;
+    }
+    if (pb > 8) {
+      const int s1 = bits - 8, w1 = 8;
+      TRY(radix_sort_pairs<u32, u32>(a_pos, a_head, b_pos, b_head, count, &s1, &w1, 1, wd.pws, st,
+                                     nullptr, nullptr));
+      wpos = b_pos; whead = b_head;
+    }
+    const int wb = bits - pb;
+    const u32 nbuckets = (u32) div_up(count, 1ull << wb);
+    const u32 grid = split == 2 ? ((nbuckets + 7u) / 8u) * 16u : nbuckets;
+    k_rank_window<<<grid, RW_THREADS, 0, st>>>(wpos, whead, span, wb, split, nbuckets, rt.rank32,
+                                               list, fb, nsel, M);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+
+  // builds the windows that are needed and not built (all == the whole table)
+  int build_rank(bool first) {
+    u64 nsel = 0;
+    if (rk.windows) {
+      k_win_select<<<1, 1024, 0, st>>>(rk.w_need, rk.w_built, rk.nww, rk.w_sel, rk.w_list, rk.w_pref, c->d_stats);
       HIP_TRY(hipGetLastError());
       TRY(fetch_stats(c));
-      if (c->h_stats->dfallback == 0) {
-        m0 = 0;
-        anyleft = 0;
-      } else {
-        // (a deep or a big group: the rounds take them all; the partial statistics
-        // of this attempt are dropped)
-        HIP_TRY(hipMemsetAsync(&c->d_stats->dsum, 0, 8, st));
-        HIP_TRY(hipMemsetAsync(&c->d_stats->dmax, 0, 4, st));
-      }
+      nsel = c->h_stats->count;
+      if (nsel == 0) return 0;
+      if (first && nsel * 2 > rk.nwin) rk.windows = false;   // most of the text: all of it
+      if (debug)
+        fprintf(stderr, "gtamd: rank table: %llu of %llu windows of 2^%d positions%s\n",
+                (unsigned long long) nsel, (unsigned long long) rk.nwin, rt.fb,
+                rk.windows ? "" : " -> whole table");
     }
-    // ---- rank table of a single build: the windows of positions the rounds can
-    // touch (all of them when that is most of the text)
-    int rk_wb = 0;
-    u64 rk_nwin = 0, rk_h0 = 0;
+    if (!rk.windows) {
+      if (debug)
+        fprintf(stderr, "gtamd: part %u: rank table: whole table of %llu entries\n", c->part,
+                (unsigned long long) NL);
+      if (rt.heads_array) {
+        k_heads<<<(u32) div_up(NL, 1024), 256, 0, st>>>(tiebits2, wd.carry, NL, 0u, pair_swp, rt.heads);
+        HIP_TRY(hipGetLastError());
+      }
+      // (heads is dead by the second pass, which writes there)
+      TRY(rank_windows(rt.spos, rt.heads_array ? rt.heads : nullptr, rt.ppos, rt.phead, rt.qpos,
+                       rt.qhead, NL, nb, rt.pb, rt.split, NL, nullptr, 0, 0u, 0));
+      rank_built = NL;
+      return 0;
+    }
+    // the pairs of the selected windows, with compact positions, partitioned down
+    // to the windows the LDS takes
+    HIP_TRY(hipMemsetAsync(&c->d_stats->count, 0, 4, st));
     // (tests: the window bitmap of k_win_filter read from global memory, as a text of more
     // than 3.22 G symbols has it: (N / 2^13 / 32 + 6) * 5 > WF_LDS_MAX)
-    const bool wf_global = sw.win_filter_global;
-    bool rk_windows = false;          // only some windows are built
-    u32 *w_need = nullptr, *w_built = nullptr, *w_sel = nullptr, *w_list = nullptr;
-    // builds the windows that are needed and not built (all == the whole table)
-    std::function<int(bool)> build_rank = [](bool) -> int { return 0; };
-    if (anyleft > 0 && !dist) {
-      TRY(ensure_buf(c, c->isa_tmp, (NL + 8) * 8, "the rank table build"));
-      u32 *rank32 = fval;
-      rank = reinterpret_cast<P *>(rank32);
-      u32 *heads = reinterpret_cast<u32 *>(fkey);          // free key buffer
-      u32 *ppos = c->isa_tmp.as<u32>(), *phead = ppos + ((NL + 3) & ~3ull);  // (skey is still
-                                                           // being read by the emission)
-      u32 *qhead = heads, *qpos = heads + ((NL + 3) & ~3ull);
-      const int wmax = sw.rank_window_bits;
-      const u32 *spos = reinterpret_cast<const u32 *>(sa);
-      const bool heads_array = bits_for(N - 1) <= wmax;
-      // Partition down to windows that fit the LDS (one or two passes), then
-      // k_rank_window.  (Measured at 3 Gbp: direct scatter 120 ms; one 8-bit
-      // pass + global scatter 84 ms; two passes + LDS window 30 ms.)
-      // GTAMD_RANK_WINDOW_BITS shrinks the window so that tests reach every
-      // shape at small N.
-      int pb = nb > wmax ? nb - wmax : 0;
-      if (pb > 16) pb = 16;
-      const int wb = nb - pb;             // wmax, or wmax + 1 with two halves
-      if (wb > wmax + 1) {
-        gtamd_set_error("rank table: %d position bits do not fit two passes and a "
-                        "%d-bit window", nb, wmax);
+    const WinFilterTies ties = {tiebits2, wd.carry, pair_swp};
+    TRY(launch_win_filter<u32>(c, sw, rt.spos, NL, rt.fb, rk.w_sel, rk.nww, (u32) rk.nww, rk.w_pref,
+                               ties, rt.ppos, rt.phead, ~0ull, nsel));
+    TRY(fetch_stats(c));
+    const u64 M = c->h_stats->count;   // nsel windows (the last one of the text is short)
+    if (M == 0) return 0;
+    rank_built += M;
+    int mb = bits_for(((u64) nsel << rt.fb) - 1);
+    if (mb < rt.fb) mb = rt.fb;
+    int pbm = mb > rt.wmax ? mb - rt.wmax : 0;
+    if (pbm > 16) pbm = 16;
+    const int wbm = mb - pbm;          // (<= wmax + 1, as mb <= nb)
+    const int splitm = wbm > rt.wmax ? 2 : 1;
+    return rank_windows(rt.ppos, rt.phead, rt.qpos, rt.qhead, rt.ppos, rt.phead, M, mb, pbm, splitm,
+                        N, rk.w_list, rt.fb, (u32) nsel, M);
+  }
+
+  // ---- part builds: the first ranks go to the owners of the positions, ISA_CHUNK
+  // entries at a time -- only for the windows of positions the rounds can
+  // reach (the union over the parts; see k_win_mark), which is a fifth of the
+  // text for the human-like workload: the exchange shrinks accordingly
+  int prepare_rank_exchange() {
+    isa = WIDE ? reinterpret_cast<P *>(fkey) : reinterpret_cast<P *>(fval);
+    rk.wb = 16;
+    rk.nwin = div_up(N, 1ull << rk.wb);
+    rk.nww = rk.nwin / 32 + 2;
+    rk.windows = !sw.rank_all_windows;
+    // (a part that cannot get the buffers of this step says so in the first
+    // allgather of send_ranks)
+    fail |= ensure_buf(c, c->winbuf, (3 * rk.nww + 16) * 4, "the rank windows") != 0;
+    if (fail && R == 1) return -1;
+    rk.w_need = c->winbuf.as<u32>(); rk.w_built = rk.w_need + rk.nww; rk.w_sel = rk.w_built + rk.nww;
+    rk.h_need.assign(rk.nww, 0u); rk.h_built.assign(rk.nww, 0u); rk.h_all.assign((size_t) rk.nww * R, 0u);
+    if (!fail) HIP_TRY(hipMemsetAsync(rk.w_need, 0, 3 * rk.nww * 4, st));
+    rk.h0 = (u64) K::KNOWN << 9;
+    if (rk.h0 > (3ull << rk.wb)) rk.h0 = 3ull << rk.wb;
+    if (!fail && rk.windows && m0 > 0) {
+      k_win_mark<P><<<(u32) div_up(m0, 256), 256, 0, st>>>(ar.upos, m0, 0, rk.h0, rk.wb, rk.nwin,
+                                                          rk.w_need);
+      HIP_TRY(hipGetLastError());
+    }
+    if (!WIDE) {
+      rk.list_cap = NL;
+      rk.lpos = c->isa_tmp.as<P>();
+      rk.lhead = c->isa_tmp.as<u32>() + ((NL + 3) & ~3ull);
+    } else if (msd_part && c->posw.bytes >= 4096) {
+      rk.list_cap = (c->posw.bytes - 256) / 12;
+      rk.lpos = c->posw.as<P>();
+      rk.lhead = reinterpret_cast<u32 *>(c->posw.as<u8>() + ((rk.list_cap * 8 + 255) & ~255ull));
+      rk.list_cap -= 64;
+    }
+    return 0;
+  }
+
+  // the tile of no part gets more than it has positions (every part sees the whole
+  // matrix of counts, count(s, q) from part s to part q: all of them leave, or none)
+  template <typename F>
+  bool tile_overrun(const F &count) const {
+    for (u32 q = 0; q < R; q++) {
+      u64 tot = 0;
+      for (u32 s = 0; s < R; s++) tot += count(s, q);
+      if (tot > tl.count(q, N)) return true;
+    }
+    return false;
+  }
+
+  int send_ranks() {
+    // the windows any part needs and nobody has sent yet (the first allgather of
+    // this step also says whether a part could not get its buffers)
+    const u32 *d_sel = nullptr;
+    u64 fresh_windows = 0;
+    int agreed = 0;
+    if (debug && !rk.windows)
+      fprintf(stderr, "gtamd: part %u: rank exchange: all windows\n", c->part);
+    if (rk.windows) {
+      if (!fail) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy(rk.h_need.data(), rk.w_need, rk.nww * 4, hipMemcpyDeviceToHost));
+      }
+      TRY(comm_allgather(c, fail, rk.h_need.data(), rk.h_all.data(), (u32) (rk.nww * 4)));
+      agreed = 1;
+      u64 fresh = 0, all = 0;
+      for (u64 w = 0; w < rk.nww; w++) {
+        u32 x = 0;
+        for (u32 r = 0; r < R; r++) x |= rk.h_all[(size_t) r * rk.nww + w];
+        x &= ~rk.h_built[w];
+        rk.h_need[w] = x;
+        rk.h_built[w] |= x;
+        fresh += (u64) __builtin_popcount(x);
+        all += (u64) __builtin_popcount(rk.h_built[w]);
+      }
+      if (debug)
+        fprintf(stderr, "gtamd: part %u: ranks of %llu more windows of 2^%d positions travel "
+                "(%llu of %llu so far)\n", c->part, (unsigned long long) fresh, rk.wb,
+                (unsigned long long) all, (unsigned long long) rk.nwin);
+      if (fresh == 0) return 0;
+      fresh_windows = fresh;
+      HIP_TRY(hipMemcpyAsync(rk.w_sel, rk.h_need.data(), rk.nww * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(rk.w_built, rk.h_built.data(), rk.nww * 4, hipMemcpyHostToDevice, st));
+      d_sel = rk.w_sel;
+    }
+    // the entries of those windows, listed in one walk over the slice (a fifth of
+    // it for the human-like workload): what is bucketed and sent is the list.  A
+    // list that does not fit its buffer (or all windows): the slice itself, chunk
+    // by chunk.
+    bool listed = false;
+    u64 M = 0;
+    if (!fail && d_sel != nullptr && NL > 0 && rk.list_cap > 0) {
+      HIP_TRY(hipMemsetAsync(&c->d_stats->count, 0, 8, st));     // count, count2
+      const WinFilterTies ties = {tiebits2, wd.carry, pair_swp};
+      TRY(launch_win_filter<P>(c, sw, sa, NL, rk.wb, d_sel, rk.nww, 0u, nullptr, ties, rk.lpos,
+                               rk.lhead, rk.list_cap, fresh_windows));
+      TRY(fetch_stats(c));
+      listed = c->h_stats->count2 == 0;
+      M = c->h_stats->count;
+    }
+    const u64 items = listed ? M : NL, per = listed ? (xm ? xm : 1) : ISA_CHUNK;
+    u64 chunks = div_up(items, per);
+    if (R > 1 || !agreed) TRY(allgather_word(c, agreed ? 0 : fail, RED_MAX, &chunks));
+    for (u64 ch = 0; ch < chunks; ch++) {
+      const u64 c0 = ch * per < items ? ch * per : items;
+      const u64 cm = items - c0 < per ? items - c0 : per;
+      if (listed) {
+        FilteredRanks<P> fr;
+        fr.fpos = rk.lpos + c0; fr.fhead = rk.lhead + c0; fr.index_offset = index_offset; fr.tl = tl;
+        fr.isa = isa; fr.srec = ar.xmsg;
+        TRY(dest_count(c, fr, cm, ar.xdest_q, ar.xbc_q, ar.xbo_q, ar.scanws2, 0));
+        HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, DEST_MAXPARTS * 4,
+                               hipMemcpyDeviceToHost, st));
+        TRY(dest_place(c, fr, cm, ar.xdest_q, ar.xbo_q));
+      } else {
+        InitialRanks<P> ir;
+        ir.sa = sa; ir.tiebits = tiebits2; ir.carry = wd.carry; ir.c0 = c0;
+        ir.index_offset = index_offset; ir.tl = tl; ir.isa = isa; ir.srec = ar.xmsg;
+        ir.sel = d_sel; ir.wb = rk.wb; ir.swp = pair_swp;
+        TRY(dest_count(c, ir, cm, ar.xdest_q, ar.xbc_q, ar.xbo_q, ar.scanws2, 0));
+        HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, DEST_MAXPARTS * 4,
+                               hipMemcpyDeviceToHost, st));
+        TRY(dest_place(c, ir, cm, ar.xdest_q, ar.xbo_q));
+      }
+      HIP_TRY(hipStreamSynchronize(st));
+      std::vector<u64> sc(R), rc(R), mat((size_t) R * R);
+      for (u32 r = 0; r < R; r++) sc[r] = c->h_counts[r];
+      TRY(comm_allgather(c, 0, sc.data(), mat.data(), R * 8));
+      u64 nrecv = 0;
+      for (u32 s = 0; s < R; s++) { rc[s] = mat[(size_t) s * R + c->part]; nrecv += rc[s]; }
+      const u32 parts = R;
+      const bool toobig = tile_overrun([&mat, parts](u32 s, u32 q) { return mat[(size_t) s * parts + q]; });
+      if (toobig || nrecv + 64 > xrecv_n) {
+        gtamd_set_error("rank exchange: %llu ranks for a tile of %llu positions",
+                        (unsigned long long) nrecv, (unsigned long long) Tn);
         return -1;
       }
-      const int split = wb > wmax ? 2 : 1;
-      // the windows that are selected are finer than the windows the LDS takes
-      const int fb = wmax < RW_FINE ? wmax : RW_FINE;
-      rk_wb = fb;
-      rk_nwin = div_up(N, 1ull << fb);
-      const u64 nww = rk_nwin / 32 + 2;
-      const bool all_windows = sw.rank_all_windows || pb == 0;
-      u32 *w_pref = nullptr;
-      if (!all_windows) {
-        TRY(ensure_buf(c, c->winbuf, (4 * nww + rk_nwin + 16) * 4, "the rank windows"));
-        w_need = c->winbuf.as<u32>(); w_built = w_need + nww; w_sel = w_built + nww;
-        w_pref = w_sel + nww;
-        w_list = w_pref + nww;
-        HIP_TRY(hipMemsetAsync(w_need, 0, 2 * nww * 4, st));
-        // offsets of the first rounds
-        rk_h0 = (u64) K::KNOWN << 9;
-        if (rk_h0 > (3ull << wb)) rk_h0 = 3ull << wb;
-        if (m0 > 0) {
-          k_win_mark<P><<<(u32) div_up(m0, 256), 256, 0, st>>>(upos, m0, 0, rk_h0, fb, rk_nwin,
-                                                              w_need);
-          HIP_TRY(hipGetLastError());
-        }
-        rk_windows = true;
+      TRY(comm_alltoallv(c, ar.xmsg, sc.data(), xrecv_msg, rc.data(), (u32) (4 * RANKREC), "first ranks"));
+      if (nrecv > 0) {
+        k_isa_store_rec<P><<<(u32) div_up(nrecv, 256), 256, 0, st>>>(xrecv_msg, nrecv, isa);
+        HIP_TRY(hipGetLastError());
       }
-      const GroupHeadValues headgen = {tiebits2, carry, nwords, 0u, pair_swp};
-      build_rank = [=, &rk_windows, &rank_built](bool first) -> int {
-        u64 nsel = 0;
-        if (rk_windows) {
-          k_win_select<<<1, 1024, 0, st>>>(w_need, w_built, nww, w_sel, w_list, w_pref, c->d_stats);
-          HIP_TRY(hipGetLastError());
-          TRY(fetch_stats(c));
-          nsel = c->h_stats->count;
-          if (nsel == 0) return 0;
-          if (first && nsel * 2 > rk_nwin) rk_windows = false;   // most of the text: all of it
-          if (debug)
-            fprintf(stderr, "gtamd: rank table: %llu of %llu windows of 2^%d positions%s\n",
-                    (unsigned long long) nsel, (unsigned long long) rk_nwin, fb,
-                    rk_windows ? "" : " -> whole table");
-        }
-        if (!rk_windows) {
-          if (debug)
-            fprintf(stderr, "gtamd: part %u: rank table: whole table of %llu entries\n", c->part,
-                    (unsigned long long) NL);
-          if (heads_array) {
-            k_heads<<<(u32) div_up(NL, 1024), 256, 0, st>>>(tiebits2, carry, NL, 0u, pair_swp, heads);
-            HIP_TRY(hipGetLastError());
-          }
-          const u32 *wpos = spos, *whead = heads;
-          if (pb > 8) {
-            const int s0 = nb - pb, w0 = pb - 8, s1 = nb - 8, w1 = 8;   // heads is dead by then
-            if (heads_array)
-              TRY(radix_partition_u32(spos, heads, ppos, phead, NL, s0, w0, pws, st));
-            else
-              TRY(radix_pass_group_heads(spos, headgen, ppos, phead, NL, s0, w0, pws, st));
-            // (the second pass has to keep the first one's grouping: the sort's stable pass)
-            TRY(radix_sort_pairs<u32, u32>(ppos, phead, qpos, qhead, NL, &s1, &w1, 1, pws, st,
-                                           nullptr, nullptr));
-            wpos = qpos; whead = qhead;
-          } else if (pb > 0) {
-            const int s0 = nb - pb, w0 = pb;
-            if (heads_array)
-              TRY(radix_partition_u32(spos, heads, ppos, phead, NL, s0, w0, pws, st));
-            else
-              TRY(radix_pass_group_heads(spos, headgen, ppos, phead, NL, s0, pb, pws, st));
-            wpos = ppos; whead = phead;
-          }
-          const u32 nbuckets = (u32) div_up(NL, 1ull << wb);
-          const u32 grid = split == 2 ? ((nbuckets + 7u) / 8u) * 16u : nbuckets;
-          k_rank_window<<<grid, RW_THREADS, 0, st>>>(wpos, whead, NL, wb, split, nbuckets, rank32,
-                                                     nullptr, 0, 0u, 0);
-          HIP_TRY(hipGetLastError());
-          rank_built = NL;
-          return 0;
-        }
-        // the pairs of the selected windows, with compact positions, partitioned down
-        // to the windows the LDS takes
-        HIP_TRY(hipMemsetAsync(&c->d_stats->count, 0, 4, st));
-        const bool wf_lds = (nww + 4) * 5 <= WF_LDS_MAX && !wf_global;
-        if (debug)
-          fprintf(stderr, "gtamd: part %u: win filter: bitmap=%s windows=%llu\n", c->part,
-                  wf_lds ? "lds" : "global", (unsigned long long) nsel);
-        if (wf_lds) {
-          // (more than the 64 KB a kernel gets without asking)
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_win_filter<u32, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int) wf_lds_bytes<u32>(nww, true)));
-          k_win_filter<u32, true><<<(u32) div_up(NL, WF_SPAN * WF_ITER), WF_THREADS, wf_lds_bytes<u32>(nww, true), st>>>(
-              spos, NL, fb, w_sel, (u32) nww, w_pref, tiebits2, carry, pair_swp, ppos, phead, ~0ull,
-              c->d_stats);
-        } else
-          k_win_filter<u32, false><<<(u32) div_up(NL, WF_SPAN * WF_ITER), WF_THREADS, wf_lds_bytes<u32>(nww, false), st>>>(
-              spos, NL, fb, w_sel, (u32) nww, w_pref, tiebits2, carry, pair_swp, ppos, phead, ~0ull,
-              c->d_stats);
-        HIP_TRY(hipGetLastError());
-        TRY(fetch_stats(c));
-        const u64 M = c->h_stats->count;   // nsel windows (the last one of the text is short)
-        if (M == 0) return 0;
-        rank_built += M;
-        int mb = bits_for(((u64) nsel << fb) - 1);
-        if (mb < fb) mb = fb;
-        int pbm = mb > wmax ? mb - wmax : 0;
-        if (pbm > 16) pbm = 16;
-        const int wbm = mb - pbm;          // (<= wmax + 1, as mb <= nb)
-        const int splitm = wbm > wmax ? 2 : 1;
-        const u32 *wpos = ppos, *whead = phead;
-        if (pbm > 8) {
-          const int s0 = mb - pbm, w0 = pbm - 8, s1 = mb - 8, w1 = 8;
-          TRY(radix_partition_u32(ppos, phead, qpos, qhead, M, s0, w0, pws, st));
-          TRY(radix_sort_pairs<u32, u32>(qpos, qhead, ppos, phead, M, &s1, &w1, 1, pws, st,
-                                         nullptr, nullptr));
-        } else if (pbm > 0) {
-          const int s0 = mb - pbm, w0 = pbm;
-          TRY(radix_partition_u32(ppos, phead, qpos, qhead, M, s0, w0, pws, st));
-          wpos = qpos; whead = qhead;
-        }
-        const u32 nbuckets = (u32) div_up(M, 1ull << wbm);
-        const u32 grid = splitm == 2 ? ((nbuckets + 7u) / 8u) * 16u : nbuckets;
-        k_rank_window<<<grid, RW_THREADS, 0, st>>>(wpos, whead, N, wbm, splitm, nbuckets, rank32,
-                                                   w_list, fb, (u32) nsel, M);
-        HIP_TRY(hipGetLastError());
-        return 0;
-      };
-      TRY(build_rank(true));
     }
-    std::vector<u64> qcounts(R), ucounts(R), zero(R, 0);
-    const size_t GW = 2 * (size_t) R + 2;    // a part's row in a round's allgather
-    std::vector<u64> gathered((size_t) R * GW), mine(GW);
-    // part builds: the first ranks go to the owners of the positions, ISA_CHUNK
-    // entries at a time -- only for the windows of positions the rounds can
-    // reach (the union over the parts; see k_win_mark), which is a fifth of the
-    // text for the human-like workload: the exchange shrinks accordingly
-    std::vector<u32> h_need, h_built, h_all;
-    u64 dw_nww = 0;
-    std::function<int()> send_ranks = []() -> int { return 0; };
-    if (anyleft > 0 && dist) {
-      isa = WIDE ? reinterpret_cast<P *>(fkey) : reinterpret_cast<P *>(fval);
-      rk_wb = 16;
-      rk_nwin = div_up(N, 1ull << rk_wb);
-      dw_nww = rk_nwin / 32 + 2;
-      rk_windows = !sw.rank_all_windows;
-      // (a part that cannot get the buffers of this step says so in the first
-      // allgather of send_ranks)
-      fail |= ensure_buf(c, c->winbuf, (3 * dw_nww + 16) * 4, "the rank windows") != 0;
-      if (fail && R == 1) return -1;
-      w_need = c->winbuf.as<u32>(); w_built = w_need + dw_nww; w_sel = w_built + dw_nww;
-      h_need.assign(dw_nww, 0u); h_built.assign(dw_nww, 0u); h_all.assign((size_t) dw_nww * R, 0u);
-      if (!fail) HIP_TRY(hipMemsetAsync(w_need, 0, 3 * dw_nww * 4, st));
-      rk_h0 = (u64) K::KNOWN << 9;
-      if (rk_h0 > (3ull << rk_wb)) rk_h0 = 3ull << rk_wb;
-      if (!fail && rk_windows && m0 > 0) {
-        k_win_mark<P><<<(u32) div_up(m0, 256), 256, 0, st>>>(upos, m0, 0, rk_h0, rk_wb, rk_nwin,
-                                                            w_need);
-        HIP_TRY(hipGetLastError());
-      }
-      // where the entries of the windows that travel are listed: a buffer that has
-      // done its work (the keys the part filtered from the text; their positions)
-      P *fpos = nullptr;
-      u32 *fhead = nullptr;
-      u64 list_cap = 0;
-      if (!WIDE) {
-        list_cap = NL;
-        fpos = c->isa_tmp.as<P>();
-        fhead = c->isa_tmp.as<u32>() + ((NL + 3) & ~3ull);
-      } else if (msd_part && c->posw.bytes >= 4096) {
-        list_cap = (c->posw.bytes - 256) / 12;
-        fpos = c->posw.as<P>();
-        fhead = reinterpret_cast<u32 *>(c->posw.as<u8>() + ((list_cap * 8 + 255) & ~255ull));
-        list_cap -= 64;
-      }
-      send_ranks = [&]() -> int {
-        // the windows any part needs and nobody has sent yet (the first allgather of
-        // this step also says whether a part could not get its buffers)
-        const u32 *d_sel = nullptr;
-        u64 fresh_windows = 0;
-        int agreed = 0;
-        if (debug && !rk_windows)
-          fprintf(stderr, "gtamd: part %u: rank exchange: all windows\n", c->part);
-        if (rk_windows) {
-          if (!fail) {
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipMemcpy(h_need.data(), w_need, dw_nww * 4, hipMemcpyDeviceToHost));
-          }
-          TRY(comm_allgather(c, fail, h_need.data(), h_all.data(), (u32) (dw_nww * 4)));
-          agreed = 1;
-          u64 fresh = 0, all = 0;
-          for (u64 w = 0; w < dw_nww; w++) {
-            u32 x = 0;
-            for (u32 r = 0; r < R; r++) x |= h_all[(size_t) r * dw_nww + w];
-            x &= ~h_built[w];
-            h_need[w] = x;
-            h_built[w] |= x;
-            fresh += (u64) __builtin_popcount(x);
-            all += (u64) __builtin_popcount(h_built[w]);
-          }
-          if (debug)
-            fprintf(stderr, "gtamd: part %u: ranks of %llu more windows of 2^%d positions travel "
-                    "(%llu of %llu so far)\n", c->part, (unsigned long long) fresh, rk_wb,
-                    (unsigned long long) all, (unsigned long long) rk_nwin);
-          if (fresh == 0) return 0;
-          fresh_windows = fresh;
-          HIP_TRY(hipMemcpyAsync(w_sel, h_need.data(), dw_nww * 4, hipMemcpyHostToDevice, st));
-          HIP_TRY(hipMemcpyAsync(w_built, h_built.data(), dw_nww * 4, hipMemcpyHostToDevice, st));
-          d_sel = w_sel;
-        }
-        // the entries of those windows, listed in one walk over the slice (a fifth of
-        // it for the human-like workload): what is bucketed and sent is the list.  A
-        // list that does not fit its buffer (or all windows): the slice itself, chunk
-        // by chunk.
-        bool listed = false;
-        u64 M = 0;
-        if (!fail && d_sel != nullptr && NL > 0 && list_cap > 0) {
-          HIP_TRY(hipMemsetAsync(&c->d_stats->count, 0, 8, st));     // count, count2
-          // (the bitmap of the windows of 64 K positions: 6 KB for 3 Gbp -- in LDS whenever it fits)
-          const bool wf_lds = (dw_nww + 4) * 5 <= WF_LDS_MAX && !wf_global;
-          if (debug)
-            fprintf(stderr, "gtamd: part %u: win filter: bitmap=%s windows=%llu\n", c->part,
-                    wf_lds ? "lds" : "global", (unsigned long long) fresh_windows);
-          if (wf_lds) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_win_filter<P, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int) wf_lds_bytes<P>(dw_nww, true)));
-            k_win_filter<P, true><<<(u32) div_up(NL, WF_SPAN * WF_ITER), WF_THREADS, wf_lds_bytes<P>(dw_nww, true), st>>>(
-                sa, NL, rk_wb, d_sel, (u32) dw_nww, nullptr, tiebits2, carry, pair_swp, fpos, fhead,
-                list_cap, c->d_stats);
-          } else
-            k_win_filter<P, false><<<(u32) div_up(NL, WF_SPAN * WF_ITER), WF_THREADS, wf_lds_bytes<P>(0, false), st>>>(
-                sa, NL, rk_wb, d_sel, 0u, nullptr, tiebits2, carry, pair_swp, fpos, fhead, list_cap,
-                c->d_stats);
-          HIP_TRY(hipGetLastError());
-          TRY(fetch_stats(c));
-          listed = c->h_stats->count2 == 0;
-          M = c->h_stats->count;
-        }
-        const u64 items = listed ? M : NL, per = listed ? (xm ? xm : 1) : ISA_CHUNK;
-        u64 chunks = div_up(items, per);
-        if (R > 1 || !agreed) {
-          std::vector<u64> all(R);
-          TRY(comm_allgather(c, agreed ? 0 : fail, &chunks, all.data(), 8));
-          for (u32 r = 0; r < R; r++) chunks = all[r] > chunks ? all[r] : chunks;
-        }
-        for (u64 ch = 0; ch < chunks; ch++) {
-          const u64 c0 = ch * per < items ? ch * per : items;
-          const u64 cm = items - c0 < per ? items - c0 : per;
-          if (listed) {
-            FilteredRanks<P> fr;
-            fr.fpos = fpos + c0; fr.fhead = fhead + c0; fr.index_offset = index_offset; fr.tl = tl;
-            fr.isa = isa; fr.srec = xmsg;
-            TRY(dest_count(c, fr, cm, xdest_q, xbc_q, xbo_q, scanws2, 0));
-            HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, DEST_MAXPARTS * 4,
-                                   hipMemcpyDeviceToHost, st));
-            TRY(dest_place(c, fr, cm, xdest_q, xbo_q));
-          } else {
-            InitialRanks<P> ir;
-            ir.sa = sa; ir.tiebits = tiebits2; ir.carry = carry; ir.c0 = c0;
-            ir.index_offset = index_offset; ir.tl = tl; ir.isa = isa; ir.srec = xmsg;
-            ir.sel = d_sel; ir.wb = rk_wb; ir.swp = pair_swp;
-            TRY(dest_count(c, ir, cm, xdest_q, xbc_q, xbo_q, scanws2, 0));
-            HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, DEST_MAXPARTS * 4,
-                                   hipMemcpyDeviceToHost, st));
-            TRY(dest_place(c, ir, cm, xdest_q, xbo_q));
-          }
-          HIP_TRY(hipStreamSynchronize(st));
-          std::vector<u64> sc(R), rc(R), mat((size_t) R * R);
-          for (u32 r = 0; r < R; r++) sc[r] = c->h_counts[r];
-          TRY(comm_allgather(c, 0, sc.data(), mat.data(), R * 8));
-          u64 nrecv = 0;
-          for (u32 s = 0; s < R; s++) { rc[s] = mat[(size_t) s * R + c->part]; nrecv += rc[s]; }
-          // (every part sees the whole matrix: all of them leave here, or none)
-          int toobig = 0;
-          for (u32 q = 0; q < R && !toobig; q++) {
-            u64 tot = 0;
-            for (u32 s = 0; s < R; s++) tot += mat[(size_t) s * R + q];
-            const u64 first_q = (u64) q * tl.T < N ? (u64) q * tl.T : N;
-            const u64 tile_q = first_q + tl.T < N ? tl.T : N - first_q;
-            if (tot > tile_q) toobig = 1;
-          }
-          if (toobig || nrecv + 64 > xrecv_n) {
-            gtamd_set_error("rank exchange: %llu ranks for a tile of %llu positions",
-                            (unsigned long long) nrecv, (unsigned long long) Tn);
-            return -1;
-          }
-          TRY(comm_alltoallv(c, xmsg, sc.data(), xrecv_msg, rc.data(), (u32) (4 * RANKREC), "first ranks"));
-          if (nrecv > 0) {
-            k_isa_store_rec<P><<<(u32) div_up(nrecv, 256), 256, 0, st>>>(xrecv_msg, nrecv, isa);
-            HIP_TRY(hipGetLastError());
-          }
-        }
-        return 0;
-      };
-      TRY(send_ranks());
-    }
-    TRY(launch_emission());   // (if the pair path has not started it)
-    if (apply_early == 2) TRY(apply_beside());
-    // ---- doubling rounds
-    int gs[8], gw[8];
-    const int gn = passes_for(nbl, gs, gw);
-    u64 m = m0, h = (u64) K::KNOWN;
-    // nominal distance of the round tiles' starts: the rest of a tile is the
-    // slack for the group that lies across (a group larger than the slack goes
-    // through the global path, forty launches per round)
-    const u32 rt_stride = sw.round_stride;
+    return 0;
+  }
+
+  // ---- doubling rounds ----------------------------------------------------------------
+  // what one round hands to the next
+  struct RoundState {
+    u64 m, h;                 // suffixes on the list, known prefix length
     // part builds: the queries of the coming round and the rank updates of the
     // last one are bucketed by owner before the parts agree on the counts
     RankQueries<P> rq;
     RankUpdates<P> ru;
     u64 m_upd = 0;            // slots of the last round (its updates are pending)
+    size_t GW = 0;            // a part's row in a round's allgather
+    std::vector<u64> gathered, mine;
+    int gs[8], gw[8], gn;     // radix passes over an index into the slice
+  };
+
+  int doubling_rounds() {
+    RoundState s;
+    s.gn = passes_for(0, nbl, s.gs, s.gw);
+    s.m = m0;
+    s.h = (u64) K::KNOWN;
+    s.GW = 2 * (size_t) R + 2;
+    s.gathered.resize((size_t) R * s.GW);
+    s.mine.resize(s.GW);
     if (anyleft > 0 && dist) {
-      rq.upos = upos; rq.h = h; rq.n = n; rq.tl = tl; rq.isa = isa; rq.k2 = k2;
-      rq.sendq = xqoff; rq.order = xorder;
-      TRY(dest_count(c, rq, m, xdest_q, xbc_q, xbo_q, scanws2, 0));
+      s.rq.upos = ar.upos; s.rq.h = s.h; s.rq.n = n; s.rq.tl = tl; s.rq.isa = isa; s.rq.k2 = ar.k2;
+      s.rq.sendq = ar.xqoff; s.rq.order = ar.xorder;
+      TRY(dest_count(c, s.rq, s.m, ar.xdest_q, ar.xbc_q, ar.xbo_q, ar.scanws2, 0));
       HIP_TRY(hipMemsetAsync(c->d_counts + DEST_MAXPARTS, 0, DEST_MAXPARTS * 4, st));
     }
     for (;;) {
       if (anyleft == 0) break;
-      if (!dist && m == 0) break;
+      if (!dist && s.m == 0) break;
       if (rounds >= 64) {
         gtamd_set_error("prefix doubling did not converge after 64 rounds");
         return -1;
       }
       if (dist) {
-        // does this round's offset reach windows whose ranks have not travelled?
-        // (never while h <= rk_h0; the parts decide together, in the allgather below)
-        u64 more = 0;
-        if (rk_windows && h > rk_h0) {
-          HIP_TRY(hipMemsetAsync(&c->d_stats->count2, 0, 4, st));
-          if (m > 0) {
-            k_win_check<P><<<(u32) div_up(m, 256), 256, 0, st>>>(upos, m, h, rk_wb, rk_nwin, w_built,
-                                                               w_need, c->d_stats);
-            HIP_TRY(hipGetLastError());
-          }
-          HIP_TRY(hipMemcpyAsync(c->h_stats, c->d_stats, sizeof(Stats), hipMemcpyDeviceToHost, st));
-        }
-        // ONE allgather per round: pending updates, queries, who is left, and
-        // whether more first ranks have to travel
-        HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, 2 * DEST_MAXPARTS * 4,
-                               hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (rk_windows && h > rk_h0) more = c->h_stats->count2 != 0;
-        for (u32 r = 0; r < R; r++) {
-          mine[r] = c->h_counts[r];                        // queries to r
-          mine[R + r] = c->h_counts[DEST_MAXPARTS + r];    // updates to r
-        }
-        mine[2 * R] = m;
-        mine[2 * R + 1] = more;
-        TRY(comm_allgather(c, 0, mine.data(), gathered.data(), (u32) (GW * 8)));
-        u64 left = 0;
-        for (u32 s = 0; s < R; s++) {
-          left += gathered[(size_t) s * GW + 2 * R];
-          more |= gathered[(size_t) s * GW + 2 * R + 1];
-        }
-        if (left == 0) break;   // (ranks nobody will ask for need not travel)
-        if (more) {
-          TRY(send_ranks());
-          // (the exchange used the bucketing buffers of this round's queries; the
-          // counts come out the same)
-          TRY(dest_count(c, rq, m, xdest_q, xbc_q, xbo_q, scanws2, 0));
-        }
-        // the new ranks of the last round and the queries of this one: bucketed by
-        // owner (own tile: stored / answered in place) ...
-        if (m_upd > 0) TRY(dest_place(c, ru, m_upd, xdest_u, xbo_u));
-        m_upd = 0;
-        rq.sendq = xqoff; rq.order = xorder;
-        TRY(dest_place(c, rq, m, xdest_q, xbo_q));
-        if (R > 1) {
-          // ... and sent as ONE message per part: its update records, then its query
-          // offsets; the owners store the updates before they look anything up
-          // (k_fuse_updates, then k_fuse_answers) and send the answers back
-          constexpr u32 W = (u32) RANKREC;
-          FuseTab ts, tr;
-          ts.n = tr.n = R;
-          std::vector<u64> sw(R), rw(R), sq(R), rqc(R);
-          ts.upre[0] = ts.qpre[0] = tr.upre[0] = tr.qpre[0] = 0;
-          ts.wpre[0] = tr.wpre[0] = 0;
-          for (u32 r = 0; r < R; r++) {
-            const u64 us = mine[R + r], qs = mine[r];
-            const u64 ur = gathered[(size_t) r * GW + R + c->part], qr = gathered[(size_t) r * GW + c->part];
-            sw[r] = us * W + qs; rw[r] = ur * W + qr;
-            sq[r] = qs; rqc[r] = qr;
-            ts.upre[r + 1] = ts.upre[r] + (u32) us; ts.qpre[r + 1] = ts.qpre[r] + (u32) qs;
-            ts.wpre[r + 1] = ts.wpre[r] + sw[r];
-            tr.upre[r + 1] = tr.upre[r] + (u32) ur; tr.qpre[r + 1] = tr.qpre[r] + (u32) qr;
-            tr.wpre[r + 1] = tr.wpre[r] + rw[r];
-          }
-          // (a position of a tile is updated and asked for at most once per round;
-          // every part sees the whole matrix, so all of them leave here or none)
-          int toobig = 0;
-          for (u32 q = 0; q < R; q++) {
-            u64 tu = 0, tq = 0;
-            for (u32 s = 0; s < R; s++) {
-              tu += gathered[(size_t) s * GW + R + q];
-              tq += gathered[(size_t) s * GW + q];
-            }
-            const u64 first_q = (u64) q * tl.T < N ? (u64) q * tl.T : N;
-            const u64 tile_q = first_q + tl.T < N ? tl.T : N - first_q;
-            if (tu > tile_q || tq > tile_q) toobig = 1;
-          }
-          if (toobig || (u64) tr.upre[R] + 64 > xrecv_n || (u64) tr.qpre[R] + 64 > xrecv_n) {
-            gtamd_set_error("rank exchange: %u updates and %u queries for a tile of %llu positions",
-                            tr.upre[R], tr.qpre[R], (unsigned long long) Tn);
-            return -1;
-          }
-          const u64 nsend = (u64) ts.upre[R] + ts.qpre[R];
-          if (nsend > 0) {
-            k_fuse_pack<P><<<(u32) div_up(nsend, 256), 256, 0, st>>>(ts, xoff, xrank, xqoff, xmsg);
-            HIP_TRY(hipGetLastError());
-          }
-          TRY(comm_alltoallv(c, xmsg, sw.data(), xrecv_msg, rw.data(), 4, "new ranks and queries"));
-          if (tr.upre[R] > 0) {
-            k_fuse_updates<P><<<(u32) div_up(tr.upre[R], 256), 256, 0, st>>>(tr, xrecv_msg, isa);
-            HIP_TRY(hipGetLastError());
-          }
-          if (tr.qpre[R] > 0) {
-            k_fuse_answers<P><<<(u32) div_up(tr.qpre[R], 256), 256, 0, st>>>(tr, xrecv_msg, isa, xrecv_ans);
-            HIP_TRY(hipGetLastError());
-          }
-          // (the look-ups in the own tile, now that everybody's new ranks are in)
-          if (m > 0) {
-            k_local_lookups<P><<<(u32) div_up(m, 256), 256, 0, st>>>(rq, m);
-            HIP_TRY(hipGetLastError());
-          }
-          TRY(comm_alltoallv(c, xrecv_ans, rqc.data(), xans, sq.data(), sizeof(P), "answers"));
-          if (ts.qpre[R] > 0) {
-            k_k2_scatter<P><<<(u32) div_up(ts.qpre[R], 256), 256, 0, st>>>(xans, xorder, ts.qpre[R], k2);
-            HIP_TRY(hipGetLastError());
-          }
-        } else if (m > 0) {
-          k_local_lookups<P><<<(u32) div_up(m, 256), 256, 0, st>>>(rq, m);
-          HIP_TRY(hipGetLastError());
-        }
+        bool nobody_left = false;
+        TRY(exchange_round(s, &nobody_left));
+        if (nobody_left) break;
       }
       rounds++;
       if (debug)
         fprintf(stderr, "gtamd: part %u round %u h=%llu tied=%llu\n", c->part, rounds,
-                (unsigned long long) h, (unsigned long long) m);
-      if (m == 0) {   // only serving other parts' queries
-        h *= 2;
+                (unsigned long long) s.h, (unsigned long long) s.m);
+      if (s.m == 0) {   // only serving other parts' queries
+        s.h *= 2;
         HIP_TRY(hipMemsetAsync(c->d_counts, 0, 2 * DEST_MAXPARTS * 4, st));
         continue;
       }
-      if (!dist && rk_windows && h > rk_h0) {
-        // an offset beyond the windows built so far?  then build what it reaches
-        HIP_TRY(hipMemsetAsync(&c->d_stats->count2, 0, 4, st));
-        k_win_check<P><<<(u32) div_up(m, 256), 256, 0, st>>>(upos, m, h, rk_wb, rk_nwin, w_built,
-                                                           w_need, c->d_stats);
-        HIP_TRY(hipGetLastError());
-        TRY(fetch_stats(c));
-        if (c->h_stats->count2 != 0) TRY(build_rank(false));
-      }
-      const u32 g = (u32) div_up(m, 256);
-      const u32 ntiles = (u32) div_up(m, rt_stride);   // tiles that start at group borders
-      const u32 nfb = (u32) div_up(m, RT_TILE);         // blocks of the deferred-slot bitmap
-      u32 *tilecnt = koff, *tileoff = koff + nfb + 16;  // (free until the apply step)
-      HIP_TRY(hipMemsetAsync(flagbits, 0, (u64) nfb * (RT_TILE / 8), st));
-      k_tile_starts<<<ntiles / 256 + 1, 256, 0, st>>>(ugrp, m, ntiles, rt_stride, tstart);
-      HIP_TRY(hipGetLastError());
-      k_round_tile<P><<<ntiles, RT_THREADS, 0, st>>>(
-          uidx, upos, ugrp, k2, m, cvo, hv, tstart, flagbits, dist ? nullptr : rank, h, n);
-      HIP_TRY(hipGetLastError());
-      k_flag_count<<<nfb / 256 + 1, 256, 0, st>>>(flagbits, m, nfb, tilecnt);
-      HIP_TRY(hipGetLastError());
-      TRY(scan_u32(SCAN_SUM, tilecnt, tileoff, nfb, false, scanws2, st));
-      k_total<<<1, 1, 0, st>>>(tileoff, tilecnt, nfb, c->d_stats);
-      HIP_TRY(hipGetLastError());
-      TRY(fetch_stats(c));
-      const u64 nf = c->h_stats->count;
-      if (debug)
-        fprintf(stderr, "gtamd: part %u round %u: %llu entries in groups across tile borders "
-                "(%u tiles, stride %u)\n", c->part, rounds, (unsigned long long) nf, ntiles, rt_stride);
-      if (nf > 0) {
-        // groups crossing a tile border / larger than a tile: ordered by
-        // (group, k2) through two stable sorts of an index
-        k_flag_gather<P><<<nfb, RT_THREADS, 0, st>>>(flagbits, tileoff, ugrp, k2, upos, m, fk2,
-                                                       fk2s_a, fgrp, fpos, fj, perm_a);
-        HIP_TRY(hipGetLastError());
-        TRY(radix_sort_pairs<P, u32>(fk2s_a, perm_a, fk2s_b, perm_b, nf, ps, pw, pn, rws2, st,
-                                     nullptr, nullptr));
-        u32 *perm1 = (pn & 1) ? perm_b : perm_a, *permx = (pn & 1) ? perm_a : perm_b;
-        const u32 gf = (u32) div_up(nf, 256);
-        k_gather_u32<<<gf, 256, 0, st>>>(fgrp, perm1, nf, gk_a);
-        HIP_TRY(hipGetLastError());
-        TRY(radix_sort_pairs<u32, u32>(gk_a, perm1, gk_b, permx, nf, gs, gw, gn, rws2, st,
-                                       nullptr, nullptr));
-        const u32 *perm2 = (gn & 1) ? permx : perm1;
-        k_flag_heads<P><<<gf, 256, 0, st>>>(perm2, fgrp, fk2, fpos, uidx, fj, nf, fhv, cvs);
-        HIP_TRY(hipGetLastError());
-        TRY(scan_u32(SCAN_MAX, fhv, fhv, nf, true, scanws2, st));
-        k_flag_scatter<P><<<gf, 256, 0, st>>>(cvs, fhv, fj, nf, cvo, hv);
-        HIP_TRY(hipGetLastError());
-      }
-      // (koff doubles as the per-block survivor counts and their scan)
-      u32 *bcnt = koff, *boffs = koff + g + 16;
-      k_round_apply<P><<<g, 256, 0, st>>>(cvo, hv, uidx, ugrp, m, index_offset, sa,
-                                          dist ? nullptr : rank, keep, bcnt);
-      HIP_TRY(hipGetLastError());
-      TRY(scan_u32(SCAN_SUM, bcnt, boffs, g, false, scanws2, st));
-      k_round_compact<P><<<g, 256, 0, st>>>(keep, boffs, bcnt, uidx, cvo, hv, m, uidx2,
-                                            upos2, ugrp2, c->d_stats);
-      HIP_TRY(hipGetLastError());
-      TRY(fetch_stats(c));
-      const u64 m_old = m;
-      m = c->h_stats->count;
-      h *= 2;
-      if (dist) {
-        // the new ranks of this round (slots of the old list) and the queries
-        // of the next (the compacted list): counted now, exchanged at the top
-        ru.cval = cvo; ru.gnew = hv; ru.ugrp = ugrp; ru.index_offset = index_offset;
-        ru.tl = tl; ru.isa = isa; ru.soff = xoff; ru.srank = xrank;
-        m_upd = m_old;
-        TRY(dest_count(c, ru, m_upd, xdest_u, xbc_u, xbo_u, scanws2, 1));
-        rq.upos = upos2; rq.h = h;
-        TRY(dest_count(c, rq, m, xdest_q, xbc_q, xbo_q, scanws2, 0));
-      }
-      u32 *t;
-      t = uidx; uidx = uidx2; uidx2 = t;
-      t = ugrp; ugrp = ugrp2; ugrp2 = t;
-      P *tp = upos; upos = upos2; upos2 = tp;
-      if (dist) ru.ugrp = ugrp2;   // (the old list's groups, after the swap)
+      TRY(refine_round(s));
     }
-    HIP_TRY(hipEventRecord(c->ev[5], st));
-    // ---- final entries of the tied suffixes (after the emission has
-    // written its provisional values)
+    HIP_TRY(hipEventRecord(c->ev[EV_REFINE_END], st));
+    return 0;
+  }
+
+  // one round, the exchange of a part build: the ranks h further on arrive in ar.k2
+  int exchange_round(RoundState &s, bool *nobody_left) {
+    const u64 m = s.m, h = s.h;
+    const size_t GW = s.GW;
+    std::vector<u64> &mine = s.mine, &gathered = s.gathered;
+    // does this round's offset reach windows whose ranks have not travelled?
+    // (never while h <= rk.h0; the parts decide together, in the allgather below)
+    u64 more = 0;
+    if (rk.windows && h > rk.h0) {
+      HIP_TRY(hipMemsetAsync(&c->d_stats->count2, 0, 4, st));
+      if (m > 0) {
+        k_win_check<P><<<(u32) div_up(m, 256), 256, 0, st>>>(ar.upos, m, h, rk.wb, rk.nwin, rk.w_built,
+                                                           rk.w_need, c->d_stats);
+        HIP_TRY(hipGetLastError());
+      }
+      HIP_TRY(hipMemcpyAsync(c->h_stats, c->d_stats, sizeof(Stats), hipMemcpyDeviceToHost, st));
+    }
+    // ONE allgather per round: pending updates, queries, who is left, and
+    // whether more first ranks have to travel
+    HIP_TRY(hipMemcpyAsync(c->h_counts, c->d_counts, 2 * DEST_MAXPARTS * 4,
+                           hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (rk.windows && h > rk.h0) more = c->h_stats->count2 != 0;
+    for (u32 r = 0; r < R; r++) {
+      mine[r] = c->h_counts[r];                        // queries to r
+      mine[R + r] = c->h_counts[DEST_MAXPARTS + r];    // updates to r
+    }
+    mine[2 * R] = m;
+    mine[2 * R + 1] = more;
+    TRY(comm_allgather(c, 0, mine.data(), gathered.data(), (u32) (GW * 8)));
+    u64 left = 0;
+    for (u32 p = 0; p < R; p++) {
+      left += gathered[(size_t) p * GW + 2 * R];
+      more |= gathered[(size_t) p * GW + 2 * R + 1];
+    }
+    if (left == 0) {   // (ranks nobody will ask for need not travel)
+      *nobody_left = true;
+      return 0;
+    }
+    if (more) {
+      TRY(send_ranks());
+      // (the exchange used the bucketing buffers of this round's queries; the
+      // counts come out the same)
+      TRY(dest_count(c, s.rq, m, ar.xdest_q, ar.xbc_q, ar.xbo_q, ar.scanws2, 0));
+    }
+    // the new ranks of the last round and the queries of this one: bucketed by
+    // owner (own tile: stored / answered in place) ...
+    if (s.m_upd > 0) TRY(dest_place(c, s.ru, s.m_upd, ar.xdest_u, ar.xbo_u));
+    s.m_upd = 0;
+    s.rq.sendq = ar.xqoff; s.rq.order = ar.xorder;
+    TRY(dest_place(c, s.rq, m, ar.xdest_q, ar.xbo_q));
+    if (R == 1) {
+      if (m > 0) {
+        k_local_lookups<P><<<(u32) div_up(m, 256), 256, 0, st>>>(s.rq, m);
+        HIP_TRY(hipGetLastError());
+      }
+      return 0;
+    }
+    // ... and sent as ONE message per part: its update records, then its query
+    // offsets; the owners store the updates before they look anything up
+    // (k_fuse_updates, then k_fuse_answers) and send the answers back
+    constexpr u32 W = (u32) RANKREC;
+    FuseTab ts, tr;
+    ts.n = tr.n = R;
+    std::vector<u64> sendw(R), recvw(R), sq(R), rqc(R);    // words / queries to and from a part
+    ts.upre[0] = ts.qpre[0] = tr.upre[0] = tr.qpre[0] = 0;
+    ts.wpre[0] = tr.wpre[0] = 0;
+    for (u32 r = 0; r < R; r++) {
+      const u64 us = mine[R + r], qs = mine[r];
+      const u64 ur = gathered[(size_t) r * GW + R + c->part], qr = gathered[(size_t) r * GW + c->part];
+      sendw[r] = us * W + qs; recvw[r] = ur * W + qr;
+      sq[r] = qs; rqc[r] = qr;
+      ts.upre[r + 1] = ts.upre[r] + (u32) us; ts.qpre[r + 1] = ts.qpre[r] + (u32) qs;
+      ts.wpre[r + 1] = ts.wpre[r] + sendw[r];
+      tr.upre[r + 1] = tr.upre[r] + (u32) ur; tr.qpre[r + 1] = tr.qpre[r] + (u32) qr;
+      tr.wpre[r + 1] = tr.wpre[r] + recvw[r];
+    }
+    // (a position of a tile is updated and asked for at most once per round)
+    const u32 parts = R;
+    const bool toobig =
+        tile_overrun([&gathered, GW, parts](u32 p, u32 q) { return gathered[(size_t) p * GW + parts + q]; }) ||
+        tile_overrun([&gathered, GW](u32 p, u32 q) { return gathered[(size_t) p * GW + q]; });
+    if (toobig || (u64) tr.upre[R] + 64 > xrecv_n || (u64) tr.qpre[R] + 64 > xrecv_n) {
+      gtamd_set_error("rank exchange: %u updates and %u queries for a tile of %llu positions",
+                      tr.upre[R], tr.qpre[R], (unsigned long long) Tn);
+      return -1;
+    }
+    const u64 nsend = (u64) ts.upre[R] + ts.qpre[R];
+    if (nsend > 0) {
+      k_fuse_pack<P><<<(u32) div_up(nsend, 256), 256, 0, st>>>(ts, ar.xoff, ar.xrank, ar.xqoff, ar.xmsg);
+      HIP_TRY(hipGetLastError());
+    }
+    TRY(comm_alltoallv(c, ar.xmsg, sendw.data(), xrecv_msg, recvw.data(), 4, "new ranks and queries"));
+    if (tr.upre[R] > 0) {
+      k_fuse_updates<P><<<(u32) div_up(tr.upre[R], 256), 256, 0, st>>>(tr, xrecv_msg, isa);
+      HIP_TRY(hipGetLastError());
+    }
+    if (tr.qpre[R] > 0) {
+      k_fuse_answers<P><<<(u32) div_up(tr.qpre[R], 256), 256, 0, st>>>(tr, xrecv_msg, isa, xrecv_ans);
+      HIP_TRY(hipGetLastError());
+    }
+    // (the look-ups in the own tile, now that everybody's new ranks are in)
+    if (m > 0) {
+      k_local_lookups<P><<<(u32) div_up(m, 256), 256, 0, st>>>(s.rq, m);
+      HIP_TRY(hipGetLastError());
+    }
+    TRY(comm_alltoallv(c, xrecv_ans, rqc.data(), ar.xans, sq.data(), sizeof(P), "answers"));
+    if (ts.qpre[R] > 0) {
+      k_k2_scatter<P><<<(u32) div_up(ts.qpre[R], 256), 256, 0, st>>>(ar.xans, ar.xorder, ts.qpre[R], ar.k2);
+      HIP_TRY(hipGetLastError());
+    }
+    return 0;
+  }
+
+  // one round: tiles, groups across tile borders, apply, compact; the lists swap
+  int refine_round(RoundState &s) {
+    const u64 m = s.m, h = s.h;
+    if (!dist && rk.windows && h > rk.h0) {
+      // an offset beyond the windows built so far?  then build what it reaches
+      HIP_TRY(hipMemsetAsync(&c->d_stats->count2, 0, 4, st));
+      k_win_check<P><<<(u32) div_up(m, 256), 256, 0, st>>>(ar.upos, m, h, rk.wb, rk.nwin, rk.w_built,
+                                                         rk.w_need, c->d_stats);
+      HIP_TRY(hipGetLastError());
+      TRY(fetch_stats(c));
+      if (c->h_stats->count2 != 0) TRY(build_rank(false));
+    }
+    // nominal distance of the round tiles' starts: the rest of a tile is the
+    // slack for the group that lies across (a group larger than the slack goes
+    // through the global path, forty launches per round)
+    const u32 rt_stride = sw.round_stride;
+    const u32 g = (u32) div_up(m, 256);
+    const u32 ntiles = (u32) div_up(m, rt_stride);   // tiles that start at group borders
+    const u32 nfb = (u32) div_up(m, RT_TILE);         // blocks of the deferred-slot bitmap
+    u32 *tilecnt = ar.koff, *tileoff = ar.koff + nfb + 16;  // (free until the apply step)
+    HIP_TRY(hipMemsetAsync(ar.flagbits, 0, (u64) nfb * (RT_TILE / 8), st));
+    k_tile_starts<<<ntiles / 256 + 1, 256, 0, st>>>(ar.ugrp, m, ntiles, rt_stride, ar.tstart);
+    HIP_TRY(hipGetLastError());
+    k_round_tile<P><<<ntiles, RT_THREADS, 0, st>>>(
+        ar.uidx, ar.upos, ar.ugrp, ar.k2, m, ar.cvo, ar.hv, ar.tstart, ar.flagbits, dist ? nullptr : rank, h, n);
+    HIP_TRY(hipGetLastError());
+    k_flag_count<<<nfb / 256 + 1, 256, 0, st>>>(ar.flagbits, m, nfb, tilecnt);
+    HIP_TRY(hipGetLastError());
+    TRY(scan_u32(SCAN_SUM, tilecnt, tileoff, nfb, false, ar.scanws2, st));
+    k_total<<<1, 1, 0, st>>>(tileoff, tilecnt, nfb, c->d_stats);
+    HIP_TRY(hipGetLastError());
+    TRY(fetch_stats(c));
+    const u64 nf = c->h_stats->count;
+    if (debug)
+      fprintf(stderr, "gtamd: part %u round %u: %llu entries in groups across tile borders "
+              "(%u tiles, stride %u)\n", c->part, rounds, (unsigned long long) nf, ntiles, rt_stride);
+    if (nf > 0) {
+      // groups crossing a tile border / larger than a tile: ordered by
+      // (group, k2) through two stable sorts of an index
+      k_flag_gather<P><<<nfb, RT_THREADS, 0, st>>>(ar.flagbits, tileoff, ar.ugrp, ar.k2, ar.upos, m, ar.fk2,
+                                                     ar.fk2s_a, ar.fgrp, ar.fpos, ar.fj, ar.perm_a);
+      HIP_TRY(hipGetLastError());
+      TRY(radix_sort_pairs<P, u32>(ar.fk2s_a, ar.perm_a, ar.fk2s_b, ar.perm_b, nf, ps, pw, pn, ar.rws2, st,
+                                   nullptr, nullptr));
+      u32 *perm1 = (pn & 1) ? ar.perm_b : ar.perm_a, *permx = (pn & 1) ? ar.perm_a : ar.perm_b;
+      const u32 gf = (u32) div_up(nf, 256);
+      k_gather_u32<<<gf, 256, 0, st>>>(ar.fgrp, perm1, nf, ar.gk_a);
+      HIP_TRY(hipGetLastError());
+      TRY(radix_sort_pairs<u32, u32>(ar.gk_a, perm1, ar.gk_b, permx, nf, s.gs, s.gw, s.gn, ar.rws2, st,
+                                     nullptr, nullptr));
+      const u32 *perm2 = (s.gn & 1) ? permx : perm1;
+      k_flag_heads<P><<<gf, 256, 0, st>>>(perm2, ar.fgrp, ar.fk2, ar.fpos, ar.uidx, ar.fj, nf, ar.fhv, ar.cvs);
+      HIP_TRY(hipGetLastError());
+      TRY(scan_u32(SCAN_MAX, ar.fhv, ar.fhv, nf, true, ar.scanws2, st));
+      k_flag_scatter<P><<<gf, 256, 0, st>>>(ar.cvs, ar.fhv, ar.fj, nf, ar.cvo, ar.hv);
+      HIP_TRY(hipGetLastError());
+    }
+    // (koff doubles as the per-block survivor counts and their scan)
+    u32 *bcnt = ar.koff, *boffs = ar.koff + g + 16;
+    k_round_apply<P><<<g, 256, 0, st>>>(ar.cvo, ar.hv, ar.uidx, ar.ugrp, m, index_offset, sa,
+                                        dist ? nullptr : rank, ar.keep, bcnt);
+    HIP_TRY(hipGetLastError());
+    TRY(scan_u32(SCAN_SUM, bcnt, boffs, g, false, ar.scanws2, st));
+    k_round_compact<P><<<g, 256, 0, st>>>(ar.keep, boffs, bcnt, ar.uidx, ar.cvo, ar.hv, m, ar.uidx2,
+                                          ar.upos2, ar.ugrp2, c->d_stats);
+    HIP_TRY(hipGetLastError());
+    TRY(fetch_stats(c));
+    s.m = c->h_stats->count;
+    s.h *= 2;
+    if (dist) {
+      // the new ranks of this round (slots of the old list) and the queries
+      // of the next (the compacted list): counted now, exchanged at the top
+      s.ru.cval = ar.cvo; s.ru.gnew = ar.hv; s.ru.ugrp = ar.ugrp; s.ru.index_offset = index_offset;
+      s.ru.tl = tl; s.ru.isa = isa; s.ru.soff = ar.xoff; s.ru.srank = ar.xrank;
+      s.m_upd = m;
+      TRY(dest_count(c, s.ru, s.m_upd, ar.xdest_u, ar.xbc_u, ar.xbo_u, ar.scanws2, 1));
+      s.rq.upos = ar.upos2; s.rq.h = s.h;
+      TRY(dest_count(c, s.rq, s.m, ar.xdest_q, ar.xbc_q, ar.xbo_q, ar.scanws2, 0));
+    }
+    std::swap(ar.uidx, ar.uidx2);
+    std::swap(ar.ugrp, ar.ugrp2);
+    std::swap(ar.upos, ar.upos2);
+    if (dist) s.ru.ugrp = ar.ugrp2;   // (the old list's groups, after the swap)
+    return 0;
+  }
+
+  // ---- final entries of the tied suffixes (after the emission has
+  // written its provisional values), .llv
+  int tie_fix() {
     TRY(launch_emission());
     HIP_TRY(hipStreamWaitEvent(st, c->ev_emitted, 0));
     // 32-bit LCP values that do not fit the byte, by table index: in a buffer
@@ -5296,32 +5541,31 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
     }
     if (!apply_early) TRY(launch_apply(st));
     const u32 g0 = (u32) div_up(m0, 256);
-    u32 *bcnt0 = koff, *boff0 = koff + g0 + 16;   // per-workgroup counts and their scan
+    u32 *bcnt0 = ar.koff, *boff0 = ar.koff + g0 + 16;   // per-workgroup counts and their scan
     if (m0 > 0) {
       // .suf/.bwt of the tied entries: random accesses, on the second stream
       // (behind the emission there) while this stream sorts the LCP pairs
-      HIP_TRY(hipEventRecord(c->ev_sorted, st));          // rounds are done
-      HIP_TRY(hipStreamWaitEvent(c->st2, c->ev_sorted, 0));
-      k_fix_basic<BITS, P><<<g0, 256, 0, c->st2>>>(c->text, uidx0, m0, sa, d_suf, d_bwt,
+      TRY(fork_second_stream());          // rounds are done
+      k_fix_basic<BITS, P><<<g0, 256, 0, c->st2>>>(c->text, ar.uidx0, m0, sa, d_suf, d_bwt,
                                                    c->d_stats, index_offset);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipEventRecord(c->ev_emitted, c->st2));
     }
     if (want_lcp && m0 > 0) {
       // entries tied with their predecessor, sorted by text position
-      k_tied_counts<<<g0, 256, 0, st>>>(uidx0, m0, tiebits2, bcnt0);
+      k_tied_counts<<<g0, 256, 0, st>>>(ar.uidx0, m0, tiebits2, bcnt0);
       HIP_TRY(hipGetLastError());
-      TRY(scan_u32(SCAN_SUM, bcnt0, boff0, g0, false, scanws2, st));
+      TRY(scan_u32(SCAN_SUM, bcnt0, boff0, g0, false, ar.scanws2, st));
       k_total<<<1, 1, 0, st>>>(boff0, bcnt0, g0, c->d_stats);
       HIP_TRY(hipGetLastError());
       TRY(fetch_stats(c));
       const u64 m1 = c->h_stats->count;
-      k_lcp_pairs<P><<<g0, 256, 0, st>>>(boff0, tiebits2, uidx0, sa, m0, lk_a, lv_a);
+      k_lcp_pairs<P><<<g0, 256, 0, st>>>(boff0, tiebits2, ar.uidx0, sa, m0, ar.lk_a, ar.lv_a);
       HIP_TRY(hipGetLastError());
-      TRY(radix_sort_pairs<P, u32>(lk_a, lv_a, lk_b, lv_b, m1, ps, pw, pn, rws2, st,
+      TRY(radix_sort_pairs<P, u32>(ar.lk_a, ar.lv_a, ar.lk_b, ar.lv_b, m1, ps, pw, pn, ar.rws2, st,
                                    nullptr, nullptr));
-      const P *pk = (pn & 1) ? lk_b : lk_a;
-      const u32 *pv = (pn & 1) ? lv_b : lv_a;
+      const P *pk = (pn & 1) ? ar.lk_b : ar.lk_a;
+      const u32 *pv = (pn & 1) ? ar.lv_b : ar.lv_a;
       k_lcp_chunks<BITS, P><<<stride_grid(div_up(div_up(m1, LCP_CHUNK), 256)), 256, 0, st>>>(
           c->text, pk, pv, m1, sa, d_lcp, lcpfull, c->d_stats);
       HIP_TRY(hipGetLastError());
@@ -5329,101 +5573,104 @@ static int run_impl(gtamd_esa_ctx *c, const Switches &sw, u32 want, bool dist) {
     // (the pairs' entries written beside all this: the tie fix above touches
     // other entries; the walk over the whole LCP table below needs them)
     if (apply_early) HIP_TRY(hipStreamWaitEvent(st, c->ev_applied, 0));
-    if (want_lcp) {
-      // .llv from the byte table and the side table
-      TRY(fetch_stats(c));
-      const u64 pairs = c->h_stats->numlarge;
-      if (pairs > c->llv_cap) {
-        free_dev(c->llv);
-        c->llv = nullptr;
-        c->llv_cap = 0;
-        HIP_TRY(hipMalloc(&c->llv, (pairs + pairs / 4 + 1024) * 16));
-        c->llv_cap = pairs + pairs / 4 + 1024;
-      }
-      if (pairs > 0) {
-        const u32 gl = (u32) div_up(NL, LLV_TILE);
-        // (counts and their scan: the round buffers are free, but sized for the
-        // tied suffixes -- the per-word arrays of the radix workspace hold
-        // NL / 64 + 16 words each, more than the NL / 4096 needed here)
-        u32 *lc = cntw, *lo = offw;
-        k_large_counts<<<gl, 256, 0, st>>>(d_lcp, NL, lc);
-        HIP_TRY(hipGetLastError());
-        TRY(scan_u32(SCAN_SUM, lc, lo, gl, false, scanws, st));
-        k_llv_emit<<<gl, 256, 0, st>>>(d_lcp, NL, lcpfull, lo, index_offset, c->llv);
-        HIP_TRY(hipGetLastError());
-      }
-      c->llv_pairs = pairs;
-    }
-    }  // !settled
-  }
-  TRY(launch_emission());
-  HIP_TRY(hipStreamWaitEvent(st, c->ev_emitted, 0));
-  HIP_TRY(hipEventRecord(c->ev[6], st));
-  TRY(fetch_stats(c));
-
-  // results (of this part; the caller combines parts: sums, max, and the one
-  // part that holds suffix 0 reports `longest`)
-  c->stats.totallength = n;
-  c->stats.numberofallsortedsuffixes = N;
-  c->stats.longest = c->h_stats->longest;
-  c->stats.largelcpvalues = want_lcp ? c->h_stats->numlarge : 0;
-  c->stats.maxbranchdepth =
-      want_lcp ? (c->h_stats->maxlcp > c->h_stats->dmax ? c->h_stats->maxlcp
-                                                         : c->h_stats->dmax) : 0;
-  c->stats.lcptabsum = want_lcp ? c->h_stats->lcpsum + c->h_stats->dsum : 0;
-  if (long_prefix && want_lcp) {
-    HIP_TRY(hipMemsetAsync(&c->d_stats->msum, 0, 8, st));
-    if (c->NL > 0) {
-      k_masked_lcpsum<<<stride_grid(div_up(c->NL, 256)), 256, 0, st>>>(
-          c->text, c->suf.as<u64>(), c->lcp.as<u8>(), c->NL, prefixlength, c->d_stats);
-      HIP_TRY(hipGetLastError());
-    }
-    if (c->llv_pairs > 0) {
-      k_masked_llvsum<<<stride_grid(div_up(c->llv_pairs, 256)), 256, 0, st>>>(
-          c->text, c->suf.as<u64>(), c->llv, c->llv_pairs, c->index_offset, prefixlength,
-          c->d_stats);
-      HIP_TRY(hipGetLastError());
-    }
+    if (!want_lcp) return 0;
+    // .llv from the byte table and the side table
     TRY(fetch_stats(c));
-    c->stats.lcptabsum = c->h_stats->msum;
+    const u64 pairs = c->h_stats->numlarge;
+    if (pairs > c->llv_cap) {
+      free_dev(c->llv);
+      c->llv = nullptr;
+      c->llv_cap = 0;
+      HIP_TRY(hipMalloc(&c->llv, (pairs + pairs / 4 + 1024) * 16));
+      c->llv_cap = pairs + pairs / 4 + 1024;
+    }
+    if (pairs > 0) {
+      const u32 gl = (u32) div_up(NL, LLV_TILE);
+      // (counts and their scan: the round buffers are free, but sized for the
+      // tied suffixes -- the per-word arrays of the radix workspace hold
+      // NL / 64 + 16 words each, more than the NL / 4096 needed here)
+      u32 *lc = wd.cntw, *lo = wd.offw;
+      k_large_counts<<<gl, 256, 0, st>>>(d_lcp, NL, lc);
+      HIP_TRY(hipGetLastError());
+      TRY(scan_u32(SCAN_SUM, lc, lo, gl, false, wd.scanws, st));
+      k_llv_emit<<<gl, 256, 0, st>>>(d_lcp, NL, lcpfull, lo, index_offset, c->llv);
+      HIP_TRY(hipGetLastError());
+    }
+    c->llv_pairs = pairs;
+    return 0;
   }
-  c->stats.prefixlength = prefixlength;
-  c->stats.refine_rounds = rounds;
-  c->stats.tied_suffixes = (m0_tied_all ? m0_tied_all : m0) + 2 * npairs + c->h_stats->smalldone;
-  c->stats.pair_suffixes = 2 * npairs;
-  c->stats.device_bytes = c->alloc_bytes;
-  float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[6])); c->timing.total_ms = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1])); c->timing.keygen_ms = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, c->ev[1], c->ev[2])); c->timing.sort_ms = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, c->ev[2], c->ev[3])); c->timing.finalize_ms = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, c->ev[4], c->ev[5])); c->timing.refine_ms = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, c->ev[5], c->ev[6])); c->timing.tie_fix_ms = ms;
-  float sc = 0;
-  for (int i = 0; i < nev; i++) {
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_scatter[2 * i], c->ev_scatter[2 * i + 1]));
-    sc += ms;
+
+  // ---- join, statistics, timing ----------------------------------------------------
+  int report() {
+    TRY(launch_emission());
+    HIP_TRY(hipStreamWaitEvent(st, c->ev_emitted, 0));
+    HIP_TRY(hipEventRecord(c->ev[EV_DONE], st));
+    TRY(fetch_stats(c));
+
+    // results (of this part; the caller combines parts: sums, max, and the one
+    // part that holds suffix 0 reports `longest`)
+    c->stats.totallength = n;
+    c->stats.numberofallsortedsuffixes = N;
+    c->stats.longest = c->h_stats->longest;
+    c->stats.largelcpvalues = want_lcp ? c->h_stats->numlarge : 0;
+    c->stats.maxbranchdepth =
+        want_lcp ? (c->h_stats->maxlcp > c->h_stats->dmax ? c->h_stats->maxlcp
+                                                           : c->h_stats->dmax) : 0;
+    c->stats.lcptabsum = want_lcp ? c->h_stats->lcpsum + c->h_stats->dsum : 0;
+    if (long_prefix && want_lcp) {
+      HIP_TRY(hipMemsetAsync(&c->d_stats->msum, 0, 8, st));
+      if (c->NL > 0) {
+        k_masked_lcpsum<<<stride_grid(div_up(c->NL, 256)), 256, 0, st>>>(
+            c->text, c->suf.as<u64>(), c->lcp.as<u8>(), c->NL, prefixlength, c->d_stats);
+        HIP_TRY(hipGetLastError());
+      }
+      if (c->llv_pairs > 0) {
+        k_masked_llvsum<<<stride_grid(div_up(c->llv_pairs, 256)), 256, 0, st>>>(
+            c->text, c->suf.as<u64>(), c->llv, c->llv_pairs, c->index_offset, prefixlength,
+            c->d_stats);
+        HIP_TRY(hipGetLastError());
+      }
+      TRY(fetch_stats(c));
+      c->stats.lcptabsum = c->h_stats->msum;
+    }
+    c->stats.prefixlength = prefixlength;
+    c->stats.refine_rounds = rounds;
+    c->stats.tied_suffixes = (m0_tied_all ? m0_tied_all : m0) + 2 * npairs + c->h_stats->smalldone;
+    c->stats.pair_suffixes = 2 * npairs;
+    c->stats.device_bytes = c->alloc_bytes;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_START], c->ev[EV_DONE])); c->timing.total_ms = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_START], c->ev[EV_KEYS])); c->timing.keygen_ms = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_KEYS], c->ev[EV_SORTED])); c->timing.sort_ms = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_SORTED], c->ev[EV_TIEBITS])); c->timing.finalize_ms = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_REFINE_BEGIN], c->ev[EV_REFINE_END])); c->timing.refine_ms = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_REFINE_END], c->ev[EV_DONE])); c->timing.tie_fix_ms = ms;
+    float sc = 0;
+    for (int i = 0; i < nev; i++) {
+      HIP_TRY(hipEventElapsedTime(&ms, c->ev_scatter[2 * i], c->ev_scatter[2 * i + 1]));
+      sc += ms;
+    }
+    if (msd && msd_local > 0) {
+      HIP_TRY(hipEventElapsedTime(&sc, c->ev_scatter[0], c->ev_scatter[1]));
+      nev = 1;
+    }
+    c->timing.scatter_ms = sc;
+    c->timing.scatter_launches = (u32) nev;
+    c->timing.scatter_items = msd ? msd_local : NL;
+    // what the dominant kernel moves per launch: k_msd_local reads every run that fits
+    // its tile and writes the tables of those it sorts itself -- the runs with a crowded
+    // bin it only reads (k_msd_local_radix sorts and writes them)
+    c->timing.scatter_read_items = c->timing.scatter_items;
+    c->timing.scatter_written_items = msd ? msd_local - c->h_stats->crowded : NL;
+    c->stats.msd_crowded_entries = msd ? c->h_stats->crowded : 0;
+    c->stats.rank_entries_built = rank_built;
+    c->timing.dominant_kernel = msd ? 1u : 0u;
+    c->timing.alloc_ms = c->alloc_ms;
+    c->want = want;
+    c->ran = true;
+    return 0;
   }
-  if (msd && msd_local > 0) {
-    HIP_TRY(hipEventElapsedTime(&sc, c->ev_scatter[0], c->ev_scatter[1]));
-    nev = 1;
-  }
-  c->timing.scatter_ms = sc;
-  c->timing.scatter_launches = (u32) nev;
-  c->timing.scatter_items = msd ? msd_local : NL;
-  // what the dominant kernel moves per launch: k_msd_local reads every run that fits
-  // its tile and writes the tables of those it sorts itself -- the runs with a crowded
-  // bin it only reads (k_msd_local_radix sorts and writes them)
-  c->timing.scatter_read_items = c->timing.scatter_items;
-  c->timing.scatter_written_items = msd ? msd_local - c->h_stats->crowded : NL;
-  c->stats.msd_crowded_entries = msd ? c->h_stats->crowded : 0;
-  c->stats.rank_entries_built = rank_built;
-  c->timing.dominant_kernel = msd ? 1u : 0u;
-  c->timing.alloc_ms = c->alloc_ms;
-  c->want = want;
-  c->ran = true;
-  return 0;
-}
+};
 
 extern "C" int gtamd_esa_run(gtamd_esa_ctx *c, uint32_t want) {
   GTAMD_ABI_BEGIN
@@ -5467,9 +5714,9 @@ extern "C" int gtamd_esa_run(gtamd_esa_ctx *c, uint32_t want) {
   }
   int rc;
   if (c->bits == 2)
-    rc = wide ? run_impl<2, true>(c, sw, want, dist) : run_impl<2, false>(c, sw, want, dist);
+    rc = wide ? Build<2, true>(c, sw, want, dist).run() : Build<2, false>(c, sw, want, dist).run();
   else
-    rc = wide ? run_impl<5, true>(c, sw, want, dist) : run_impl<5, false>(c, sw, want, dist);
+    rc = wide ? Build<5, true>(c, sw, want, dist).run() : Build<5, false>(c, sw, want, dist).run();
   guard.ok = rc == 0;
   return rc;
   GTAMD_ABI_END(-1)
