@@ -16,21 +16,20 @@
 #include <condition_variable>
 #include <mutex>
 #include <vector>
-#include <dlfcn.h>
-#include "esa_common.h"
+#include "esa_own.h"
 #include "../../include/gtamd_esa.h"
 
 struct NcclId { char internal[128]; };      // ncclUniqueId (rccl.h: NCCL_UNIQUE_ID_BYTES 128)
 
 struct gtamd_comm {
-  int kind;               // 0 threads, 1 rccl
-  u32 numparts;
+  int kind = 0;           // 0 threads, 1 rccl
+  u32 numparts = 0;
   // ---- threads
   std::mutex mu;
   std::condition_variable cv;
-  u32 arrived;
-  u64 generation;
-  bool broken;
+  u32 arrived = 0;
+  u64 generation = 0;
+  bool broken = false;
   std::vector<const void *> send;            // per part: what it has published
   std::vector<const u64 *> counts;
   std::vector<int> device;
@@ -39,13 +38,12 @@ struct gtamd_comm {
   struct View { gtamd_comm *g; u32 part; int device; };
   std::vector<View> views;
   // ---- rccl
-  void *lib;
-  void *nccl;             // ncclComm_t
-  u32 rank;
-  int rdevice;
-  u8 *d_stage;
-  u64 stage_bytes;
-  hipStream_t rstream;
+  SharedLib lib;
+  void *nccl = nullptr;   // ncclComm_t
+  u32 rank = 0;
+  int rdevice = 0;
+  Stream rstream;
+  Dev<u8> d_stage;
   int (*p_ncclCommInitRank)(void **, int, NcclId, int);
   int (*p_ncclCommDestroy)(void *);
   int (*p_ncclGroupStart)();
@@ -139,12 +137,10 @@ extern "C" gtamd_comm *gtamd_comm_threads_create(uint32_t numparts) {
   gtamd_comm *g = new gtamd_comm();
   g->kind = 0;
   g->numparts = numparts;
-  g->arrived = 0; g->generation = 0; g->broken = false;
   g->send.assign(numparts, nullptr); g->counts.assign(numparts, nullptr);
   g->device.assign(numparts, 0); g->elem.assign(numparts, 0);
   g->slot.resize(numparts);
   g->views.resize(numparts);
-  g->lib = nullptr; g->nccl = nullptr; g->d_stage = nullptr; g->stage_bytes = 0;
   return g;
   GTAMD_ABI_END(nullptr)
 }
@@ -156,12 +152,7 @@ static int rc_allgather(void *user, const void *send, void *recv, uint32_t bytes
   gtamd_comm *g = (gtamd_comm *) user;
   const u64 need = (u64) (g->numparts + 1) * (bytes ? bytes : 1);
   if (hipSetDevice(g->rdevice) != hipSuccess) return -1;
-  if (need > g->stage_bytes) {
-    if (g->d_stage) (void) hipFree(g->d_stage);
-    g->d_stage = nullptr; g->stage_bytes = 0;
-    if (hipMalloc(&g->d_stage, need + 4096) != hipSuccess) return -1;
-    g->stage_bytes = need + 4096;
-  }
+  if (need > g->d_stage.bytes && g->d_stage.alloc(need + 4096) != hipSuccess) return -1;
   if (bytes == 0) {   // (an agreement without payload still is a meeting point)
     u8 z = 0;
     if (hipMemcpyAsync(g->d_stage, &z, 1, hipMemcpyHostToDevice, g->rstream) != hipSuccess) return -1;
@@ -200,18 +191,17 @@ static int rc_alltoallv(void *user, const void *send, const uint64_t *sendcounts
   return bad ? -1 : 0;
 }
 
-static void *rccl_open() {
+static SharedLib rccl_open() {
   const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so"};
-  for (const char *n : names) {
-    void *h = dlopen(n, RTLD_NOW | RTLD_LOCAL);
-    if (h != nullptr) return h;
-  }
-  return nullptr;
+  SharedLib h;
+  for (const char *n : names)
+    if (open_lib(h, n)) break;
+  return h;
 }
 
 extern "C" int gtamd_comm_rccl_unique_id(uint8_t id[128]) {
   GTAMD_ABI_BEGIN
-  void *h = rccl_open();
+  SharedLib h = rccl_open();
   if (h == nullptr) { gtamd_set_error("cannot load librccl: %s", dlerror()); return -1; }
   int (*get)(NcclId *) = (int (*)(NcclId *)) dlsym(h, "ncclGetUniqueId");
   NcclId nid;
@@ -225,19 +215,18 @@ extern "C" gtamd_comm *gtamd_comm_rccl_create(const uint8_t id[128], uint32_t ra
                                               int device) {
   GTAMD_ABI_BEGIN
   if (numparts == 0 || numparts > 128 || rank >= numparts) { gtamd_set_error("invalid rank %u of %u", rank, numparts); return nullptr; }
-  void *h = rccl_open();
+  SharedLib h = rccl_open();
   if (h == nullptr) { gtamd_set_error("cannot load librccl: %s", dlerror()); return nullptr; }
   gtamd_comm *g = new gtamd_comm();
   g->kind = 1; g->numparts = numparts; g->rank = rank; g->rdevice = device;
-  g->arrived = 0; g->generation = 0; g->broken = false;
-  g->lib = h; g->nccl = nullptr; g->d_stage = nullptr; g->stage_bytes = 0; g->rstream = nullptr;
-  g->p_ncclCommInitRank = (int (*)(void **, int, NcclId, int)) dlsym(h, "ncclCommInitRank");
-  g->p_ncclCommDestroy = (int (*)(void *)) dlsym(h, "ncclCommDestroy");
-  g->p_ncclGroupStart = (int (*)()) dlsym(h, "ncclGroupStart");
-  g->p_ncclGroupEnd = (int (*)()) dlsym(h, "ncclGroupEnd");
-  g->p_ncclSend = (int (*)(const void *, size_t, int, int, void *, hipStream_t)) dlsym(h, "ncclSend");
-  g->p_ncclRecv = (int (*)(void *, size_t, int, int, void *, hipStream_t)) dlsym(h, "ncclRecv");
-  g->p_ncclAllGather = (int (*)(const void *, void *, size_t, int, void *, hipStream_t)) dlsym(h, "ncclAllGather");
+  g->lib = std::move(h);
+  g->p_ncclCommInitRank = (int (*)(void **, int, NcclId, int)) dlsym(g->lib, "ncclCommInitRank");
+  g->p_ncclCommDestroy = (int (*)(void *)) dlsym(g->lib, "ncclCommDestroy");
+  g->p_ncclGroupStart = (int (*)()) dlsym(g->lib, "ncclGroupStart");
+  g->p_ncclGroupEnd = (int (*)()) dlsym(g->lib, "ncclGroupEnd");
+  g->p_ncclSend = (int (*)(const void *, size_t, int, int, void *, hipStream_t)) dlsym(g->lib, "ncclSend");
+  g->p_ncclRecv = (int (*)(void *, size_t, int, int, void *, hipStream_t)) dlsym(g->lib, "ncclRecv");
+  g->p_ncclAllGather = (int (*)(const void *, void *, size_t, int, void *, hipStream_t)) dlsym(g->lib, "ncclAllGather");
   NcclId nid;
   memcpy(nid.internal, id, 128);
   if (g->p_ncclCommInitRank == nullptr || g->p_ncclCommDestroy == nullptr || g->p_ncclGroupStart == nullptr ||
@@ -247,10 +236,9 @@ extern "C" gtamd_comm *gtamd_comm_rccl_create(const uint8_t id[128], uint32_t ra
     delete g;
     return nullptr;
   }
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&g->rstream, hipStreamNonBlocking) != hipSuccess ||
+  if (hipSetDevice(device) != hipSuccess || create(g->rstream, hipStreamNonBlocking) != hipSuccess ||
       g->p_ncclCommInitRank(&g->nccl, (int) numparts, nid, (int) rank) != 0) {
     gtamd_set_error("cannot create the RCCL communicator of rank %u of %u on device %d", rank, numparts, device);
-    if (g->rstream) (void) hipStreamDestroy(g->rstream);
     delete g;
     return nullptr;
   }
@@ -283,8 +271,6 @@ extern "C" void gtamd_comm_destroy(gtamd_comm *g) {
   if (g->kind == 1) {
     (void) hipSetDevice(g->rdevice);
     if (g->nccl != nullptr) (void) g->p_ncclCommDestroy(g->nccl);
-    if (g->d_stage != nullptr) (void) hipFree(g->d_stage);
-    if (g->rstream != nullptr) (void) hipStreamDestroy(g->rstream);
   }
   delete g;
 }

@@ -33,6 +33,7 @@
 #include "../../include/gtamd_esa.h"
 #include "esa_prims.h"
 #include "esa_devutil.h"
+#include "esa_own.h"
 
 namespace {
 
@@ -555,9 +556,8 @@ struct InputFile {
   bool fastq;
 };
 
-template <typename T> int dev_alloc(T **p, u64 count) {
-  *p = nullptr;
-  if (hipMalloc(reinterpret_cast<void **>(p), (count ? count : 1) * sizeof(T)) != hipSuccess) {
+template <typename T> int dev_alloc(Dev<T> &p, u64 count) {
+  if (p.alloc((count ? count : 1) * sizeof(T)) != hipSuccess) {
     gtamd_set_error("cannot allocate %llu bytes of device memory for the encoder",
                     (unsigned long long) (count * sizeof(T)));
     return -1;
@@ -568,32 +568,28 @@ template <typename T> int dev_alloc(T **p, u64 count) {
 }  // namespace
 
 struct gtamd_encoder {
-  int device;
-  bool finished;
+  int device = 0;
+  bool finished = false;
   u8 lut[256];             // code per input byte, LUT_UNDEF, LUT_BLANK
-  u32 sigma, packbits;     // alphabet size; bits per symbol of the bit packing
+  u32 sigma = 0, packbits = 0;   // alphabet size; bits per symbol of the bit packing
   std::vector<InputFile> files;
-  hipStream_t st;
-  hipEvent_t ev[4];
-  u8 *d_enc;
-  u64 n, cap_enc;
-  u64 *d_desc_start, *d_desc_end;
-  u64 ndesc, cap_desc;
-  gtamd_encode_summary sum;
-  float total_ms, parse_ms, stats_ms;
-  u64 input_bytes;
+  Stream st;               // (before the buffers: they go first)
+  Event ev[4];
+  Dev<u8> d_enc;
+  u64 n = 0;
+  Dev<u64> d_desc_start, d_desc_end;   // room for the same number of descriptions each
+  u64 ndesc = 0;
+  gtamd_encode_summary sum = {};
+  float total_ms = 0, parse_ms = 0, stats_ms = 0;
+  u64 input_bytes = 0;
   // FASTQ input: a record's sequence and description lengths (the file length
   // table of the reference's FASTQ reader is made from them), in input order
   std::vector<u32> rec_seqlen, rec_desclen, rec_file;
-  bool declined;           // the last finish met FASTQ input the device reader does not take
+  bool declined = false;   // the last finish met FASTQ input the device reader does not take
 };
 
 static void enc_free(gtamd_encoder *e) {
-  if (e->d_enc) (void) hipFree(e->d_enc);
-  if (e->d_desc_start) (void) hipFree(e->d_desc_start);
-  if (e->d_desc_end) (void) hipFree(e->d_desc_end);
-  e->d_enc = nullptr; e->d_desc_start = e->d_desc_end = nullptr;
-  e->cap_enc = e->cap_desc = 0;
+  e->d_enc.reset(); e->d_desc_start.reset(); e->d_desc_end.reset();
 }
 
 extern "C" gtamd_encoder *gtamd_encoder_create(int device, int protein) {
@@ -622,7 +618,7 @@ extern "C" gtamd_encoder *gtamd_encoder_create_map(int device, const uint8_t *sy
     return nullptr;
   }
   gtamd_encoder *e = new gtamd_encoder();
-  e->device = device; e->finished = false;
+  e->device = device;
   e->sigma = numofchars; e->packbits = bitspersymbol;
   for (int c = 0; c < 256; c++) {
     const u8 v = symbolmap[c];
@@ -630,16 +626,12 @@ extern "C" gtamd_encoder *gtamd_encoder_create_map(int device, const uint8_t *sy
   }
   // isspace() of the C locale is skipped between symbols
   e->lut[' '] = e->lut['\t'] = e->lut['\n'] = e->lut['\r'] = e->lut['\v'] = e->lut['\f'] = LUT_BLANK;
-  e->d_enc = nullptr; e->d_desc_start = e->d_desc_end = nullptr;
-  e->n = e->cap_enc = e->ndesc = e->cap_desc = 0;
-  e->total_ms = e->parse_ms = e->stats_ms = 0; e->input_bytes = 0;
-  memset(&e->sum, 0, sizeof e->sum);
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&e->st) != hipSuccess) {
+  if (hipSetDevice(device) != hipSuccess || create(e->st) != hipSuccess) {
     gtamd_set_error("cannot create a stream on device %d", device);
     delete e;
     return nullptr;
   }
-  for (auto &ev : e->ev) (void) hipEventCreate(&ev);
+  for (Event &ev : e->ev) (void) create(ev);
   return e;
   GTAMD_ABI_END(nullptr)
 }
@@ -647,9 +639,6 @@ extern "C" gtamd_encoder *gtamd_encoder_create_map(int device, const uint8_t *sy
 extern "C" void gtamd_encoder_destroy(gtamd_encoder *e) {
   if (e == nullptr) return;
   (void) hipSetDevice(e->device);
-  enc_free(e);
-  for (auto &ev : e->ev) (void) hipEventDestroy(ev);
-  (void) hipStreamDestroy(e->st);
   delete e;
 }
 
@@ -677,19 +666,17 @@ extern "C" int gtamd_encoder_add_file(gtamd_encoder *e, const char *name,
 
 // descriptions seen so far do not fit: grow both arrays, keep the contents
 static int grow_desc(gtamd_encoder *e, u64 need) {
-  if (need <= e->cap_desc) return 0;
+  if (need * 8 <= e->d_desc_start.bytes) return 0;
   const u64 cap = need + need / 2 + 1024;
-  u64 *ns, *ne;
-  TRY(dev_alloc(&ns, cap));
-  TRY(dev_alloc(&ne, cap));
+  Dev<u64> ns, ne;
+  TRY(dev_alloc(ns, cap));
+  TRY(dev_alloc(ne, cap));
   if (e->ndesc > 0) {
     HIP_TRY(hipMemcpyAsync(ns, e->d_desc_start, e->ndesc * 8, hipMemcpyDeviceToDevice, e->st));
     HIP_TRY(hipMemcpyAsync(ne, e->d_desc_end, e->ndesc * 8, hipMemcpyDeviceToDevice, e->st));
   }
   HIP_TRY(hipStreamSynchronize(e->st));
-  if (e->d_desc_start) (void) hipFree(e->d_desc_start);
-  if (e->d_desc_end) (void) hipFree(e->d_desc_end);
-  e->d_desc_start = ns; e->d_desc_end = ne; e->cap_desc = cap;
+  e->d_desc_start = std::move(ns); e->d_desc_end = std::move(ne);
   return 0;
 }
 
@@ -724,20 +711,16 @@ static int encode_files(gtamd_encoder *e, u8 *d_raw, u8 *d_lut, u32 *d_tile,
     HIP_TRY(hipMemcpyAsync(d_raw, f.bytes, f.length, hipMemcpyHostToDevice, e->st));
     if (f.fastq) {
       // ---- the strict four-line form, or not for the device
-      FqGlobals *d_fq = nullptr;
-      u32 *d_nl = nullptr, *d_rs = nullptr, *d_rd = nullptr;
+      Dev<FqGlobals> d_fq;
+      Dev<u32> d_nl, d_rs, d_rd;
       auto decline = [&]() -> int {
-        if (d_fq) (void) hipFree(d_fq);
-        if (d_nl) (void) hipFree(d_nl);
-        if (d_rs) (void) hipFree(d_rs);
-        if (d_rd) (void) hipFree(d_rd);
         e->declined = true;
         gtamd_set_error("FASTQ file '%s' is not in the strict four-line form the device reader "
                         "takes (the host reader reads it)", f.name.c_str());
         return -1;
       };
       if (f.bytes[f.length - 1] != '\n') return decline();
-      TRY(dev_alloc(&d_fq, 1));
+      TRY(dev_alloc(d_fq, 1));
       HIP_TRY(hipMemsetAsync(d_fq, 0, sizeof(FqGlobals), e->st));
       u32 *t_nlc = t_last, *t_nlo = t_state;
       k_fq_tile<0><<<(u32) ntiles, EN_THREADS, 0, e->st>>>(d_raw, f.length, d_lut, nullptr, nullptr, t_nlc,
@@ -759,9 +742,7 @@ static int encode_files(gtamd_encoder *e, u8 *d_raw, u8 *d_lut, u32 *d_tile,
       const u64 nlines = (u64) last[0] + last[1], nsym = (u64) last[2] + last[3];
       if (got.bad != 0 || nlines == 0 || (nlines & 3) != 0) return decline();
       const u64 nrec = nlines / 4;
-      if (dev_alloc(&d_nl, nlines) != 0 || dev_alloc(&d_rs, nrec) != 0 || dev_alloc(&d_rd, nrec) != 0) {
-        (void) decline();
-        e->declined = false;
+      if (dev_alloc(d_nl, nlines) != 0 || dev_alloc(d_rs, nrec) != 0 || dev_alloc(d_rd, nrec) != 0) {
         gtamd_set_error("cannot allocate device memory for the %llu records of '%s'",
                         (unsigned long long) nrec, f.name.c_str());
         return -1;
@@ -785,7 +766,6 @@ static int encode_files(gtamd_encoder *e, u8 *d_raw, u8 *d_lut, u32 *d_tile,
       e->rec_seqlen.resize(r0 + nrec); e->rec_desclen.resize(r0 + nrec); e->rec_file.resize(r0 + nrec, (u32) fi);
       HIP_TRY(hipMemcpy(e->rec_seqlen.data() + r0, d_rs, nrec * 4, hipMemcpyDeviceToHost));
       HIP_TRY(hipMemcpy(e->rec_desclen.data() + r0, d_rd, nrec * 4, hipMemcpyDeviceToHost));
-      (void) hipFree(d_fq); (void) hipFree(d_nl); (void) hipFree(d_rs); (void) hipFree(d_rd);
       for (int c = 0; c < 256; c++) e->sum.originaldistribution[c] += got.origdist[c];
       f.out_len = nsym + nrec - (seen_record ? 0 : 1);
       f.ndesc = nrec;
@@ -861,31 +841,27 @@ static int summarise(gtamd_encoder *e) {
                     e->files.empty() ? "(symbols)" : e->files.back().name.c_str());
     return -1;
   }
-  RunSum<u32> *d_tiles;
-  unsigned long long *d_small;     // 32 counters + first empty sequence
-  TRY(dev_alloc(&d_tiles, ntiles * CL_COUNT));
-  if (dev_alloc(&d_small, 33) != 0) { (void) hipFree(d_tiles); return -1; }
+  Dev<RunSum<u32>> d_tiles;
+  Dev<unsigned long long> d_small;     // 32 counters + first empty sequence
+  TRY(dev_alloc(d_tiles, ntiles * CL_COUNT));
+  TRY(dev_alloc(d_small, 33));
   std::vector<RunSum<u32>> tiles(ntiles * CL_COUNT);
   unsigned long long small[33];
   memset(small, 0, sizeof small);
   small[32] = NONE64;
-  int rc = 0;
-  do {
-    if (hipMemcpyAsync(d_small, small, sizeof small, hipMemcpyHostToDevice, e->st) != hipSuccess) { rc = -1; break; }
-    k_empty_sequence<<<(u32) div_up(n, 256), 256, 0, e->st>>>(e->d_enc, n, d_small + 32);
-    k_run_summary<<<(u32) ntiles, EN_THREADS, 0, e->st>>>(e->d_enc, n, d_tiles, d_small);
-    if (hipGetLastError() != hipSuccess) { rc = -1; break; }
-    // blocking copies: the destinations are pageable (a vector, the stack) and
-    // gone when this function returns
-    if (hipStreamSynchronize(e->st) != hipSuccess) { rc = -1; break; }
-    if (hipMemcpy(tiles.data(), d_tiles, tiles.size() * sizeof(RunSum<u32>),
-                  hipMemcpyDeviceToHost) != hipSuccess) { rc = -1; break; }
-    if (hipMemcpy(small, d_small, sizeof small, hipMemcpyDeviceToHost) != hipSuccess) { rc = -1; break; }
-  } while (0);
-  (void) hipStreamSynchronize(e->st);   // on every exit: nothing in flight behind this frame
-  (void) hipFree(d_tiles);
-  (void) hipFree(d_small);
-  if (rc != 0) { gtamd_set_error("device statistics of the encoded sequence failed"); return -1; }
+  const hipError_t up = hipMemcpyAsync(d_small, small, sizeof small, hipMemcpyHostToDevice, e->st);
+  if (up != hipSuccess) (void) hipStreamSynchronize(e->st);   // nothing in flight behind this frame
+  HIP_TRY(up);
+  k_empty_sequence<<<(u32) div_up(n, 256), 256, 0, e->st>>>(e->d_enc, n, d_small + 32);
+  k_run_summary<<<(u32) ntiles, EN_THREADS, 0, e->st>>>(e->d_enc, n, d_tiles, d_small);
+  const hipError_t launched = hipGetLastError();
+  // blocking copies: the destinations are pageable (a vector, the stack) and
+  // gone when this function returns; the synchronisation is on every exit behind
+  // the upload from `small`
+  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(launched);
+  HIP_TRY(hipMemcpy(tiles.data(), d_tiles, tiles.size() * sizeof(RunSum<u32>), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(small, d_small, sizeof small, hipMemcpyDeviceToHost));
   if (small[32] != NONE64) {
     // the file whose '>' produced the offending separator (or the last one)
     if (e->files.empty()) {
@@ -937,6 +913,37 @@ static int summarise(gtamd_encoder *e) {
   return 0;
 }
 
+// the device part of gtamd_encoder_finish; its scratch buffers go with the frame
+static int encode_and_summarise(gtamd_encoder *e, u64 total, u64 longest) {
+  const u64 max_tiles = div_up(longest, EN_TILE) + 1;
+  Dev<u8> d_raw, d_lut;
+  Dev<u32> d_tile, d_ws;
+  Dev<FaGlobals> d_glob;
+  TRY(dev_alloc(e->d_enc, total + EN_TILE));
+  TRY(dev_alloc(d_raw, longest + EN_TILE));
+  TRY(dev_alloc(d_lut, 256));
+  TRY(dev_alloc(d_tile, 6 * max_tiles));
+  TRY(dev_alloc(d_ws, scan_workspace_words(max_tiles)));
+  TRY(dev_alloc(d_glob, 1));
+  if (hipMemcpyAsync(d_lut, e->lut, 256, hipMemcpyHostToDevice, e->st) != hipSuccess) {
+    gtamd_set_error("cannot copy the symbol map to the device");
+    return -1;
+  }
+  (void) hipEventRecord(e->ev[0], e->st);
+  TRY(encode_files(e, d_raw, d_lut, d_tile, d_ws, d_glob, max_tiles));
+  (void) hipEventRecord(e->ev[1], e->st);
+  TRY(summarise(e));
+  (void) hipEventRecord(e->ev[2], e->st);
+  if (hipStreamSynchronize(e->st) != hipSuccess) {
+    gtamd_set_error("device encoder failed: %s", hipGetErrorString(hipGetLastError()));
+    return -1;
+  }
+  (void) hipEventElapsedTime(&e->parse_ms, e->ev[0], e->ev[1]);
+  (void) hipEventElapsedTime(&e->stats_ms, e->ev[1], e->ev[2]);
+  (void) hipEventElapsedTime(&e->total_ms, e->ev[0], e->ev[2]);
+  return 0;
+}
+
 extern "C" int gtamd_encoder_finish(gtamd_encoder *e) {
   GTAMD_ABI_BEGIN
   if (e == nullptr) { gtamd_set_error("null encoder"); return -1; }
@@ -964,44 +971,7 @@ extern "C" int gtamd_encoder_finish(gtamd_encoder *e) {
   }
   memset(&e->sum, 0, sizeof e->sum);
   e->input_bytes = total;
-  const u64 max_tiles = div_up(longest, EN_TILE) + 1;
-  u8 *d_raw = nullptr, *d_lut = nullptr;
-  const u8 *lut = e->lut;
-  u32 *d_tile = nullptr, *d_ws = nullptr;
-  FaGlobals *d_glob = nullptr;
-  int rc = -1;
-  do {
-    if (dev_alloc(&e->d_enc, total + EN_TILE) != 0) break;
-    e->cap_enc = total + EN_TILE;
-    if (dev_alloc(&d_raw, longest + EN_TILE) != 0 || dev_alloc(&d_lut, 256) != 0 ||
-        dev_alloc(&d_tile, 6 * max_tiles) != 0 ||
-        dev_alloc(&d_ws, scan_workspace_words(max_tiles)) != 0 ||
-        dev_alloc(&d_glob, 1) != 0)
-      break;
-    if (hipMemcpyAsync(d_lut, lut, 256, hipMemcpyHostToDevice, e->st) != hipSuccess) {
-      gtamd_set_error("cannot copy the symbol map to the device");
-      break;
-    }
-    (void) hipEventRecord(e->ev[0], e->st);
-    if (encode_files(e, d_raw, d_lut, d_tile, d_ws, d_glob, max_tiles) != 0) break;
-    (void) hipEventRecord(e->ev[1], e->st);
-    if (summarise(e) != 0) break;
-    (void) hipEventRecord(e->ev[2], e->st);
-    if (hipStreamSynchronize(e->st) != hipSuccess) {
-      gtamd_set_error("device encoder failed: %s", hipGetErrorString(hipGetLastError()));
-      break;
-    }
-    (void) hipEventElapsedTime(&e->parse_ms, e->ev[0], e->ev[1]);
-    (void) hipEventElapsedTime(&e->stats_ms, e->ev[1], e->ev[2]);
-    (void) hipEventElapsedTime(&e->total_ms, e->ev[0], e->ev[2]);
-    rc = 0;
-  } while (0);
-  if (d_raw) (void) hipFree(d_raw);
-  if (d_lut) (void) hipFree(d_lut);
-  if (d_tile) (void) hipFree(d_tile);
-  if (d_ws) (void) hipFree(d_ws);
-  if (d_glob) (void) hipFree(d_glob);
-  if (rc != 0) { enc_free(e); e->n = 0; e->ndesc = 0; return -1; }
+  if (encode_and_summarise(e, total, longest) != 0) { enc_free(e); e->n = 0; e->ndesc = 0; return -1; }
   e->finished = true;
   return 0;
   GTAMD_ABI_END(-1)
@@ -1021,8 +991,7 @@ extern "C" int gtamd_encoder_set_symbols(gtamd_encoder *e, const uint8_t *symbol
   memset(&e->sum, 0, sizeof e->sum);
   e->input_bytes = n;
   e->ndesc = 0;
-  if (dev_alloc(&e->d_enc, n + EN_TILE) != 0) return -1;
-  e->cap_enc = n + EN_TILE;
+  TRY(dev_alloc(e->d_enc, n + EN_TILE));
   e->n = n;
   (void) hipEventRecord(e->ev[0], e->st);
   if (n > 0 && hipMemcpyAsync(e->d_enc, symbols, n, hipMemcpyHostToDevice, e->st) != hipSuccess) {
@@ -1188,21 +1157,15 @@ extern "C" int gtamd_encoder_pack_twobit(const gtamd_encoder *e, int bitaccess,
   HIP_TRY(hipSetDevice(e->device));
   const u64 units = e->n < 32 ? 2 : 2 + (e->n - 1) / 32;
   TRY(check_capacity("two-bit encoding", units, capacity));
-  u64 *d;
+  Dev<u64> d;
   u32 blocks;
-  TRY(dev_alloc(&d, units));
-  int rc = launch_1d(units, &blocks);
-  if (rc == 0) {
-    k_esq_twobit<<<blocks, 256, 0, e->st>>>(e->d_enc, e->n, units, bitaccess, fillcode & 3, d);
-    if (hipGetLastError() != hipSuccess ||
-        hipStreamSynchronize(e->st) != hipSuccess ||
-        hipMemcpy(words, d, units * 8, hipMemcpyDeviceToHost) != hipSuccess) {
-      gtamd_set_error("packing the two-bit encoding on the device failed");
-      rc = -1;
-    }
-  }
-  (void) hipFree(d);
-  return rc;
+  TRY(dev_alloc(d, units));
+  TRY(launch_1d(units, &blocks));
+  k_esq_twobit<<<blocks, 256, 0, e->st>>>(e->d_enc, e->n, units, bitaccess, fillcode & 3, d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(hipMemcpy(words, d, units * 8, hipMemcpyDeviceToHost));
+  return 0;
   GTAMD_ABI_END(-1)
 }
 
@@ -1213,21 +1176,15 @@ extern "C" int gtamd_encoder_pack_specialbits(const gtamd_encoder *e, uint64_t *
   HIP_TRY(hipSetDevice(e->device));
   const u64 units = 1 + (e->n + 63) / 64;
   TRY(check_capacity("special bits", units, capacity));
-  u64 *d;
+  Dev<u64> d;
   u32 blocks;
-  TRY(dev_alloc(&d, units));
-  int rc = launch_1d(units, &blocks);
-  if (rc == 0) {
-    k_esq_specialbits<<<blocks, 256, 0, e->st>>>(e->d_enc, e->n, units, d);
-    if (hipGetLastError() != hipSuccess ||
-        hipStreamSynchronize(e->st) != hipSuccess ||
-        hipMemcpy(words, d, units * 8, hipMemcpyDeviceToHost) != hipSuccess) {
-      gtamd_set_error("packing the special bits on the device failed");
-      rc = -1;
-    }
-  }
-  (void) hipFree(d);
-  return rc;
+  TRY(dev_alloc(d, units));
+  TRY(launch_1d(units, &blocks));
+  k_esq_specialbits<<<blocks, 256, 0, e->st>>>(e->d_enc, e->n, units, d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(hipMemcpy(words, d, units * 8, hipMemcpyDeviceToHost));
+  return 0;
   GTAMD_ABI_END(-1)
 }
 
@@ -1239,21 +1196,15 @@ extern "C" int gtamd_encoder_pack_bytecompress(const gtamd_encoder *e, uint8_t *
   const u32 sigma = e->sigma, bits = e->packbits;
   const u64 nbytes = ((u64) bits * e->n + 7) / 8;
   TRY(check_capacity("bit-packed symbols", nbytes, capacity));
-  u8 *d;
+  Dev<u8> d;
   u32 blocks;
-  TRY(dev_alloc(&d, nbytes));
-  int rc = launch_1d(div_up(e->n, 8), &blocks);
-  if (rc == 0) {
-    k_esq_bitpack<<<blocks, 256, 0, e->st>>>(e->d_enc, e->n, sigma, bits, nbytes, d);
-    if (hipGetLastError() != hipSuccess ||
-        hipStreamSynchronize(e->st) != hipSuccess ||
-        hipMemcpy(bytes, d, nbytes, hipMemcpyDeviceToHost) != hipSuccess) {
-      gtamd_set_error("bit-packing the symbols on the device failed");
-      rc = -1;
-    }
-  }
-  (void) hipFree(d);
-  return rc;
+  TRY(dev_alloc(d, nbytes));
+  TRY(launch_1d(div_up(e->n, 8), &blocks));
+  k_esq_bitpack<<<blocks, 256, 0, e->st>>>(e->d_enc, e->n, sigma, bits, nbytes, d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(hipMemcpy(bytes, d, nbytes, hipMemcpyDeviceToHost));
+  return 0;
   GTAMD_ABI_END(-1)
 }
 
@@ -1261,43 +1212,30 @@ extern "C" int gtamd_encoder_pack_bytecompress(const gtamd_encoder *e, uint8_t *
 static int positions_to_host(const gtamd_encoder *e, int kind, u64 expected, u64 *out) {
   if (expected == 0) return 0;
   const u64 ntiles = div_up(e->n, EN_TILE);
-  u32 *d_cnt = nullptr, *d_ws = nullptr;
-  u64 *d_out = nullptr;
-  int rc = -1;
-  do {
-    if (dev_alloc(&d_cnt, 2 * ntiles) != 0 || dev_alloc(&d_out, expected) != 0 ||
-        dev_alloc(&d_ws, scan_workspace_words(ntiles)) != 0)
-      break;
-    k_positions<0><<<(u32) ntiles, EN_THREADS, 0, e->st>>>(e->d_enc, e->n, kind, d_cnt,
-                                                          nullptr, nullptr);
-    if (hipGetLastError() != hipSuccess) { gtamd_set_error("k_positions launch failed"); break; }
-    if (scan_u32(SCAN_SUM, d_cnt, d_cnt + ntiles, ntiles, false, d_ws, e->st) != 0) break;
-    u32 last[2];
-    if (hipStreamSynchronize(e->st) != hipSuccess ||
-        hipMemcpy(&last[0], d_cnt + ntiles - 1, 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(&last[1], d_cnt + 2 * ntiles - 1, 4, hipMemcpyDeviceToHost) != hipSuccess) {
-      gtamd_set_error("reading position counts from the device failed");
-      break;
-    }
-    if ((u64) last[0] + last[1] != expected) {
-      gtamd_set_error("found %llu positions, the sequence statistics say %llu",
-                      (unsigned long long) last[0] + last[1], (unsigned long long) expected);
-      break;
-    }
-    k_positions<1><<<(u32) ntiles, EN_THREADS, 0, e->st>>>(e->d_enc, e->n, kind, nullptr,
-                                                          d_cnt + ntiles, d_out);
-    if (hipGetLastError() != hipSuccess ||
-        hipStreamSynchronize(e->st) != hipSuccess ||
-        hipMemcpy(out, d_out, expected * 8, hipMemcpyDeviceToHost) != hipSuccess) {
-      gtamd_set_error("collecting positions on the device failed");
-      break;
-    }
-    rc = 0;
-  } while (0);
-  if (d_cnt) (void) hipFree(d_cnt);
-  if (d_out) (void) hipFree(d_out);
-  if (d_ws) (void) hipFree(d_ws);
-  return rc;
+  Dev<u32> d_cnt, d_ws;
+  Dev<u64> d_out;
+  TRY(dev_alloc(d_cnt, 2 * ntiles));
+  TRY(dev_alloc(d_out, expected));
+  TRY(dev_alloc(d_ws, scan_workspace_words(ntiles)));
+  k_positions<0><<<(u32) ntiles, EN_THREADS, 0, e->st>>>(e->d_enc, e->n, kind, d_cnt,
+                                                        nullptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  TRY(scan_u32(SCAN_SUM, d_cnt, d_cnt + ntiles, ntiles, false, d_ws, e->st));
+  u32 last[2];
+  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(hipMemcpy(&last[0], d_cnt + ntiles - 1, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&last[1], d_cnt + 2 * ntiles - 1, 4, hipMemcpyDeviceToHost));
+  if ((u64) last[0] + last[1] != expected) {
+    gtamd_set_error("found %llu positions, the sequence statistics say %llu",
+                    (unsigned long long) last[0] + last[1], (unsigned long long) expected);
+    return -1;
+  }
+  k_positions<1><<<(u32) ntiles, EN_THREADS, 0, e->st>>>(e->d_enc, e->n, kind, nullptr,
+                                                        d_cnt + ntiles, d_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->st));
+  HIP_TRY(hipMemcpy(out, d_out, expected * 8, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 extern "C" int gtamd_encoder_get_wildcard_runs(const gtamd_encoder *e, uint64_t *start,

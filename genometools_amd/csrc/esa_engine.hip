@@ -35,6 +35,7 @@
 #include "../../include/gtamd_esa.h"
 #include "esa_prims.h"
 #include "esa_devutil.h"
+#include "esa_own.h"
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3039,27 +3040,22 @@ static Switches read_switches() {
 // ---------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------
-// device buffer that only grows; growing loses the contents
-struct DevBuf {
-  void *p;
-  u64 bytes;
-  template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
+// (the streams stand before the buffers: the buffers go first)
 struct gtamd_esa_ctx {
-  int device;
-  u32 sigma;
-  int bits;                // 2 or 5
-  u64 max_n, n, N;         // N = n + 1 entries
-  int readmode;            // GtReadmode of the sequence handed in as bytes
-  hipStream_t st, st2;     // st2: table emission beside the refinement
-  hipEvent_t ev_sorted, ev_emitted, ev_applied;
+  int device = 0;
+  u32 sigma = 0;
+  int bits = 0;            // 2 or 5
+  u64 max_n = 0, n = 0, N = 0;   // N = n + 1 entries
+  int readmode = 0;        // GtReadmode of the sequence handed in as bytes
+  Stream st, st2;          // st2: table emission beside the refinement
+  Event ev_sorted, ev_emitted, ev_applied;
   // resident sequence
   DevBuf tb_own, sp_own;
-  Text text;
-  bool have_text;
+  Text text = {};
+  bool have_text = false;
   // workspace, allocated by the first run that needs it (what a run needs
-  // depends on the tables wanted and, in a part build, on the slice size)
+  // depends on the tables wanted and, in a part build, on the slice size);
+  // ensure_buf only grows these, and growing loses the contents
   DevBuf k0, k1, v0, v1;   // ping-pong (key, position) pairs of the radix sort
   DevBuf isa_tmp;          // 8 B per entry: partitioned pairs of the rank build /
                            // bucketing scratch and 64-bit positions of a part build
@@ -3076,37 +3072,38 @@ struct gtamd_esa_ctx {
   DevBuf partws;           // part builds: suffixes kept per text tile, and their scan
   DevBuf posw;             // part builds with 64-bit positions: positions of the kept
                            // suffixes in text order
-  u64 *llv;
-  u64 llv_pairs, llv_cap;
-  u32 *bck;                      // .bck sections, back to back
-  u64 bck_codes, bck_special, bck_dist;
-  Stats *d_stats, *h_stats;   // h_stats: pinned host mirror
-  u32 *h_counts;              // pinned: per-part counters read back per round
-  u32 *h_hist;                // pinned: key-bin histogram of the own tile
+  Dev<u64> llv;                  // (llv and bck are not counted in alloc_bytes)
+  u64 llv_pairs = 0;
+  Dev<u32> bck;                  // .bck sections, back to back
+  u64 bck_codes = 0, bck_special = 0, bck_dist = 0;
+  Dev<Stats> d_stats;
+  Pinned<Stats> h_stats;      // pinned host mirror
+  Pinned<u32> h_counts;       // pinned: per-part counters read back per round
+  Pinned<u32> h_hist;         // pinned: key-bin histogram of the own tile
   // (every asynchronous device-to-host copy of the engine lands in pinned memory
   // the context owns, never on a stack frame or in a container that goes away)
-  u32 user_prefixlength;   // 0 = automatic
+  u32 user_prefixlength = 0;   // 0 = automatic
   // part build (lexicographic range `part` of `numparts`)
-  u32 part, numparts;
-  gtamd_allgather_fn comm_allgather;
-  gtamd_alltoallv_fn comm_alltoallv;
-  void (*comm_abort)(void *);   // called when a part build fails: the other parts must not wait
-  void *comm_abort_user;
-  void *comm_user;
-  u64 NL, index_offset;    // entries and offset of this part's slice
-  u32 *d_parthist;         // PART_BINS counters
-  u8 *d_owner;             // bin -> owning part
-  u32 *d_counts;           // 4 x DEST_MAXPARTS per-part counters
+  u32 part = 0, numparts = 1;
+  gtamd_allgather_fn comm_allgather = nullptr;
+  gtamd_alltoallv_fn comm_alltoallv = nullptr;
+  void (*comm_abort)(void *) = nullptr;   // called when a part build fails: the other parts must not wait
+  void *comm_abort_user = nullptr;
+  void *comm_user = nullptr;
+  u64 NL = 0, index_offset = 0;   // entries and offset of this part's slice
+  Dev<u32> d_parthist;     // PART_BINS counters
+  Dev<u8> d_owner;         // bin -> owning part
+  Dev<u32> d_counts;       // 4 x DEST_MAXPARTS per-part counters
   // results
-  u32 want;
-  bool ran;
-  gtamd_esa_stats stats;
-  gtamd_esa_timing timing;
-  u64 alloc_bytes;         // device memory held by the context
-  float alloc_ms;          // host time of the allocations since the last run started
+  u32 want = 0;
+  bool ran = false;
+  gtamd_esa_stats stats = {};
+  gtamd_esa_timing timing = {};
+  u64 alloc_bytes = 0;     // device memory held by the context
+  float alloc_ms = 0;      // host time of the allocations since the last run started
   // events: ev[] by TimingEvent
-  hipEvent_t ev[8];
-  hipEvent_t ev_scatter[2 * 16];
+  Event ev[8];
+  Event ev_scatter[2 * 16];
 };
 
 // what the timing events c->ev[] mark on the first stream (gtamd_esa_timing is made of
@@ -3121,9 +3118,6 @@ enum TimingEvent {
   EV_DONE            // tables final, emission joined
 };
 
-static void free_dev(void *p) { if (p != nullptr) (void) hipFree(p); }
-static void free_buf(DevBuf &b) { free_dev(b.p); b.p = nullptr; b.bytes = 0; }
-
 // grow-only; whoever calls this knows that the old contents are dead
 static int ensure_buf(gtamd_esa_ctx *c, DevBuf &b, u64 bytes, const char *what) {
   if (bytes <= b.bytes) return 0;
@@ -3131,13 +3125,12 @@ static int ensure_buf(gtamd_esa_ctx *c, DevBuf &b, u64 bytes, const char *what) 
   HIP_TRY(hipStreamSynchronize(c->st2));
   const auto t0 = std::chrono::steady_clock::now();
   c->alloc_bytes -= b.bytes;
-  free_buf(b);
+  b.reset();
   bytes = (bytes + 255) & ~255ull;
-  const hipError_t me = hipMalloc(&b.p, bytes);
+  const hipError_t me = b.alloc(bytes);
   c->alloc_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (me != hipSuccess) {
     (void) hipGetLastError();
-    b.p = nullptr;
     size_t mfree = 0, mtotal = 0;
     (void) hipMemGetInfo(&mfree, &mtotal);
     gtamd_set_error("cannot allocate %llu bytes of device memory for %s: the "
@@ -3148,7 +3141,6 @@ static int ensure_buf(gtamd_esa_ctx *c, DevBuf &b, u64 bytes, const char *what) 
                     (unsigned long long) mtotal);
     return -1;
   }
-  b.bytes = bytes;
   c->alloc_bytes += bytes;
   return 0;
 }
@@ -3158,36 +3150,8 @@ extern "C" void gtamd_esa_destroy(gtamd_esa_ctx *c) {
   (void) hipSetDevice(c->device);
   if (c->st != nullptr) (void) hipStreamSynchronize(c->st);
   if (c->st2 != nullptr) (void) hipStreamSynchronize(c->st2);
-  DevBuf *bufs[] = {&c->tb_own, &c->sp_own, &c->k0, &c->k1, &c->v0, &c->v1, &c->isa_tmp,
-                    &c->rws, &c->suf, &c->lcp, &c->bwt, &c->tiebits,
-                    &c->tiebits2, &c->arena, &c->arena_p, &c->xrecv, &c->winbuf, &c->msd,
-                    &c->lcpfull_buf, &c->partws, &c->posw};
-  for (DevBuf *b : bufs) free_buf(*b);
-  free_dev(c->llv); free_dev(c->bck); free_dev(c->d_stats);
-  free_dev(c->d_parthist); free_dev(c->d_owner); free_dev(c->d_counts);
-  if (c->h_stats != nullptr) (void) hipHostFree(c->h_stats);
-  if (c->h_counts != nullptr) (void) hipHostFree(c->h_counts);
-  if (c->h_hist != nullptr) (void) hipHostFree(c->h_hist);
-  for (auto &e : c->ev) if (e != nullptr) (void) hipEventDestroy(e);
-  for (auto &e : c->ev_scatter) if (e != nullptr) (void) hipEventDestroy(e);
-  if (c->ev_sorted != nullptr) (void) hipEventDestroy(c->ev_sorted);
-  if (c->ev_emitted != nullptr) (void) hipEventDestroy(c->ev_emitted);
-  if (c->ev_applied != nullptr) (void) hipEventDestroy(c->ev_applied);
-  if (c->st2 != nullptr) (void) hipStreamDestroy(c->st2);
-  if (c->st != nullptr) (void) hipStreamDestroy(c->st);
   delete c;
 }
-
-#define CTX_TRY(expr)                                                         \
-  do {                                                                        \
-    hipError_t e_ = (expr);                                                   \
-    if (e_ != hipSuccess) {                                                   \
-      gtamd_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),  \
-                      __FILE__, __LINE__);                                    \
-      gtamd_esa_destroy(c);                                                   \
-      return nullptr;                                                         \
-    }                                                                         \
-  } while (0)
 
 // positions a build can address: 32 bits in the sort's value plus the spare
 // key bits (part builds; a single build keeps everything 32-bit)
@@ -3197,6 +3161,26 @@ static u64 max_positions(int bits) {
   return 1ull << total;
 }
 constexpr u64 SINGLE_LIMIT = (1ull << 32) - 4096;   // entries of one slice / single build
+
+// streams, events and the small fixed buffers of a new context
+static int create_resources(gtamd_esa_ctx *c) {
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(create(c->st, hipStreamNonBlocking));
+  HIP_TRY(create(c->st2, hipStreamNonBlocking));
+  HIP_TRY(create(c->ev_sorted, hipEventDisableTiming));
+  HIP_TRY(create(c->ev_emitted, hipEventDisableTiming));
+  HIP_TRY(create(c->ev_applied, hipEventDisableTiming));
+  HIP_TRY(c->d_stats.alloc(sizeof(Stats)));
+  HIP_TRY(c->h_stats.alloc(sizeof(Stats)));
+  HIP_TRY(c->h_counts.alloc(4 * DEST_MAXPARTS * 4));
+  HIP_TRY(c->h_hist.alloc(PART_BINS * 4));
+  HIP_TRY(c->d_parthist.alloc(PART_BINS * 4));
+  HIP_TRY(c->d_owner.alloc(PART_BINS));
+  HIP_TRY(c->d_counts.alloc(4 * DEST_MAXPARTS * 4));
+  for (Event &e : c->ev) HIP_TRY(create(e));
+  for (Event &e : c->ev_scatter) HIP_TRY(create(e));
+  return 0;
+}
 
 extern "C" gtamd_esa_ctx *gtamd_esa_create(int device, uint64_t max_n,
                                            uint32_t numofchars) {
@@ -3218,27 +3202,11 @@ extern "C" gtamd_esa_ctx *gtamd_esa_create(int device, uint64_t max_n,
     return nullptr;
   }
   gtamd_esa_ctx *c = new gtamd_esa_ctx();
-  memset((void *) c, 0, sizeof *c);
   c->device = device;
   c->sigma = numofchars;
   c->bits = bits;
   c->max_n = max_n;
-  CTX_TRY(hipSetDevice(device));
-  CTX_TRY(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-  CTX_TRY(hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking));
-  CTX_TRY(hipEventCreateWithFlags(&c->ev_sorted, hipEventDisableTiming));
-  CTX_TRY(hipEventCreateWithFlags(&c->ev_emitted, hipEventDisableTiming));
-  CTX_TRY(hipEventCreateWithFlags(&c->ev_applied, hipEventDisableTiming));
-  CTX_TRY(hipMalloc(&c->d_stats, sizeof(Stats)));
-  CTX_TRY(hipHostMalloc(&c->h_stats, sizeof(Stats), hipHostMallocDefault));
-  CTX_TRY(hipHostMalloc(&c->h_counts, 4 * DEST_MAXPARTS * 4, hipHostMallocDefault));
-  CTX_TRY(hipHostMalloc(&c->h_hist, PART_BINS * 4, hipHostMallocDefault));
-  CTX_TRY(hipMalloc(&c->d_parthist, PART_BINS * 4));
-  CTX_TRY(hipMalloc(&c->d_owner, PART_BINS));
-  CTX_TRY(hipMalloc(&c->d_counts, 4 * DEST_MAXPARTS * 4));
-  c->numparts = 1;
-  for (auto &e : c->ev) CTX_TRY(hipEventCreate(&e));
-  for (auto &e : c->ev_scatter) CTX_TRY(hipEventCreate(&e));
+  if (create_resources(c) != 0) { gtamd_esa_destroy(c); return nullptr; }
   return c;
   GTAMD_ABI_END(nullptr)
 }
@@ -3338,14 +3306,10 @@ extern "C" int gtamd_esa_set_sequence_bytes(gtamd_esa_ctx *c,
   TRY(ensure_buf(c, c->tb_own, (nw_tb + 2) * 8, "the packed sequence"));
   TRY(ensure_buf(c, c->sp_own, (nw_sp + 2) * 8, "the special bitmap"));
   const u8 *d_enc = enc;
-  u8 *staged = nullptr;
+  Dev<u8> staged;
   if (!is_device && n > 0) {
-    HIP_TRY(hipMalloc(&staged, n));
-    if (hipMemcpyAsync(staged, enc, n, hipMemcpyHostToDevice, c->st) != hipSuccess) {
-      free_dev(staged);
-      gtamd_set_error("copying the sequence to the device failed");
-      return -1;
-    }
+    HIP_TRY(staged.alloc(n));
+    HIP_TRY(hipMemcpyAsync(staged, enc, n, hipMemcpyHostToDevice, c->st));
     d_enc = staged;
   }
   u64 *tb = c->tb_own.as<u64>(), *sp = c->sp_own.as<u64>();
@@ -3354,12 +3318,10 @@ extern "C" int gtamd_esa_set_sequence_bytes(gtamd_esa_ctx *c,
     k_pack_symbols<2><<<(u32) div_up(nw_tb, 256), 256, 0, c->st>>>(d_enc, n, tb, nw_tb, rev, cpl);
   else
     k_pack_symbols<5><<<(u32) div_up(nw_tb, 256), 256, 0, c->st>>>(d_enc, n, tb, nw_tb, rev, cpl);
-  hipError_t e1 = hipGetLastError();
+  HIP_TRY(hipGetLastError());
   k_pack_specials<<<(u32) div_up(nw_sp, 256), 256, 0, c->st>>>(d_enc, n, sp, nw_sp, rev);
-  hipError_t e2 = hipGetLastError();
-  hipError_t e3 = hipStreamSynchronize(c->st);
-  free_dev(staged);
-  HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->st));
   c->text.tb = tb; c->text.sp = sp; c->text.n = n;
   c->text.nw_tb = nw_tb; c->text.nw_sp = nw_sp;
   c->have_text = true;
@@ -3528,9 +3490,7 @@ static int build_bcktab(gtamd_esa_ctx *c, const u64 *skey, const u32 *spos, u64 
   for (u32 j = 0; j + 1 < k; j++) special *= c->sigma;
   for (u32 j = 1; j + 1 < k; j++) { pw *= c->sigma; dist += pw; }
   const u64 total = codes + 1 + special + dist;
-  free_dev(c->bck);
-  c->bck = nullptr;
-  HIP_TRY(hipMalloc(&c->bck, total * 4));
+  HIP_TRY(c->bck.alloc(total * 4));
   HIP_TRY(hipMemsetAsync(c->bck, 0, total * 4, st));
   if (NL > 0) {
     k_bck_count<BITS><<<(u32) div_up(NL, 256), 256, 0, st>>>(
@@ -3541,14 +3501,12 @@ static int build_bcktab(gtamd_esa_ctx *c, const u64 *skey, const u32 *spos, u64 
   // left borders: exclusive prefix sums; the last entry becomes the number of
   // suffixes that are in a bucket
   u32 *ws = c->rws.as<u32>();
-  u32 *own = nullptr;
+  Dev<u32> own;
   if (scan_workspace_words(codes + 1) * 4 > c->rws.bytes) {
-    HIP_TRY(hipMalloc(&own, scan_workspace_words(codes + 1) * 4));
+    HIP_TRY(own.alloc(scan_workspace_words(codes + 1) * 4));
     ws = own;
   }
-  const int rc = scan_u32(SCAN_SUM, c->bck, c->bck, codes + 1, false, ws, st);
-  if (own != nullptr) { (void) hipStreamSynchronize(st); free_dev(own); }
-  TRY(rc);
+  TRY(scan_u32(SCAN_SUM, c->bck, c->bck, codes + 1, false, ws, st));
   c->bck_codes = codes; c->bck_special = special; c->bck_dist = dist;
   return 0;
 }
@@ -3749,7 +3707,7 @@ static int msd_sort_emit(gtamd_esa_ctx *c, const Switches &sw, u32 want, u32 pre
     // how deep level C has to cut, from the ranges level B leaves (the host
     // waits here while the device moves the entries of level B)
     float *d_exp = reinterpret_cast<float *>(w.counters);
-    float *h_exp = reinterpret_cast<float *>(c->h_counts);
+    float *h_exp = c->h_counts.as<float>();
     HIP_TRY(hipMemsetAsync(d_exp, 0, 16, st));
     k_msd_skew<<<MSD_PARENTS / 256, 256, 0, st>>>(w.startB, cmax, d_exp);
     HIP_TRY(hipGetLastError());
@@ -4452,8 +4410,8 @@ struct Build {
     const u32 ntT = (u32) ntT64;
     TRY(ensure_buf(c, c->partws, ((u64) ntT + 64 + scan_workspace_words(ntT)) * 4, "the tile counts of the part"));
     u32 *tkeep = c->partws.as<u32>(), *tscan = tkeep + ntT + 32;
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(c->d_counts);
-    unsigned long long *hacc = reinterpret_cast<unsigned long long *>(c->h_counts);
+    unsigned long long *acc = c->d_counts.as<unsigned long long>();
+    unsigned long long *hacc = c->h_counts.as<unsigned long long>();
     HIP_TRY(hipMemsetAsync(acc, 0, 32, st));
     HIP_TRY(hipMemsetAsync(tkeep, 0, (u64) ntT * 4, st));
     k_part_count<<<ntT < 4096u ? ntT : 4096u, MS_THREADS, 0, st>>>(c->text, N, ntT, lo, hi, tkeep, acc);
@@ -4638,9 +4596,12 @@ struct Build {
         *kb = pass0_done ? c->k0.as<u64>() : c->k1.as<u64>();
     u32 *va = pass0_done ? c->v1.as<u32>() : c->v0.as<u32>(),
         *vb = pass0_done ? c->v0.as<u32>() : c->v1.as<u32>();
-    if (!msd)
+    if (!msd) {
+      hipEvent_t evs[2 * 16];   // (the sort takes plain handles)
+      for (int i = 0; i < 2 * 16; i++) evs[i] = c->ev_scatter[i];
       TRY(radix_sort_pairs<u64, u32>(ka, va, kb, vb, NL, shifts, widths, np,
-                                c->rws.as<u32>(), st, c->ev_scatter, &nev));
+                                c->rws.as<u32>(), st, evs, &nev));
+    }
     skey = (np & 1) ? kb : ka;        // sorted keys
     u32 *sa32 = (np & 1) ? vb : va;   // positions in suffix order (low half)
     fkey = (np & 1) ? ka : kb;        // free key-sized buffer
@@ -5577,13 +5538,7 @@ struct Build {
     // .llv from the byte table and the side table
     TRY(fetch_stats(c));
     const u64 pairs = c->h_stats->numlarge;
-    if (pairs > c->llv_cap) {
-      free_dev(c->llv);
-      c->llv = nullptr;
-      c->llv_cap = 0;
-      HIP_TRY(hipMalloc(&c->llv, (pairs + pairs / 4 + 1024) * 16));
-      c->llv_cap = pairs + pairs / 4 + 1024;
-    }
+    if (pairs * 16 > c->llv.bytes) HIP_TRY(c->llv.alloc((pairs + pairs / 4 + 1024) * 16));
     if (pairs > 0) {
       const u32 gl = (u32) div_up(NL, LLV_TILE);
       // (counts and their scan: the round buffers are free, but sized for the

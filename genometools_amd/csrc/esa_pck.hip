@@ -23,6 +23,7 @@
 #include <vector>
 #include "esa_common.h"
 #include "esa_devutil.h"
+#include "esa_own.h"
 #include "esa_pck_replay.h"
 #include "../../include/gtamd_pck.h"
 
@@ -643,22 +644,21 @@ __global__ void k_pck_ctxmap(const u64 *__restrict__ suf, u64 N, u32 ilog, u32 b
 }  // namespace
 
 struct gtamd_pck {
-  int device;
-  hipStream_t st;
-  hipEvent_t ev0, ev1;
-  u64 *lut; u64 lut_entries; u32 lut_sigma, lut_B;
-  u8 *img; u64 img_cap;
-  u64 *tile_tot; u64 tile_tot_cap;
-  u64 *rlist; u64 rlist_cap;
-  u64 *d_totals;
-  u64 *d_tail;
-  u64 tail_cap;          // buckets d_tail has room for
-  u64 *spbits; u64 spbits_cap;     // -sprank: bitmap of the text's specials, word prefix counts,
-  u32 *sppre; u64 sppre_cap;       // scan workspace
-  u32 *spws; u64 spws_cap;
-  u8 *cxm; u64 cxm_cap, cxm_bytes;   // image of INDEX.<ilog>cxm
-  gtamd_pck_info info;
-  bool built;
+  int device = 0;
+  Stream st;             // (before the buffers: they go first)
+  Event ev0, ev1;
+  Dev<u64> lut; u64 lut_entries = 0; u32 lut_sigma = 0, lut_B = 0;
+  Dev<u8> img;
+  Dev<u64> tile_tot;
+  Dev<u64> rlist;
+  Dev<u64> d_totals;
+  Dev<u64> d_tail;       // one var offset per bucket it has room for
+  Dev<u64> spbits;       // -sprank: bitmap of the text's specials, word prefix counts,
+  Dev<u32> sppre;        // scan workspace
+  Dev<u32> spws;
+  Dev<u8> cxm; u64 cxm_bytes = 0;   // image of INDEX.<ilog>cxm
+  gtamd_pck_info info = {};
+  bool built = false;
 };
 
 extern "C" int gtamd_pck_default_toggles(uint32_t block_size, uint32_t bucket_blocks,
@@ -682,17 +682,14 @@ extern "C" gtamd_pck *gtamd_pck_create(int device) {
   }
   if (hipSetDevice(device) != hipSuccess) { gtamd_set_error("hipSetDevice(%d) failed", device); return nullptr; }
   gtamd_pck *p = new gtamd_pck();
-  memset(p, 0, sizeof *p);
   p->device = device;
-  if (hipStreamCreate(&p->st) != hipSuccess || hipEventCreate(&p->ev0) != hipSuccess ||
-      hipEventCreate(&p->ev1) != hipSuccess ||
-      hipMalloc(&p->d_totals, (PCK_MAX_SIGMA + 8) * sizeof(u64)) != hipSuccess ||
-      hipMalloc(&p->d_tail, PCK_TAIL_RECORDS * sizeof(u64)) != hipSuccess) {
+  if (create(p->st) != hipSuccess || create(p->ev0) != hipSuccess || create(p->ev1) != hipSuccess ||
+      p->d_totals.alloc((PCK_MAX_SIGMA + 8) * sizeof(u64)) != hipSuccess ||
+      p->d_tail.alloc(PCK_TAIL_RECORDS * sizeof(u64)) != hipSuccess) {
     gtamd_set_error("cannot create the packed-index builder on device %d", device);
     delete p;
     return nullptr;
   }
-  p->tail_cap = PCK_TAIL_RECORDS;
   return p;
   GTAMD_ABI_END(nullptr)
 }
@@ -701,32 +698,16 @@ extern "C" void gtamd_pck_destroy(gtamd_pck *p) {
   if (p == nullptr) return;
   (void) hipSetDevice(p->device);
   (void) hipStreamSynchronize(p->st);
-  if (p->lut) (void) hipFree(p->lut);
-  if (p->img) (void) hipFree(p->img);
-  if (p->tile_tot) (void) hipFree(p->tile_tot);
-  if (p->rlist) (void) hipFree(p->rlist);
-  if (p->d_totals) (void) hipFree(p->d_totals);
-  if (p->d_tail) (void) hipFree(p->d_tail);
-  if (p->spbits) (void) hipFree(p->spbits);
-  if (p->sppre) (void) hipFree(p->sppre);
-  if (p->spws) (void) hipFree(p->spws);
-  if (p->cxm) (void) hipFree(p->cxm);
-  (void) hipEventDestroy(p->ev0);
-  (void) hipEventDestroy(p->ev1);
-  (void) hipStreamDestroy(p->st);
   delete p;
 }
 
-template <typename T> static int grow(T **buf, u64 *cap, u64 need_bytes) {
-  if (*cap >= need_bytes && *buf != nullptr) return 0;
-  if (*buf) (void) hipFree(*buf);
-  *buf = nullptr; *cap = 0;
-  if (hipMalloc((void **) buf, need_bytes) != hipSuccess) {
+// at least need_bytes in b; growing loses the contents
+static int ensure(DevBuf &b, u64 need_bytes) {
+  if (b.grow(need_bytes) != hipSuccess) {
     gtamd_set_error("cannot allocate %llu bytes of device memory for the packed index",
                     (unsigned long long) need_bytes);
     return -1;
   }
-  *cap = need_bytes;
   return 0;
 }
 
@@ -815,9 +796,8 @@ extern "C" int gtamd_pck_build(gtamd_pck *p, const uint8_t *bwt, const uint64_t 
   u64 entries = 1;
   for (u32 i = 0; i < B && entries <= (1ull << 24); i++) entries *= sigma;
   if (entries > (1ull << 24)) entries = 0;
-  if (entries && (p->lut == nullptr || p->lut_sigma != sigma || p->lut_B != B)) {
-    if (p->lut) { (void) hipFree(p->lut); p->lut = nullptr; }
-    if (hipMalloc(&p->lut, entries * sizeof(u64)) != hipSuccess) { gtamd_set_error("packed index: cannot allocate the block table"); return -1; }
+  if (entries && (p->lut.p == nullptr || p->lut_sigma != sigma || p->lut_B != B)) {
+    if (p->lut.alloc(entries * sizeof(u64)) != hipSuccess) { gtamd_set_error("packed index: cannot allocate the block table"); return -1; }
     k_pck_lut<<<(u32) div_up(entries, 256), 256, 0, p->st>>>(entries, sigma, B, p->lut);
     HIP_TRY(hipGetLastError());
     p->lut_entries = entries; p->lut_sigma = sigma; p->lut_B = B;
@@ -825,9 +805,7 @@ extern "C" int gtamd_pck_build(gtamd_pck *p, const uint8_t *bwt, const uint64_t 
   g.lut_entries = entries;
 
   const u64 ncols = sigma + PCK_EXTRA_COLS;
-  u64 tt_cap_bytes = p->tile_tot_cap;
-  TRY(grow(&p->tile_tot, &tt_cap_bytes, ncols * g.ntiles * sizeof(u64)));
-  p->tile_tot_cap = tt_cap_bytes;
+  TRY(ensure(p->tile_tot, ncols * g.ntiles * sizeof(u64)));
 
   HIP_TRY(hipEventRecord(p->ev0, p->st));
   // rows from first_special_row on hold the suffixes that start with a special:
@@ -835,7 +813,7 @@ extern "C" int gtamd_pck_build(gtamd_pck *p, const uint8_t *bwt, const uint64_t 
   // before suffix p + 1; the undefined symbol before suffix 0 stands for the
   // virtual end)
   HIP_TRY(hipMemsetAsync(p->d_totals, 0, (PCK_MAX_SIGMA + 8) * sizeof(u64), p->st));
-  k_pck_count_specials<<<1024, 256, 0, p->st>>>(bwt, total_len, (unsigned long long *) p->d_totals);
+  k_pck_count_specials<<<1024, 256, 0, p->st>>>(bwt, total_len, p->d_totals.as<unsigned long long>());
   HIP_TRY(hipGetLastError());
   u64 nspecial = 0;
   HIP_TRY(hipStreamSynchronize(p->st));
@@ -857,11 +835,11 @@ extern "C" int gtamd_pck_build(gtamd_pck *p, const uint8_t *bwt, const uint64_t 
     if (g.total_specials >= (1ull << 32)) { gtamd_set_error("packed index: -sprank with more than 2^32 specials"); return -1; }
     g.bits_orig_rank = reqbits(g.total_specials);
     const u64 nwords = total_len / 64 + 1;
-    u64 cap = p->spbits_cap; TRY(grow(&p->spbits, &cap, nwords * 8)); p->spbits_cap = cap;
-    cap = p->sppre_cap; TRY(grow(&p->sppre, &cap, nwords * 4)); p->sppre_cap = cap;
-    cap = p->spws_cap; TRY(grow(&p->spws, &cap, scan_workspace_words(nwords) * 4 + 64)); p->spws_cap = cap;
+    TRY(ensure(p->spbits, nwords * 8));
+    TRY(ensure(p->sppre, nwords * 4));
+    TRY(ensure(p->spws, scan_workspace_words(nwords) * 4 + 64));
     HIP_TRY(hipMemsetAsync(p->spbits, 0, nwords * 8, p->st));
-    k_pck_special_bitmap<<<2048, 256, 0, p->st>>>(bwt, suf, total_len, (unsigned long long *) p->spbits);
+    k_pck_special_bitmap<<<2048, 256, 0, p->st>>>(bwt, suf, total_len, p->spbits.as<unsigned long long>());
     HIP_TRY(hipGetLastError());
     k_pck_popc_words<<<(u32) div_up(nwords, 256), 256, 0, p->st>>>(p->spbits, nwords, p->sppre);
     HIP_TRY(hipGetLastError());
@@ -949,14 +927,10 @@ extern "C" int gtamd_pck_build(gtamd_pck *p, const uint8_t *bwt, const uint64_t 
   const u64 range_enc_pos = var_data_pos + var_bits_total / 8 + ((var_bits_total % 8) ? 1 : 0);
   const u64 file_bytes = range_enc_pos + 8 + 16 * (nregions + 1);
 
-  u64 img_cap = p->img_cap;
-  TRY(grow(&p->img, &img_cap, ((file_bytes + 7) & ~7ull) + 64));
-  p->img_cap = img_cap;
-  u64 rl_cap = p->rlist_cap;
-  TRY(grow(&p->rlist, &rl_cap, std::max<u64>(1, nregions) * 2 * sizeof(u64)));
-  p->rlist_cap = rl_cap;
+  TRY(ensure(p->img, ((file_bytes + 7) & ~7ull) + 64));
+  TRY(ensure(p->rlist, std::max<u64>(1, nregions) * 2 * sizeof(u64)));
   HIP_TRY(hipMemsetAsync(p->img, 0, ((file_bytes + 7) & ~7ull) + 64, p->st));
-  u64 tail_n = std::min<u64>(g.nb, std::max<u64>(PCK_TAIL_RECORDS, p->tail_cap));
+  u64 tail_n = std::min<u64>(g.nb, std::max<u64>(PCK_TAIL_RECORDS, p->d_tail.bytes / sizeof(u64)));
   // LDS copies of a tile's parts of the bit strings: the whole cw part, and as
   // much of the 64 KB as is left (at most 24 KB) for the var part -- a tile with
   // more var bits writes them straight into the image, and so does every tile
@@ -970,7 +944,7 @@ extern "C" int gtamd_pck_build(gtamd_pck *p, const uint8_t *bwt, const uint64_t 
       g.lds_var_off = (u32) lds_emit; g.lds_var_words = (u32) var_words; lds_emit += var_words * 8;
     }
   }
-  k_pck_tile<true><<<g.ntiles, PCK_THREADS, lds_emit, p->st>>>(g, bwt, suf, p->lut, p->tile_tot, (u64 *) p->img,
+  k_pck_tile<true><<<g.ntiles, PCK_THREADS, lds_emit, p->st>>>(g, bwt, suf, p->lut, p->tile_tot, p->img.as<u64>(),
                                                          p->rlist, p->rlist + std::max<u64>(1, nregions),
                                                          p->d_tail, g.nb - tail_n, p->spbits, p->sppre);
   HIP_TRY(hipGetLastError());
@@ -1034,16 +1008,11 @@ extern "C" int gtamd_pck_build(gtamd_pck *p, const uint8_t *bwt, const uint64_t 
     // as many and emit again (the emission ORs the same bits into the same places
     // and the replay has not patched anything yet, so the image is unchanged)
     tail_n = std::min<u64>(g.nb, tail_n * 16);
-    if (tail_n > p->tail_cap) {
-      (void) hipFree(p->d_tail);
-      p->d_tail = nullptr; p->tail_cap = 0;
-      if (hipMalloc(&p->d_tail, tail_n * sizeof(u64)) != hipSuccess) {
-        gtamd_set_error("packed index: cannot allocate the var offsets of %llu buckets", (unsigned long long) tail_n);
-        return -1;
-      }
-      p->tail_cap = tail_n;
+    if (p->d_tail.grow(tail_n * sizeof(u64)) != hipSuccess) {
+      gtamd_set_error("packed index: cannot allocate the var offsets of %llu buckets", (unsigned long long) tail_n);
+      return -1;
     }
-    k_pck_tile<true><<<g.ntiles, PCK_THREADS, lds_emit, p->st>>>(g, bwt, suf, p->lut, p->tile_tot, (u64 *) p->img,
+    k_pck_tile<true><<<g.ntiles, PCK_THREADS, lds_emit, p->st>>>(g, bwt, suf, p->lut, p->tile_tot, p->img.as<u64>(),
                                                            p->rlist, p->rlist + std::max<u64>(1, nregions),
                                                            p->d_tail, g.nb - tail_n, p->spbits, p->sppre);
     HIP_TRY(hipGetLastError());
@@ -1086,22 +1055,17 @@ extern "C" int gtamd_pck_build_host(gtamd_pck *p, const uint8_t *bwt, const uint
   GTAMD_ABI_BEGIN
   if (p == nullptr || bwt == nullptr || pp == nullptr) { gtamd_set_error("invalid argument to gtamd_pck_build_host"); return -1; }
   HIP_TRY(hipSetDevice(p->device));
-  u8 *d_bwt = nullptr;
-  u64 *d_suf = nullptr;
-  int rc = -1;
-  if (hipMalloc(&d_bwt, total_len) != hipSuccess ||
-      (suf != nullptr && hipMalloc(&d_suf, total_len * sizeof(u64)) != hipSuccess)) {
+  Dev<u8> d_bwt;
+  Dev<u64> d_suf;
+  if (d_bwt.alloc(total_len) != hipSuccess ||
+      (suf != nullptr && d_suf.alloc(total_len * sizeof(u64)) != hipSuccess)) {
     gtamd_set_error("packed index: cannot allocate device memory for the tables of %llu entries",
                     (unsigned long long) total_len);
-  } else if (hipMemcpy(d_bwt, bwt, total_len, hipMemcpyHostToDevice) != hipSuccess ||
-             (suf != nullptr &&
-              hipMemcpy(d_suf, suf, total_len * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess)) {
-    gtamd_set_error("packed index: cannot copy the tables to the device");
-  } else
-    rc = gtamd_pck_build(p, d_bwt, d_suf, total_len, sigma, longest, pp);
-  if (d_bwt) (void) hipFree(d_bwt);
-  if (d_suf) (void) hipFree(d_suf);
-  return rc;
+    return -1;
+  }
+  HIP_TRY(hipMemcpy(d_bwt, bwt, total_len, hipMemcpyHostToDevice));
+  if (suf != nullptr) HIP_TRY(hipMemcpy(d_suf, suf, total_len * sizeof(u64), hipMemcpyHostToDevice));
+  return gtamd_pck_build(p, d_bwt, d_suf, total_len, sigma, longest, pp);
   GTAMD_ABI_END(-1)
 }
 
@@ -1114,7 +1078,7 @@ extern "C" int gtamd_pck_get_info(const gtamd_pck *p, gtamd_pck_info *info) {
 }
 extern "C" const void *gtamd_pck_image_device(const gtamd_pck *p) {
   GTAMD_ABI_BEGIN
-  return (p != nullptr && p->built) ? p->img : nullptr;
+  return (p != nullptr && p->built) ? p->img.p : nullptr;
   GTAMD_ABI_END(nullptr)
 }
 extern "C" int gtamd_pck_image_copy(gtamd_pck *p, void *dst, uint64_t offset, uint64_t count) {
@@ -1149,12 +1113,10 @@ extern "C" int gtamd_pck_ctxmap_build(gtamd_pck *p, const uint64_t *suf, uint64_
   const u32 bits = reqbits(total_len - 1);
   const u64 nentries = (total_len + (1ull << ilog) - 1) >> ilog;
   const u64 size = 4 + (bits * nentries + 7) / 8;
-  u64 cap = p->cxm_cap;
-  TRY(grow(&p->cxm, &cap, ((size + 7) & ~7ull) + 16));
-  p->cxm_cap = cap;
+  TRY(ensure(p->cxm, ((size + 7) & ~7ull) + 16));
   p->cxm_bytes = 0;
   HIP_TRY(hipMemsetAsync(p->cxm, 0, ((size + 7) & ~7ull) + 16, p->st));
-  k_pck_ctxmap<<<4096, 256, 0, p->st>>>(suf, total_len, (u32) ilog, bits, (u64 *) p->cxm);
+  k_pck_ctxmap<<<4096, 256, 0, p->st>>>(suf, total_len, (u32) ilog, bits, p->cxm.as<u64>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(p->st));
   // header: interval log and entry width, 16 bits each, most significant bit
@@ -1194,16 +1156,13 @@ extern "C" int gtamd_pck_ctxmap_build_host(gtamd_pck *p, const uint64_t *suf, ui
   GTAMD_ABI_BEGIN
   if (p == nullptr || suf == nullptr) { gtamd_set_error("invalid argument to gtamd_pck_ctxmap_build_host"); return -1; }
   HIP_TRY(hipSetDevice(p->device));
-  u64 *d_suf = nullptr;
-  int rc = -1;
-  if (hipMalloc(&d_suf, total_len * sizeof(u64)) != hipSuccess)
+  Dev<u64> d_suf;
+  if (d_suf.alloc(total_len * sizeof(u64)) != hipSuccess) {
     gtamd_set_error("context map: cannot allocate device memory for %llu suffix-array entries", (unsigned long long) total_len);
-  else if (hipMemcpy(d_suf, suf, total_len * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess)
-    gtamd_set_error("context map: cannot copy the suffix array to the device");
-  else
-    rc = gtamd_pck_ctxmap_build(p, d_suf, total_len, ilog, ilog_used);
-  if (d_suf) (void) hipFree(d_suf);
-  return rc;
+    return -1;
+  }
+  HIP_TRY(hipMemcpy(d_suf, suf, total_len * sizeof(u64), hipMemcpyHostToDevice));
+  return gtamd_pck_ctxmap_build(p, d_suf, total_len, ilog, ilog_used);
   GTAMD_ABI_END(-1)
 }
 

@@ -103,7 +103,36 @@ def test_exceptions_do_not_cross_the_c_abi():
     assert b"memory" in lib.gtamd_esa_last_error()
     # the barrier is in every entry point that has a body of its own
     import re
-    for f in ("esa_engine.hip", "esa_encode.hip", "esa_pck.hip", "esa_synth.hip"):
-        src = open(os.path.join(_lib.HERE, "csrc", f)).read()
+    for f in _lib.SOURCES:
+        src = open(f).read()
         for m in re.finditer(r'^extern "C" (?!void)[^\n;{]*?\b(gtamd_\w+)\([^;{]*\{\n(.*)$', src, re.M):
             assert "GTAMD_ABI_BEGIN" in m.group(2), (f, m.group(1))
+
+
+def test_resources_are_created_and_released_in_one_place():
+    """device memory, pinned memory, streams, events and dlopen handles are held
+    by the owning types of csrc/esa_own.h, which has the only calls that create
+    or release one: a frame left early (HIP_TRY, TRY, an exception on its way
+    to the ABI barrier) then has nothing to clean up by hand.  And no context
+    is zeroed as a whole behind `new`: the members initialise themselves."""
+    import glob
+    owner = os.path.join(_lib.HERE, "csrc", "esa_own.h")
+    assert owner in _lib.HEADERS
+    files = sorted(set(_lib.SOURCES + glob.glob(os.path.join(_lib.HERE, "csrc", "*.h"))))
+    assert owner in files and len(files) >= len(_lib.SOURCES) + 2
+    raw = re.compile(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree|hipStreamCreate\w*|"
+                     r"hipStreamDestroy|hipEventCreate\w*|hipEventDestroy|dlopen|dlclose)\s*\(")
+    whole = re.compile(r"\bmemset\s*\([^;]*\bsizeof\s*\(?\s*\*\s*[cpe]\s*\)?\s*\)")
+    calls = 0
+    for f in files:
+        src = open(f).read()
+        src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+        src = re.sub(r"//[^\n]*", " ", src)
+        for n, line in enumerate(src.split("\n"), 1):
+            m = raw.search(line)
+            if f == owner:
+                calls += m is not None
+            else:
+                assert m is None, "%s:%d calls %s outside esa_own.h" % (f, n, m.group(1))
+        assert whole.search(src) is None, "%s zeroes a whole context with memset" % f
+    assert calls >= 8     # (the scan does see the calls where they are allowed)
