@@ -402,14 +402,29 @@ done:
 
 typedef struct { const uint8_t *p; uint64_t len, off; int bad; } infile;
 
+/* bytes left behind the read position; the padding of the last section may
+   have carried the position past the end of a file cut short */
+static uint64_t bytes_left(const infile *in)
+{
+  return in->off < in->len ? in->len - in->off : 0;
+}
+
 static const void *take(infile *in, uint64_t bytes)
 {
   const void *q = in->p + in->off;
   if (bytes == 0) return q;
-  if (in->bad || in->off + bytes > in->len) { in->bad = 1; return NULL; }
+  if (in->bad || bytes > bytes_left(in)) { in->bad = 1; return NULL; }
   in->off += bytes;
   if (in->off % 8 != 0) in->off += 8 - in->off % 8;
   return q;
+}
+
+/* a section of `items` entries of `width` bytes: the sizes come from the file,
+   so their product is formed only once it is known to fit what is left */
+static const void *take_items(infile *in, uint64_t width, uint64_t items)
+{
+  if (in->bad || items > bytes_left(in) / width) { in->bad = 1; return NULL; }
+  return take(in, width * items);
 }
 
 static uint64_t take_word(infile *in)
@@ -453,9 +468,9 @@ static int sw_apply(infile *in, int kind, int withlengths, uint64_t n, uint64_t 
   const uint64_t *endidx, numofpages = n / sw_maxv[kind] + 1;
   uint64_t idx = 0;
   if (items == 0) return 0;
-  positions = take(in, sw_width[kind] * items);
-  if (withlengths) lengths = take(in, sw_width[kind] * items);
-  endidx = take(in, 8 * numofpages);
+  positions = take_items(in, sw_width[kind], items);
+  if (withlengths) lengths = take_items(in, sw_width[kind], items);
+  endidx = take_items(in, 8, numofpages);
   if (in->bad) return -1;
   for (uint64_t page = 0; page < numofpages; page++) {
     if (endidx[page] > items || endidx[page] < idx) return -1;
@@ -495,7 +510,7 @@ int gtamd_read_esq_alpha(const char *indexname, uint8_t **enc_out, uint64_t *n_o
   const uint64_t *sci;
   infile in;
   uint32_t numofchars;
-  int rc = -1;
+  int rc = -1, fits;
 
   memset(alpha, 0, sizeof *alpha);
   snprintf(path, sizeof path, "%s.esq", indexname);
@@ -537,15 +552,27 @@ int gtamd_read_esq_alpha(const char *indexname, uint8_t **enc_out, uint64_t *n_o
   (void) take(&in, namelen);
   (void) take(&in, 1);                                 /* maxsubalphasize */
   (void) take_word(&in);                               /* numofallchars */
-  (void) take(&in, 16 * numfiles);
-  (void) take(&in, 8 * (uint64_t) numofchars);
+  (void) take_items(&in, sizeof (gtamd_filelength), numfiles);
+  (void) take_items(&in, 8, numofchars);
   if (in.bad || numseq == 0 || n + 1 < numseq) goto corrupt;
+  /* n is what the header says: the symbols' own section has to fit what is
+     left of the file before n bytes are asked for */
+  if (sat == GTAMD_SAT_DIRECTACCESS) fits = n <= bytes_left(&in);
+  else if (sat == GTAMD_SAT_BYTECOMPRESS) fits = n <= 8 * bytes_left(&in) / alpha->bitspersymbol;
+  else if (sat <= GTAMD_SAT_UINT32TABLES)
+    fits = (n < 32 ? 2 : 2 + (n - 1) / 32) <= bytes_left(&in) / 8;
+  else fits = 0;
+  if (!fits) goto corrupt;
   enc = malloc(n ? n : 1);
   if (enc == NULL) { snprintf(err, errlen, "out of memory"); goto done; }
 
   if (sat == GTAMD_SAT_DIRECTACCESS) {
     const uint8_t *plain = take(&in, n);
     if (in.bad) goto corrupt;
+    /* the symbols as they are: a byte that is no code of the alphabet and no
+       special would index past every table built from them */
+    for (uint64_t pos = 0; pos < n; pos++)
+      if (plain[pos] >= numofchars && plain[pos] < GTAMD_WILDCARD) goto corrupt;
     memcpy(enc, plain, n);
   } else if (sat == GTAMD_SAT_BYTECOMPRESS) {
     const unsigned bits = alpha->bitspersymbol;
@@ -562,7 +589,7 @@ int gtamd_read_esq_alpha(const char *indexname, uint8_t **enc_out, uint64_t *n_o
     }
   } else if (sat <= GTAMD_SAT_UINT32TABLES) {
     const uint64_t units = n < 32 ? 2 : 2 + (n - 1) / 32,
-                   *twobit = take(&in, 8 * units);
+                   *twobit = take_items(&in, 8, units);
     if (numofchars != 4 || in.bad) goto corrupt;
     for (uint64_t pos = 0; pos < n; pos++)
       enc[pos] = (uint8_t) ((twobit[pos / 32] >> (62 - 2 * (pos % 32))) & 3);
@@ -573,7 +600,7 @@ int gtamd_read_esq_alpha(const char *indexname, uint8_t **enc_out, uint64_t *n_o
       for (uint64_t s = 0; s + 1 < numseq; s++) enc[s * (seqlen + 1) + seqlen] = GTAMD_SEPARATOR;
     } else if (sat == GTAMD_SAT_BITACCESS) {
       if (wildcardranges > 0 || numseq > 1) {
-        const uint64_t *specialbits = take(&in, 8 * (1 + (n + 63) / 64));
+        const uint64_t *specialbits = take_items(&in, 8, 1 + (n + 63) / 64);
         if (in.bad) goto corrupt;
         for (uint64_t pos = 0; pos < n; pos++)
           if ((specialbits[pos / 64] >> (63 - pos % 64)) & 1)

@@ -3,7 +3,10 @@
 tests/test_switches_gpu.py.  Both take them in the same order -- sequence,
 prefix length, MSD switches (not in a case of 64-bit positions), part switches
 -- so case k of the replay has the switches of case k of
-`fuzz_gpu.py --seed REPLAY_SEED`, up to its part build."""
+`fuzz_gpu.py --seed REPLAY_SEED`, up to its part build.  The writers of the
+fuzzer's FASTA and FASTQ files and its packed-index options are here too: the
+sanitized run of the checker (test_host_sanitized.py) takes them after the prefix
+length."""
 import numpy as np
 
 
@@ -89,3 +92,74 @@ def parts_switches(rng):
            "GTAMD_PAIR_CHUNK": str(int(rng.choice(PAIR_CHUNKS))),
            "GTAMD_NO_PAIRS": "1" if rng.integers(0, 5) == 0 else "0"}
     return parts, env
+
+
+# line widths write_fasta draws from, one per sequence
+LINE_WIDTHS = [1, 7, 60, 70, 4095, 4096, 100000]
+
+
+def _alphabet_text(sigma):
+    protein = sigma == 20
+    return (b"LVIFKREDAGSTNQYWPHMC" if protein else b"ACGT",
+            b"XUBZJO*-" if protein else b"NSYWRKVBDHM")
+
+
+def write_fasta(rng, enc, sigma, path):
+    """enc as a FASTA file: one record per sequence, a random wildcard letter for
+    every wildcard, DNA in random case, a random line width per record, one file
+    in four with CRLF line ends, a blank line after one line in twenty.  Returns
+    what was drawn: {"crlf": bool, "widths": set}."""
+    protein = sigma == 20
+    letters, wild = _alphabet_text(sigma)
+    eol = b"\r\n" if rng.integers(0, 4) == 0 else b"\n"
+    widths = set()
+    with open(path, "wb") as f:
+        start = 0
+        cuts = list(np.flatnonzero(enc == 255)) + [enc.size]
+        for i, end in enumerate(cuts):
+            f.write(b">seq%d some text\t%d" % (i, int(rng.integers(0, 1000))) + eol)
+            seq = enc[start:end]
+            txt = bytearray(len(seq))
+            for j, c in enumerate(seq):
+                ch = wild[int(rng.integers(0, len(wild)))] if c == 254 else letters[c]
+                if not protein and rng.integers(0, 3) == 0:
+                    ch = ord(chr(ch).lower())
+                txt[j] = ch
+            width = int(rng.choice(LINE_WIDTHS))
+            widths.add(width)
+            for a in range(0, len(txt), width):
+                f.write(bytes(txt[a:a + width]) + eol)
+                if rng.integers(0, 20) == 0:
+                    f.write(eol)
+            start = end + 1
+    return {"crlf": eol == b"\r\n", "widths": widths}
+
+
+def write_fastq(rng, enc, sigma, path):
+    """the same sequences as four-line FASTQ records with random qualities, one
+    record in five without a name, one in three with the name repeated behind
+    the '+'.  Returns the number of records."""
+    letters, wild = _alphabet_text(sigma)
+    cuts = list(np.flatnonzero(enc == 255)) + [enc.size]
+    with open(path, "wb") as f:
+        start = 0
+        for i, end in enumerate(cuts):
+            seq = enc[start:end]
+            txt = bytes(wild[int(rng.integers(0, len(wild)))] if c == 254 else letters[c] for c in seq)
+            name = b"read%d x=%d" % (i, int(rng.integers(0, 99))) if rng.integers(0, 5) else b""
+            qual = bytes(rng.integers(33, 127, size=len(txt), dtype=np.uint8))
+            f.write(b"@" + name + b"\n" + txt + b"\n+" + (name if rng.integers(0, 3) == 0 else b"") + b"\n" +
+                    qual + b"\n")
+            start = end + 1
+    return len(cuts)
+
+
+def pck_options(rng, sigma):
+    """options of one packed-index build: block size, blocks per bucket, locate
+    interval and mode, both flavours, -sprank"""
+    bmax = 10 if sigma == 4 else 3
+    return dict(bsize=int(rng.integers(1, bmax + 1)),
+                blbuck=int(rng.choice([1, 2, 3, 5, 8, 8, 8, 13, 64, 300])),
+                locfreq=int(rng.choice([0, 1, 2, 3, 7, 16, 16, 32, 1000])),
+                locbitmap=[None, True, False][int(rng.integers(0, 3))],
+                mkindex=bool(rng.integers(0, 2)), sprank=bool(rng.integers(0, 2)))

@@ -28,7 +28,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_util as ou  # noqa: E402
 import thread_comm  # noqa: E402
-from fuzz_cases import msd_switches, parts_switches, prefix_length, random_sequence  # noqa: E402
+from fuzz_cases import (msd_switches, parts_switches, pck_options, prefix_length,  # noqa: E402
+                        random_sequence, write_fasta, write_fastq)
 from genometools_amd import encode, esa, pck  # noqa: E402
 
 
@@ -61,12 +62,7 @@ def check_pck(rng, enc, sigma, ora):
     global _pck
     if _pck is None:
         _pck = pck.PackedIndex()
-    bmax = 10 if sigma == 4 else 3
-    kw = dict(bsize=int(rng.integers(1, bmax + 1)),
-              blbuck=int(rng.choice([1, 2, 3, 5, 8, 8, 8, 13, 64, 300])),
-              locfreq=int(rng.choice([0, 1, 2, 3, 7, 16, 16, 32, 1000])),
-              locbitmap=[None, True, False][int(rng.integers(0, 3))],
-              mkindex=bool(rng.integers(0, 2)), sprank=bool(rng.integers(0, 2)))
+    kw = pck_options(rng, sigma)
     with esa.EsaEngine(enc.size, sigma) as eng:
         eng.set_sequence(enc)
         eng.run(esa.WANT_SUF | esa.WANT_BWT)
@@ -122,28 +118,8 @@ def check_parts(rng, enc, sigma, ora):
 
 def check_encoder(rng, enc, sigma, tmp):
     protein = sigma == 20
-    letters = b"LVIFKREDAGSTNQYWPHMC" if protein else b"ACGT"
-    wild = b"XUBZJO*-" if protein else b"NSYWRKVBDHM"
     path = os.path.join(tmp, "f.fa")
-    eol = b"\r\n" if rng.integers(0, 4) == 0 else b"\n"
-    with open(path, "wb") as f:
-        start = 0
-        cuts = list(np.flatnonzero(enc == 255)) + [enc.size]
-        for i, end in enumerate(cuts):
-            f.write(b">seq%d some text\t%d" % (i, int(rng.integers(0, 1000))) + eol)
-            seq = enc[start:end]
-            txt = bytearray(len(seq))
-            for j, c in enumerate(seq):
-                ch = wild[int(rng.integers(0, len(wild)))] if c == 254 else letters[c]
-                if not protein and rng.integers(0, 3) == 0:
-                    ch = ord(chr(ch).lower())
-                txt[j] = ch
-            width = int(rng.choice([1, 7, 60, 70, 4095, 4096, 100000]))
-            for a in range(0, len(txt), width):
-                f.write(bytes(txt[a:a + width]) + eol)
-                if rng.integers(0, 20) == 0:
-                    f.write(eol)
-            start = end + 1
+    write_fasta(rng, enc, sigma, path)
     with open(path, "rb") as f:
         written = f.read()
     try:
@@ -183,20 +159,11 @@ def check_encoder(rng, enc, sigma, tmp):
                                                  second.size))
     # the same sequences as four-line FASTQ records
     qpath = os.path.join(tmp, "f.fastq")
-    with open(qpath, "wb") as f:
-        start = 0
-        for i, end in enumerate(cuts):
-            seq = enc[start:end]
-            txt = bytes(wild[int(rng.integers(0, len(wild)))] if c == 254 else letters[c] for c in seq)
-            name = b"read%d x=%d" % (i, int(rng.integers(0, 99))) if rng.integers(0, 5) else b""
-            qual = bytes(rng.integers(33, 127, size=len(txt), dtype=np.uint8))
-            f.write(b"@" + name + b"\n" + txt + b"\n+" + (name if rng.integers(0, 3) == 0 else b"") + b"\n" +
-                    qual + b"\n")
-            start = end + 1
+    records = write_fastq(rng, enc, sigma, qpath)
     with encode.DeviceEncoder(protein=protein) as de:
         de.encode([qpath])
         assert np.array_equal(de.symbols(), enc), "device FASTQ reader symbols"
-        assert int(de.fastq_records()[1].sum()) + len(cuts) - 1 == enc.size
+        assert int(de.fastq_records()[1].sum()) + records - 1 == enc.size
     with encode.DeviceEncoder(protein=protein) as de:
         de.encode([path])
         assert np.array_equal(de.symbols(), enc), "device reader symbols"
