@@ -13,10 +13,11 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libgtamd_esa.so")
 SOURCES = [os.path.join(HERE, "csrc", f) for f in
            ("esa_prims.hip", "esa_engine.hip", "esa_synth.hip", "esa_encode.hip",
-            "esa_pck.hip", "esa_comm.hip")]
+            "esa_pck.hip", "esa_comm.hip", "esa_check.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
                                                      "esa_pck_replay.h")] + \
-          [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h")]
+          [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
+                                                       "gtamd_check.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -105,6 +106,15 @@ class PckInfo(ctypes.Structure):         # gtamd_pck_info
                [("cw_bits", ctypes.c_uint32), ("build_ms", ctypes.c_float)]
 
 
+class CheckReport(ctypes.Structure):     # gtamd_check_report, include/gtamd_check.h
+    _fields_ = [("ok", ctypes.c_int32), ("table", ctypes.c_uint32),
+                ("criterion", ctypes.c_uint32), ("checked", ctypes.c_uint32)] + \
+               [(name, ctypes.c_uint64) for name in
+                ("index", "llv_entry", "pos_a", "pos_b", "claimed", "found", "longest",
+                 "largelcpvalues", "maxbranchdepth", "long_claims")] + \
+               [("check_ms", ctypes.c_float), ("phase_ms", ctypes.c_float * 5)]
+
+
 # every symbol include/gtamd_esa.h, gtamd_encode.h and gtamd_pck.h declare:
 # (restype, argtypes)
 _P = ctypes.c_void_p
@@ -187,6 +197,21 @@ ABI = {
     "gtamd_pck_ctxmap_copy": (_INT, [_P, _P, _U64, _U64]),
 }
 
+# every symbol include/gtamd_check.h declares.  (A table of its own: ABI is, entry
+# for entry, what the three headers above declare.)
+CHECK_ABI = {
+    "gtamd_check_create": (_P, [_INT]),
+    "gtamd_check_destroy": (None, [_P]),
+    "gtamd_check_geometry": (None, [ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "gtamd_check_tables": (_INT, [_P, _P, _U64, _P, _U32, _P, _P, _U64, _P,
+                                  ctypes.POINTER(CheckReport)]),
+    "gtamd_check_tables_host": (_INT, [_P, _P, _U64, _P, _U32, _P, _P, _U64, _P,
+                                       ctypes.POINTER(CheckReport)]),
+    "gtamd_check_esa": (_INT, [_P, _P, _P, _U64, _U32, ctypes.POINTER(CheckReport)]),
+    "gtamd_check_message": (_INT, [ctypes.POINTER(CheckReport), ctypes.c_char_p,
+                                   ctypes.c_size_t]),
+}
+
 _lib = None
 
 
@@ -209,7 +234,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in ABI.items():
+        for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -2,12 +2,25 @@
    (tool function src/tools/gt_packedindex_trsuftab.c:44-79): INDEX.bdx from
    the project's INDEX.prj / .esq / .suf / .bwt, built on the device through
    include/gtamd_pck.h.  Options and defaults: src/match/eis-bwtseq-param.c:25-67,
-   src/match/eis-blockcomp-param.c:21-36. */
+   src/match/eis-blockcomp-param.c:21-36.
+
+   And the other tool that reads a project back, with the same helpers:
+   `gt dev sfxmap [-suf] [-lcp] [-bwt] [-v] -esa INDEX` (tool function
+   src/tools/gt_sfxmap.c; what it runs for these options:
+   gt_suftab_lightweightcheck src/match/sfx-lwcheck.c:181-337,
+   gt_lcptab_lightweightcheck src/match/sfx-linlcp.c:548): the tables of an
+   existing index, written here or by GenomeTools, checked entry for entry on
+   the device through include/gtamd_check.h. */
 #include "gtamd_host.h"
 #include "gtamd_pck.h"
+#include "gtamd_check.h"
+#include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 static int pfail(char *err, size_t errlen, const char *msg, const char *arg)
 {
@@ -235,5 +248,218 @@ int gtamd_packedindex_mkctxmap(int argc, const char **argv, char *err, size_t er
     rc = write_ctxmap(pck, index, used, err, errlen);
   gtamd_pck_destroy(pck);
   free(suf);
+  return rc;
+}
+
+/* ---- gt dev sfxmap ----
+   The table files are mapped, not read: the upload takes them piece by piece,
+   as the writer streamed them. */
+/* the single-build limit of the engine: tables of more entries come in slices */
+#define SFXMAP_MAX_ENTRIES ((1ull << 32) - 4096)
+
+/* the reference's other modes (gt_sfxmap.c: the option list of the tool) */
+static const char *const refused[] = {
+  "-pck", "-stream-esq", "-sortmaxdepth", "-algbds", "-stream", "-bfcheck", "-delspranges", "-des",
+  "-sds", "-bck", "-cmpsuf", "-cmplcp", "-diffcover", "-wholeleafcheck", "-enumlcpitvs",
+  "-enumlcpitvtree", "-enumlcpitvtreeBU", "-scanesa", "-spmitv", "-ownencseq2file",
+  "-compressedesa", "-compresslcp", NULL
+};
+
+typedef struct { void *p; uint64_t bytes; } mapped;
+
+/* 0, -1 cannot open, -2 cannot map */
+static int map_file(const char *path, mapped *m)
+{
+  struct stat sb;
+  const int fd = open(path, O_RDONLY);
+  m->p = NULL;
+  m->bytes = 0;
+  if (fd < 0) return -1;
+  if (fstat(fd, &sb) != 0) { close(fd); return -2; }
+  m->bytes = (uint64_t) sb.st_size;
+  if (m->bytes) {
+    m->p = mmap(NULL, m->bytes, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (m->p == MAP_FAILED) { m->p = NULL; close(fd); return -2; }
+  }
+  close(fd);
+  return 0;
+}
+
+static void unmap_file(mapped *m)
+{
+  if (m->p != NULL) munmap(m->p, m->bytes);
+  m->p = NULL;
+}
+
+static int map_table(const char *index, const char *suffix, mapped *m, char *path, size_t pathlen,
+                     char *err, size_t errlen)
+{
+  snprintf(path, pathlen, "%s%s", index, suffix);
+  switch (map_file(path, m)) {
+    case 0: return 0;
+    case -1: return pfail(err, errlen, "cannot open file '%s'", path);
+    default: return pfail(err, errlen, "cannot map file '%s'", path);
+  }
+}
+
+int gtamd_sfxmap(int argc, const char **argv, char *err, size_t errlen)
+{
+  int want_suf = 0, want_lcp = 0, want_bwt = 0, verbose = 0, rc = -1;
+  const char *index = NULL;
+  char path[4096], msg[512];
+  unsigned long long totallength = 0, sorted = 0, longest = 0, large = 0, depth = 0, readmode = 0,
+                     mirrored = 0;
+  uint8_t *enc = NULL;
+  uint64_t n = 0, N;
+  uint32_t suf_bytes = 8;
+  mapped suf = { NULL, 0 }, lcp = { NULL, 0 }, llv = { NULL, 0 }, bwt = { NULL, 0 };
+  gtamd_alphabet alpha;
+  gtamd_seqstats ss;
+  gtamd_check *chk = NULL;
+  gtamd_check_report rep;
+
+  for (int i = 1; i < argc; i++) {
+    const char *a = argv[i];
+    if (!strcmp(a, "-suf")) want_suf = 1;
+    else if (!strcmp(a, "-lcp")) want_lcp = 1;
+    else if (!strcmp(a, "-bwt")) want_bwt = 1;
+    else if (!strcmp(a, "-v")) verbose = 1;
+    else if (!strcmp(a, "-tis") || !strcmp(a, "-ssp")) continue;   /* (always read) */
+    else if (!strcmp(a, "-esa")) {
+      if (i + 1 >= argc) return pfail(err, errlen, "missing argument to option \"%s\"", a);
+      index = argv[++i];
+    } else {
+      for (int k = 0; refused[k] != NULL; k++)
+        if (!strcmp(a, refused[k]))
+          return pfail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
+      if (a[0] == '-') return pfail(err, errlen, "unknown option: %s (try -help)", a);
+      return pfail(err, errlen, "superfluous argument \"%s\"", a);
+    }
+  }
+  if (index == NULL) return pfail(err, errlen, "option \"-%s\" is mandatory", "esa");
+  if (!want_suf && (want_lcp || want_bwt))
+    return pfail(err, errlen, "option \"-%s\" requires option \"-suf\": the table is checked through "
+                 "the suffix array", want_lcp ? "lcp" : "bwt");
+
+  snprintf(path, sizeof path, "%s.prj", index);
+  {
+    FILE *fp = fopen(path, "r");
+    if (fp == NULL) return pfail(err, errlen, "cannot open file '%s'", path);
+    fclose(fp);
+  }
+  if (prj_value(path, "totallength", &totallength) != 0 ||
+      prj_value(path, "numberofallsortedsuffixes", &sorted) != 0)
+    return pfail(err, errlen, "cannot read totallength / numberofallsortedsuffixes from file '%s'", path);
+  (void) prj_value(path, "longest", &longest);
+  (void) prj_value(path, "largelcpvalues", &large);
+  (void) prj_value(path, "maxbranchdepth", &depth);
+  (void) prj_value(path, "readmode", &readmode);
+  (void) prj_value(path, "mirrored", &mirrored);
+  if (sorted == 0 && totallength != 0)
+    return pfail(err, errlen, "file '%s' describes the project of a packed index "
+                 "(numberofallsortedsuffixes=0): it has no tables to check", path);
+  if (totallength + 1 > SFXMAP_MAX_ENTRIES) {
+    snprintf(err, errlen, "sequence of %llu symbols is beyond the limit of a single build (%llu table "
+             "entries); the slices of a build in parts are not checked", totallength,
+             SFXMAP_MAX_ENTRIES);
+    return -1;
+  }
+  if (sorted != totallength + 1 || readmode > 3)
+    return pfail(err, errlen, "file '%s' does not describe whole tables (numberofallsortedsuffixes "
+                 "is not totallength + 1, or the read mode is unknown)", path);
+
+  /* the sequence the tables describe: as stored, then -mirrored, then -dir */
+  if (gtamd_read_esq_alpha(index, &enc, &n, &alpha, &ss, err, errlen) != 0) return -1;
+  {
+    const int dnalike = alpha.numofchars == 4 && alpha.symbolmap['a'] == 0 && alpha.symbolmap['c'] == 1 &&
+                        alpha.symbolmap['g'] == 2 && alpha.symbolmap['t'] == 3;
+    gtamd_alphabet_free(&alpha);
+    if (!dnalike && (readmode >= 2 || mirrored)) {
+      pfail(err, errlen, "file '%s' asks for complemented symbols of an alphabet that is not DNA", path);
+      goto done;
+    }
+  }
+  if (mirrored) {
+    uint8_t *m = gtamd_mirror(enc, n);
+    if (m == NULL) { pfail(err, errlen, "out of memory (%s)", "-mirrored"); goto done; }
+    free(enc);
+    enc = m;
+    n = 2 * n + 1;
+  }
+  gtamd_apply_readmode(enc, n, (int) readmode);
+  if (n != totallength) {
+    pfail(err, errlen, "INDEX.esq and INDEX.prj of '%s' disagree on the total length", index);
+    goto done;
+  }
+  N = n + 1;
+
+  if (want_suf) {
+    if (map_table(index, ".suf", &suf, path, sizeof path, err, errlen) != 0) goto done;
+    if (suf.bytes == 4 * N) suf_bytes = 4;
+    else if (suf.bytes != 8 * N) {
+      snprintf(err, errlen, "file '%s' has %llu bytes, %llu (-suftabuint) or %llu expected for %llu entries",
+               path, (unsigned long long) suf.bytes, (unsigned long long) (4 * N),
+               (unsigned long long) (8 * N), (unsigned long long) N);
+      goto done;
+    }
+  }
+  if (want_lcp) {
+    if (map_table(index, ".lcp", &lcp, path, sizeof path, err, errlen) != 0) goto done;
+    if (lcp.bytes != N) {
+      snprintf(err, errlen, "file '%s' has %llu bytes, %llu expected", path,
+               (unsigned long long) lcp.bytes, (unsigned long long) N);
+      goto done;
+    }
+    if (map_table(index, ".llv", &llv, path, sizeof path, err, errlen) != 0) goto done;
+    if (llv.bytes % 16 != 0) {
+      snprintf(err, errlen, "file '%s' has %llu bytes, not a multiple of 16 (pairs of two 64-bit numbers)",
+               path, (unsigned long long) llv.bytes);
+      goto done;
+    }
+  }
+  if (want_bwt) {
+    if (map_table(index, ".bwt", &bwt, path, sizeof path, err, errlen) != 0) goto done;
+    if (bwt.bytes != N) {
+      snprintf(err, errlen, "file '%s' has %llu bytes, %llu expected", path,
+               (unsigned long long) bwt.bytes, (unsigned long long) N);
+      goto done;
+    }
+  }
+  if (!want_suf) { rc = 0; goto done; }     /* the sequence and the project file agree */
+
+  if ((chk = gtamd_check_create(0)) == NULL ||
+      gtamd_check_tables_host(chk, enc, n, suf.p, suf_bytes, lcp.p, llv.p, llv.bytes / 16, bwt.p,
+                              &rep) != 0) {
+    snprintf(err, errlen, "%s", gtamd_esa_last_error());
+    goto done;
+  }
+  if (verbose) {
+    static const char *const phase[GTAMD_CHECK_PHASES] = {
+      "suf: range and permutation", "suf: order", "bwt", "lcp/llv: structure", "lcp/llv: values" };
+    for (int k = 0; k < GTAMD_CHECK_PHASES; k++)
+      if (rep.phase_ms[k] > 0) printf("# %-27s %10.3f ms\n", phase[k], rep.phase_ms[k]);
+    printf("# %-27s %10.3f ms on the device, %llu entries, %llu long ranges\n", "total", rep.check_ms,
+           (unsigned long long) N, (unsigned long long) rep.long_claims);
+  }
+  if (!rep.ok) {
+    gtamd_check_message(&rep, msg, sizeof msg);
+    snprintf(err, errlen, "index '%s': %s", index, msg);
+    goto done;
+  }
+  snprintf(path, sizeof path, "%s.prj", index);
+  if (rep.longest != longest)
+    snprintf(err, errlen, "file '%s' says longest=%llu, suffix 0 stands at table index %llu", path,
+             longest, (unsigned long long) rep.longest);
+  else if (want_lcp && rep.largelcpvalues != large)
+    snprintf(err, errlen, "file '%s' says largelcpvalues=%llu, the .lcp table holds %llu", path, large,
+             (unsigned long long) rep.largelcpvalues);
+  else if (want_lcp && rep.maxbranchdepth != depth)
+    snprintf(err, errlen, "file '%s' says maxbranchdepth=%llu, the largest value of the tables is %llu",
+             path, depth, (unsigned long long) rep.maxbranchdepth);
+  else rc = 0;
+done:
+  gtamd_check_destroy(chk);
+  unmap_file(&suf); unmap_file(&lcp); unmap_file(&llv); unmap_file(&bwt);
+  free(enc);
   return rc;
 }

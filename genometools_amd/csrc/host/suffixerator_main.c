@@ -1,7 +1,8 @@
 /* gt-suffixerator-amd: command line entry, behaves like `gt suffixerator`
    (exit code 1 and "gt suffixerator: error: ..." on stderr, src/gt.c:48-52);
    `gt-suffixerator-amd mergeesa ...` is `gt dev mergeesa ...`,
-   `gt-suffixerator-amd packedindex mkindex|trsuftab ...` is `gt packedindex ...` */
+   `gt-suffixerator-amd packedindex mkindex|trsuftab ...` is `gt packedindex ...`,
+   `gt-suffixerator-amd sfxmap ...` is `gt dev sfxmap ...` */
 #include <stdio.h>
 #include <string.h>
 #include "gtamd_host.h"
@@ -12,6 +13,13 @@ int main(int argc, char **argv)
   if (argc > 1 && !strcmp(argv[1], "mergeesa")) {
     if (gtamd_mergeesa(argc - 1, (const char **) argv + 1, err, sizeof err) != 0) {
       fprintf(stderr, "gt dev mergeesa: error: %s\n", err);
+      return 1;
+    }
+    return 0;
+  }
+  if (argc > 1 && !strcmp(argv[1], "sfxmap")) {
+    if (gtamd_sfxmap(argc - 1, (const char **) argv + 1, err, sizeof err) != 0) {
+      fprintf(stderr, "gt dev sfxmap: error: %s\n", err);
       return 1;
     }
     return 0;

@@ -11,6 +11,10 @@
     gtamd_write_prj         gt_outprjfile (src/match/sfx-outprj.c:38-118)
     gtamd_suffixerator      the tool function, GtToolfunc shape
                             (src/core/toolbox.h:32, src/tools/gt_suffixerator.c:22)
+    gtamd_sfxmap            the checker of that path, `gt dev sfxmap -suf -lcp -bwt`
+                            (src/tools/gt_sfxmap.c; src/match/sfx-lwcheck.c:181-337,
+                            src/match/sfx-linlcp.c:548), on the device through
+                            include/gtamd_check.h
 
   Pure C (gcc); links against libgtamd_esa.so for the hot path.
 */
@@ -273,6 +277,23 @@ int gtamd_packedindex_mkindex(int argc, const char **argv, char *err, size_t err
 int gtamd_packedindex_mkctxmap(int argc, const char **argv, char *err, size_t errlen);
 int gtamd_write_prj_packedindex(const char *path, const gtamd_seqstats *ss,
                                 uint32_t prefixlength, int readmode, int mirrored);
+
+/* `gt dev sfxmap [-suf] [-lcp] [-bwt] [-v] -esa INDEX` (tool function
+   src/tools/gt_sfxmap.c): is INDEX the index of its sequence?  Reads INDEX.prj,
+   INDEX.esq (+ .ssp) and the tables asked for (.suf of 4- or 8-byte entries, by
+   its size; .lcp with .llv; .bwt), written here or by GenomeTools; applies
+   `mirrored` and `readmode` of the project file to the symbols; checks EVERY
+   table entry on the device (criteria: include/gtamd_check.h) and, against the
+   tables, `longest` (-suf), `largelcpvalues` and `maxbranchdepth` (-lcp) of the
+   project file (`averagelcp` is a rounded, masked figure and is not checked).
+   -lcp and -bwt need -suf: both tables are checked through the suffix array
+   (the reference's -bwt only prints a statistic).  Silent on success; -v prints
+   the device time of every phase.  The reference's other modes (-pck, -stream,
+   -bfcheck, -bck, -wholeleafcheck, -enumlcpitv*, -sortmaxdepth, -compressedesa
+   ...) are refused by name; indexes beyond the single-build limit (2^32 - 4096
+   entries) are refused too.  Returns 0, or -1 with the message in err (the
+   caller prints "gt dev sfxmap: error: <err>" and exits 1). */
+int gtamd_sfxmap(int argc, const char **argv, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }
