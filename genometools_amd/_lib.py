@@ -13,11 +13,11 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libgtamd_esa.so")
 SOURCES = [os.path.join(HERE, "csrc", f) for f in
            ("esa_prims.hip", "esa_engine.hip", "esa_synth.hip", "esa_encode.hip",
-            "esa_pck.hip", "esa_comm.hip", "esa_check.hip")]
+            "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
-                                                     "esa_pck_replay.h")] + \
+                                                     "esa_pck_replay.h", "esa_mstat_search.h")] + \
           [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
-                                                       "gtamd_check.h")]
+                                                       "gtamd_check.h", "gtamd_mstat.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -113,6 +113,12 @@ class CheckReport(ctypes.Structure):     # gtamd_check_report, include/gtamd_che
                 ("index", "llv_entry", "pos_a", "pos_b", "claimed", "found", "longest",
                  "largelcpvalues", "maxbranchdepth", "long_claims")] + \
                [("check_ms", ctypes.c_float), ("phase_ms", ctypes.c_float * 5)]
+
+
+class MstatInfo(ctypes.Structure):       # gtamd_mstat_info, include/gtamd_mstat.h
+    _fields_ = [("device_ms", ctypes.c_float), ("reruns", ctypes.c_uint32)] + \
+               [(name, ctypes.c_uint64) for name in
+                ("positions", "symbols_compared", "device_bytes")]
 
 
 # every symbol include/gtamd_esa.h, gtamd_encode.h and gtamd_pck.h declare:
@@ -212,6 +218,20 @@ CHECK_ABI = {
                                    ctypes.c_size_t]),
 }
 
+# every symbol include/gtamd_mstat.h declares
+MSTAT_ABI = {
+    "gtamd_mstat_create": (_P, [_INT]),
+    "gtamd_mstat_destroy": (None, [_P]),
+    "gtamd_mstat_geometry": (None, [ctypes.POINTER(_U32), ctypes.POINTER(_U32),
+                                    ctypes.POINTER(_U32)]),
+    "gtamd_mstat_set_index": (_INT, [_P, _P, _U64, _P, _U32, _U32]),
+    "gtamd_mstat_set_index_host": (_INT, [_P, _P, _U64, _P, _U32, _U32]),
+    "gtamd_mstat_set_index_esa": (_INT, [_P, _P, _P, _U64, _U32]),
+    "gtamd_mstat_matstat": (_INT, [_P, _P, _U64, _INT, _U32, _P, _P, _INT]),
+    "gtamd_mstat_uniquesub": (_INT, [_P, _P, _U64, _INT, _U32, _P, _INT]),
+    "gtamd_mstat_get_info": (_INT, [_P, ctypes.POINTER(MstatInfo)]),
+}
+
 _lib = None
 
 
@@ -234,7 +254,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()):
+        for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

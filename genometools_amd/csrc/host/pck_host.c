@@ -10,10 +10,15 @@
    gt_suftab_lightweightcheck src/match/sfx-lwcheck.c:181-337,
    gt_lcptab_lightweightcheck src/match/sfx-linlcp.c:548): the tables of an
    existing index, written here or by GenomeTools, checked entry for entry on
-   the device through include/gtamd_check.h. */
+   the device through include/gtamd_check.h.
+
+   And the first tools that ask an index a question: `gt matstat` and `gt
+   uniquesub` with -esa INDEX (tool src/tools/gt_matstat.c), on the device
+   through include/gtamd_mstat.h. */
 #include "gtamd_host.h"
 #include "gtamd_pck.h"
 #include "gtamd_check.h"
+#include "gtamd_mstat.h"
 #include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -302,19 +307,86 @@ static int map_table(const char *index, const char *suffix, mapped *m, char *pat
   }
 }
 
+/* The sequence the tables of a project describe: the symbols of INDEX.esq, then
+   -mirrored, then -dir, as INDEX.prj says.  Refuses a project without whole
+   tables; `verb` words what is not done with the slices of a build in parts.
+   *enc_out is malloc'ed; *alpha (may be NULL) receives the alphabet of
+   INDEX.esq, to be given to gtamd_alphabet_free. */
+static int load_project_sequence(const char *index, const char *verb, uint8_t **enc_out,
+                                 uint64_t *n_out, gtamd_alphabet *alpha_out, char *err, size_t errlen)
+{
+  char path[4096];
+  unsigned long long totallength = 0, sorted = 0, readmode = 0, mirrored = 0;
+  uint8_t *enc = NULL;
+  uint64_t n = 0;
+  gtamd_alphabet alpha;
+  gtamd_seqstats ss;
+  int dnalike;
+
+  snprintf(path, sizeof path, "%s.prj", index);
+  {
+    FILE *fp = fopen(path, "r");
+    if (fp == NULL) return pfail(err, errlen, "cannot open file '%s'", path);
+    fclose(fp);
+  }
+  if (prj_value(path, "totallength", &totallength) != 0 ||
+      prj_value(path, "numberofallsortedsuffixes", &sorted) != 0)
+    return pfail(err, errlen, "cannot read totallength / numberofallsortedsuffixes from file '%s'", path);
+  (void) prj_value(path, "readmode", &readmode);
+  (void) prj_value(path, "mirrored", &mirrored);
+  if (sorted == 0 && totallength != 0)
+    return pfail(err, errlen, "file '%s' describes the project of a packed index "
+                 "(numberofallsortedsuffixes=0): it has no tables to check", path);
+  if (totallength + 1 > SFXMAP_MAX_ENTRIES) {
+    snprintf(err, errlen, "sequence of %llu symbols is beyond the limit of a single build (%llu table "
+             "entries); the slices of a build in parts are not %s", totallength,
+             SFXMAP_MAX_ENTRIES, verb);
+    return -1;
+  }
+  if (sorted != totallength + 1 || readmode > 3)
+    return pfail(err, errlen, "file '%s' does not describe whole tables (numberofallsortedsuffixes "
+                 "is not totallength + 1, or the read mode is unknown)", path);
+
+  /* as stored, then -mirrored, then -dir */
+  if (gtamd_read_esq_alpha(index, &enc, &n, &alpha, &ss, err, errlen) != 0) return -1;
+  dnalike = alpha.numofchars == 4 && alpha.symbolmap['a'] == 0 && alpha.symbolmap['c'] == 1 &&
+            alpha.symbolmap['g'] == 2 && alpha.symbolmap['t'] == 3;
+  if (!dnalike && (readmode >= 2 || mirrored)) {
+    pfail(err, errlen, "file '%s' asks for complemented symbols of an alphabet that is not DNA", path);
+    goto fail;
+  }
+  if (mirrored) {
+    uint8_t *m = gtamd_mirror(enc, n);
+    if (m == NULL) { pfail(err, errlen, "out of memory (%s)", "-mirrored"); goto fail; }
+    free(enc);
+    enc = m;
+    n = 2 * n + 1;
+  }
+  gtamd_apply_readmode(enc, n, (int) readmode);
+  if (n != totallength) {
+    pfail(err, errlen, "INDEX.esq and INDEX.prj of '%s' disagree on the total length", index);
+    goto fail;
+  }
+  if (alpha_out != NULL) *alpha_out = alpha; else gtamd_alphabet_free(&alpha);
+  *enc_out = enc;
+  *n_out = n;
+  return 0;
+fail:
+  gtamd_alphabet_free(&alpha);
+  free(enc);
+  return -1;
+}
+
 int gtamd_sfxmap(int argc, const char **argv, char *err, size_t errlen)
 {
   int want_suf = 0, want_lcp = 0, want_bwt = 0, verbose = 0, rc = -1;
   const char *index = NULL;
   char path[4096], msg[512];
-  unsigned long long totallength = 0, sorted = 0, longest = 0, large = 0, depth = 0, readmode = 0,
-                     mirrored = 0;
+  unsigned long long longest = 0, large = 0, depth = 0;
   uint8_t *enc = NULL;
   uint64_t n = 0, N;
   uint32_t suf_bytes = 8;
   mapped suf = { NULL, 0 }, lcp = { NULL, 0 }, llv = { NULL, 0 }, bwt = { NULL, 0 };
-  gtamd_alphabet alpha;
-  gtamd_seqstats ss;
   gtamd_check *chk = NULL;
   gtamd_check_report rep;
 
@@ -341,56 +413,11 @@ int gtamd_sfxmap(int argc, const char **argv, char *err, size_t errlen)
     return pfail(err, errlen, "option \"-%s\" requires option \"-suf\": the table is checked through "
                  "the suffix array", want_lcp ? "lcp" : "bwt");
 
+  if (load_project_sequence(index, "checked", &enc, &n, NULL, err, errlen) != 0) goto done;
   snprintf(path, sizeof path, "%s.prj", index);
-  {
-    FILE *fp = fopen(path, "r");
-    if (fp == NULL) return pfail(err, errlen, "cannot open file '%s'", path);
-    fclose(fp);
-  }
-  if (prj_value(path, "totallength", &totallength) != 0 ||
-      prj_value(path, "numberofallsortedsuffixes", &sorted) != 0)
-    return pfail(err, errlen, "cannot read totallength / numberofallsortedsuffixes from file '%s'", path);
   (void) prj_value(path, "longest", &longest);
   (void) prj_value(path, "largelcpvalues", &large);
   (void) prj_value(path, "maxbranchdepth", &depth);
-  (void) prj_value(path, "readmode", &readmode);
-  (void) prj_value(path, "mirrored", &mirrored);
-  if (sorted == 0 && totallength != 0)
-    return pfail(err, errlen, "file '%s' describes the project of a packed index "
-                 "(numberofallsortedsuffixes=0): it has no tables to check", path);
-  if (totallength + 1 > SFXMAP_MAX_ENTRIES) {
-    snprintf(err, errlen, "sequence of %llu symbols is beyond the limit of a single build (%llu table "
-             "entries); the slices of a build in parts are not checked", totallength,
-             SFXMAP_MAX_ENTRIES);
-    return -1;
-  }
-  if (sorted != totallength + 1 || readmode > 3)
-    return pfail(err, errlen, "file '%s' does not describe whole tables (numberofallsortedsuffixes "
-                 "is not totallength + 1, or the read mode is unknown)", path);
-
-  /* the sequence the tables describe: as stored, then -mirrored, then -dir */
-  if (gtamd_read_esq_alpha(index, &enc, &n, &alpha, &ss, err, errlen) != 0) return -1;
-  {
-    const int dnalike = alpha.numofchars == 4 && alpha.symbolmap['a'] == 0 && alpha.symbolmap['c'] == 1 &&
-                        alpha.symbolmap['g'] == 2 && alpha.symbolmap['t'] == 3;
-    gtamd_alphabet_free(&alpha);
-    if (!dnalike && (readmode >= 2 || mirrored)) {
-      pfail(err, errlen, "file '%s' asks for complemented symbols of an alphabet that is not DNA", path);
-      goto done;
-    }
-  }
-  if (mirrored) {
-    uint8_t *m = gtamd_mirror(enc, n);
-    if (m == NULL) { pfail(err, errlen, "out of memory (%s)", "-mirrored"); goto done; }
-    free(enc);
-    enc = m;
-    n = 2 * n + 1;
-  }
-  gtamd_apply_readmode(enc, n, (int) readmode);
-  if (n != totallength) {
-    pfail(err, errlen, "INDEX.esq and INDEX.prj of '%s' disagree on the total length", index);
-    goto done;
-  }
   N = n + 1;
 
   if (want_suf) {
@@ -462,4 +489,164 @@ done:
   unmap_file(&suf); unmap_file(&lcp); unmap_file(&llv); unmap_file(&bwt);
   free(enc);
   return rc;
+}
+
+/* ---- gt matstat / gt uniquesub ----
+   Option handling and messages of src/tools/gt_matstat.c:96-278, output of
+   src/match/greedyfwdmat.c:168-211. */
+enum { SHOW_SEQUENCE = 1, SHOW_QUERYPOS = 2, SHOW_SUBJECTPOS = 4 };
+
+static int length_option(int argc, const char **argv, int *i, unsigned long long *out, char *err,
+                         size_t errlen)
+{
+  char *end;
+  if (*i + 1 >= argc) return pfail(err, errlen, "missing argument to option \"%s\"", argv[*i]);
+  *out = strtoull(argv[*i + 1], &end, 10);
+  if (*end != 0 || end == argv[*i + 1] || argv[*i + 1][0] == '-')
+    return pfail(err, errlen, "argument to option \"%s\" is out of range", argv[*i]);
+  if (*out < 1) return pfail(err, errlen, "argument to option \"%s\" must be an integer >= 1", argv[*i]);
+  (*i)++;
+  return 0;
+}
+
+/* doms: matching statistics, else minimum unique prefixes */
+static int greedy_forward_tool(int doms, int argc, const char **argv, char *err, size_t errlen)
+{
+  const char *index = NULL, *const *queries = NULL;
+  size_t numqueries = 0;
+  int have_min = 0, have_max = 0, have_output = 0, numflags = 0, query_seen = 0, rc = -1;
+  unsigned show = 0;
+  unsigned long long minlen = 0, maxlen = 0;
+  char path[4096];
+  uint8_t *enc = NULL, *query = NULL;
+  uint64_t n = 0, m = 0, N, desclen = 0;
+  char *desc = NULL;
+  uint32_t suf_bytes = 8, *length = NULL;
+  uint64_t *subjectpos = NULL;
+  mapped suf = { NULL, 0 };
+  gtamd_alphabet alpha;
+  int have_alpha = 0;
+  gtamd_mstat *ms = NULL;
+
+  for (int i = 1; i < argc; i++) {
+    const char *a = argv[i];
+    if (!strcmp(a, "-esa")) {
+      if (i + 1 >= argc) return pfail(err, errlen, "missing argument to option \"%s\"", a);
+      index = argv[++i];
+    } else if (!strcmp(a, "-fmi") || !strcmp(a, "-pck")) {
+      return pfail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
+    } else if (!strcmp(a, "-query")) {
+      query_seen = 1;
+      queries = argv + i + 1;
+      for (numqueries = 0; i + 1 < argc && argv[i + 1][0] != '-'; i++) numqueries++;
+      if (numqueries == 0) return pfail(err, errlen, "missing argument to option \"%s\"", a);
+    } else if (!strcmp(a, "-min")) {
+      if (length_option(argc, argv, &i, &minlen, err, errlen) != 0) return -1;
+      have_min = 1;
+    } else if (!strcmp(a, "-max")) {
+      if (length_option(argc, argv, &i, &maxlen, err, errlen) != 0) return -1;
+      have_max = 1;
+    } else if (!strcmp(a, "-output")) {
+      have_output = 1;
+      for (; i + 1 < argc && argv[i + 1][0] != '-'; i++, numflags++) {
+        const char *f = argv[i + 1];
+        if (!strcmp(f, "sequence")) show |= SHOW_SEQUENCE;
+        else if (!strcmp(f, "querypos")) show |= SHOW_QUERYPOS;
+        else if (doms && !strcmp(f, "subjectpos")) show |= SHOW_SUBJECTPOS;
+        else return pfail(err, errlen, "illegal argument \"%s\" to option -output", f);
+      }
+    } else if (doms && !strcmp(a, "-verify")) {       /* without effect with -esa, as in the reference */
+      if (i + 1 < argc && (!strcmp(argv[i + 1], "yes") || !strcmp(argv[i + 1], "no"))) i++;
+    } else if (a[0] == '-') return pfail(err, errlen, "unknown option: %s (try -help)", a);
+    else return pfail(err, errlen, "superfluous argument \"%s\"", a);
+  }
+  if (!query_seen) return pfail(err, errlen, "option \"-%s\" is mandatory", "query");
+  if (index == NULL) return pfail(err, errlen, "one of the options -esa, -pck must be %s", "used");
+  if (!have_min && !have_max) return pfail(err, errlen, "one of the options -min or -max must be %s", "set");
+  if (have_min && have_max && maxlen < minlen)
+    return pfail(err, errlen, "minvalue must be smaller or equal than %s", "maxvalue");
+  if (have_output && numflags == 0) return pfail(err, errlen, "missing arguments to option %s", "-output");
+
+  if (load_project_sequence(index, "searched", &enc, &n, &alpha, err, errlen) != 0) goto done;
+  have_alpha = 1;
+  N = n + 1;
+  if (map_table(index, ".suf", &suf, path, sizeof path, err, errlen) != 0) goto done;
+  if (suf.bytes == 4 * N) suf_bytes = 4;
+  else if (suf.bytes != 8 * N) {
+    snprintf(err, errlen, "file '%s' has %llu bytes, %llu (-suftabuint) or %llu expected for %llu entries",
+             path, (unsigned long long) suf.bytes, (unsigned long long) (4 * N),
+             (unsigned long long) (8 * N), (unsigned long long) N);
+    goto done;
+  }
+  /* the queries, with the index's alphabet: one sequence of symbols, a separator
+     between two units */
+  if (gtamd_encode_files_alpha(queries, numqueries, &alpha, &query, &m, &desc, &desclen, NULL, err,
+                               errlen) != 0)
+    goto done;
+  if (m > 0xffffffffull) {
+    snprintf(err, errlen, "queries of %llu symbols, at most %llu in one call", (unsigned long long) m,
+             0xffffffffull);
+    goto done;
+  }
+  length = malloc((m ? m : 1) * sizeof *length);
+  if (show & SHOW_SUBJECTPOS) subjectpos = malloc((m ? m : 1) * sizeof *subjectpos);
+  if (length == NULL || ((show & SHOW_SUBJECTPOS) && subjectpos == NULL)) {
+    pfail(err, errlen, "out of memory (%s)", "results");
+    goto done;
+  }
+  {
+    /* longer matches are not printed: the device stops looking there */
+    const uint32_t cap = have_max && maxlen < 0xfffffffeull ? (uint32_t) maxlen : 0;
+    if ((ms = gtamd_mstat_create(0)) == NULL ||
+        gtamd_mstat_set_index_host(ms, enc, n, suf.p, suf_bytes, alpha.numofchars) != 0 ||
+        (doms ? gtamd_mstat_matstat(ms, query, m, 0, cap, length, subjectpos, 0)
+              : gtamd_mstat_uniquesub(ms, query, m, 0, cap, length, 0)) != 0) {
+      snprintf(err, errlen, "%s", gtamd_esa_last_error());
+      goto done;
+    }
+  }
+  {
+    const char *d = desc;
+    unsigned long long unit = 0;
+    uint64_t end;
+    for (uint64_t start = 0; start < m; start = end + 1, unit++) {
+      for (end = start; end < m && query[end] != 255; end++) ;
+      printf("unit %llu", unit);
+      if (d != NULL && d < desc + desclen) {
+        if (d[0] != 0) printf(" (%s)", d);
+        d += strlen(d) + 1;
+      }
+      putchar('\n');
+      for (uint64_t k = start; k < end; k++) {
+        const uint32_t v = length[k];
+        if (v == 0 || (have_min && v < minlen) || (have_max && v > maxlen)) continue;
+        if (show & SHOW_QUERYPOS) printf("%llu ", (unsigned long long) (k - start));
+        printf("%lu", (unsigned long) v);
+        if (show & SHOW_SUBJECTPOS) printf(" %llu", (unsigned long long) subjectpos[k]);
+        if (show & SHOW_SEQUENCE) {
+          putchar(' ');
+          for (uint32_t j = 0; j < v; j++) putchar(alpha.characters[query[k + j]]);
+        }
+        putchar('\n');
+      }
+    }
+  }
+  if (fflush(stdout) != 0) { pfail(err, errlen, "cannot write to %s", "stdout"); goto done; }
+  rc = 0;
+done:
+  gtamd_mstat_destroy(ms);
+  unmap_file(&suf);
+  if (have_alpha) gtamd_alphabet_free(&alpha);
+  free(length); free(subjectpos); free(desc); free(query); free(enc);
+  return rc;
+}
+
+int gtamd_matstat(int argc, const char **argv, char *err, size_t errlen)
+{
+  return greedy_forward_tool(1, argc, argv, err, errlen);
+}
+
+int gtamd_uniquesub(int argc, const char **argv, char *err, size_t errlen)
+{
+  return greedy_forward_tool(0, argc, argv, err, errlen);
 }

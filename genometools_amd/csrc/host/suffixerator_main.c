@@ -2,7 +2,8 @@
    (exit code 1 and "gt suffixerator: error: ..." on stderr, src/gt.c:48-52);
    `gt-suffixerator-amd mergeesa ...` is `gt dev mergeesa ...`,
    `gt-suffixerator-amd packedindex mkindex|trsuftab ...` is `gt packedindex ...`,
-   `gt-suffixerator-amd sfxmap ...` is `gt dev sfxmap ...` */
+   `gt-suffixerator-amd sfxmap ...` is `gt dev sfxmap ...`,
+   `gt-suffixerator-amd matstat|uniquesub ...` is `gt matstat|uniquesub ...` */
 #include <stdio.h>
 #include <string.h>
 #include "gtamd_host.h"
@@ -20,6 +21,14 @@ int main(int argc, char **argv)
   if (argc > 1 && !strcmp(argv[1], "sfxmap")) {
     if (gtamd_sfxmap(argc - 1, (const char **) argv + 1, err, sizeof err) != 0) {
       fprintf(stderr, "gt dev sfxmap: error: %s\n", err);
+      return 1;
+    }
+    return 0;
+  }
+  if (argc > 1 && (!strcmp(argv[1], "matstat") || !strcmp(argv[1], "uniquesub"))) {
+    if ((argv[1][0] == 'm' ? gtamd_matstat : gtamd_uniquesub)(argc - 1, (const char **) argv + 1, err,
+                                                             sizeof err) != 0) {
+      fprintf(stderr, "gt %s: error: %s\n", argv[1], err);
       return 1;
     }
     return 0;

@@ -15,6 +15,10 @@
                             (src/tools/gt_sfxmap.c; src/match/sfx-lwcheck.c:181-337,
                             src/match/sfx-linlcp.c:548), on the device through
                             include/gtamd_check.h
+    gtamd_matstat, gtamd_uniquesub
+                            `gt matstat -esa` and `gt uniquesub -esa`
+                            (src/tools/gt_matstat.c), on the device through
+                            include/gtamd_mstat.h
 
   Pure C (gcc); links against libgtamd_esa.so for the hot path.
 */
@@ -294,6 +298,25 @@ int gtamd_write_prj_packedindex(const char *path, const gtamd_seqstats *ss,
    entries) are refused too.  Returns 0, or -1 with the message in err (the
    caller prints "gt dev sfxmap: error: <err>" and exits 1). */
 int gtamd_sfxmap(int argc, const char **argv, char *err, size_t errlen);
+
+/* `gt matstat` and `gt uniquesub` with -esa INDEX (tool functions
+   src/tools/gt_matstat.c, output src/match/greedyfwdmat.c:168-211): for every
+   position of every query sequence the longest prefix that occurs in the index's
+   sequence and where, or the shortest prefix that occurs exactly once, on the
+   device (semantics: include/gtamd_mstat.h).
+     -esa INDEX        reads INDEX.prj, INDEX.esq (+ .ssp) and INDEX.suf (4- or
+                       8-byte entries, by its size) as gtamd_sfxmap does
+     -query FILE...    FASTA, read with the alphabet of INDEX.esq
+     -min L  -max L    print lengths in [L, L] only; one of them is required
+     -output querypos sequence [subjectpos]    (subjectpos: matstat only)
+     -verify           matstat only; accepted, without effect with -esa
+     -fmi, -pck        refused ("option \"-X\" is not supported ...")
+   Prints `unit U[ (DESCRIPTION)]` per query sequence, U counting across all
+   files, then `[QUERYPOS ]LENGTH[ SUBJECTPOS][ SEQUENCE]` per position whose
+   length is not 0 and within -min/-max.  Returns 0, or -1 with the message in
+   err (the caller prints "gt matstat: error: <err>" and exits 1). */
+int gtamd_matstat(int argc, const char **argv, char *err, size_t errlen);
+int gtamd_uniquesub(int argc, const char **argv, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }
