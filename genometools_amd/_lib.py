@@ -13,11 +13,14 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libgtamd_esa.so")
 SOURCES = [os.path.join(HERE, "csrc", f) for f in
            ("esa_prims.hip", "esa_engine.hip", "esa_synth.hip", "esa_encode.hip",
-            "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip")]
+            "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip",
+            "esa_maxpairs.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
-                                                     "esa_pck_replay.h", "esa_mstat_search.h")] + \
+                                                     "esa_pck_replay.h", "esa_mstat_search.h",
+                                                     "esa_maxpairs_walk.h")] + \
           [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
-                                                       "gtamd_check.h", "gtamd_mstat.h")]
+                                                       "gtamd_check.h", "gtamd_mstat.h",
+                                                       "gtamd_maxpairs.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -119,6 +122,12 @@ class MstatInfo(ctypes.Structure):       # gtamd_mstat_info, include/gtamd_mstat
     _fields_ = [("device_ms", ctypes.c_float), ("reruns", ctypes.c_uint32)] + \
                [(name, ctypes.c_uint64) for name in
                 ("positions", "symbols_compared", "device_bytes")]
+
+
+class MaxPairsInfo(ctypes.Structure):    # gtamd_maxpairs_info, include/gtamd_maxpairs.h
+    _fields_ = [(name, ctypes.c_uint64) for name in
+                ("pairs", "run_suffixes", "runs", "segments", "max_pairs_of_one_suffix", "max_len",
+                 "walk_steps", "device_bytes")] + [("device_ms", ctypes.c_float)]
 
 
 # every symbol include/gtamd_esa.h, gtamd_encode.h and gtamd_pck.h declare:
@@ -232,6 +241,18 @@ MSTAT_ABI = {
     "gtamd_mstat_get_info": (_INT, [_P, ctypes.POINTER(MstatInfo)]),
 }
 
+# every symbol include/gtamd_maxpairs.h declares
+MAXPAIRS_ABI = {
+    "gtamd_maxpairs_create": (_P, [_INT]),
+    "gtamd_maxpairs_destroy": (None, [_P]),
+    "gtamd_maxpairs_set_index": (_INT, [_P, _P, _U64, _P, _U32, _P, _P, _U64]),
+    "gtamd_maxpairs_set_index_host": (_INT, [_P, _P, _U64, _P, _U32, _P, _P, _U64]),
+    "gtamd_maxpairs_set_index_esa": (_INT, [_P, _P, _P, _U64]),
+    "gtamd_maxpairs_prepare": (_INT, [_P, _U32, ctypes.POINTER(MaxPairsInfo)]),
+    "gtamd_maxpairs_emit": (_INT, [_P, ctypes.POINTER(_U64), _P, _U64, _INT, ctypes.POINTER(_U64)]),
+    "gtamd_maxpairs_get_info": (_INT, [_P, ctypes.POINTER(MaxPairsInfo)]),
+}
+
 _lib = None
 
 
@@ -254,7 +275,8 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()):
+        for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()) + \
+                list(MAXPAIRS_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -14,11 +14,17 @@
 
    And the first tools that ask an index a question: `gt matstat` and `gt
    uniquesub` with -esa INDEX (tool src/tools/gt_matstat.c), on the device
-   through include/gtamd_mstat.h. */
+   through include/gtamd_mstat.h.
+
+   And the tool that reads .suf and .lcp together: `gt repfind -l L -ii INDEX`
+   (tool src/tools/gt_repfind.c), the maximal exact repeats, on the device
+   through include/gtamd_maxpairs.h. */
 #include "gtamd_host.h"
 #include "gtamd_pck.h"
 #include "gtamd_check.h"
 #include "gtamd_mstat.h"
+#include "gtamd_maxpairs.h"
+#include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -649,4 +655,174 @@ int gtamd_matstat(int argc, const char **argv, char *err, size_t errlen)
 int gtamd_uniquesub(int argc, const char **argv, char *err, size_t errlen)
 {
   return greedy_forward_tool(0, argc, argv, err, errlen);
+}
+
+/* ---- gt repfind ----
+   Option handling of src/tools/gt_repfind.c:224-470, output of an exact match
+   as the reference displays it by default. */
+
+/* a table of the index that must be there: the reference's wording when it is not */
+static int map_required(const char *index, const char *suffix, mapped *m, char *path, size_t pathlen,
+                        char *err, size_t errlen)
+{
+  snprintf(path, pathlen, "%s%s", index, suffix);
+  if (access(path, R_OK) != 0) {
+    snprintf(err, errlen, "cannot open file \"%s\": %s", path, strerror(errno));
+    return -1;
+  }
+  return map_table(index, suffix, m, path, pathlen, err, errlen);
+}
+
+int gtamd_repfind(int argc, const char **argv, char *err, size_t errlen)
+{
+  /* other algorithms (queries against the index, seed extension) and other
+     displays: refused by name */
+  static const char *const refused[] = {
+    "-r", "-p", "-q", "-qii", "-spm", "-samples", "-maxfreq", "-seedlength", "-outfmt", "-evalue",
+    "-xdropbelow", "-err", "-minidentity", "-maxalilendiff", "-history", "-percmathistory", "-cam",
+    "-noxpolish", "-verify-alignment", "-trimstat", "-check_extend_symmetry", NULL };
+  const char *index = NULL;
+  int verbose = 0, rc = -1;
+  unsigned long long minlen = 20, readmode = 0, mirrored = 0;
+  char path[4096];
+  uint8_t *enc = NULL;
+  uint64_t n = 0, N, numseq = 1, *seqstart = NULL, capacity, cursor = 0, written = 0, total = 0;
+  uint32_t suf_bytes = 8;
+  mapped suf = { NULL, 0 }, lcp = { NULL, 0 }, llv = { NULL, 0 };
+  gtamd_maxpairs *mp = NULL;
+  gtamd_maxpairs_info info;
+  gtamd_maxpairs_record *rec = NULL;
+
+  for (int i = 1; i < argc; i++) {
+    const char *a = argv[i];
+    if (!strcmp(a, "-ii")) {
+      if (i + 1 >= argc) return pfail(err, errlen, "missing argument to option \"%s\"", a);
+      index = argv[++i];
+    } else if (!strcmp(a, "-l")) {
+      if (length_option(argc, argv, &i, &minlen, err, errlen) != 0) return -1;
+      if (minlen > 0xffffffffull) return pfail(err, errlen, "argument to option \"%s\" is out of range", a);
+    } else if (!strcmp(a, "-f") || !strcmp(a, "-scan")) {
+      if (i + 1 < argc && (!strcmp(argv[i + 1], "yes") || !strcmp(argv[i + 1], "no"))) {
+        if (a[1] == 'f' && argv[i + 1][0] == 'n')
+          return pfail(err, errlen, "option \"%s no\" leaves nothing to compute: forward repeats are all "
+                       "the MI355X engine enumerates", a);
+        i++;
+      }
+    } else if (!strcmp(a, "-v")) verbose = 1;
+    else if (!strcmp(a, "-help")) {
+      puts("Usage: gt-suffixerator-amd repfind -ii INDEX [-l L] [-f] [-scan] [-v]\n"
+           "Compute the maximal exact repeats (maximal pairs) of the sequences of INDEX on the device.\n\n"
+           "-ii    the index: INDEX.prj, .esq (.ssp), .suf, .lcp and .llv, as written by\n"
+           "       `suffixerator -suf -lcp -tis -ssp`, forward read mode, not mirrored\n"
+           "-l     minimum length of a repeat (default: 20)\n"
+           "-f     forward repeats (what is computed)\n"
+           "-scan  accepted, without effect\n"
+           "-v     figures of the enumeration as lines that start with '#'\n\n"
+           "One line per pair: `len seqnum1 relpos1 F len seqnum2 relpos2`, in TABLE ORDER: ascending\n"
+           "table index of the suffix that stands first in the suffix table, then of the other.  The\n"
+           "reference prints the same lines in the order of its traversal: compare sorted outputs.\n"
+           "Reverse, palindromic, query, seed extension and suffix-prefix options are refused.");
+      return 0;
+    } else {
+      for (int k = 0; refused[k] != NULL; k++)
+        if (!strcmp(a, refused[k]))
+          return pfail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
+      if (!strncmp(a, "-extend", 7))
+        return pfail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
+      if (a[0] == '-') return pfail(err, errlen, "unknown option: %s (try -help)", a);
+      return pfail(err, errlen, "superfluous arguments: \"%s\"", a);
+    }
+  }
+  if (index == NULL) return pfail(err, errlen, "option \"-%s\" is mandatory", "ii");
+
+  snprintf(path, sizeof path, "%s.prj", index);
+  (void) prj_value(path, "readmode", &readmode);
+  (void) prj_value(path, "mirrored", &mirrored);
+  if (readmode != 0)
+    return pfail(err, errlen, "file '%s' gives a read mode other than forward: such an index is not "
+                 "supported by the MI355X engine's repfind", path);
+  if (mirrored)
+    return pfail(err, errlen, "file '%s' describes a mirrored index: such an index is not supported by the "
+                 "MI355X engine's repfind", path);
+  if (load_project_sequence(index, "searched", &enc, &n, NULL, err, errlen) != 0) goto done;
+  N = n + 1;
+  if (map_required(index, ".suf", &suf, path, sizeof path, err, errlen) != 0) goto done;
+  if (suf.bytes == 4 * N) suf_bytes = 4;
+  else if (suf.bytes != 8 * N) {
+    snprintf(err, errlen, "file '%s' has %llu bytes, %llu (-suftabuint) or %llu expected for %llu entries",
+             path, (unsigned long long) suf.bytes, (unsigned long long) (4 * N),
+             (unsigned long long) (8 * N), (unsigned long long) N);
+    goto done;
+  }
+  if (map_required(index, ".lcp", &lcp, path, sizeof path, err, errlen) != 0) goto done;
+  if (lcp.bytes != N) {
+    snprintf(err, errlen, "file '%s' has %llu bytes, %llu expected", path, (unsigned long long) lcp.bytes,
+             (unsigned long long) N);
+    goto done;
+  }
+  if (map_required(index, ".llv", &llv, path, sizeof path, err, errlen) != 0) goto done;
+  if (llv.bytes % 16 != 0) {
+    snprintf(err, errlen, "file '%s' has %llu bytes, not a multiple of 16 (pairs of two 64-bit numbers)",
+             path, (unsigned long long) llv.bytes);
+    goto done;
+  }
+  /* where the sequences start: behind the separators (INDEX.ssp, as the reader of
+     INDEX.esq has put them into the symbols) */
+  for (uint64_t p = 0; p < n; p++) numseq += enc[p] == 255;
+  seqstart = malloc(numseq * sizeof *seqstart);
+  if (seqstart == NULL) { pfail(err, errlen, "out of memory (%s)", "sequence starts"); goto done; }
+  seqstart[0] = 0;
+  for (uint64_t p = 0, k = 1; p < n; p++)
+    if (enc[p] == 255) seqstart[k++] = p + 1;
+
+  if ((mp = gtamd_maxpairs_create(0)) == NULL ||
+      gtamd_maxpairs_set_index_host(mp, enc, n, suf.p, suf_bytes, lcp.p, llv.p, llv.bytes / 16) != 0 ||
+      gtamd_maxpairs_prepare(mp, (uint32_t) minlen, &info) != 0) {
+    snprintf(err, errlen, "%s", gtamd_esa_last_error());
+    goto done;
+  }
+  if (verbose)
+    printf("# %llu pairs, %llu suffixes in %llu runs, %llu segments, at most %llu pairs of one suffix, "
+           "longest %llu, %llu steps, %.3f ms on the device\n", (unsigned long long) info.pairs,
+           (unsigned long long) info.run_suffixes, (unsigned long long) info.runs,
+           (unsigned long long) info.segments, (unsigned long long) info.max_pairs_of_one_suffix,
+           (unsigned long long) info.max_len, (unsigned long long) info.walk_steps, info.device_ms);
+  capacity = info.max_pairs_of_one_suffix > (1u << 20) ? info.max_pairs_of_one_suffix : (1u << 20);
+  if (capacity > info.pairs) capacity = info.pairs;
+  rec = malloc((capacity ? capacity : 1) * sizeof *rec);
+  if (rec == NULL) { pfail(err, errlen, "out of memory (%s)", "records"); goto done; }
+  do {
+    if (gtamd_maxpairs_emit(mp, &cursor, rec, capacity, 0, &written) != 0) {
+      snprintf(err, errlen, "%s", gtamd_esa_last_error());
+      goto done;
+    }
+    for (uint64_t k = 0; k < written; k++) {
+      uint64_t s[2];
+      const uint64_t pos[2] = { rec[k].pos1, rec[k].pos2 };
+      for (int side = 0; side < 2; side++) {       /* the last start at or in front of the position */
+        uint64_t lo = 0, hi = numseq;
+        while (hi - lo > 1) {
+          const uint64_t mid = lo + (hi - lo) / 2;
+          if (seqstart[mid] <= pos[side]) lo = mid; else hi = mid;
+        }
+        s[side] = lo;
+      }
+      printf("%llu %llu %llu F %llu %llu %llu\n", (unsigned long long) rec[k].len, (unsigned long long) s[0],
+             (unsigned long long) (pos[0] - seqstart[s[0]]), (unsigned long long) rec[k].len,
+             (unsigned long long) s[1], (unsigned long long) (pos[1] - seqstart[s[1]]));
+    }
+    total += written;
+  } while (written != 0);
+  if (total != info.pairs) {
+    snprintf(err, errlen, "%llu pairs counted, %llu given", (unsigned long long) info.pairs,
+             (unsigned long long) total);
+    goto done;
+  }
+  if (fflush(stdout) != 0) { pfail(err, errlen, "cannot write to %s", "stdout"); goto done; }
+  rc = 0;
+done:
+  gtamd_maxpairs_destroy(mp);
+  unmap_file(&suf); unmap_file(&lcp); unmap_file(&llv);
+  free(rec); free(seqstart); free(enc);
+  return rc;
 }

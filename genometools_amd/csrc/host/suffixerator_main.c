@@ -3,7 +3,8 @@
    `gt-suffixerator-amd mergeesa ...` is `gt dev mergeesa ...`,
    `gt-suffixerator-amd packedindex mkindex|trsuftab ...` is `gt packedindex ...`,
    `gt-suffixerator-amd sfxmap ...` is `gt dev sfxmap ...`,
-   `gt-suffixerator-amd matstat|uniquesub ...` is `gt matstat|uniquesub ...` */
+   `gt-suffixerator-amd matstat|uniquesub ...` is `gt matstat|uniquesub ...`,
+   `gt-suffixerator-amd repfind ...` is `gt repfind ...` */
 #include <stdio.h>
 #include <string.h>
 #include "gtamd_host.h"
@@ -29,6 +30,13 @@ int main(int argc, char **argv)
     if ((argv[1][0] == 'm' ? gtamd_matstat : gtamd_uniquesub)(argc - 1, (const char **) argv + 1, err,
                                                              sizeof err) != 0) {
       fprintf(stderr, "gt %s: error: %s\n", argv[1], err);
+      return 1;
+    }
+    return 0;
+  }
+  if (argc > 1 && !strcmp(argv[1], "repfind")) {
+    if (gtamd_repfind(argc - 1, (const char **) argv + 1, err, sizeof err) != 0) {
+      fprintf(stderr, "gt repfind: error: %s\n", err);
       return 1;
     }
     return 0;

@@ -19,6 +19,8 @@
                             `gt matstat -esa` and `gt uniquesub -esa`
                             (src/tools/gt_matstat.c), on the device through
                             include/gtamd_mstat.h
+    gtamd_repfind           `gt repfind -l L -ii INDEX` (src/tools/gt_repfind.c),
+                            on the device through include/gtamd_maxpairs.h
 
   Pure C (gcc); links against libgtamd_esa.so for the hot path.
 */
@@ -317,6 +319,31 @@ int gtamd_sfxmap(int argc, const char **argv, char *err, size_t errlen);
    err (the caller prints "gt matstat: error: <err>" and exits 1). */
 int gtamd_matstat(int argc, const char **argv, char *err, size_t errlen);
 int gtamd_uniquesub(int argc, const char **argv, char *err, size_t errlen);
+
+/* `gt repfind -l L -ii INDEX` (tool function src/tools/gt_repfind.c): the
+   maximal exact repeats of the index's sequences, enumerated on the device from
+   .suf and .lcp together (semantics: include/gtamd_maxpairs.h).
+     -ii INDEX   reads INDEX.prj, INDEX.esq (+ .ssp), INDEX.suf (4- or 8-byte
+                 entries, by its size), INDEX.lcp and INDEX.llv, as written by
+                 `suffixerator -suf -lcp -tis -ssp`; a read mode other than
+                 forward and a mirrored index are refused
+     -l L        minimum length, default 20 (gt_repfind_arguments_check); >= 1
+     -f, -scan   accepted; -scan without effect
+     -v          the figures of gtamd_maxpairs_info as one line starting with '#'
+   Prints one line per pair, `len seqnum1 relpos1 F len seqnum2 relpos2` (the
+   reference's default display of an exact match; its two '#' header lines are
+   not printed), in TABLE ORDER: ascending table index of the suffix that stands
+   first in the table, then of the other.  The reference prints in the order of
+   its traversal; outputs are compared as sorted lines.
+   -r -p -q -qii -spm -samples -maxfreq -seedlength -extend* (and the options
+   those imply: -xdropbelow -err -minidentity -maxalilendiff -history
+   -percmathistory -cam -noxpolish -verify-alignment -trimstat) -outfmt -evalue
+   are refused ("option \"-X\" is not supported ..."): they are other
+   algorithms or other displays.  A missing INDEX.suf / .lcp gives the
+   reference's `cannot open file "INDEX.lcp": No such file or directory`.
+   Returns 0, or -1 with the message in err (the caller prints "gt repfind:
+   error: <err>" and exits 1). */
+int gtamd_repfind(int argc, const char **argv, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }
