@@ -53,3 +53,33 @@ __device__ __forceinline__ u32 block_scan_excl_sum(u32 v, u32 *total, u32 *lds4)
 __device__ __forceinline__ u32 block_scan_excl_max(u32 v, u32 *total, u32 *lds4) {
   return block_scan_excl<SCAN_MAX>(v, total, lds4);
 }
+
+// inclusive sum over the SC_THREADS values of a workgroup, 64 bits (s: SC_THREADS words)
+__device__ __forceinline__ u64 block_scan_incl_u64(u64 v, u64 *s) {
+  const u32 t = threadIdx.x;
+  s[t] = v;
+  __syncthreads();
+  for (u32 d = 1; d < SC_THREADS; d <<= 1) {
+    const u64 x = t >= d ? s[t - d] : 0;
+    __syncthreads();
+    s[t] += x;
+    __syncthreads();
+  }
+  const u64 r = s[t];
+  __syncthreads();
+  return r;
+}
+
+// one workgroup of SC_THREADS lanes: a[i] = sum of a[0..i), *total = the sum of all
+__device__ __forceinline__ void block_scan_excl_array_u64(u64 *a, u64 count, u64 *total, u64 *s) {
+  u64 carry = 0;
+  for (u64 base = 0; base < count; base += SC_THREADS) {
+    const u64 i = base + threadIdx.x;
+    const u64 v = i < count ? a[i] : 0;
+    const u64 incl = block_scan_incl_u64(v, s);
+    if (i < count) a[i] = carry + incl - v;
+    carry += s[SC_THREADS - 1];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *total = carry;
+}

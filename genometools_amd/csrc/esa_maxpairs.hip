@@ -22,7 +22,7 @@
 
 namespace {
 
-constexpr int MP_THREADS = 256;
+constexpr int MP_THREADS = SC_THREADS;          // (the block scans of esa_devutil.h)
 constexpr u32 MP_PER = 4;                         // consecutive items of one lane in a select pass
 constexpr u32 MP_TILE = MP_THREADS * MP_PER;      // items of one workgroup there
 constexpr u32 MP_WALK_TILE = MP_THREADS;          // entries of one workgroup in a walk: one a lane
@@ -164,35 +164,10 @@ __global__ __launch_bounds__(MP_THREADS) void k_mp_count(MpSegments g, const u8 
   }
 }
 
-// inclusive sum over the MP_THREADS values of a workgroup, 64 bits (s: MP_THREADS words)
-__device__ __forceinline__ u64 block_scan_incl_u64(u64 v, u64 *s) {
-  const u32 t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (u32 d = 1; d < MP_THREADS; d <<= 1) {
-    const u64 x = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += x;
-    __syncthreads();
-  }
-  const u64 r = s[t];
-  __syncthreads();
-  return r;
-}
-
 // one workgroup: a[i] = sum of a[0..i), *total = the sum of all
 __global__ __launch_bounds__(MP_THREADS) void k_mp_scan64(u64 *a, u64 count, u64 *total) {
   __shared__ u64 s[MP_THREADS];
-  u64 carry = 0;
-  for (u64 base = 0; base < count; base += MP_THREADS) {
-    const u64 i = base + threadIdx.x;
-    const u64 v = i < count ? a[i] : 0;
-    const u64 incl = block_scan_incl_u64(v, s);
-    if (i < count) a[i] = carry + incl - v;
-    carry += s[MP_THREADS - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = carry;
+  block_scan_excl_array_u64(a, count, total, s);
 }
 
 // off[k] = the records in front of entry k; off[M] = all

@@ -1,0 +1,469 @@
+// esa_qmatch.hip -- maximal exact matches of a query against .suf and the
+// sequence in device memory: `gt repfind -q`, `-r`, `-p` (C ABI, the semantics
+// and the algorithm: include/gtamd_qmatch.h).
+//
+//   a  k_qm_intervals     one lane per query position: the interval of the
+//                         suffixes that start with its L symbols
+//                         (esa_qmatch_core.h), the sum of the widths per tile
+//   b  k_qm_scan64, k_qm_offsets   64-bit exclusive scan of the widths
+//   c  k_qm_emit<false>   one lane per candidate of a chunk: the left-maximal
+//                         ones, counted per workgroup; scan (esa_prims)
+//      k_qm_emit<true>    the same lanes extend theirs to the right and write
+//                         the records, compacted in candidate order
+//
+// Every working array has m entries (or one per tile of positions or of
+// candidates of a chunk), none has N.
+#include "esa_common.h"
+#include "esa_own.h"
+#include "esa_prims.h"
+#include "esa_devutil.h"
+#include "esa_qmatch_core.h"
+#include "../../include/gtamd_qmatch.h"
+
+namespace {
+
+constexpr int QM_THREADS = SC_THREADS;
+constexpr u32 QM_TILE = QM_THREADS;               // query positions, or candidates, of one workgroup: one a lane
+constexpr u64 QM_MIN_CHUNK = 4 * QM_TILE;         // the smallest chunk of candidates, and capacity
+constexpr u64 QM_MAX_CHUNK = 1ull << 24;          // the largest: 65536 workgroups a launch
+constexpr u64 QM_MAX_ENTRIES = (1ull << 32) - 4096;   // single-build limit of esa_engine.hip
+constexpr u64 QM_MAX_QUERY = (1ull << 32) - 1;
+constexpr u64 UPLOAD_PIECE = 64ull << 20;
+
+enum { W_CANDIDATES = 0, W_SEEDS, W_MAXWIDTH, W_SEARCH, W_EXTENSION, W_WORDS };
+
+// what the lanes of steps a and c are given
+template <typename S> struct QmInput {
+  const u8 *enc; u64 n; const S *suf;
+  const u8 *q; u64 m;
+  u32 L;
+};
+
+// ---- step a ----------------------------------------------------------------------
+template <typename S>
+__global__ __launch_bounds__(QM_THREADS) void k_qm_intervals(QmInput<S> in, u32 *lo, u32 *width, u64 *tsum, u64 *w) {
+  __shared__ unsigned long long ssum, ssearch;
+  __shared__ u32 sseeds, smax;
+  if (threadIdx.x == 0) { ssum = 0; ssearch = 0; sseeds = 0; smax = 0; }
+  __syncthreads();
+  const u64 i = (u64) blockIdx.x * QM_TILE + threadIdx.x;
+  if (i < in.m) {
+    Lane c = { in.q, in.m, i, in.enc, in.n, 0 };
+    u32 l, wd;
+    qm_interval(c, in.suf, in.n + 1, in.L, &l, &wd);
+    lo[i] = l;
+    width[i] = wd;
+    if (wd) { atomicAdd(&ssum, (unsigned long long) wd); atomicAdd(&sseeds, 1u); atomicMax(&smax, wd); }
+    if (c.compared) atomicAdd(&ssearch, (unsigned long long) c.compared);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    tsum[blockIdx.x] = ssum;
+    if (sseeds) {
+      atomicAdd((unsigned long long *) &w[W_SEEDS], (unsigned long long) sseeds);
+      atomicMax((unsigned long long *) &w[W_MAXWIDTH], (unsigned long long) smax);
+    }
+    if (ssearch) atomicAdd((unsigned long long *) &w[W_SEARCH], ssearch);
+  }
+}
+
+// ---- step b ----------------------------------------------------------------------
+// one workgroup: a[i] = sum of a[0..i), *total = the sum of all
+__global__ __launch_bounds__(QM_THREADS) void k_qm_scan64(u64 *a, u64 count, u64 *total) {
+  __shared__ u64 s[QM_THREADS];
+  block_scan_excl_array_u64(a, count, total, s);
+}
+
+// off[i] = the candidates in front of position i; off[m] = all
+__global__ __launch_bounds__(QM_THREADS) void k_qm_offsets(const u32 *width, const u64 *tsum, u64 m, u64 *off) {
+  __shared__ u64 s[QM_THREADS];
+  const u64 i = (u64) blockIdx.x * QM_TILE + threadIdx.x;
+  const u64 v = i < m ? width[i] : 0;
+  const u64 incl = block_scan_incl_u64(v, s) + tsum[blockIdx.x];
+  if (i < m) {
+    off[i] = incl - v;
+    if (i + 1 == m) off[m] = incl;
+  }
+}
+
+// ---- step c ----------------------------------------------------------------------
+// the last position of [a, b) whose first candidate is not behind candidate g;
+// off[a] <= g, and off[b] is not read
+__device__ __forceinline__ u64 position_of(const u64 *off, u64 a, u64 b, u64 g) {
+  while (b - a > 1) {
+    const u64 mid = a + (b - a) / 2;
+    if (off[mid] <= g) a = mid; else b = mid;
+  }
+  return a;
+}
+
+// Candidates [c0, c1) of all off[m], QM_TILE a workgroup.  WRITE false:
+// tiles[b] = the number of left-maximal candidates of workgroup b.  WRITE true:
+// tiles[b] is where their records go in out, in candidate order.
+template <typename S, bool WRITE>
+__global__ __launch_bounds__(QM_THREADS) void k_qm_emit(QmInput<S> in, const u32 *lo, const u64 *off, u64 c0, u64 c1,
+                                                        u32 *tiles, QmRecord *out, u64 *w) {
+  __shared__ u64 span[2];                 // the positions of the workgroup's first and last candidate
+  __shared__ u32 wave_kept[QM_THREADS / 64];
+  __shared__ unsigned long long sext;
+  const u64 first = c0 + (u64) blockIdx.x * QM_TILE;
+  const u64 last = (c1 - first < QM_TILE ? c1 : first + QM_TILE) - 1;
+  if (threadIdx.x < 2) span[threadIdx.x] = position_of(off, 0, in.m, threadIdx.x == 0 ? first : last);
+  if (threadIdx.x == 0) sext = 0;
+  __syncthreads();
+  const u64 g = first + threadIdx.x;
+  bool keep = false;
+  QmRecord rec = { 0, 0, 0 };
+  if (g <= last) {
+    const u64 i = position_of(off, span[0], span[1] + 1, g);
+    Lane c = { in.q, in.m, i, in.enc, in.n, 0 };
+    u64 p;
+    keep = qm_kept(c, in.suf, lo[i], (u32) (g - off[i]), &p);
+    if (WRITE && keep) {
+      qm_extend(c, p, in.L, &rec);
+      atomicAdd(&sext, (unsigned long long) c.compared);
+    }
+  }
+  // the kept candidates in front of this one: in its wave, in the waves before
+  const u64 mask = __ballot(keep);
+  const u32 before = __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
+  const u32 wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) wave_kept[wave] = (u32) __popcll(mask);
+  __syncthreads();
+  u32 base = 0, total = 0;
+#pragma unroll
+  for (u32 k = 0; k < QM_THREADS / 64; k++) {
+    const u32 v = wave_kept[k];
+    if (k < wave) base += v;
+    total += v;
+  }
+  if (!WRITE) {
+    if (threadIdx.x == 0) tiles[blockIdx.x] = total;
+    return;
+  }
+  if (keep) out[(u64) tiles[blockIdx.x] + base + before] = rec;
+  if (threadIdx.x == 0 && sext) atomicAdd((unsigned long long *) &w[W_EXTENSION], sext);
+}
+
+}  // namespace
+
+struct gtamd_qmatch {
+  int device = 0;
+  Stream st;             // (before the buffers: they go first)
+  Event ev[2];
+  Dev<u8> own_enc, own_suf;       // an index set from host memory
+  const u8 *enc = nullptr;        // the index: the caller's, an engine's or the two above
+  const void *suf = nullptr;
+  u64 n = 0;
+  u32 suf_bytes = 0;
+  bool have_index = false, prepared = false;
+  // what a prepare leaves for the emit calls
+  Dev<u8> own_query;
+  const u8 *q = nullptr;
+  u64 m = 0;
+  u32 L = 0;
+  Dev<u32> lo, width, tiles, scanws;
+  Dev<u64> tsum, off, words;
+  Dev<u8> out;                    // records on their way to host memory
+  gtamd_qmatch_info info = gtamd_qmatch_info();
+};
+
+namespace {
+
+void drop_index(gtamd_qmatch *qm) {
+  qm->have_index = qm->prepared = false;
+  qm->own_enc.reset();
+  qm->own_suf.reset();
+  qm->enc = nullptr;
+  qm->suf = nullptr;
+}
+
+// what every way of setting an index refuses, before anything is touched
+int index_arguments(const gtamd_qmatch *qm, const void *enc, u64 n, const void *suf, u32 suf_bytes) {
+  if (qm == nullptr || suf == nullptr || (enc == nullptr && n)) {
+    gtamd_set_error("invalid argument to gtamd_qmatch_set_index");
+    return -1;
+  }
+  if (suf_bytes != 4 && suf_bytes != 8) {
+    gtamd_set_error("query matches: .suf entries of %u bytes, 4 or 8 expected", suf_bytes);
+    return -1;
+  }
+  if (n >= QM_MAX_ENTRIES) {
+    gtamd_set_error("query matches: sequence of %llu symbols is beyond the limit of a single build "
+                    "(%llu table entries); the slices of a build in parts are not searched",
+                    (unsigned long long) n, (unsigned long long) QM_MAX_ENTRIES);
+    return -1;
+  }
+  return 0;
+}
+
+void take_index(gtamd_qmatch *qm, const u8 *enc, u64 n, const void *suf, u32 suf_bytes) {
+  qm->enc = enc;
+  qm->n = n;
+  qm->suf = suf;
+  qm->suf_bytes = suf_bytes;
+  qm->have_index = true;
+  qm->prepared = false;
+}
+
+// host memory -> a device buffer of its own, piece by piece
+int upload(Dev<u8> &d, const void *src, u64 bytes, const char *what) {
+  if (d.alloc(bytes ? bytes : 1) != hipSuccess) {
+    gtamd_set_error("query matches: cannot allocate %llu bytes of device memory for %s",
+                    (unsigned long long) bytes, what);
+    return -1;
+  }
+  for (u64 off = 0; off < bytes; off += UPLOAD_PIECE) {
+    const u64 cnt = bytes - off < UPLOAD_PIECE ? bytes - off : UPLOAD_PIECE;
+    HIP_TRY(hipMemcpy((u8 *) d.p + off, (const u8 *) src + off, cnt, hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+
+u64 held_bytes(const gtamd_qmatch *qm) {
+  return qm->own_enc.bytes + qm->own_suf.bytes + qm->own_query.bytes + qm->lo.bytes + qm->width.bytes +
+         qm->tiles.bytes + qm->scanws.bytes + qm->tsum.bytes + qm->off.bytes + qm->words.bytes + qm->out.bytes;
+}
+
+int out_of_memory(u64 entries, const char *of) {
+  gtamd_set_error("query matches: cannot allocate device memory for %llu %s", (unsigned long long) entries, of);
+  return -1;
+}
+
+template <typename S> QmInput<S> input(const gtamd_qmatch *qm) {
+  return QmInput<S>{ qm->enc, qm->n, (const S *) qm->suf, qm->q, qm->m, qm->L };
+}
+
+template <typename S> int prepare(gtamd_qmatch *qm) {
+  hipStream_t st = qm->st;
+  const u64 m = qm->m, T = div_up(m, QM_TILE);
+  HIP_TRY(hipMemsetAsync(qm->words, 0, W_WORDS * sizeof(u64), st));
+  HIP_TRY(hipEventRecord(qm->ev[0], st));
+  if (m != 0) {
+    k_qm_intervals<S><<<(u32) T, QM_THREADS, 0, st>>>(input<S>(qm), qm->lo, qm->width, qm->tsum, qm->words);
+    HIP_TRY(hipGetLastError());
+    k_qm_scan64<<<1, QM_THREADS, 0, st>>>(qm->tsum, T, qm->words + W_CANDIDATES);
+    HIP_TRY(hipGetLastError());
+    k_qm_offsets<<<(u32) T, QM_THREADS, 0, st>>>(qm->width, qm->tsum, m, qm->off);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(qm->ev[1], st));
+  u64 h[W_WORDS];
+  HIP_TRY(hipMemcpyAsync(h, qm->words, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipEventElapsedTime(&qm->info.device_ms, qm->ev[0], qm->ev[1]));
+  qm->info.positions = m;
+  qm->info.seeds = h[W_SEEDS];
+  qm->info.candidates = h[W_CANDIDATES];
+  qm->info.max_width = h[W_MAXWIDTH];
+  qm->info.search_symbols = h[W_SEARCH];
+  return 0;
+}
+
+// one chunk: candidates [c0, c1) -> *kept records at dst
+template <typename S> int emit_chunk(gtamd_qmatch *qm, u64 c0, u64 c1, QmRecord *dst, u64 *kept, u64 *extension) {
+  hipStream_t st = qm->st;
+  const u64 blocks = div_up(c1 - c0, QM_TILE);
+  if (qm->tiles.grow((blocks + 1) * sizeof(u32)) != hipSuccess ||
+      qm->scanws.grow(scan_workspace_words(blocks + 1) * sizeof(u32)) != hipSuccess)
+    return out_of_memory(blocks + 1, "tiles of candidates");
+  HIP_TRY(hipMemsetAsync(qm->tiles, 0, (blocks + 1) * sizeof(u32), st));
+  k_qm_emit<S, false><<<(u32) blocks, QM_THREADS, 0, st>>>(input<S>(qm), qm->lo, qm->off, c0, c1, qm->tiles, nullptr,
+                                                           qm->words);
+  HIP_TRY(hipGetLastError());
+  TRY(scan_u32(SCAN_SUM, qm->tiles, qm->tiles, blocks + 1, false, qm->scanws, st));
+  k_qm_emit<S, true><<<(u32) blocks, QM_THREADS, 0, st>>>(input<S>(qm), qm->lo, qm->off, c0, c1, qm->tiles, dst,
+                                                          qm->words);
+  HIP_TRY(hipGetLastError());
+  u32 total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, qm->tiles + blocks, sizeof total, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(extension, qm->words + W_EXTENSION, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *kept = total;
+  return 0;
+}
+
+int emit(gtamd_qmatch *qm, u64 *cursor, gtamd_qmatch_record *out, u64 capacity, int out_on_device, u64 *written) {
+  *written = 0;
+  const u64 C = qm->info.candidates;
+  u64 cur = *cursor, total = 0;
+  if (cur > C) {
+    gtamd_set_error("query matches: cursor %llu is not one of this enumeration (%llu candidates)",
+                    (unsigned long long) cur, (unsigned long long) C);
+    return -1;
+  }
+  if (capacity < QM_MIN_CHUNK) {
+    gtamd_set_error("query matches: a capacity of %llu records is too small: a capacity of at least %llu is needed",
+                    (unsigned long long) capacity, (unsigned long long) QM_MIN_CHUNK);
+    return -1;
+  }
+  if (cur == C) return 0;
+  QmRecord *dst = (QmRecord *) out;
+  if (!out_on_device) {
+    const u64 most = capacity < C - cur ? capacity : C - cur;
+    if (qm->out.grow(most * sizeof(QmRecord)) != hipSuccess) return out_of_memory(most, "records");
+    dst = (QmRecord *) qm->out.p;
+  }
+  // a chunk of `room` candidates gives at most `room` records
+  while (cur < C && capacity - total >= QM_MIN_CHUNK) {
+    u64 chunk = capacity - total, kept = 0;
+    if (chunk > C - cur) chunk = C - cur;
+    if (chunk > QM_MAX_CHUNK) chunk = QM_MAX_CHUNK;
+    TRY(qm->suf_bytes == 4 ? emit_chunk<u32>(qm, cur, cur + chunk, dst + total, &kept, &qm->info.extension_symbols)
+                           : emit_chunk<u64>(qm, cur, cur + chunk, dst + total, &kept, &qm->info.extension_symbols));
+    total += kept;
+    cur += chunk;
+  }
+  if (!out_on_device && total) {
+    HIP_TRY(hipMemcpyAsync(out, dst, total * sizeof(QmRecord), hipMemcpyDeviceToHost, qm->st));
+    HIP_TRY(hipStreamSynchronize(qm->st));
+  }
+  qm->info.matches += total;
+  *cursor = cur;
+  *written = total;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" gtamd_qmatch *gtamd_qmatch_create(int device) {
+  GTAMD_ABI_BEGIN
+  if (gtamd_device_count() <= device || device < 0) {
+    gtamd_set_error("no HIP device %d available (this library has no CPU fallback)", device);
+    return nullptr;
+  }
+  if (hipSetDevice(device) != hipSuccess) { gtamd_set_error("hipSetDevice(%d) failed", device); return nullptr; }
+  gtamd_qmatch *qm = new gtamd_qmatch();
+  qm->device = device;
+  if (create(qm->st) != hipSuccess || create(qm->ev[0]) != hipSuccess || create(qm->ev[1]) != hipSuccess ||
+      qm->words.alloc(W_WORDS * sizeof(u64)) != hipSuccess) {
+    gtamd_set_error("cannot create the query matcher on device %d", device);
+    delete qm;
+    return nullptr;
+  }
+  return qm;
+  GTAMD_ABI_END(nullptr)
+}
+
+extern "C" void gtamd_qmatch_destroy(gtamd_qmatch *qm) {
+  if (qm == nullptr) return;
+  (void) hipSetDevice(qm->device);
+  (void) hipStreamSynchronize(qm->st);
+  delete qm;
+}
+
+extern "C" void gtamd_qmatch_geometry(uint32_t *tile_positions, uint64_t *min_capacity) {
+  if (tile_positions != nullptr) *tile_positions = QM_TILE;
+  if (min_capacity != nullptr) *min_capacity = QM_MIN_CHUNK;
+}
+
+extern "C" int gtamd_qmatch_set_index(gtamd_qmatch *qm, const uint8_t *enc, uint64_t n, const void *suf,
+                                      uint32_t suf_bytes) {
+  GTAMD_ABI_BEGIN
+  TRY(index_arguments(qm, enc, n, suf, suf_bytes));
+  HIP_TRY(hipSetDevice(qm->device));
+  drop_index(qm);
+  take_index(qm, enc, n, suf, suf_bytes);
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_qmatch_set_index_host(gtamd_qmatch *qm, const uint8_t *enc, uint64_t n, const void *suf,
+                                           uint32_t suf_bytes) {
+  GTAMD_ABI_BEGIN
+  TRY(index_arguments(qm, enc, n, suf, suf_bytes));
+  HIP_TRY(hipSetDevice(qm->device));
+  drop_index(qm);
+  TRY(upload(qm->own_enc, enc, n, "the sequence"));
+  TRY(upload(qm->own_suf, suf, (n + 1) * suf_bytes, "the .suf table"));
+  take_index(qm, qm->own_enc, n, qm->own_suf.p, suf_bytes);
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_qmatch_set_index_esa(gtamd_qmatch *qm, const gtamd_esa_ctx *esa, const uint8_t *enc,
+                                          uint64_t n) {
+  GTAMD_ABI_BEGIN
+  if (qm == nullptr || esa == nullptr) { gtamd_set_error("invalid argument to gtamd_qmatch_set_index_esa"); return -1; }
+  const void *suf = gtamd_esa_table_device(esa, GTAMD_TAB_SUF);
+  if (suf == nullptr) { gtamd_set_error("query matches: the last run did not produce the .suf table"); return -1; }
+  if (gtamd_esa_table_offset(esa) != 0 || gtamd_esa_table_entries(esa, GTAMD_TAB_SUF) != n + 1) {
+    gtamd_set_error("query matches: the context holds %llu entries from table index %llu on, not the "
+                    "whole table of %llu symbols; the slices of a build in parts are not searched",
+                    (unsigned long long) gtamd_esa_table_entries(esa, GTAMD_TAB_SUF),
+                    (unsigned long long) gtamd_esa_table_offset(esa), (unsigned long long) n);
+    return -1;
+  }
+  TRY(index_arguments(qm, enc, n, suf, 8));
+  HIP_TRY(hipSetDevice(qm->device));
+  drop_index(qm);
+  take_index(qm, enc, n, suf, 8);
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_qmatch_prepare(gtamd_qmatch *qm, const uint8_t *query, uint64_t m, int is_device,
+                                    uint32_t min_len, gtamd_qmatch_info *info) {
+  GTAMD_ABI_BEGIN
+  if (qm == nullptr || (query == nullptr && m)) { gtamd_set_error("invalid argument to gtamd_qmatch_prepare"); return -1; }
+  if (!qm->have_index) {
+    gtamd_set_error("query matches: no index is set (gtamd_qmatch_set_index)");
+    return -1;
+  }
+  if (min_len == 0) {
+    gtamd_set_error("query matches: a minimum length of 0 is refused, 1 or more expected");
+    return -1;
+  }
+  if (m > QM_MAX_QUERY) {
+    gtamd_set_error("query matches: query of %llu symbols, at most %llu in one call", (unsigned long long) m,
+                    (unsigned long long) QM_MAX_QUERY);
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(qm->device));
+  qm->prepared = false;
+  qm->info = gtamd_qmatch_info();
+  const u64 T = div_up(m, QM_TILE);
+  if ((!is_device && qm->own_query.grow(m ? m : 1) != hipSuccess) || qm->lo.grow((m ? m : 1) * 4) != hipSuccess ||
+      qm->width.grow((m ? m : 1) * 4) != hipSuccess || qm->off.grow((m + 1) * 8) != hipSuccess ||
+      qm->tsum.grow((T ? T : 1) * 8) != hipSuccess)
+    return out_of_memory(m, "query positions");
+  qm->q = query;
+  if (!is_device) {
+    if (m) HIP_TRY(hipMemcpyAsync(qm->own_query, query, m, hipMemcpyHostToDevice, qm->st));
+    qm->q = qm->own_query;
+  }
+  qm->m = m;
+  qm->L = min_len;
+  TRY(qm->suf_bytes == 4 ? prepare<u32>(qm) : prepare<u64>(qm));
+  qm->info.device_bytes = held_bytes(qm);
+  qm->prepared = true;
+  if (info != nullptr) *info = qm->info;
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_qmatch_emit(gtamd_qmatch *qm, uint64_t *cursor, gtamd_qmatch_record *out, uint64_t capacity,
+                                 int out_on_device, uint64_t *written) {
+  GTAMD_ABI_BEGIN
+  if (qm == nullptr || cursor == nullptr || written == nullptr || (out == nullptr && capacity)) {
+    gtamd_set_error("invalid argument to gtamd_qmatch_emit");
+    return -1;
+  }
+  if (!qm->prepared) {
+    gtamd_set_error("query matches: nothing is prepared (gtamd_qmatch_prepare)");
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(qm->device));
+  TRY(emit(qm, cursor, out, capacity, out_on_device, written));
+  qm->info.device_bytes = held_bytes(qm);
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_qmatch_get_info(const gtamd_qmatch *qm, gtamd_qmatch_info *info) {
+  GTAMD_ABI_BEGIN
+  if (qm == nullptr || info == nullptr) { gtamd_set_error("invalid argument to gtamd_qmatch_get_info"); return -1; }
+  *info = qm->info;
+  return 0;
+  GTAMD_ABI_END(-1)
+}

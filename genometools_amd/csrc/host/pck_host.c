@@ -24,6 +24,7 @@
 #include "gtamd_check.h"
 #include "gtamd_mstat.h"
 #include "gtamd_maxpairs.h"
+#include "gtamd_qmatch.h"
 #include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
@@ -824,5 +825,239 @@ done:
   gtamd_maxpairs_destroy(mp);
   unmap_file(&suf); unmap_file(&lcp); unmap_file(&llv);
   free(rec); free(seqstart); free(enc);
+  return rc;
+}
+
+/* ---- gt repfind -q / -r / -p ----
+   Option handling of src/tools/gt_repfind.c:224-470, the calls it sends to
+   gt_callenumquerymatches (:562-757); display and the `ordered` filter of
+   src/match/querymatch.c:202-213, 357-369. */
+
+/* the last of the numstart ascending starts at or in front of pos */
+static uint64_t unit_of(const uint64_t *start, uint64_t numstart, uint64_t pos)
+{
+  uint64_t lo = 0, hi = numstart;
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (start[mid] <= pos) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+/* where the sequences of seq[0..len) start: behind the separators; *num = their number */
+static uint64_t *sequence_starts(const uint8_t *seq, uint64_t len, uint64_t *num)
+{
+  uint64_t count = 1, *start;
+  for (uint64_t p = 0; p < len; p++) count += seq[p] == 255;
+  start = malloc((count + 1) * sizeof *start);
+  if (start == NULL) return NULL;
+  start[0] = 0;
+  for (uint64_t p = 0, k = 1; p < len; p++)
+    if (seq[p] == 255) start[k++] = p + 1;
+  start[count] = len + 1;              /* (as if one more separator followed) */
+  *num = count;
+  return start;
+}
+
+/* gt_mmsearch_accessquery: mode 1 reverses every sequence on its own, mode 2
+   complements its letters in addition */
+static void transform_query(uint8_t *out, const uint8_t *query, const uint64_t *start, uint64_t numunits, int mode)
+{
+  for (uint64_t u = 0; u < numunits; u++) {
+    const uint64_t s = start[u], len = start[u + 1] - 1 - s;
+    for (uint64_t k = 0; k < len; k++) {
+      const uint8_t c = query[s + (mode ? len - 1 - k : k)];
+      out[s + k] = mode == 2 && c < 254 ? (uint8_t) (3 - c) : c;
+    }
+    if (u + 1 < numunits) out[s + len] = 255;
+  }
+}
+
+#define QUERYMATCH_CALL_LIMIT 0xffffffffull      /* symbols of one gtamd_qmatch_prepare */
+#define QUERYMATCH_CAPACITY (1u << 20)           /* records of one gtamd_qmatch_emit */
+
+int gtamd_querymatch(int argc, const char **argv, char *err, size_t errlen)
+{
+  /* a query from an index, seed extension, other displays: refused by name */
+  static const char *const refused[] = {
+    "-qii", "-scan", "-spm", "-samples", "-maxfreq", "-seedlength", "-outfmt", "-evalue", "-xdropbelow", "-err",
+    "-minidentity", "-maxalilendiff", "-history", "-percmathistory", "-cam", "-noxpolish",
+    "-verify-alignment", "-trimstat", "-check_extend_symmetry", NULL };
+  static const char modechar[3] = { 'F', 'R', 'P' };
+  const char *index = NULL, *const *queries = NULL;
+  size_t numqueries = 0;
+  int mode_on[3] = { 0, 0, 0 }, f_given = 0, have_q = 0, verbose = 0, have_alpha = 0, rc = -1;
+  unsigned long long minlen = 20, readmode = 0, mirrored = 0;
+  char path[4096];
+  uint8_t *enc = NULL, *query_own = NULL, *tq = NULL;
+  const uint8_t *query;
+  uint64_t n = 0, m = 0, N, numseq = 0, numunits = 0, *seqstart = NULL, *unitstart = NULL, desclen = 0;
+  char *desc = NULL;
+  uint32_t suf_bytes = 8;
+  mapped suf = { NULL, 0 };
+  gtamd_alphabet alpha;
+  gtamd_qmatch *qm = NULL;
+  gtamd_qmatch_info info;
+  gtamd_qmatch_record *rec = NULL;
+
+  for (int i = 1; i < argc; i++) {
+    const char *a = argv[i];
+    if (!strcmp(a, "-ii")) {
+      if (i + 1 >= argc) return pfail(err, errlen, "missing argument to option \"%s\"", a);
+      index = argv[++i];
+    } else if (!strcmp(a, "-l")) {
+      if (length_option(argc, argv, &i, &minlen, err, errlen) != 0) return -1;
+      if (minlen > 0xffffffffull) return pfail(err, errlen, "argument to option \"%s\" is out of range", a);
+    } else if (!strcmp(a, "-f") || !strcmp(a, "-r") || !strcmp(a, "-p")) {
+      const int k = a[1] == 'f' ? 0 : a[1] == 'r' ? 1 : 2;
+      mode_on[k] = 1;
+      if (i + 1 < argc && (!strcmp(argv[i + 1], "yes") || !strcmp(argv[i + 1], "no")))
+        mode_on[k] = argv[++i][0] == 'y';
+      if (k == 0) f_given = 1;
+    } else if (!strcmp(a, "-q")) {
+      have_q = 1;
+      queries = argv + i + 1;
+      for (numqueries = 0; i + 1 < argc && argv[i + 1][0] != '-'; i++) numqueries++;
+      if (numqueries == 0) return pfail(err, errlen, "missing argument to option \"%s\"", a);
+    } else if (!strcmp(a, "-v")) verbose = 1;
+    else if (!strcmp(a, "-help")) {
+      puts("Usage: gt-suffixerator-amd querymatch -ii INDEX [-l L] [-f] [-r] [-p] [-q FILE...] [-v]\n"
+           "Compute the maximal exact matches of query sequences against the sequences of INDEX on the\n"
+           "device: what `gt repfind` computes with -q, -r or -p.\n\n"
+           "-ii    the index: INDEX.prj, .esq (.ssp) and .suf, as written by `suffixerator -suf -tis -ssp`,\n"
+           "       forward read mode, not mirrored\n"
+           "-l     minimum length of a match (default: 20)\n"
+           "-q     FASTA files with the queries, read with the alphabet of INDEX; their sequences are\n"
+           "       numbered across all files.  Without -q the sequences of INDEX are the queries of -r and\n"
+           "       -p, and of two records that show the same pair only one is kept\n"
+           "-f     forward matches (the default, unless -r or -p is given without -f); needs -q: the\n"
+           "       forward repeats of an index are the business of the repfind sub-command\n"
+           "-r     reverse matches: every query sequence is read backwards\n"
+           "-p     reverse-complement matches (DNA only)\n"
+           "-v     figures of every search as lines that start with '#'\n\n"
+           "One line per match: `len dbseqnum dbrelpos F|R|P len querynum querystart`, querystart on the\n"
+           "forward strand of the query, in the reference's order: the modes f, r, p one after the other,\n"
+           "in each ascending query number and offset (of the query as read), then ascending table index\n"
+           "of the subject suffix.  -qii, -scan, seed extension, -spm and the display options are refused.");
+      return 0;
+    } else {
+      for (int k = 0; refused[k] != NULL; k++)
+        if (!strcmp(a, refused[k]))
+          return pfail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
+      if (!strncmp(a, "-extend", 7))
+        return pfail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
+      if (a[0] == '-') return pfail(err, errlen, "unknown option: %s (try -help)", a);
+      return pfail(err, errlen, "superfluous arguments: \"%s\"", a);
+    }
+  }
+  if (index == NULL) return pfail(err, errlen, "option \"-%s\" is mandatory", "ii");
+  /* gt_repfind_arguments_check: forward unless -r or -p is given without -f */
+  if (!f_given) mode_on[0] = !(mode_on[1] || mode_on[2]);
+  if (!have_q && mode_on[0])
+    return pfail(err, errlen, "forward matches of the index with itself are its maximal repeats: use the "
+                 "%s sub-command for them (querymatch takes -q FILE..., -r or -p)", "repfind");
+  if (!(mode_on[0] || mode_on[1] || mode_on[2]))
+    return pfail(err, errlen, "none of the options -f, -r and -p is %s", "set");
+
+  snprintf(path, sizeof path, "%s.prj", index);
+  (void) prj_value(path, "readmode", &readmode);
+  (void) prj_value(path, "mirrored", &mirrored);
+  if (readmode != 0)
+    return pfail(err, errlen, "file '%s' gives a read mode other than forward: such an index is not "
+                 "supported by the MI355X engine's querymatch", path);
+  if (mirrored)
+    return pfail(err, errlen, "file '%s' describes a mirrored index: such an index is not supported by the "
+                 "MI355X engine's querymatch", path);
+  if (load_project_sequence(index, "searched", &enc, &n, &alpha, err, errlen) != 0) goto done;
+  have_alpha = 1;
+  if (mode_on[2] && !(alpha.numofchars == 4 && alpha.symbolmap['a'] == 0 && alpha.symbolmap['c'] == 1 &&
+                      alpha.symbolmap['g'] == 2 && alpha.symbolmap['t'] == 3)) {
+    pfail(err, errlen, "option \"%s\" needs a DNA alphabet: the index has none, and its letters have no "
+          "complement", "-p");
+    goto done;
+  }
+  N = n + 1;
+  if (map_required(index, ".suf", &suf, path, sizeof path, err, errlen) != 0) goto done;
+  if (suf.bytes == 4 * N) suf_bytes = 4;
+  else if (suf.bytes != 8 * N) {
+    snprintf(err, errlen, "file '%s' has %llu bytes, %llu (-suftabuint) or %llu expected for %llu entries",
+             path, (unsigned long long) suf.bytes, (unsigned long long) (4 * N),
+             (unsigned long long) (8 * N), (unsigned long long) N);
+    goto done;
+  }
+  /* the queries, with the index's alphabet: one sequence of symbols, a separator
+     between two units; without -q the index's own */
+  query = enc;
+  m = n;
+  if (have_q) {
+    if (gtamd_encode_files_alpha(queries, numqueries, &alpha, &query_own, &m, &desc, &desclen, NULL, err,
+                                 errlen) != 0)
+      goto done;
+    query = query_own;
+  }
+  seqstart = sequence_starts(enc, n, &numseq);
+  unitstart = sequence_starts(query, m, &numunits);
+  tq = malloc(m ? m : 1);
+  rec = malloc(QUERYMATCH_CAPACITY * sizeof *rec);
+  if (seqstart == NULL || unitstart == NULL || tq == NULL || rec == NULL) {
+    pfail(err, errlen, "out of memory (%s)", "queries and records");
+    goto done;
+  }
+  if ((qm = gtamd_qmatch_create(0)) == NULL || gtamd_qmatch_set_index_host(qm, enc, n, suf.p, suf_bytes) != 0) {
+    snprintf(err, errlen, "%s", gtamd_esa_last_error());
+    goto done;
+  }
+  for (int mode = 0; mode < 3; mode++) {
+    if (!mode_on[mode]) continue;
+    transform_query(tq, query, unitstart, numunits, mode);
+    /* one call per run of whole units that fits its limit */
+    for (uint64_t a = 0, b; a < numunits; a = b) {
+      uint64_t cursor = 0, written = 0, first = unitstart[a], len;
+      for (b = a + 1; b < numunits && unitstart[b + 1] - 1 - first <= QUERYMATCH_CALL_LIMIT; b++) ;
+      len = unitstart[b] - 1 - first;
+      if (len > QUERYMATCH_CALL_LIMIT) {
+        snprintf(err, errlen, "query sequence %llu has %llu symbols, at most %llu in one search",
+                 (unsigned long long) a, (unsigned long long) len, QUERYMATCH_CALL_LIMIT);
+        goto done;
+      }
+      if (gtamd_qmatch_prepare(qm, tq + first, len, 0, (uint32_t) minlen, &info) != 0) {
+        snprintf(err, errlen, "%s", gtamd_esa_last_error());
+        goto done;
+      }
+      if (verbose)
+        printf("# %c: %llu positions, %llu seeds, %llu candidates, widest interval %llu, %llu symbols "
+               "compared by the searches, %.3f ms on the device\n", modechar[mode],
+               (unsigned long long) info.positions, (unsigned long long) info.seeds,
+               (unsigned long long) info.candidates, (unsigned long long) info.max_width,
+               (unsigned long long) info.search_symbols, info.device_ms);
+      do {
+        if (gtamd_qmatch_emit(qm, &cursor, rec, QUERYMATCH_CAPACITY, 0, &written) != 0) {
+          snprintf(err, errlen, "%s", gtamd_esa_last_error());
+          goto done;
+        }
+        for (uint64_t k = 0; k < written; k++) {
+          const uint64_t qpos = first + rec[k].qpos, reclen = rec[k].len;
+          const uint64_t unit = unit_of(unitstart, numunits, qpos), offset = qpos - unitstart[unit];
+          const uint64_t unitlen = unitstart[unit + 1] - 1 - unitstart[unit];
+          const uint64_t dbseq = unit_of(seqstart, numseq, rec[k].dbpos), dbrel = rec[k].dbpos - seqstart[dbseq];
+          /* gt_querymatch_position_convert: the start on the forward strand */
+          const uint64_t qfwd = mode == 0 ? offset : unitlen - offset - reclen;
+          /* gt_querymatch_ordered: of the two records of one pair, the one whose
+             subject side comes first */
+          if (!have_q && !(dbseq < unit || (dbseq == unit && dbrel < qfwd + (mode != 0)))) continue;
+          printf("%llu %llu %llu %c %llu %llu %llu\n", (unsigned long long) reclen, (unsigned long long) dbseq,
+                 (unsigned long long) dbrel, modechar[mode], (unsigned long long) reclen,
+                 (unsigned long long) unit, (unsigned long long) qfwd);
+        }
+      } while (written != 0);
+    }
+  }
+  if (fflush(stdout) != 0) { pfail(err, errlen, "cannot write to %s", "stdout"); goto done; }
+  rc = 0;
+done:
+  gtamd_qmatch_destroy(qm);
+  unmap_file(&suf);
+  if (have_alpha) gtamd_alphabet_free(&alpha);
+  free(rec); free(tq); free(unitstart); free(seqstart); free(desc); free(query_own); free(enc);
   return rc;
 }

@@ -19,6 +19,8 @@
                             `gt matstat -esa` and `gt uniquesub -esa`
                             (src/tools/gt_matstat.c), on the device through
                             include/gtamd_mstat.h
+    gtamd_querymatch        `gt repfind` with -q, -r or -p: maximal exact matches of
+                            queries against the index
     gtamd_repfind           `gt repfind -l L -ii INDEX` (src/tools/gt_repfind.c),
                             on the device through include/gtamd_maxpairs.h
 
@@ -344,6 +346,36 @@ int gtamd_uniquesub(int argc, const char **argv, char *err, size_t errlen);
    Returns 0, or -1 with the message in err (the caller prints "gt repfind:
    error: <err>" and exits 1). */
 int gtamd_repfind(int argc, const char **argv, char *err, size_t errlen);
+
+/* `gt repfind` with -q FILE..., -r or -p (the calls the tool function sends to
+   gt_callenumquerymatches, src/tools/gt_repfind.c:562-757): the maximal exact
+   matches of query sequences against the index's sequences, on the device from
+   .suf and the sequence (semantics and order: include/gtamd_qmatch.h).  The
+   sub-command `querymatch`; `repfind` keeps refusing these options.
+     -ii INDEX    reads INDEX.prj, INDEX.esq (+ .ssp) and INDEX.suf (4- or 8-byte
+                  entries, by its size); a read mode other than forward and a
+                  mirrored index are refused
+     -l L         minimum length, default 20; >= 1
+     -q FILE...   FASTA, read with the alphabet of INDEX.esq; the sequences
+                  (units) are numbered across all files, one shorter than L is
+                  counted and gives nothing.  Files of more symbols than one
+                  search takes (2^32 - 1) are searched in runs of whole units
+     -f -r -p     forward, reverse, reverse-complement matches, in this order,
+                  each a whole pass; -f is on unless -r or -p is given without
+                  it (gt_repfind_arguments_check).  -p needs a DNA alphabet.
+                  Without -q the index's own sequences are the queries of -r and
+                  -p, and a record is kept only if gt_querymatch_ordered holds
+                  (src/match/querymatch.c:357-369); forward matches without -q
+                  are the maximal repeats: refused with a pointer to `repfind`
+     -v           the figures of every search as a line starting with '#'
+   Prints one line per match, `len dbseqnum dbrelpos F|R|P len unit querystart`,
+   querystart on the forward strand (gt_querymatch_position_convert), in the
+   reference's order; its two '#' header lines are not printed.
+   -qii -scan -spm -samples -maxfreq -seedlength -extend* (and the options those
+   imply) -outfmt -evalue are refused ("option \"-X\" is not supported ...").
+   Returns 0, or -1 with the message in err (the caller prints "gt repfind:
+   error: <err>" and exits 1). */
+int gtamd_querymatch(int argc, const char **argv, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }
