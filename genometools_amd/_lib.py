@@ -14,13 +14,15 @@ LIB_PATH = os.path.join(HERE, "libgtamd_esa.so")
 SOURCES = [os.path.join(HERE, "csrc", f) for f in
            ("esa_prims.hip", "esa_engine.hip", "esa_synth.hip", "esa_encode.hip",
             "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip",
-            "esa_maxpairs.hip", "esa_qmatch.hip")]
+            "esa_maxpairs.hip", "esa_qmatch.hip", "esa_spm.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
                                                      "esa_pck_replay.h", "esa_mstat_search.h",
-                                                     "esa_maxpairs_walk.h", "esa_qmatch_core.h")] + \
+                                                     "esa_maxpairs_walk.h", "esa_qmatch_core.h",
+                                                     "esa_spm_core.h")] + \
           [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
                                                        "gtamd_check.h", "gtamd_mstat.h",
-                                                       "gtamd_maxpairs.h", "gtamd_qmatch.h")]
+                                                       "gtamd_maxpairs.h", "gtamd_qmatch.h",
+                                                       "gtamd_spm.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -134,6 +136,12 @@ class QmatchInfo(ctypes.Structure):      # gtamd_qmatch_info, include/gtamd_qmat
     _fields_ = [(name, ctypes.c_uint64) for name in
                 ("positions", "seeds", "candidates", "max_width", "matches", "search_symbols",
                  "extension_symbols", "device_bytes")] + [("device_ms", ctypes.c_float)]
+
+
+class SpmInfo(ctypes.Structure):         # gtamd_spm_info, include/gtamd_spm.h
+    _fields_ = [(name, ctypes.c_uint64) for name in
+                ("table_entries", "terminal_suffixes", "read_starts", "matches", "max_width",
+                 "max_matches_of_one_suffix", "search_symbols", "device_bytes")] + [("device_ms", ctypes.c_float)]
 
 
 # every symbol include/gtamd_esa.h, gtamd_encode.h and gtamd_pck.h declare:
@@ -272,6 +280,19 @@ QMATCH_ABI = {
     "gtamd_qmatch_get_info": (_INT, [_P, ctypes.POINTER(QmatchInfo)]),
 }
 
+# every symbol include/gtamd_spm.h declares
+SPM_ABI = {
+    "gtamd_spm_create": (_P, [_INT]),
+    "gtamd_spm_destroy": (None, [_P]),
+    "gtamd_spm_geometry": (None, [ctypes.POINTER(_U32), ctypes.POINTER(_U64)]),
+    "gtamd_spm_set_index": (_INT, [_P, _P, _U64, _P, _U32, _P, _P, _U64]),
+    "gtamd_spm_set_index_host": (_INT, [_P, _P, _U64, _P, _U32, _P, _P, _U64]),
+    "gtamd_spm_set_index_esa": (_INT, [_P, _P, _P, _U64]),
+    "gtamd_spm_prepare": (_INT, [_P, _U32, ctypes.POINTER(SpmInfo)]),
+    "gtamd_spm_emit": (_INT, [_P, ctypes.POINTER(_U64), _P, _U64, _INT, ctypes.POINTER(_U64)]),
+    "gtamd_spm_get_info": (_INT, [_P, ctypes.POINTER(SpmInfo)]),
+}
+
 _lib = None
 
 
@@ -295,7 +316,7 @@ def load():
             pass
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()) + \
-                list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()):
+                list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()) + list(SPM_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

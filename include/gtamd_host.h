@@ -23,6 +23,9 @@
                             queries against the index
     gtamd_repfind           `gt repfind -l L -ii INDEX` (src/tools/gt_repfind.c),
                             on the device through include/gtamd_maxpairs.h
+    gtamd_encseq2spm        `gt encseq2spm -l L -ii INDEX -spm show|count`
+                            (src/tools/gt_encseq2spm.c), on the device through
+                            the engine and include/gtamd_spm.h
 
   Pure C (gcc); links against libgtamd_esa.so for the hot path.
 */
@@ -376,6 +379,37 @@ int gtamd_repfind(int argc, const char **argv, char *err, size_t errlen);
    Returns 0, or -1 with the message in err (the caller prints "gt repfind:
    error: <err>" and exits 1). */
 int gtamd_querymatch(int argc, const char **argv, char *err, size_t errlen);
+
+/* `gt encseq2spm -l L -ii INDEX [-spm show|count]` (tool function
+   src/tools/gt_encseq2spm.c; the traversal it replaces: src/match/esa-spmsk.c):
+   all suffix-prefix matches of at least L letters of the reads of INDEX, on both
+   strands (semantics and order: include/gtamd_spm.h).  The sub-command
+   `encseq2spm`.
+     -ii INDEX   reads INDEX.prj and INDEX.esq (+ .ssp) and no table: the reads
+                 are mirrored (gtamd_mirror: R reads give 2R sequences, number
+                 R + j the reverse complement of read R - 1 - j), .suf and .lcp of
+                 the mirrored reads are built by the engine in this process and
+                 handed to the matcher where they lie.  A protein index is
+                 refused with the reference's message; so is a project with a
+                 read mode other than forward or a mirrored one
+     -l L        minimum length, >= 1; mandatory, as in the reference
+     -spm show   one line `s t len` per match, in TABLE ORDER: ascending table
+                 index of the matching suffix of sequence s, then of the start
+                 of sequence t.  The reference prints in the order of its
+                 traversal; outputs are compared as sorted lines
+     -spm count  the line `number of suffix-prefix matches=Z`
+                 without -spm nothing is computed and the exit code is 0, as
+                 after the reference's sort
+     -v          the build time and the figures of gtamd_spm_info as lines
+                 starting with '#'
+   -singlestrand is answered with the reference's own "option -singlestand is
+   not implemented".  -parts -memlimit -checksuftab -onlyaccum
+   -onlyallfirstcodes -addbscachedepth -phase2extra -radixlarge -radixparts
+   -singlescan -forcek steer or check the reference's own sort and are refused
+   ("option \"-X\" is not supported ...").
+   Returns 0, or -1 with the message in err (the caller prints "gt encseq2spm:
+   error: <err>" and exits 1). */
+int gtamd_encseq2spm(int argc, const char **argv, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }
