@@ -5,7 +5,9 @@ in table order.  The tables come from the engine, in this process.
 
 The shapes are the smallest at which each part can go wrong: a select pass
 takes 1024 items a workgroup, a walk 256 entries; .lcp holds a byte 255 from
-255 letters on."""
+255 letters on.  The second level of each -- more than 65,536 run suffixes, more
+than 4096 select tiles, a table of more than one upload piece -- is in
+tests/test_scale_gpu.py."""
 import functools
 
 import numpy as np

@@ -5,7 +5,10 @@ from the engine, in this process, as 8- and as 4-byte entries.
 
 The shapes are the smallest at which each part can go wrong: a workgroup takes
 T query positions in the interval pass and T candidates in the emit passes, an
-emit call takes chunks of at least LEAST candidates (qmatch.geometry())."""
+emit call takes chunks of at least LEAST candidates (qmatch.geometry()).  The
+second level of each -- more than 65,536 query positions, more than 2^24
+candidates in one emit call, a table of more than one upload piece -- is in
+tests/test_scale_gpu.py."""
 import functools
 import math
 import threading

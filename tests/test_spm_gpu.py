@@ -6,7 +6,9 @@ this process, and are used as 8- and as 4-byte entries.
 The shapes are the smallest at which each part can go wrong: a select pass takes
 1024 table entries a workgroup, the interval pass T terminal suffixes and the
 emit pass T records, an emit call takes a capacity of at least LEAST records
-(spm.geometry()); .lcp holds a byte 255 from 255 letters on."""
+(spm.geometry()); .lcp holds a byte 255 from 255 letters on.  The second level
+of each -- more than 65,536 terminal suffixes, more than 4096 select tiles, more
+than 2^24 records in one emit call -- is in tests/test_scale_gpu.py."""
 import functools
 import os
 
