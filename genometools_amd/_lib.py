@@ -15,7 +15,7 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in
            ("esa_prims.hip", "esa_engine.hip", "esa_synth.hip", "esa_encode.hip",
             "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip",
             "esa_maxpairs.hip", "esa_qmatch.hip", "esa_spm.hip")]
-HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
+HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_index.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
                                                      "esa_pck_replay.h", "esa_mstat_search.h",
                                                      "esa_maxpairs_walk.h", "esa_qmatch_core.h",
                                                      "esa_spm_core.h")] + \

@@ -16,6 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from ._consumer import Consumer, ptr
 from ._lib import CheckReport, check
 
 SUF, LCP, LLV, BWT = 1, 2, 4, 8                  # CheckResult.table
@@ -57,36 +58,13 @@ class CheckResult:
         return self.ok
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-class EsaChecker:
+class EsaChecker(Consumer):
     """checker of index tables on one device; TILE and LONG_CLAIM: geometry()"""
+    NAME = "check"
 
     def __init__(self, device=0):
-        self._lib = _lib.load()
         self.TILE, self.LONG_CLAIM = geometry()
-        self._p = self._lib.gtamd_check_create(device)
-        if not self._p:
-            raise _lib.EsaError(self._lib.gtamd_esa_last_error().decode())
-
-    def close(self):
-        if self._p:
-            self._lib.gtamd_check_destroy(self._p)
-            self._p = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(device)
 
     def _result(self, rep):
         buf = ctypes.create_string_buffer(512)
@@ -116,8 +94,8 @@ class EsaChecker:
             raise ValueError("llv holds pairs and goes with lcp")
         rep = CheckReport()
         check(self._lib.gtamd_check_tables_host(
-            self._p, _ptr(enc), enc.size, _ptr(suf), suf.dtype.itemsize, _ptr(lcp),
-            _ptr(llv) if llv.size else None, llv.size // 2, _ptr(bwt), ctypes.byref(rep)))
+            self._p, ptr(enc), enc.size, ptr(suf), suf.dtype.itemsize, ptr(lcp),
+            ptr(llv) if llv.size else None, llv.size // 2, ptr(bwt), ctypes.byref(rep)))
         return self._result(rep)
 
     def check_device(self, enc_ptr, n, suf_ptr, suf_bytes=8, lcp_ptr=None, llv_ptr=None, llv_pairs=0,

@@ -17,7 +17,8 @@
 // in LDS, one atomicMin per workgroup on a 64-bit slot.  What a report says
 // beyond that index the host reads from the tables afterwards.
 #include "esa_common.h"
-#include "esa_own.h"
+#include "esa_index.h"
+#include "esa_devutil.h"
 #include "../../include/gtamd_check.h"
 
 namespace {
@@ -26,10 +27,8 @@ constexpr int CHK_THREADS = 256;
 constexpr u32 CHK_TILE = 2048;           // table entries per workgroup
 constexpr u32 CHK_LONG_CLAIM = 512;      // longer ranges of (b) go to the work list
 constexpr u32 CHK_LONG_BLOCKS = 2048;    // workgroups that share the work list
-constexpr u64 CHK_MAX_ENTRIES = (1ull << 32) - 4096;   // single-build limit of esa_engine.hip
 constexpr u32 RANK_UNSET = 0xffffffffu;
 constexpr u64 NONE = ~0ull;
-constexpr u64 UPLOAD_PIECE = 64ull << 20;
 
 // the words the kernels report through
 enum { W_FAIL = 0, W_LONGEST, W_COUNT255, W_DEPTH, W_LISTED, W_TRUE_LCP, W_WORDS };
@@ -114,16 +113,6 @@ __global__ __launch_bounds__(CHK_THREADS) void k_chk_bwt(const u8 *enc, const S 
 }
 
 // ---- phase 4 --------------------------------------------------------------
-// the pair of table index r: its number, or where it would stand
-__device__ __forceinline__ u64 llv_lower_bound(const u64 *llv, u64 m, u64 r) {
-  u64 lo = 0, hi = m;
-  while (lo < hi) {
-    const u64 mid = (lo + hi) >> 1;
-    if (llv[2 * mid] < r) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(CHK_THREADS) void k_chk_llv_pairs(const u8 *lcp, const u64 *llv, u64 m,
                                                                u64 n, u64 *w) {
   const u64 base = (u64) blockIdx.x * CHK_TILE;
@@ -323,16 +312,14 @@ __global__ __launch_bounds__(CHK_THREADS) void k_chk_true_lcp(const u8 *enc, u64
 
 }  // namespace
 
-struct gtamd_check {
-  int device = 0;
-  Stream st;             // (before the buffers: they go first)
-  Event ev[GTAMD_CHECK_PHASES + 1];
+struct gtamd_check : ConsumerBase<GTAMD_CHECK_PHASES + 1> {
   Dev<u32> rank;         // the inverse of the suffix table
   Dev<u32> list;         // positions with a long range (b)
-  Dev<u64> words;
 };
 
 namespace {
+
+const char FEATURE[] = "index check";
 
 struct Tables {
   const u8 *enc; u64 n;
@@ -341,22 +328,18 @@ struct Tables {
   const u8 *bwt;
 };
 
-int read_words(gtamd_check *c, u64 *h) {
-  HIP_TRY(hipMemcpyAsync(h, c->words, W_WORDS * sizeof(u64), hipMemcpyDeviceToHost, c->st));
-  HIP_TRY(hipStreamSynchronize(c->st));
-  return 0;
+Tables tables(const IndexView &v, const u8 *bwt) {
+  return Tables{ v.enc, v.n, v.suf, v.suf_bytes, v.lcp, v.llv, v.llv_pairs, bwt };
 }
+
+int read_words(gtamd_check *c, u64 *h) { return fetch(c->st, { { c->words, h, W_WORDS * sizeof(u64) } }); }
 
 int reset_fail(gtamd_check *c) {
   HIP_TRY(hipMemsetAsync(c->words, 0xff, sizeof(u64), c->st));    // W_FAIL = NONE
   return 0;
 }
 
-int fetch(gtamd_check *c, const void *src, u64 bytes, void *dst) {
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->st));
-  HIP_TRY(hipStreamSynchronize(c->st));
-  return 0;
-}
+int fetch(gtamd_check *c, const void *src, u64 bytes, void *dst) { return ::fetch(c->st, { { src, dst, bytes } }); }
 
 template <typename S> int fetch_suf(gtamd_check *c, const S *suf, u64 i, u64 *out) {
   S v;
@@ -543,17 +526,9 @@ int run_check(gtamd_check *c, const Tables &tb, gtamd_check_report *rep) {
     gtamd_set_error("invalid argument to gtamd_check_tables");
     return -1;
   }
-  if (tb.suf_bytes != 4 && tb.suf_bytes != 8) {
-    gtamd_set_error("index check: .suf entries of %u bytes, 4 or 8 expected", tb.suf_bytes);
-    return -1;
-  }
+  TRY(refuse_suf_bytes(FEATURE, tb.suf_bytes));
+  TRY(refuse_sizes(FEATURE, tb.n, 0, "checked"));
   const u64 N = tb.n + 1;
-  if (tb.n >= CHK_MAX_ENTRIES) {
-    gtamd_set_error("index check: sequence of %llu symbols is beyond the limit of a single build "
-                    "(%llu table entries); the slices of a build in parts are not checked",
-                    (unsigned long long) tb.n, (unsigned long long) CHK_MAX_ENTRIES);
-    return -1;
-  }
   HIP_TRY(hipSetDevice(c->device));
   *rep = gtamd_check_report();
   rep->ok = 1;
@@ -575,49 +550,15 @@ int run_check(gtamd_check *c, const Tables &tb, gtamd_check_report *rep) {
   return 0;
 }
 
-// host memory -> a device buffer of its own, piece by piece
-template <typename T> int upload(Dev<T> &d, const void *src, u64 bytes, const char *what) {
-  if (src == nullptr) return 0;
-  if (d.alloc(bytes ? bytes : 1) != hipSuccess) {
-    gtamd_set_error("index check: cannot allocate %llu bytes of device memory for %s",
-                    (unsigned long long) bytes, what);
-    return -1;
-  }
-  for (u64 off = 0; off < bytes; off += UPLOAD_PIECE) {
-    const u64 cnt = bytes - off < UPLOAD_PIECE ? bytes - off : UPLOAD_PIECE;
-    HIP_TRY(hipMemcpy((u8 *) d.p + off, (const u8 *) src + off, cnt, hipMemcpyHostToDevice));
-  }
-  return 0;
-}
-
 }  // namespace
 
 extern "C" gtamd_check *gtamd_check_create(int device) {
   GTAMD_ABI_BEGIN
-  if (gtamd_device_count() <= device || device < 0) {
-    gtamd_set_error("no HIP device %d available (this library has no CPU fallback)", device);
-    return nullptr;
-  }
-  if (hipSetDevice(device) != hipSuccess) { gtamd_set_error("hipSetDevice(%d) failed", device); return nullptr; }
-  gtamd_check *c = new gtamd_check();
-  c->device = device;
-  bool ok = create(c->st) == hipSuccess && c->words.alloc(W_WORDS * sizeof(u64)) == hipSuccess;
-  for (int k = 0; ok && k <= GTAMD_CHECK_PHASES; k++) ok = create(c->ev[k]) == hipSuccess;
-  if (!ok) {
-    gtamd_set_error("cannot create the index checker on device %d", device);
-    delete c;
-    return nullptr;
-  }
-  return c;
+  return create_consumer<gtamd_check>(device, W_WORDS, "the index checker");
   GTAMD_ABI_END(nullptr)
 }
 
-extern "C" void gtamd_check_destroy(gtamd_check *c) {
-  if (c == nullptr) return;
-  (void) hipSetDevice(c->device);
-  (void) hipStreamSynchronize(c->st);
-  delete c;
-}
+extern "C" void gtamd_check_destroy(gtamd_check *c) { destroy_consumer(c); }
 
 extern "C" void gtamd_check_geometry(uint32_t *tile_entries, uint32_t *long_claim) {
   if (tile_entries != nullptr) *tile_entries = CHK_TILE;
@@ -637,7 +578,7 @@ extern "C" int gtamd_check_tables_host(gtamd_check *c, const uint8_t *enc, uint6
                                        uint32_t suf_bytes, const uint8_t *lcp, const uint64_t *llv,
                                        uint64_t llv_pairs, const uint8_t *bwt, gtamd_check_report *rep) {
   GTAMD_ABI_BEGIN
-  if (c == nullptr || suf == nullptr || (suf_bytes != 4 && suf_bytes != 8) || n >= CHK_MAX_ENTRIES ||
+  if (c == nullptr || suf == nullptr || (suf_bytes != 4 && suf_bytes != 8) || n >= SINGLE_LIMIT ||
       (llv_pairs && (llv == nullptr || lcp == nullptr))) {
     const Tables tb = { enc, n, suf, suf_bytes, lcp, llv, llv_pairs, bwt };
     return run_check(c, tb, rep);        // (words the refusal)
@@ -645,11 +586,12 @@ extern "C" int gtamd_check_tables_host(gtamd_check *c, const uint8_t *enc, uint6
   HIP_TRY(hipSetDevice(c->device));
   Dev<u8> d_enc, d_suf, d_lcp, d_bwt;
   Dev<u64> d_llv;
-  TRY(upload(d_enc, enc != nullptr ? (const void *) enc : (const void *) "", n, "the sequence"));
-  TRY(upload(d_suf, suf, (n + 1) * suf_bytes, "the .suf table"));
-  TRY(upload(d_lcp, lcp, n + 1, "the .lcp table"));
-  TRY(upload(d_llv, llv_pairs ? llv : nullptr, llv_pairs * 16, "the .llv table"));
-  TRY(upload(d_bwt, bwt, n + 1, "the .bwt table"));
+  // (a table that is not given stays a null pointer: it is not checked)
+  TRY(upload(d_enc, enc != nullptr ? (const void *) enc : (const void *) "", n, FEATURE, "the sequence"));
+  TRY(upload(d_suf, suf, (n + 1) * suf_bytes, FEATURE, "the .suf table"));
+  if (lcp != nullptr) TRY(upload(d_lcp, lcp, n + 1, FEATURE, "the .lcp table"));
+  if (llv_pairs) TRY(upload(d_llv, llv, llv_pairs * 16, FEATURE, "the .llv table"));
+  if (bwt != nullptr) TRY(upload(d_bwt, bwt, n + 1, FEATURE, "the .bwt table"));
   const Tables tb = { d_enc, n, d_suf.p, suf_bytes, d_lcp, d_llv, llv_pairs, d_bwt };
   return run_check(c, tb, rep);
   GTAMD_ABI_END(-1)
@@ -660,16 +602,9 @@ extern "C" int gtamd_check_esa(gtamd_check *c, const gtamd_esa_ctx *esa, const u
   GTAMD_ABI_BEGIN
   if (c == nullptr || esa == nullptr || rep == nullptr) { gtamd_set_error("invalid argument to gtamd_check_esa"); return -1; }
   if (!(want & GTAMD_WANT_SUF)) { gtamd_set_error("index check: the .lcp and .bwt tables are checked through the .suf table"); return -1; }
-  const void *suf = gtamd_esa_table_device(esa, GTAMD_TAB_SUF);
-  if (suf == nullptr) { gtamd_set_error("index check: the last run did not produce the .suf table"); return -1; }
-  if (gtamd_esa_table_offset(esa) != 0 || gtamd_esa_table_entries(esa, GTAMD_TAB_SUF) != n + 1) {
-    gtamd_set_error("index check: the context holds %llu entries from table index %llu on, not the whole "
-                    "table of %llu symbols; the slices of a build in parts are not checked",
-                    (unsigned long long) gtamd_esa_table_entries(esa, GTAMD_TAB_SUF),
-                    (unsigned long long) gtamd_esa_table_offset(esa), (unsigned long long) n);
-    return -1;
-  }
-  Tables tb = { enc, n, suf, 8, nullptr, nullptr, 0, nullptr };
+  IndexView v;
+  TRY(engine_tables(FEATURE, esa, enc, n, false, &v, "checked"));
+  Tables tb = tables(v, nullptr);
   if (want & GTAMD_WANT_LCP) {
     tb.lcp = (const u8 *) gtamd_esa_table_device(esa, GTAMD_TAB_LCP);
     tb.m = gtamd_esa_table_entries(esa, GTAMD_TAB_LLV);

@@ -35,6 +35,10 @@ void gtamd_set_error(const char *fmt, ...);
 
 static inline u64 div_up(u64 a, u64 b) { return (a + b - 1) / b; }
 
+// table entries of one slice / single build: what the engine builds at once, and
+// what everything that reads whole tables takes
+constexpr u64 SINGLE_LIMIT = (1ull << 32) - 4096;
+
 // Exception barrier of the C ABI.  The callers are C (GenomeTools' GtError
 // convention: -1 / NULL + message); a std::bad_alloc or std::length_error from a
 // host container -- e.g. one sized from a number read back from the device --

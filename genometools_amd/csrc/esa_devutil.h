@@ -70,6 +70,27 @@ __device__ __forceinline__ u64 block_scan_incl_u64(u64 v, u64 *s) {
   return r;
 }
 
+// the last entry of [a, b) whose first record is not behind record g, from the
+// ascending offsets of offsets_u64 (esa_prims.h); off[a] <= g, and off[b] is not read
+__device__ __forceinline__ u64 entry_of(const u64 *off, u64 a, u64 b, u64 g) {
+  while (b - a > 1) {
+    const u64 mid = a + (b - a) / 2;
+    if (off[mid] <= g) a = mid; else b = mid;
+  }
+  return a;
+}
+
+// the .llv pair (table index, value) of table index r among m ascending pairs:
+// its number, or where it would stand
+__device__ __forceinline__ u64 llv_lower_bound(const u64 *llv, u64 m, u64 r) {
+  u64 lo = 0, hi = m;
+  while (lo < hi) {
+    const u64 mid = (lo + hi) >> 1;
+    if (llv[2 * mid] < r) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 // one workgroup of SC_THREADS lanes: a[i] = sum of a[0..i), *total = the sum of all
 __device__ __forceinline__ void block_scan_excl_array_u64(u64 *a, u64 count, u64 *total, u64 *s) {
   u64 carry = 0;

@@ -3160,7 +3160,6 @@ static u64 max_positions(int bits) {
   const int total = 32 + spare > 40 ? 40 : 32 + spare;   // ranks travel in 40 bits
   return 1ull << total;
 }
-constexpr u64 SINGLE_LIMIT = (1ull << 32) - 4096;   // entries of one slice / single build
 
 // streams, events and the small fixed buffers of a new context
 static int create_resources(gtamd_esa_ctx *c) {

@@ -9,12 +9,12 @@
 //                              segment starts, the segment of every entry
 //      k_mp_segments           one lane per segment: esa_maxpairs_walk.h
 //   3  k_mp_count              one lane per entry: the walk that counts
-//      k_mp_scan64, k_mp_offsets   64-bit exclusive scan of the counts
+//      offsets_u64 (esa_prims)     64-bit exclusive scan of the counts
 //   4  k_mp_emit               one lane per entry: the walk that writes
 //
 // Every working array has M entries (or one per tile), none has N.
 #include "esa_common.h"
-#include "esa_own.h"
+#include "esa_index.h"
 #include "esa_prims.h"
 #include "esa_devutil.h"
 #include "esa_maxpairs_walk.h"
@@ -26,19 +26,8 @@ constexpr int MP_THREADS = SC_THREADS;          // (the block scans of esa_devut
 constexpr u32 MP_PER = 4;                         // consecutive items of one lane in a select pass
 constexpr u32 MP_TILE = MP_THREADS * MP_PER;      // items of one workgroup there
 constexpr u32 MP_WALK_TILE = MP_THREADS;          // entries of one workgroup in a walk: one a lane
-constexpr u64 MP_MAX_ENTRIES = (1ull << 32) - 4096;   // single-build limit of esa_engine.hip
-constexpr u64 UPLOAD_PIECE = 64ull << 20;
 
 enum { W_RUNS = 0, W_PAIRS, W_MAXCNT, W_MAXLEN, W_STEPS, W_WORDS };
-
-__device__ __forceinline__ u64 llv_lower_bound(const u64 *llv, u64 m, u64 r) {
-  u64 lo = 0, hi = m;
-  while (lo < hi) {
-    const u64 mid = (lo + hi) >> 1;
-    if (llv[2 * mid] < r) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 // ---- steps 1 and 2: select ---------------------------------------------------
 // table index i lies in a run: lcp[i] >= L or lcp[i + 1] >= L
@@ -164,24 +153,6 @@ __global__ __launch_bounds__(MP_THREADS) void k_mp_count(MpSegments g, const u8 
   }
 }
 
-// one workgroup: a[i] = sum of a[0..i), *total = the sum of all
-__global__ __launch_bounds__(MP_THREADS) void k_mp_scan64(u64 *a, u64 count, u64 *total) {
-  __shared__ u64 s[MP_THREADS];
-  block_scan_excl_array_u64(a, count, total, s);
-}
-
-// off[k] = the records in front of entry k; off[M] = all
-__global__ __launch_bounds__(MP_THREADS) void k_mp_offsets(const u32 *cnt, const u64 *tsum, u32 M, u64 *off) {
-  __shared__ u64 s[MP_THREADS];
-  const u64 k = (u64) blockIdx.x * MP_WALK_TILE + threadIdx.x;
-  const u64 v = k < M ? cnt[k] : 0;
-  const u64 incl = block_scan_incl_u64(v, s) + tsum[blockIdx.x];
-  if (k < M) {
-    off[k] = incl - v;
-    if (k + 1 == M) off[M] = incl;
-  }
-}
-
 // ---- step 4 --------------------------------------------------------------------
 // entries [k0, k1): their records to out, the record at off[k0] first
 template <typename S>
@@ -193,24 +164,14 @@ __global__ __launch_bounds__(MP_THREADS) void k_mp_emit(MpSegments g, const u8 *
 
 }  // namespace
 
-struct gtamd_maxpairs {
-  int device = 0;
-  Stream st;             // (before the buffers: they go first)
-  Event ev[2];
-  Dev<u8> own_enc, own_suf, own_lcp;   // an index set from host memory
-  Dev<u64> own_llv;
-  const u8 *enc = nullptr;             // the index: the caller's, an engine's or the four above
-  const void *suf = nullptr;
-  const u8 *lcp = nullptr;
-  const u64 *llv = nullptr;
-  u64 n = 0, llv_pairs = 0;
-  u32 suf_bytes = 0;
-  bool have_index = false, prepared = false;
+struct gtamd_maxpairs : ConsumerBase<> {
+  ResidentIndex index;
+  bool prepared = false;
   // what a prepare leaves for the emit calls
   Dev<u32> tiles, scanws, idx, val, tmin, seg_of, cnt, seg_first, seg_min;
   Dev<u16> seg_info;
   Dev<u8> cls;
-  Dev<u64> tsum, off, words;
+  Dev<u64> tsum, off;
   Dev<u8> out;                         // records on their way to host memory
   u32 M = 0, nseg = 0;
   gtamd_maxpairs_info info = gtamd_maxpairs_info();
@@ -218,64 +179,28 @@ struct gtamd_maxpairs {
 
 namespace {
 
-void drop_index(gtamd_maxpairs *mp) {
-  mp->have_index = mp->prepared = false;
-  mp->own_enc.reset(); mp->own_suf.reset(); mp->own_lcp.reset(); mp->own_llv.reset();
-  mp->enc = nullptr; mp->suf = nullptr; mp->lcp = nullptr; mp->llv = nullptr;
-}
+const char FEATURE[] = "maximal pairs";
 
-// what every way of setting an index refuses, before anything is touched
-int index_arguments(const gtamd_maxpairs *mp, const void *enc, u64 n, const void *suf, u32 suf_bytes,
-                    const void *lcp, const void *llv, u64 llv_pairs) {
-  if (mp == nullptr || suf == nullptr || lcp == nullptr || (enc == nullptr && n) || (llv == nullptr && llv_pairs)) {
+// every way of setting an index: what is refused, before anything is touched
+int set_index(gtamd_maxpairs *mp, const IndexView &v, bool from_host) {
+  if (mp == nullptr || v.suf == nullptr || v.lcp == nullptr || (v.enc == nullptr && v.n) ||
+      (v.llv == nullptr && v.llv_pairs)) {
     gtamd_set_error("invalid argument to gtamd_maxpairs_set_index");
     return -1;
   }
-  if (suf_bytes != 4 && suf_bytes != 8) {
-    gtamd_set_error("maximal pairs: .suf entries of %u bytes, 4 or 8 expected", suf_bytes);
-    return -1;
-  }
-  if (n >= MP_MAX_ENTRIES) {
-    gtamd_set_error("maximal pairs: sequence of %llu symbols is beyond the limit of a single build "
-                    "(%llu table entries); the slices of a build in parts are not searched",
-                    (unsigned long long) n, (unsigned long long) MP_MAX_ENTRIES);
-    return -1;
-  }
-  if (llv_pairs > n) {
-    gtamd_set_error("maximal pairs: %llu .llv pairs for %llu symbols", (unsigned long long) llv_pairs,
-                    (unsigned long long) n);
-    return -1;
-  }
-  return 0;
-}
-
-void take_index(gtamd_maxpairs *mp, const u8 *enc, u64 n, const void *suf, u32 suf_bytes, const u8 *lcp,
-                const u64 *llv, u64 llv_pairs) {
-  mp->enc = enc; mp->n = n; mp->suf = suf; mp->suf_bytes = suf_bytes;
-  mp->lcp = lcp; mp->llv = llv; mp->llv_pairs = llv_pairs;
-  mp->have_index = true;
+  TRY(refuse_suf_bytes(FEATURE, v.suf_bytes));
+  TRY(refuse_sizes(FEATURE, v.n, v.llv_pairs));
+  HIP_TRY(hipSetDevice(mp->device));
   mp->prepared = false;
-}
-
-// host memory -> a device buffer of its own, piece by piece
-template <typename T> int upload(Dev<T> &d, const void *src, u64 bytes, const char *what) {
-  if (d.alloc(bytes ? bytes : 1) != hipSuccess) {
-    gtamd_set_error("maximal pairs: cannot allocate %llu bytes of device memory for %s",
-                    (unsigned long long) bytes, what);
-    return -1;
-  }
-  for (u64 off = 0; off < bytes; off += UPLOAD_PIECE) {
-    const u64 cnt = bytes - off < UPLOAD_PIECE ? bytes - off : UPLOAD_PIECE;
-    HIP_TRY(hipMemcpy((u8 *) d.p + off, (const u8 *) src + off, cnt, hipMemcpyHostToDevice));
-  }
+  if (from_host) return mp->index.upload_from_host(FEATURE, v);
+  mp->index.borrow(v);
   return 0;
 }
 
 u64 held_bytes(const gtamd_maxpairs *mp) {
-  return mp->own_enc.bytes + mp->own_suf.bytes + mp->own_lcp.bytes + mp->own_llv.bytes + mp->tiles.bytes +
-         mp->scanws.bytes + mp->idx.bytes + mp->val.bytes + mp->tmin.bytes + mp->seg_of.bytes + mp->cnt.bytes +
-         mp->seg_first.bytes + mp->seg_min.bytes + mp->seg_info.bytes + mp->cls.bytes + mp->tsum.bytes +
-         mp->off.bytes + mp->words.bytes + mp->out.bytes;
+  return mp->index.bytes() + mp->tiles.bytes + mp->scanws.bytes + mp->idx.bytes + mp->val.bytes + mp->tmin.bytes +
+         mp->seg_of.bytes + mp->cnt.bytes + mp->seg_first.bytes + mp->seg_min.bytes + mp->seg_info.bytes +
+         mp->cls.bytes + mp->tsum.bytes + mp->off.bytes + mp->words.bytes + mp->out.bytes;
 }
 
 MpSegments view(const gtamd_maxpairs *mp) {
@@ -297,8 +222,7 @@ int select(gtamd_maxpairs *mp, const P &p, u64 count, u64 *tally, u32 *selected,
     k_mp_select<P, false><<<(u32) T, MP_THREADS, 0, st>>>(p, count, mp->tiles, tally);
     HIP_TRY(hipGetLastError());
     TRY(scan_u32(SCAN_SUM, mp->tiles, mp->tiles, T + 1, false, mp->scanws, st));
-    HIP_TRY(hipMemcpyAsync(selected, mp->tiles + T, sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    TRY(fetch(st, { { mp->tiles + T, selected, sizeof(u32) } }));
   } else {
     k_mp_select<P, true><<<(u32) T, MP_THREADS, 0, st>>>(p, count, mp->tiles, tally);
     HIP_TRY(hipGetLastError());
@@ -308,7 +232,8 @@ int select(gtamd_maxpairs *mp, const P &p, u64 count, u64 *tally, u32 *selected,
 
 template <typename S> int prepare(gtamd_maxpairs *mp, u32 L) {
   hipStream_t st = mp->st;
-  const u64 N = mp->n + 1, T = div_up(N, MP_TILE);
+  const ResidentIndex &x = mp->index;
+  const u64 N = x.n + 1, T = div_up(N, MP_TILE);
   if (mp->tiles.grow((T + 1) * sizeof(u32)) != hipSuccess ||
       mp->scanws.grow(scan_workspace_words(T + 1) * sizeof(u32)) != hipSuccess)
     return out_of_memory(T + 1, "tiles");
@@ -316,7 +241,7 @@ template <typename S> int prepare(gtamd_maxpairs *mp, u32 L) {
   HIP_TRY(hipEventRecord(mp->ev[0], st));
 
   // 1: the suffixes in runs
-  InRun<S> in = { mp->enc, mp->n, (const S *) mp->suf, mp->lcp, mp->llv, mp->llv_pairs, L,
+  InRun<S> in = { x.enc, x.n, (const S *) x.suf, x.lcp, x.llv, x.llv_pairs, L,
                   nullptr, nullptr, nullptr };
   u32 M = 0, nseg = 0;
   TRY(select(mp, in, N, mp->words + W_RUNS, &M, false));
@@ -349,15 +274,11 @@ template <typename S> int prepare(gtamd_maxpairs *mp, u32 L) {
     const u32 tiles = (u32) div_up(M, MP_WALK_TILE);
     k_mp_count<<<tiles, MP_THREADS, 0, st>>>(view(mp), mp->cls, M, mp->cnt, mp->tsum, mp->words);
     HIP_TRY(hipGetLastError());
-    k_mp_scan64<<<1, MP_THREADS, 0, st>>>(mp->tsum, tiles, mp->words + W_PAIRS);
-    HIP_TRY(hipGetLastError());
-    k_mp_offsets<<<tiles, MP_THREADS, 0, st>>>(mp->cnt, mp->tsum, M, mp->off);
-    HIP_TRY(hipGetLastError());
+    TRY(offsets_u64(mp->cnt, M, mp->tsum, mp->off, mp->words + W_PAIRS, st));
   }
   HIP_TRY(hipEventRecord(mp->ev[1], st));
   u64 h[W_WORDS];
-  HIP_TRY(hipMemcpyAsync(h, mp->words, sizeof h, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  TRY(fetch(st, { { mp->words, h, sizeof h } }));
   HIP_TRY(hipEventElapsedTime(&mp->info.device_ms, mp->ev[0], mp->ev[1]));
   mp->info.pairs = h[W_PAIRS];
   mp->info.run_suffixes = M;
@@ -370,11 +291,7 @@ template <typename S> int prepare(gtamd_maxpairs *mp, u32 L) {
 }
 
 // off[k] of the prepared object, k <= M
-int offset_at(gtamd_maxpairs *mp, u64 k, u64 *v) {
-  HIP_TRY(hipMemcpyAsync(v, mp->off + k, sizeof(u64), hipMemcpyDeviceToHost, mp->st));
-  HIP_TRY(hipStreamSynchronize(mp->st));
-  return 0;
-}
+int offset_at(gtamd_maxpairs *mp, u64 k, u64 *v) { return fetch(mp->st, { { mp->off + k, v, sizeof(u64) } }); }
 
 int emit(gtamd_maxpairs *mp, u64 *cursor, gtamd_maxpairs_record *out, u64 capacity, int out_on_device,
          u64 *written) {
@@ -411,23 +328,18 @@ int emit(gtamd_maxpairs *mp, u64 *cursor, gtamd_maxpairs_record *out, u64 capaci
     count -= base;
   }
   // (capacity >= the pairs of any one suffix: k1 > k0)
-  MpRecord *dst = (MpRecord *) out;
-  if (!out_on_device && count) {
-    if (mp->out.grow(count * sizeof(MpRecord)) != hipSuccess) return out_of_memory(count, "records");
-    dst = (MpRecord *) mp->out.p;
-  }
   if (count) {
+    RecordStage<MpRecord> stage(out, out_on_device);
+    if (stage.begin(mp->out, count) != hipSuccess) return out_of_memory(count, "records");
     const u32 blocks = (u32) div_up(k1 - k0, MP_WALK_TILE);
-    if (mp->suf_bytes == 4)
-      k_mp_emit<u32><<<blocks, MP_THREADS, 0, mp->st>>>(view(mp), mp->cls, mp->idx, (const u32 *) mp->suf, mp->off,
-                                                       (u32) k0, (u32) k1, base, dst);
+    if (mp->index.suf_bytes == 4)
+      k_mp_emit<u32><<<blocks, MP_THREADS, 0, mp->st>>>(view(mp), mp->cls, mp->idx, (const u32 *) mp->index.suf,
+                                                       mp->off, (u32) k0, (u32) k1, base, stage.dst);
     else
-      k_mp_emit<u64><<<blocks, MP_THREADS, 0, mp->st>>>(view(mp), mp->cls, mp->idx, (const u64 *) mp->suf, mp->off,
-                                                       (u32) k0, (u32) k1, base, dst);
+      k_mp_emit<u64><<<blocks, MP_THREADS, 0, mp->st>>>(view(mp), mp->cls, mp->idx, (const u64 *) mp->index.suf,
+                                                       mp->off, (u32) k0, (u32) k1, base, stage.dst);
     HIP_TRY(hipGetLastError());
-    if (!out_on_device)
-      HIP_TRY(hipMemcpyAsync(out, dst, count * sizeof(MpRecord), hipMemcpyDeviceToHost, mp->st));
-    HIP_TRY(hipStreamSynchronize(mp->st));
+    TRY(stage.finish(count, mp->st));
   }
   *cursor = k1;
   *written = count;
@@ -438,39 +350,17 @@ int emit(gtamd_maxpairs *mp, u64 *cursor, gtamd_maxpairs_record *out, u64 capaci
 
 extern "C" gtamd_maxpairs *gtamd_maxpairs_create(int device) {
   GTAMD_ABI_BEGIN
-  if (gtamd_device_count() <= device || device < 0) {
-    gtamd_set_error("no HIP device %d available (this library has no CPU fallback)", device);
-    return nullptr;
-  }
-  if (hipSetDevice(device) != hipSuccess) { gtamd_set_error("hipSetDevice(%d) failed", device); return nullptr; }
-  gtamd_maxpairs *mp = new gtamd_maxpairs();
-  mp->device = device;
-  if (create(mp->st) != hipSuccess || create(mp->ev[0]) != hipSuccess || create(mp->ev[1]) != hipSuccess ||
-      mp->words.alloc(W_WORDS * sizeof(u64)) != hipSuccess) {
-    gtamd_set_error("cannot create the maximal pairs enumerator on device %d", device);
-    delete mp;
-    return nullptr;
-  }
-  return mp;
+  return create_consumer<gtamd_maxpairs>(device, W_WORDS, "the maximal pairs enumerator");
   GTAMD_ABI_END(nullptr)
 }
 
-extern "C" void gtamd_maxpairs_destroy(gtamd_maxpairs *mp) {
-  if (mp == nullptr) return;
-  (void) hipSetDevice(mp->device);
-  (void) hipStreamSynchronize(mp->st);
-  delete mp;
-}
+extern "C" void gtamd_maxpairs_destroy(gtamd_maxpairs *mp) { destroy_consumer(mp); }
 
 extern "C" int gtamd_maxpairs_set_index(gtamd_maxpairs *mp, const uint8_t *enc, uint64_t n, const void *suf,
                                         uint32_t suf_bytes, const uint8_t *lcp, const uint64_t *llv,
                                         uint64_t llv_pairs) {
   GTAMD_ABI_BEGIN
-  TRY(index_arguments(mp, enc, n, suf, suf_bytes, lcp, llv, llv_pairs));
-  HIP_TRY(hipSetDevice(mp->device));
-  drop_index(mp);
-  take_index(mp, enc, n, suf, suf_bytes, lcp, llv, llv_pairs);
-  return 0;
+  return set_index(mp, IndexView{ enc, n, suf, suf_bytes, lcp, llv, llv_pairs }, false);
   GTAMD_ABI_END(-1)
 }
 
@@ -478,15 +368,7 @@ extern "C" int gtamd_maxpairs_set_index_host(gtamd_maxpairs *mp, const uint8_t *
                                              uint32_t suf_bytes, const uint8_t *lcp, const uint64_t *llv,
                                              uint64_t llv_pairs) {
   GTAMD_ABI_BEGIN
-  TRY(index_arguments(mp, enc, n, suf, suf_bytes, lcp, llv, llv_pairs));
-  HIP_TRY(hipSetDevice(mp->device));
-  drop_index(mp);
-  TRY(upload(mp->own_enc, enc, n, "the sequence"));
-  TRY(upload(mp->own_suf, suf, (n + 1) * suf_bytes, "the .suf table"));
-  TRY(upload(mp->own_lcp, lcp, n + 1, "the .lcp table"));
-  TRY(upload(mp->own_llv, llv, llv_pairs * 16, "the .llv table"));
-  take_index(mp, mp->own_enc, n, mp->own_suf.p, suf_bytes, mp->own_lcp, mp->own_llv, llv_pairs);
-  return 0;
+  return set_index(mp, IndexView{ enc, n, suf, suf_bytes, lcp, llv, llv_pairs }, true);
   GTAMD_ABI_END(-1)
 }
 
@@ -494,33 +376,16 @@ extern "C" int gtamd_maxpairs_set_index_esa(gtamd_maxpairs *mp, const gtamd_esa_
                                             uint64_t n) {
   GTAMD_ABI_BEGIN
   if (mp == nullptr || esa == nullptr) { gtamd_set_error("invalid argument to gtamd_maxpairs_set_index_esa"); return -1; }
-  const void *suf = gtamd_esa_table_device(esa, GTAMD_TAB_SUF);
-  const u8 *lcp = (const u8 *) gtamd_esa_table_device(esa, GTAMD_TAB_LCP);
-  const u64 pairs = gtamd_esa_table_entries(esa, GTAMD_TAB_LLV);
-  const u64 *llv = pairs ? (const u64 *) gtamd_esa_table_device(esa, GTAMD_TAB_LLV) : nullptr;
-  if (suf == nullptr || lcp == nullptr || (pairs && llv == nullptr)) {
-    gtamd_set_error("maximal pairs: the last run did not produce the .suf and .lcp tables");
-    return -1;
-  }
-  if (gtamd_esa_table_offset(esa) != 0 || gtamd_esa_table_entries(esa, GTAMD_TAB_SUF) != n + 1) {
-    gtamd_set_error("maximal pairs: the context holds %llu entries from table index %llu on, not the "
-                    "whole table of %llu symbols; the slices of a build in parts are not searched",
-                    (unsigned long long) gtamd_esa_table_entries(esa, GTAMD_TAB_SUF),
-                    (unsigned long long) gtamd_esa_table_offset(esa), (unsigned long long) n);
-    return -1;
-  }
-  TRY(index_arguments(mp, enc, n, suf, 8, lcp, llv, pairs));
-  HIP_TRY(hipSetDevice(mp->device));
-  drop_index(mp);
-  take_index(mp, enc, n, suf, 8, lcp, llv, pairs);
-  return 0;
+  IndexView v;
+  TRY(engine_tables(FEATURE, esa, enc, n, true, &v));
+  return set_index(mp, v, false);
   GTAMD_ABI_END(-1)
 }
 
 extern "C" int gtamd_maxpairs_prepare(gtamd_maxpairs *mp, uint32_t min_len, gtamd_maxpairs_info *info) {
   GTAMD_ABI_BEGIN
   if (mp == nullptr) { gtamd_set_error("invalid argument to gtamd_maxpairs_prepare"); return -1; }
-  if (!mp->have_index) {
+  if (!mp->index.set) {
     gtamd_set_error("maximal pairs: no index is set (gtamd_maxpairs_set_index)");
     return -1;
   }
@@ -532,7 +397,7 @@ extern "C" int gtamd_maxpairs_prepare(gtamd_maxpairs *mp, uint32_t min_len, gtam
   mp->prepared = false;
   mp->info = gtamd_maxpairs_info();
   mp->M = mp->nseg = 0;
-  TRY(mp->suf_bytes == 4 ? prepare<u32>(mp, min_len) : prepare<u64>(mp, min_len));
+  TRY(mp->index.suf_bytes == 4 ? prepare<u32>(mp, min_len) : prepare<u64>(mp, min_len));
   mp->info.device_bytes = held_bytes(mp);
   mp->prepared = true;
   if (info != nullptr) *info = mp->info;
@@ -560,8 +425,6 @@ extern "C" int gtamd_maxpairs_emit(gtamd_maxpairs *mp, uint64_t *cursor, gtamd_m
 
 extern "C" int gtamd_maxpairs_get_info(const gtamd_maxpairs *mp, gtamd_maxpairs_info *info) {
   GTAMD_ABI_BEGIN
-  if (mp == nullptr || info == nullptr) { gtamd_set_error("invalid argument to gtamd_maxpairs_get_info"); return -1; }
-  *info = mp->info;
-  return 0;
+  return consumer_info(mp, info, "gtamd_maxpairs_get_info");
   GTAMD_ABI_END(-1)
 }

@@ -8,7 +8,7 @@
 // (the witness) or one more comparison (the second neighbour, for uniqueness):
 // esa_mstat_search.h.  Letters are compared MST_WORD at a time through 4-byte words.
 #include "esa_common.h"
-#include "esa_own.h"
+#include "esa_index.h"
 #include "esa_mstat_search.h"
 #include "../../include/gtamd_mstat.h"
 
@@ -16,9 +16,7 @@ namespace {
 
 constexpr int MST_THREADS = 256;
 constexpr u32 MST_TILE = 256;            // query positions per workgroup, one a lane
-constexpr u64 MST_MAX_ENTRIES = (1ull << 32) - 4096;   // single-build limit of esa_engine.hip
 constexpr u64 MST_MAX_QUERY = (1ull << 32) - 1;
-constexpr u64 UPLOAD_PIECE = 64ull << 20;
 
 enum { W_COMPARED = 0, W_RERUNS, W_WORDS };
 
@@ -51,89 +49,46 @@ __global__ __launch_bounds__(MST_THREADS) void k_mstat(const u8 *enc, u64 n, con
 
 }  // namespace
 
-struct gtamd_mstat {
-  int device = 0;
-  Stream st;             // (before the buffers: they go first)
-  Event ev[2];
-  Dev<u8> own_enc, own_suf;       // an index set from host memory
-  const u8 *enc = nullptr;        // the index: the caller's, an engine's or the two above
-  const void *suf = nullptr;
-  u64 n = 0;
-  u32 suf_bytes = 0, numofchars = 0;
-  bool have_index = false;
+struct gtamd_mstat : ConsumerBase<> {
+  ResidentIndex index;
+  u32 numofchars = 0;
   Dev<u8> query;
   Dev<u32> len;
   Dev<u64> pos;
-  Dev<u64> words;
   gtamd_mstat_info info = gtamd_mstat_info();
 };
 
 namespace {
 
-void drop_index(gtamd_mstat *ms) {
-  ms->have_index = false;
-  ms->own_enc.reset();
-  ms->own_suf.reset();
-  ms->enc = nullptr;
-  ms->suf = nullptr;
-}
+const char FEATURE[] = "matching statistics";
 
-// what every way of setting an index refuses, before anything is touched
-int index_arguments(const gtamd_mstat *ms, const void *enc, u64 n, const void *suf, u32 suf_bytes,
-                    u32 numofchars) {
-  if (ms == nullptr || suf == nullptr || (enc == nullptr && n)) {
+// every way of setting an index: what is refused, before anything is touched
+int set_index(gtamd_mstat *ms, const IndexView &v, u32 numofchars, bool from_host) {
+  if (ms == nullptr || v.suf == nullptr || (v.enc == nullptr && v.n)) {
     gtamd_set_error("invalid argument to gtamd_mstat_set_index");
     return -1;
   }
-  if (suf_bytes != 4 && suf_bytes != 8) {
-    gtamd_set_error("matching statistics: .suf entries of %u bytes, 4 or 8 expected", suf_bytes);
-    return -1;
-  }
+  TRY(refuse_suf_bytes(FEATURE, v.suf_bytes));
   if (numofchars < 1 || numofchars > 253) {
     gtamd_set_error("matching statistics: an alphabet of %u letters, 1 to 253 expected", numofchars);
     return -1;
   }
-  if (n >= MST_MAX_ENTRIES) {
-    gtamd_set_error("matching statistics: sequence of %llu symbols is beyond the limit of a single build "
-                    "(%llu table entries); the slices of a build in parts are not searched",
-                    (unsigned long long) n, (unsigned long long) MST_MAX_ENTRIES);
-    return -1;
-  }
-  return 0;
-}
-
-void take_index(gtamd_mstat *ms, const u8 *enc, u64 n, const void *suf, u32 suf_bytes, u32 numofchars) {
-  ms->enc = enc;
-  ms->n = n;
-  ms->suf = suf;
-  ms->suf_bytes = suf_bytes;
+  TRY(refuse_sizes(FEATURE, v.n, 0));
+  HIP_TRY(hipSetDevice(ms->device));
   ms->numofchars = numofchars;
-  ms->have_index = true;
-}
-
-// host memory -> a device buffer of its own, piece by piece
-int upload(Dev<u8> &d, const void *src, u64 bytes, const char *what) {
-  if (d.alloc(bytes ? bytes : 1) != hipSuccess) {
-    gtamd_set_error("matching statistics: cannot allocate %llu bytes of device memory for %s",
-                    (unsigned long long) bytes, what);
-    return -1;
-  }
-  for (u64 off = 0; off < bytes; off += UPLOAD_PIECE) {
-    const u64 cnt = bytes - off < UPLOAD_PIECE ? bytes - off : UPLOAD_PIECE;
-    HIP_TRY(hipMemcpy((u8 *) d.p + off,(const u8 *) src + off, cnt, hipMemcpyHostToDevice));
-  }
+  if (from_host) return ms->index.upload_from_host(FEATURE, v);
+  ms->index.borrow(v);
   return 0;
 }
 
 u64 held_bytes(const gtamd_mstat *ms) {
-  return ms->own_enc.bytes + ms->own_suf.bytes + ms->query.bytes + ms->len.bytes + ms->pos.bytes +
-         ms->words.bytes;
+  return ms->index.bytes() + ms->query.bytes + ms->len.bytes + ms->pos.bytes + ms->words.bytes;
 }
 
 template <typename S, bool MATSTAT>
 void launch(gtamd_mstat *ms, const u8 *q, u64 m, u32 limit, u32 *len, u64 *pos) {
   k_mstat<S, MATSTAT><<<(u32) div_up(m, MST_TILE), MST_THREADS, 0, ms->st>>>(
-      ms->enc, ms->n, (const S *) ms->suf, q, m, limit, len, pos, ms->words);
+      ms->index.enc, ms->index.n, (const S *) ms->index.suf, q, m, limit, len, pos, ms->words);
 }
 
 int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_device, u32 max_len,
@@ -142,7 +97,7 @@ int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_devi
     gtamd_set_error("invalid argument to gtamd_mstat_%s", matstat ? "matstat" : "uniquesub");
     return -1;
   }
-  if (!ms->have_index) {
+  if (!ms->index.set) {
     gtamd_set_error("matching statistics: no index is set (gtamd_mstat_set_index)");
     return -1;
   }
@@ -175,20 +130,17 @@ int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_devi
   const u32 limit = max_len == 0 || max_len >= MST_MAX_QUERY ? (u32) MST_MAX_QUERY : max_len + 1;
   HIP_TRY(hipMemsetAsync(ms->words, 0, W_WORDS * sizeof(u64), st));
   HIP_TRY(hipEventRecord(ms->ev[0], st));
-  if (ms->suf_bytes == 4) {
+  if (ms->index.suf_bytes == 4) {
     if (matstat) launch<u32, true>(ms, q, m, limit, len, pos); else launch<u32, false>(ms, q, m, limit, len, pos);
   } else {
     if (matstat) launch<u64, true>(ms, q, m, limit, len, pos); else launch<u64, false>(ms, q, m, limit, len, pos);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ms->ev[1], st));
-  if (!out_is_device) {
-    HIP_TRY(hipMemcpyAsync(length_out, len, m * sizeof(u32), hipMemcpyDeviceToHost, st));
-    if (want_pos) HIP_TRY(hipMemcpyAsync(subjectpos_out, pos, m * sizeof(u64), hipMemcpyDeviceToHost, st));
-  }
   u64 h[W_WORDS];
-  HIP_TRY(hipMemcpyAsync(h, ms->words, sizeof h, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  TRY(fetch(st, { { len, length_out, out_is_device ? 0 : m * sizeof(u32) },
+                  { pos, subjectpos_out, out_is_device || !want_pos ? 0 : m * sizeof(u64) },
+                  { ms->words, h, sizeof h } }));
   HIP_TRY(hipEventElapsedTime(&ms->info.device_ms, ms->ev[0], ms->ev[1]));
   ms->info.symbols_compared = h[W_COMPARED];
   ms->info.reruns = (u32) h[W_RERUNS];
@@ -200,29 +152,11 @@ int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_devi
 
 extern "C" gtamd_mstat *gtamd_mstat_create(int device) {
   GTAMD_ABI_BEGIN
-  if (gtamd_device_count() <= device || device < 0) {
-    gtamd_set_error("no HIP device %d available (this library has no CPU fallback)", device);
-    return nullptr;
-  }
-  if (hipSetDevice(device) != hipSuccess) { gtamd_set_error("hipSetDevice(%d) failed", device); return nullptr; }
-  gtamd_mstat *ms = new gtamd_mstat();
-  ms->device = device;
-  if (create(ms->st) != hipSuccess || create(ms->ev[0]) != hipSuccess || create(ms->ev[1]) != hipSuccess ||
-      ms->words.alloc(W_WORDS * sizeof(u64)) != hipSuccess) {
-    gtamd_set_error("cannot create the matching statistics searcher on device %d", device);
-    delete ms;
-    return nullptr;
-  }
-  return ms;
+  return create_consumer<gtamd_mstat>(device, W_WORDS, "the matching statistics searcher");
   GTAMD_ABI_END(nullptr)
 }
 
-extern "C" void gtamd_mstat_destroy(gtamd_mstat *ms) {
-  if (ms == nullptr) return;
-  (void) hipSetDevice(ms->device);
-  (void) hipStreamSynchronize(ms->st);
-  delete ms;
-}
+extern "C" void gtamd_mstat_destroy(gtamd_mstat *ms) { destroy_consumer(ms); }
 
 extern "C" void gtamd_mstat_geometry(uint32_t *tile_positions, uint32_t *word_symbols, uint32_t *word_min) {
   if (tile_positions != nullptr) *tile_positions = MST_TILE;
@@ -233,24 +167,14 @@ extern "C" void gtamd_mstat_geometry(uint32_t *tile_positions, uint32_t *word_sy
 extern "C" int gtamd_mstat_set_index(gtamd_mstat *ms, const uint8_t *enc, uint64_t n, const void *suf,
                                      uint32_t suf_bytes, uint32_t numofchars) {
   GTAMD_ABI_BEGIN
-  TRY(index_arguments(ms, enc, n, suf, suf_bytes, numofchars));
-  HIP_TRY(hipSetDevice(ms->device));
-  drop_index(ms);
-  take_index(ms, enc, n, suf, suf_bytes, numofchars);
-  return 0;
+  return set_index(ms, IndexView{ enc, n, suf, suf_bytes }, numofchars, false);
   GTAMD_ABI_END(-1)
 }
 
 extern "C" int gtamd_mstat_set_index_host(gtamd_mstat *ms, const uint8_t *enc, uint64_t n, const void *suf,
                                           uint32_t suf_bytes, uint32_t numofchars) {
   GTAMD_ABI_BEGIN
-  TRY(index_arguments(ms, enc, n, suf, suf_bytes, numofchars));
-  HIP_TRY(hipSetDevice(ms->device));
-  drop_index(ms);
-  TRY(upload(ms->own_enc, enc, n, "the sequence"));
-  TRY(upload(ms->own_suf, suf, (n + 1) * suf_bytes, "the .suf table"));
-  take_index(ms, ms->own_enc, n, ms->own_suf.p, suf_bytes, numofchars);
-  return 0;
+  return set_index(ms, IndexView{ enc, n, suf, suf_bytes }, numofchars, true);
   GTAMD_ABI_END(-1)
 }
 
@@ -258,20 +182,9 @@ extern "C" int gtamd_mstat_set_index_esa(gtamd_mstat *ms, const gtamd_esa_ctx *e
                                          uint64_t n, uint32_t numofchars) {
   GTAMD_ABI_BEGIN
   if (ms == nullptr || esa == nullptr) { gtamd_set_error("invalid argument to gtamd_mstat_set_index_esa"); return -1; }
-  const void *suf = gtamd_esa_table_device(esa, GTAMD_TAB_SUF);
-  if (suf == nullptr) { gtamd_set_error("matching statistics: the last run did not produce the .suf table"); return -1; }
-  if (gtamd_esa_table_offset(esa) != 0 || gtamd_esa_table_entries(esa, GTAMD_TAB_SUF) != n + 1) {
-    gtamd_set_error("matching statistics: the context holds %llu entries from table index %llu on, not the "
-                    "whole table of %llu symbols; the slices of a build in parts are not searched",
-                    (unsigned long long) gtamd_esa_table_entries(esa, GTAMD_TAB_SUF),
-                    (unsigned long long) gtamd_esa_table_offset(esa), (unsigned long long) n);
-    return -1;
-  }
-  TRY(index_arguments(ms, enc, n, suf, 8, numofchars));
-  HIP_TRY(hipSetDevice(ms->device));
-  drop_index(ms);
-  take_index(ms, enc, n, suf, 8, numofchars);
-  return 0;
+  IndexView v;
+  TRY(engine_tables(FEATURE, esa, enc, n, false, &v));
+  return set_index(ms, v, numofchars, false);
   GTAMD_ABI_END(-1)
 }
 
@@ -292,8 +205,6 @@ extern "C" int gtamd_mstat_uniquesub(gtamd_mstat *ms, const uint8_t *query, uint
 
 extern "C" int gtamd_mstat_get_info(const gtamd_mstat *ms, gtamd_mstat_info *info) {
   GTAMD_ABI_BEGIN
-  if (ms == nullptr || info == nullptr) { gtamd_set_error("invalid argument to gtamd_mstat_get_info"); return -1; }
-  *info = ms->info;
-  return 0;
+  return consumer_info(ms, info, "gtamd_mstat_get_info");
   GTAMD_ABI_END(-1)
 }

@@ -10,6 +10,12 @@ u64 scan_workspace_words(u64 n);
 int scan_u32(int op, const u32 *in, u32 *out, u64 n, bool inclusive, u32 *ws,
              hipStream_t st);
 
+// off[i] = cnt[0] + ... + cnt[i - 1] in 64 bits for i <= count, count >= 1 and
+// at most 2^32 - 256; *total_dev = off[count].  tsum: one word per 256 counts, which
+// holds their sum when the call is made (the kernel that writes cnt fills it) and
+// the sum of the tiles in front of it afterwards.  Two launches, no wait.
+int offsets_u64(const u32 *cnt, u64 count, u64 *tsum, u64 *off, u64 *total_dev, hipStream_t st);
+
 // workspace (u32 words) for sorting n pairs
 u64 radix_workspace_words(u64 n);
 // Stable LSD radix sort of (key, value) pairs (K = u64 or u32 keys) on the digits

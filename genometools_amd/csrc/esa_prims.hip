@@ -99,6 +99,38 @@ int scan_u32(int op, const u32 *in, u32 *out, u64 n, bool inclusive, u32 *ws,
                         : scan_rec<SCAN_MAX>(in, out, n, inclusive, ws, st);
 }
 
+// ---- 64-bit offsets of 32-bit counts ---------------------------------------
+namespace {
+
+// one workgroup: a[i] = sum of a[0..i), *total = the sum of all
+__global__ __launch_bounds__(SC_THREADS) void k_scan64(u64 *a, u64 count, u64 *total) {
+  __shared__ u64 s[SC_THREADS];
+  block_scan_excl_array_u64(a, count, total, s);
+}
+
+// off[i] = the sum of the counts in front of count i; off[count] = the sum of all
+__global__ __launch_bounds__(SC_THREADS) void k_offsets(const u32 *cnt, const u64 *tsum, u64 count, u64 *off) {
+  __shared__ u64 s[SC_THREADS];
+  const u64 i = (u64) blockIdx.x * SC_THREADS + threadIdx.x;
+  const u64 v = i < count ? cnt[i] : 0;
+  const u64 incl = block_scan_incl_u64(v, s) + tsum[blockIdx.x];
+  if (i < count) {
+    off[i] = incl - v;
+    if (i + 1 == count) off[count] = incl;
+  }
+}
+
+}  // namespace
+
+int offsets_u64(const u32 *cnt, u64 count, u64 *tsum, u64 *off, u64 *total_dev, hipStream_t st) {
+  const u64 tiles = div_up(count, SC_THREADS);
+  k_scan64<<<1, SC_THREADS, 0, st>>>(tsum, tiles, total_dev);
+  HIP_TRY(hipGetLastError());
+  k_offsets<<<(u32) tiles, SC_THREADS, 0, st>>>(cnt, tsum, count, off);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // ===========================================================================
 // radix sort
 // ===========================================================================

@@ -5,7 +5,7 @@
 //   a  k_qm_intervals     one lane per query position: the interval of the
 //                         suffixes that start with its L symbols
 //                         (esa_qmatch_core.h), the sum of the widths per tile
-//   b  k_qm_scan64, k_qm_offsets   64-bit exclusive scan of the widths
+//   b  offsets_u64 (esa_prims)     64-bit exclusive scan of the widths
 //   c  k_qm_emit<false>   one lane per candidate of a chunk: the left-maximal
 //                         ones, counted per workgroup; scan (esa_prims)
 //      k_qm_emit<true>    the same lanes extend theirs to the right and write
@@ -14,7 +14,7 @@
 // Every working array has m entries (or one per tile of positions or of
 // candidates of a chunk), none has N.
 #include "esa_common.h"
-#include "esa_own.h"
+#include "esa_index.h"
 #include "esa_prims.h"
 #include "esa_devutil.h"
 #include "esa_qmatch_core.h"
@@ -26,9 +26,7 @@ constexpr int QM_THREADS = SC_THREADS;
 constexpr u32 QM_TILE = QM_THREADS;               // query positions, or candidates, of one workgroup: one a lane
 constexpr u64 QM_MIN_CHUNK = 4 * QM_TILE;         // the smallest chunk of candidates, and capacity
 constexpr u64 QM_MAX_CHUNK = 1ull << 24;          // the largest: 65536 workgroups a launch
-constexpr u64 QM_MAX_ENTRIES = (1ull << 32) - 4096;   // single-build limit of esa_engine.hip
 constexpr u64 QM_MAX_QUERY = (1ull << 32) - 1;
-constexpr u64 UPLOAD_PIECE = 64ull << 20;
 
 enum { W_CANDIDATES = 0, W_SEEDS, W_MAXWIDTH, W_SEARCH, W_EXTENSION, W_WORDS };
 
@@ -67,36 +65,7 @@ __global__ __launch_bounds__(QM_THREADS) void k_qm_intervals(QmInput<S> in, u32 
   }
 }
 
-// ---- step b ----------------------------------------------------------------------
-// one workgroup: a[i] = sum of a[0..i), *total = the sum of all
-__global__ __launch_bounds__(QM_THREADS) void k_qm_scan64(u64 *a, u64 count, u64 *total) {
-  __shared__ u64 s[QM_THREADS];
-  block_scan_excl_array_u64(a, count, total, s);
-}
-
-// off[i] = the candidates in front of position i; off[m] = all
-__global__ __launch_bounds__(QM_THREADS) void k_qm_offsets(const u32 *width, const u64 *tsum, u64 m, u64 *off) {
-  __shared__ u64 s[QM_THREADS];
-  const u64 i = (u64) blockIdx.x * QM_TILE + threadIdx.x;
-  const u64 v = i < m ? width[i] : 0;
-  const u64 incl = block_scan_incl_u64(v, s) + tsum[blockIdx.x];
-  if (i < m) {
-    off[i] = incl - v;
-    if (i + 1 == m) off[m] = incl;
-  }
-}
-
 // ---- step c ----------------------------------------------------------------------
-// the last position of [a, b) whose first candidate is not behind candidate g;
-// off[a] <= g, and off[b] is not read
-__device__ __forceinline__ u64 position_of(const u64 *off, u64 a, u64 b, u64 g) {
-  while (b - a > 1) {
-    const u64 mid = a + (b - a) / 2;
-    if (off[mid] <= g) a = mid; else b = mid;
-  }
-  return a;
-}
-
 // Candidates [c0, c1) of all off[m], QM_TILE a workgroup.  WRITE false:
 // tiles[b] = the number of left-maximal candidates of workgroup b.  WRITE true:
 // tiles[b] is where their records go in out, in candidate order.
@@ -108,14 +77,14 @@ __global__ __launch_bounds__(QM_THREADS) void k_qm_emit(QmInput<S> in, const u32
   __shared__ unsigned long long sext;
   const u64 first = c0 + (u64) blockIdx.x * QM_TILE;
   const u64 last = (c1 - first < QM_TILE ? c1 : first + QM_TILE) - 1;
-  if (threadIdx.x < 2) span[threadIdx.x] = position_of(off, 0, in.m, threadIdx.x == 0 ? first : last);
+  if (threadIdx.x < 2) span[threadIdx.x] = entry_of(off, 0, in.m, threadIdx.x == 0 ? first : last);
   if (threadIdx.x == 0) sext = 0;
   __syncthreads();
   const u64 g = first + threadIdx.x;
   bool keep = false;
   QmRecord rec = { 0, 0, 0 };
   if (g <= last) {
-    const u64 i = position_of(off, span[0], span[1] + 1, g);
+    const u64 i = entry_of(off, span[0], span[1] + 1, g);
     Lane c = { in.q, in.m, i, in.enc, in.n, 0 };
     u64 p;
     keep = qm_kept(c, in.suf, lo[i], (u32) (g - off[i]), &p);
@@ -147,82 +116,42 @@ __global__ __launch_bounds__(QM_THREADS) void k_qm_emit(QmInput<S> in, const u32
 
 }  // namespace
 
-struct gtamd_qmatch {
-  int device = 0;
-  Stream st;             // (before the buffers: they go first)
-  Event ev[2];
-  Dev<u8> own_enc, own_suf;       // an index set from host memory
-  const u8 *enc = nullptr;        // the index: the caller's, an engine's or the two above
-  const void *suf = nullptr;
-  u64 n = 0;
-  u32 suf_bytes = 0;
-  bool have_index = false, prepared = false;
+struct gtamd_qmatch : ConsumerBase<> {
+  ResidentIndex index;
+  bool prepared = false;
   // what a prepare leaves for the emit calls
   Dev<u8> own_query;
   const u8 *q = nullptr;
   u64 m = 0;
   u32 L = 0;
   Dev<u32> lo, width, tiles, scanws;
-  Dev<u64> tsum, off, words;
+  Dev<u64> tsum, off;
   Dev<u8> out;                    // records on their way to host memory
   gtamd_qmatch_info info = gtamd_qmatch_info();
 };
 
 namespace {
 
-void drop_index(gtamd_qmatch *qm) {
-  qm->have_index = qm->prepared = false;
-  qm->own_enc.reset();
-  qm->own_suf.reset();
-  qm->enc = nullptr;
-  qm->suf = nullptr;
-}
+const char FEATURE[] = "query matches";
 
-// what every way of setting an index refuses, before anything is touched
-int index_arguments(const gtamd_qmatch *qm, const void *enc, u64 n, const void *suf, u32 suf_bytes) {
-  if (qm == nullptr || suf == nullptr || (enc == nullptr && n)) {
+// every way of setting an index: what is refused, before anything is touched
+int set_index(gtamd_qmatch *qm, const IndexView &v, bool from_host) {
+  if (qm == nullptr || v.suf == nullptr || (v.enc == nullptr && v.n)) {
     gtamd_set_error("invalid argument to gtamd_qmatch_set_index");
     return -1;
   }
-  if (suf_bytes != 4 && suf_bytes != 8) {
-    gtamd_set_error("query matches: .suf entries of %u bytes, 4 or 8 expected", suf_bytes);
-    return -1;
-  }
-  if (n >= QM_MAX_ENTRIES) {
-    gtamd_set_error("query matches: sequence of %llu symbols is beyond the limit of a single build "
-                    "(%llu table entries); the slices of a build in parts are not searched",
-                    (unsigned long long) n, (unsigned long long) QM_MAX_ENTRIES);
-    return -1;
-  }
-  return 0;
-}
-
-void take_index(gtamd_qmatch *qm, const u8 *enc, u64 n, const void *suf, u32 suf_bytes) {
-  qm->enc = enc;
-  qm->n = n;
-  qm->suf = suf;
-  qm->suf_bytes = suf_bytes;
-  qm->have_index = true;
+  TRY(refuse_suf_bytes(FEATURE, v.suf_bytes));
+  TRY(refuse_sizes(FEATURE, v.n, 0));
+  HIP_TRY(hipSetDevice(qm->device));
   qm->prepared = false;
-}
-
-// host memory -> a device buffer of its own, piece by piece
-int upload(Dev<u8> &d, const void *src, u64 bytes, const char *what) {
-  if (d.alloc(bytes ? bytes : 1) != hipSuccess) {
-    gtamd_set_error("query matches: cannot allocate %llu bytes of device memory for %s",
-                    (unsigned long long) bytes, what);
-    return -1;
-  }
-  for (u64 off = 0; off < bytes; off += UPLOAD_PIECE) {
-    const u64 cnt = bytes - off < UPLOAD_PIECE ? bytes - off : UPLOAD_PIECE;
-    HIP_TRY(hipMemcpy((u8 *) d.p + off, (const u8 *) src + off, cnt, hipMemcpyHostToDevice));
-  }
+  if (from_host) return qm->index.upload_from_host(FEATURE, v);
+  qm->index.borrow(v);
   return 0;
 }
 
 u64 held_bytes(const gtamd_qmatch *qm) {
-  return qm->own_enc.bytes + qm->own_suf.bytes + qm->own_query.bytes + qm->lo.bytes + qm->width.bytes +
-         qm->tiles.bytes + qm->scanws.bytes + qm->tsum.bytes + qm->off.bytes + qm->words.bytes + qm->out.bytes;
+  return qm->index.bytes() + qm->own_query.bytes + qm->lo.bytes + qm->width.bytes + qm->tiles.bytes +
+         qm->scanws.bytes + qm->tsum.bytes + qm->off.bytes + qm->words.bytes + qm->out.bytes;
 }
 
 int out_of_memory(u64 entries, const char *of) {
@@ -231,26 +160,22 @@ int out_of_memory(u64 entries, const char *of) {
 }
 
 template <typename S> QmInput<S> input(const gtamd_qmatch *qm) {
-  return QmInput<S>{ qm->enc, qm->n, (const S *) qm->suf, qm->q, qm->m, qm->L };
+  return QmInput<S>{ qm->index.enc, qm->index.n, (const S *) qm->index.suf, qm->q, qm->m, qm->L };
 }
 
 template <typename S> int prepare(gtamd_qmatch *qm) {
   hipStream_t st = qm->st;
-  const u64 m = qm->m, T = div_up(m, QM_TILE);
+  const u64 m = qm->m;
   HIP_TRY(hipMemsetAsync(qm->words, 0, W_WORDS * sizeof(u64), st));
   HIP_TRY(hipEventRecord(qm->ev[0], st));
   if (m != 0) {
-    k_qm_intervals<S><<<(u32) T, QM_THREADS, 0, st>>>(input<S>(qm), qm->lo, qm->width, qm->tsum, qm->words);
+    k_qm_intervals<S><<<(u32) div_up(m, QM_TILE), QM_THREADS, 0, st>>>(input<S>(qm), qm->lo, qm->width, qm->tsum, qm->words);
     HIP_TRY(hipGetLastError());
-    k_qm_scan64<<<1, QM_THREADS, 0, st>>>(qm->tsum, T, qm->words + W_CANDIDATES);
-    HIP_TRY(hipGetLastError());
-    k_qm_offsets<<<(u32) T, QM_THREADS, 0, st>>>(qm->width, qm->tsum, m, qm->off);
-    HIP_TRY(hipGetLastError());
+    TRY(offsets_u64(qm->width, m, qm->tsum, qm->off, qm->words + W_CANDIDATES, st));
   }
   HIP_TRY(hipEventRecord(qm->ev[1], st));
   u64 h[W_WORDS];
-  HIP_TRY(hipMemcpyAsync(h, qm->words, sizeof h, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  TRY(fetch(st, { { qm->words, h, sizeof h } }));
   HIP_TRY(hipEventElapsedTime(&qm->info.device_ms, qm->ev[0], qm->ev[1]));
   qm->info.positions = m;
   qm->info.seeds = h[W_SEEDS];
@@ -276,9 +201,7 @@ template <typename S> int emit_chunk(gtamd_qmatch *qm, u64 c0, u64 c1, QmRecord 
                                                           qm->words);
   HIP_TRY(hipGetLastError());
   u32 total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, qm->tiles + blocks, sizeof total, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(extension, qm->words + W_EXTENSION, sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  TRY(fetch(st, { { qm->tiles + blocks, &total, sizeof total }, { qm->words + W_EXTENSION, extension, sizeof(u64) } }));
   *kept = total;
   return 0;
 }
@@ -298,26 +221,21 @@ int emit(gtamd_qmatch *qm, u64 *cursor, gtamd_qmatch_record *out, u64 capacity, 
     return -1;
   }
   if (cur == C) return 0;
-  QmRecord *dst = (QmRecord *) out;
-  if (!out_on_device) {
-    const u64 most = capacity < C - cur ? capacity : C - cur;
-    if (qm->out.grow(most * sizeof(QmRecord)) != hipSuccess) return out_of_memory(most, "records");
-    dst = (QmRecord *) qm->out.p;
-  }
+  RecordStage<QmRecord> stage(out, out_on_device);
+  const u64 most = capacity < C - cur ? capacity : C - cur;
+  if (stage.begin(qm->out, most) != hipSuccess) return out_of_memory(most, "records");
+  QmRecord *dst = stage.dst;
   // a chunk of `room` candidates gives at most `room` records
   while (cur < C && capacity - total >= QM_MIN_CHUNK) {
     u64 chunk = capacity - total, kept = 0;
     if (chunk > C - cur) chunk = C - cur;
     if (chunk > QM_MAX_CHUNK) chunk = QM_MAX_CHUNK;
-    TRY(qm->suf_bytes == 4 ? emit_chunk<u32>(qm, cur, cur + chunk, dst + total, &kept, &qm->info.extension_symbols)
+    TRY(qm->index.suf_bytes == 4 ? emit_chunk<u32>(qm, cur, cur + chunk, dst + total, &kept, &qm->info.extension_symbols)
                            : emit_chunk<u64>(qm, cur, cur + chunk, dst + total, &kept, &qm->info.extension_symbols));
     total += kept;
     cur += chunk;
   }
-  if (!out_on_device && total) {
-    HIP_TRY(hipMemcpyAsync(out, dst, total * sizeof(QmRecord), hipMemcpyDeviceToHost, qm->st));
-    HIP_TRY(hipStreamSynchronize(qm->st));
-  }
+  if (!out_on_device && total) TRY(stage.finish(total, qm->st));      // (every chunk has waited for its own)
   qm->info.matches += total;
   *cursor = cur;
   *written = total;
@@ -328,29 +246,11 @@ int emit(gtamd_qmatch *qm, u64 *cursor, gtamd_qmatch_record *out, u64 capacity, 
 
 extern "C" gtamd_qmatch *gtamd_qmatch_create(int device) {
   GTAMD_ABI_BEGIN
-  if (gtamd_device_count() <= device || device < 0) {
-    gtamd_set_error("no HIP device %d available (this library has no CPU fallback)", device);
-    return nullptr;
-  }
-  if (hipSetDevice(device) != hipSuccess) { gtamd_set_error("hipSetDevice(%d) failed", device); return nullptr; }
-  gtamd_qmatch *qm = new gtamd_qmatch();
-  qm->device = device;
-  if (create(qm->st) != hipSuccess || create(qm->ev[0]) != hipSuccess || create(qm->ev[1]) != hipSuccess ||
-      qm->words.alloc(W_WORDS * sizeof(u64)) != hipSuccess) {
-    gtamd_set_error("cannot create the query matcher on device %d", device);
-    delete qm;
-    return nullptr;
-  }
-  return qm;
+  return create_consumer<gtamd_qmatch>(device, W_WORDS, "the query matcher");
   GTAMD_ABI_END(nullptr)
 }
 
-extern "C" void gtamd_qmatch_destroy(gtamd_qmatch *qm) {
-  if (qm == nullptr) return;
-  (void) hipSetDevice(qm->device);
-  (void) hipStreamSynchronize(qm->st);
-  delete qm;
-}
+extern "C" void gtamd_qmatch_destroy(gtamd_qmatch *qm) { destroy_consumer(qm); }
 
 extern "C" void gtamd_qmatch_geometry(uint32_t *tile_positions, uint64_t *min_capacity) {
   if (tile_positions != nullptr) *tile_positions = QM_TILE;
@@ -360,24 +260,14 @@ extern "C" void gtamd_qmatch_geometry(uint32_t *tile_positions, uint64_t *min_ca
 extern "C" int gtamd_qmatch_set_index(gtamd_qmatch *qm, const uint8_t *enc, uint64_t n, const void *suf,
                                       uint32_t suf_bytes) {
   GTAMD_ABI_BEGIN
-  TRY(index_arguments(qm, enc, n, suf, suf_bytes));
-  HIP_TRY(hipSetDevice(qm->device));
-  drop_index(qm);
-  take_index(qm, enc, n, suf, suf_bytes);
-  return 0;
+  return set_index(qm, IndexView{ enc, n, suf, suf_bytes }, false);
   GTAMD_ABI_END(-1)
 }
 
 extern "C" int gtamd_qmatch_set_index_host(gtamd_qmatch *qm, const uint8_t *enc, uint64_t n, const void *suf,
                                            uint32_t suf_bytes) {
   GTAMD_ABI_BEGIN
-  TRY(index_arguments(qm, enc, n, suf, suf_bytes));
-  HIP_TRY(hipSetDevice(qm->device));
-  drop_index(qm);
-  TRY(upload(qm->own_enc, enc, n, "the sequence"));
-  TRY(upload(qm->own_suf, suf, (n + 1) * suf_bytes, "the .suf table"));
-  take_index(qm, qm->own_enc, n, qm->own_suf.p, suf_bytes);
-  return 0;
+  return set_index(qm, IndexView{ enc, n, suf, suf_bytes }, true);
   GTAMD_ABI_END(-1)
 }
 
@@ -385,20 +275,9 @@ extern "C" int gtamd_qmatch_set_index_esa(gtamd_qmatch *qm, const gtamd_esa_ctx 
                                           uint64_t n) {
   GTAMD_ABI_BEGIN
   if (qm == nullptr || esa == nullptr) { gtamd_set_error("invalid argument to gtamd_qmatch_set_index_esa"); return -1; }
-  const void *suf = gtamd_esa_table_device(esa, GTAMD_TAB_SUF);
-  if (suf == nullptr) { gtamd_set_error("query matches: the last run did not produce the .suf table"); return -1; }
-  if (gtamd_esa_table_offset(esa) != 0 || gtamd_esa_table_entries(esa, GTAMD_TAB_SUF) != n + 1) {
-    gtamd_set_error("query matches: the context holds %llu entries from table index %llu on, not the "
-                    "whole table of %llu symbols; the slices of a build in parts are not searched",
-                    (unsigned long long) gtamd_esa_table_entries(esa, GTAMD_TAB_SUF),
-                    (unsigned long long) gtamd_esa_table_offset(esa), (unsigned long long) n);
-    return -1;
-  }
-  TRY(index_arguments(qm, enc, n, suf, 8));
-  HIP_TRY(hipSetDevice(qm->device));
-  drop_index(qm);
-  take_index(qm, enc, n, suf, 8);
-  return 0;
+  IndexView v;
+  TRY(engine_tables(FEATURE, esa, enc, n, false, &v));
+  return set_index(qm, v, false);
   GTAMD_ABI_END(-1)
 }
 
@@ -406,7 +285,7 @@ extern "C" int gtamd_qmatch_prepare(gtamd_qmatch *qm, const uint8_t *query, uint
                                     uint32_t min_len, gtamd_qmatch_info *info) {
   GTAMD_ABI_BEGIN
   if (qm == nullptr || (query == nullptr && m)) { gtamd_set_error("invalid argument to gtamd_qmatch_prepare"); return -1; }
-  if (!qm->have_index) {
+  if (!qm->index.set) {
     gtamd_set_error("query matches: no index is set (gtamd_qmatch_set_index)");
     return -1;
   }
@@ -434,7 +313,7 @@ extern "C" int gtamd_qmatch_prepare(gtamd_qmatch *qm, const uint8_t *query, uint
   }
   qm->m = m;
   qm->L = min_len;
-  TRY(qm->suf_bytes == 4 ? prepare<u32>(qm) : prepare<u64>(qm));
+  TRY(qm->index.suf_bytes == 4 ? prepare<u32>(qm) : prepare<u64>(qm));
   qm->info.device_bytes = held_bytes(qm);
   qm->prepared = true;
   if (info != nullptr) *info = qm->info;
@@ -462,8 +341,6 @@ extern "C" int gtamd_qmatch_emit(gtamd_qmatch *qm, uint64_t *cursor, gtamd_qmatc
 
 extern "C" int gtamd_qmatch_get_info(const gtamd_qmatch *qm, gtamd_qmatch_info *info) {
   GTAMD_ABI_BEGIN
-  if (qm == nullptr || info == nullptr) { gtamd_set_error("invalid argument to gtamd_qmatch_get_info"); return -1; }
-  *info = qm->info;
-  return 0;
+  return consumer_info(qm, info, "gtamd_qmatch_get_info");
   GTAMD_ABI_END(-1)
 }

@@ -8,14 +8,14 @@
 //         k_sp_select<true>    the same lanes write the three lists, in order
 //   3     k_sp_intervals       one lane per terminal suffix: its interval
 //                              (esa_spm_core.h) and the read starts inside it
-//   4     k_sp_scan64, k_sp_offsets   64-bit exclusive scan of those numbers
+//   4     offsets_u64 (esa_prims)     64-bit exclusive scan of those numbers
 //   5     k_sp_emit            one lane per (terminal suffix, read start) pair
 //                              of a chunk: every one is a record
 //
 // Every working array has one entry per terminal suffix, per read start, per
 // separator or per tile; none has N.
 #include "esa_common.h"
-#include "esa_own.h"
+#include "esa_index.h"
 #include "esa_prims.h"
 #include "esa_devutil.h"
 #include "esa_spm_core.h"
@@ -30,8 +30,6 @@ constexpr u32 SP_SEL_TILE = SP_THREADS * SP_PER;  // items of one workgroup ther
 constexpr u32 SP_TILE = SP_THREADS;               // terminal suffixes, or candidates, of one workgroup: one a lane
 constexpr u64 SP_MIN_CAPACITY = SP_TILE;          // the smallest capacity of an emit call
 constexpr u64 SP_MAX_CHUNK = 1ull << 24;          // candidates of one launch: 65536 workgroups
-constexpr u64 SP_MAX_ENTRIES = (1ull << 32) - 4096;   // single-build limit of esa_engine.hip
-constexpr u64 UPLOAD_PIECE = 64ull << 20;
 
 enum { K_TERMINAL = 0, K_START, K_SEPARATOR, K_KINDS };
 enum { W_MATCHES = 0, W_MAXWIDTH, W_MAXCOUNT, W_SEARCH, W_WORDS };
@@ -127,36 +125,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_intervals(SpIndex<S> x, const
   }
 }
 
-// ---- step 4 ----------------------------------------------------------------------
-// one workgroup: a[i] = sum of a[0..i), *total = the sum of all
-__global__ __launch_bounds__(SP_THREADS) void k_sp_scan64(u64 *a, u64 count, u64 *total) {
-  __shared__ u64 s[SP_THREADS];
-  block_scan_excl_array_u64(a, count, total, s);
-}
-
-// off[k] = the records in front of terminal suffix k; off[M] = all
-__global__ __launch_bounds__(SP_THREADS) void k_sp_offsets(const u32 *cnt, const u64 *tsum, u32 M, u64 *off) {
-  __shared__ u64 s[SP_THREADS];
-  const u64 k = (u64) blockIdx.x * SP_TILE + threadIdx.x;
-  const u64 v = k < M ? cnt[k] : 0;
-  const u64 incl = block_scan_incl_u64(v, s) + tsum[blockIdx.x];
-  if (k < M) {
-    off[k] = incl - v;
-    if (k + 1 == M) off[M] = incl;
-  }
-}
-
 // ---- step 5 ----------------------------------------------------------------------
-// the last terminal suffix of [a, b) whose first record is not behind record g;
-// off[a] <= g, and off[b] is not read
-__device__ __forceinline__ u64 suffix_of(const u64 *off, u64 a, u64 b, u64 g) {
-  while (b - a > 1) {
-    const u64 mid = a + (b - a) / 2;
-    if (off[mid] <= g) a = mid; else b = mid;
-  }
-  return a;
-}
-
 // records [c0, c1) of all off[M] to out, SP_TILE a workgroup
 template <typename S>
 __global__ __launch_bounds__(SP_THREADS) void k_sp_emit(SpIndex<S> x, SpLists l, const u32 *first, const u64 *off, u32 M,
@@ -164,11 +133,11 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_emit(SpIndex<S> x, SpLists l,
   __shared__ u64 span[2];                 // the terminal suffixes of the workgroup's first and last record
   const u64 g0 = c0 + (u64) blockIdx.x * SP_TILE;
   const u64 last = (c1 - g0 < SP_TILE ? c1 : g0 + SP_TILE) - 1;
-  if (threadIdx.x < 2) span[threadIdx.x] = suffix_of(off, 0, M, threadIdx.x == 0 ? g0 : last);
+  if (threadIdx.x < 2) span[threadIdx.x] = entry_of(off, 0, M, threadIdx.x == 0 ? g0 : last);
   __syncthreads();
   const u64 g = g0 + threadIdx.x;
   if (g > last) return;
-  const u64 k = suffix_of(off, span[0], span[1] + 1, g);
+  const u64 k = entry_of(off, span[0], span[1] + 1, g);
   SpRecord rec;
   sp_record(x, l.starts, l.seps, nseps, l.idx[k], l.len[k], first[k], g - off[k], &rec);
   out[g - c0] = rec;
@@ -176,22 +145,12 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_emit(SpIndex<S> x, SpLists l,
 
 }  // namespace
 
-struct gtamd_spm {
-  int device = 0;
-  Stream st;             // (before the buffers: they go first)
-  Event ev[2];
-  Dev<u8> own_enc, own_suf, own_lcp;   // an index set from host memory
-  Dev<u64> own_llv;
-  const u8 *enc = nullptr;             // the index: the caller's, an engine's or the four above
-  const void *suf = nullptr;
-  const u8 *lcp = nullptr;
-  const u64 *llv = nullptr;
-  u64 n = 0, llv_pairs = 0;
-  u32 suf_bytes = 0;
-  bool have_index = false, prepared = false;
+struct gtamd_spm : ConsumerBase<> {
+  ResidentIndex index;
+  bool prepared = false;
   // what a prepare leaves for the emit calls
   Dev<u32> tiles, scanws, idx, len, starts, seps, first, cnt;
-  Dev<u64> tsum, off, words;
+  Dev<u64> tsum, off;
   Dev<u8> out;                         // records on their way to host memory
   u32 M = 0, R = 0, nseps = 0;
   gtamd_spm_info info = gtamd_spm_info();
@@ -199,67 +158,31 @@ struct gtamd_spm {
 
 namespace {
 
-void drop_index(gtamd_spm *sp) {
-  sp->have_index = sp->prepared = false;
-  sp->own_enc.reset(); sp->own_suf.reset(); sp->own_lcp.reset(); sp->own_llv.reset();
-  sp->enc = nullptr; sp->suf = nullptr; sp->lcp = nullptr; sp->llv = nullptr;
-}
+const char FEATURE[] = "suffix-prefix matches";
 
-// what every way of setting an index refuses, before anything is touched
-int index_arguments(const gtamd_spm *sp, const void *enc, u64 n, const void *suf, u32 suf_bytes, const void *lcp,
-                    const void *llv, u64 llv_pairs) {
-  if (sp == nullptr || suf == nullptr || (enc == nullptr && n) || (llv == nullptr && llv_pairs)) {
+// every way of setting an index: what is refused, before anything is touched
+int set_index(gtamd_spm *sp, const IndexView &v, bool from_host) {
+  if (sp == nullptr || v.suf == nullptr || (v.enc == nullptr && v.n) || (v.llv == nullptr && v.llv_pairs)) {
     gtamd_set_error("invalid argument to gtamd_spm_set_index");
     return -1;
   }
-  if (lcp == nullptr) {
+  if (v.lcp == nullptr) {
     gtamd_set_error("suffix-prefix matches: no .lcp table is given: the matches are found from .suf and .lcp together");
     return -1;
   }
-  if (suf_bytes != 4 && suf_bytes != 8) {
-    gtamd_set_error("suffix-prefix matches: .suf entries of %u bytes, 4 or 8 expected", suf_bytes);
-    return -1;
-  }
-  if (n >= SP_MAX_ENTRIES) {
-    gtamd_set_error("suffix-prefix matches: sequence of %llu symbols is beyond the limit of a single build "
-                    "(%llu table entries); the slices of a build in parts are not searched",
-                    (unsigned long long) n, (unsigned long long) SP_MAX_ENTRIES);
-    return -1;
-  }
-  if (llv_pairs > n) {
-    gtamd_set_error("suffix-prefix matches: %llu .llv pairs for %llu symbols", (unsigned long long) llv_pairs,
-                    (unsigned long long) n);
-    return -1;
-  }
-  return 0;
-}
-
-void take_index(gtamd_spm *sp, const u8 *enc, u64 n, const void *suf, u32 suf_bytes, const u8 *lcp, const u64 *llv,
-                u64 llv_pairs) {
-  sp->enc = enc; sp->n = n; sp->suf = suf; sp->suf_bytes = suf_bytes;
-  sp->lcp = lcp; sp->llv = llv; sp->llv_pairs = llv_pairs;
-  sp->have_index = true;
+  TRY(refuse_suf_bytes(FEATURE, v.suf_bytes));
+  TRY(refuse_sizes(FEATURE, v.n, v.llv_pairs));
+  HIP_TRY(hipSetDevice(sp->device));
   sp->prepared = false;
-}
-
-// host memory -> a device buffer of its own, piece by piece
-template <typename T> int upload(Dev<T> &d, const void *src, u64 bytes, const char *what) {
-  if (d.alloc(bytes ? bytes : 1) != hipSuccess) {
-    gtamd_set_error("suffix-prefix matches: cannot allocate %llu bytes of device memory for %s",
-                    (unsigned long long) bytes, what);
-    return -1;
-  }
-  for (u64 off = 0; off < bytes; off += UPLOAD_PIECE) {
-    const u64 cnt = bytes - off < UPLOAD_PIECE ? bytes - off : UPLOAD_PIECE;
-    HIP_TRY(hipMemcpy((u8 *) d.p + off, (const u8 *) src + off, cnt, hipMemcpyHostToDevice));
-  }
+  if (from_host) return sp->index.upload_from_host(FEATURE, v);
+  sp->index.borrow(v);
   return 0;
 }
 
 u64 held_bytes(const gtamd_spm *sp) {
-  return sp->own_enc.bytes + sp->own_suf.bytes + sp->own_lcp.bytes + sp->own_llv.bytes + sp->tiles.bytes +
-         sp->scanws.bytes + sp->idx.bytes + sp->len.bytes + sp->starts.bytes + sp->seps.bytes + sp->first.bytes +
-         sp->cnt.bytes + sp->tsum.bytes + sp->off.bytes + sp->words.bytes + sp->out.bytes;
+  return sp->index.bytes() + sp->tiles.bytes + sp->scanws.bytes + sp->idx.bytes + sp->len.bytes + sp->starts.bytes +
+         sp->seps.bytes + sp->first.bytes + sp->cnt.bytes + sp->tsum.bytes + sp->off.bytes + sp->words.bytes +
+         sp->out.bytes;
 }
 
 int out_of_memory(u64 entries, const char *of) {
@@ -268,14 +191,15 @@ int out_of_memory(u64 entries, const char *of) {
 }
 
 template <typename S> SpIndex<S> view(const gtamd_spm *sp) {
-  return SpIndex<S>{ sp->enc, sp->n, (const S *) sp->suf, sp->lcp, sp->llv, sp->llv_pairs };
+  const ResidentIndex &x = sp->index;
+  return SpIndex<S>{ x.enc, x.n, (const S *) x.suf, x.lcp, x.llv, x.llv_pairs };
 }
 
 SpLists lists(const gtamd_spm *sp) { return SpLists{ sp->idx, sp->len, sp->starts, sp->seps }; }
 
 template <typename S> int prepare(gtamd_spm *sp, u32 L) {
   hipStream_t st = sp->st;
-  const u64 N = sp->n + 1, T = div_up(N, SP_SEL_TILE), stride = T + 1;
+  const u64 N = sp->index.n + 1, T = div_up(N, SP_SEL_TILE), stride = T + 1;
   if (sp->tiles.grow(K_KINDS * stride * sizeof(u32)) != hipSuccess ||
       sp->scanws.grow(scan_workspace_words(stride) * sizeof(u32)) != hipSuccess)
     return out_of_memory(stride, "tiles");
@@ -286,13 +210,11 @@ template <typename S> int prepare(gtamd_spm *sp, u32 L) {
   // 1, 2: the terminal suffixes, the read starts, the separators
   k_sp_select<S, false><<<(u32) T, SP_THREADS, 0, st>>>(view<S>(sp), L, sp->tiles, stride, SpLists());
   HIP_TRY(hipGetLastError());
-  u32 total[K_KINDS];
-  for (u32 k = 0; k < K_KINDS; k++) {
+  for (u32 k = 0; k < K_KINDS; k++)
     TRY(scan_u32(SCAN_SUM, sp->tiles + k * stride, sp->tiles + k * stride, stride, false, sp->scanws, st));
-    HIP_TRY(hipMemcpyAsync(&total[k], sp->tiles + k * stride + T, sizeof(u32), hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  const u32 M = total[K_TERMINAL], R = total[K_START], nseps = total[K_SEPARATOR];
+  u32 M, R, nseps;
+  TRY(fetch(st, { { sp->tiles + K_TERMINAL * stride + T, &M, sizeof M }, { sp->tiles + K_START * stride + T, &R, sizeof R },
+                  { sp->tiles + K_SEPARATOR * stride + T, &nseps, sizeof nseps } }));
   const u32 tiles = (u32) div_up(M, SP_TILE);
   if (sp->idx.grow((M ? (u64) M : 1) * 4) != hipSuccess || sp->len.grow((M ? (u64) M : 1) * 4) != hipSuccess ||
       sp->first.grow((M ? (u64) M : 1) * 4) != hipSuccess || sp->cnt.grow((M ? (u64) M : 1) * 4) != hipSuccess ||
@@ -309,15 +231,11 @@ template <typename S> int prepare(gtamd_spm *sp, u32 L) {
     k_sp_intervals<S><<<tiles, SP_THREADS, 0, st>>>(view<S>(sp), sp->idx, sp->len, M, sp->starts, R, sp->first, sp->cnt,
                                                    sp->tsum, sp->words);
     HIP_TRY(hipGetLastError());
-    k_sp_scan64<<<1, SP_THREADS, 0, st>>>(sp->tsum, tiles, sp->words + W_MATCHES);
-    HIP_TRY(hipGetLastError());
-    k_sp_offsets<<<tiles, SP_THREADS, 0, st>>>(sp->cnt, sp->tsum, M, sp->off);
-    HIP_TRY(hipGetLastError());
+    TRY(offsets_u64(sp->cnt, M, sp->tsum, sp->off, sp->words + W_MATCHES, st));
   }
   HIP_TRY(hipEventRecord(sp->ev[1], st));
   u64 h[W_WORDS];
-  HIP_TRY(hipMemcpyAsync(h, sp->words, sizeof h, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  TRY(fetch(st, { { sp->words, h, sizeof h } }));
   HIP_TRY(hipEventElapsedTime(&sp->info.device_ms, sp->ev[0], sp->ev[1]));
   sp->info.table_entries = N;
   sp->info.terminal_suffixes = M;
@@ -355,14 +273,11 @@ int emit(gtamd_spm *sp, u64 *cursor, gtamd_spm_record *out, u64 capacity, int ou
   }
   if (cur == Z) return 0;
   const u64 count = capacity < Z - cur ? capacity : Z - cur;
-  SpRecord *dst = (SpRecord *) out;
-  if (!out_on_device) {
-    if (sp->out.grow(count * sizeof(SpRecord)) != hipSuccess) return out_of_memory(count, "records");
-    dst = (SpRecord *) sp->out.p;
-  }
-  TRY(sp->suf_bytes == 4 ? emit_records<u32>(sp, cur, count, dst) : emit_records<u64>(sp, cur, count, dst));
-  if (!out_on_device) HIP_TRY(hipMemcpyAsync(out, dst, count * sizeof(SpRecord), hipMemcpyDeviceToHost, sp->st));
-  HIP_TRY(hipStreamSynchronize(sp->st));
+  RecordStage<SpRecord> stage(out, out_on_device);
+  if (stage.begin(sp->out, count) != hipSuccess) return out_of_memory(count, "records");
+  TRY(sp->index.suf_bytes == 4 ? emit_records<u32>(sp, cur, count, stage.dst)
+                               : emit_records<u64>(sp, cur, count, stage.dst));
+  TRY(stage.finish(count, sp->st));
   *cursor = cur + count;
   *written = count;
   return 0;
@@ -372,29 +287,11 @@ int emit(gtamd_spm *sp, u64 *cursor, gtamd_spm_record *out, u64 capacity, int ou
 
 extern "C" gtamd_spm *gtamd_spm_create(int device) {
   GTAMD_ABI_BEGIN
-  if (gtamd_device_count() <= device || device < 0) {
-    gtamd_set_error("no HIP device %d available (this library has no CPU fallback)", device);
-    return nullptr;
-  }
-  if (hipSetDevice(device) != hipSuccess) { gtamd_set_error("hipSetDevice(%d) failed", device); return nullptr; }
-  gtamd_spm *sp = new gtamd_spm();
-  sp->device = device;
-  if (create(sp->st) != hipSuccess || create(sp->ev[0]) != hipSuccess || create(sp->ev[1]) != hipSuccess ||
-      sp->words.alloc(W_WORDS * sizeof(u64)) != hipSuccess) {
-    gtamd_set_error("cannot create the suffix-prefix matcher on device %d", device);
-    delete sp;
-    return nullptr;
-  }
-  return sp;
+  return create_consumer<gtamd_spm>(device, W_WORDS, "the suffix-prefix matcher");
   GTAMD_ABI_END(nullptr)
 }
 
-extern "C" void gtamd_spm_destroy(gtamd_spm *sp) {
-  if (sp == nullptr) return;
-  (void) hipSetDevice(sp->device);
-  (void) hipStreamSynchronize(sp->st);
-  delete sp;
-}
+extern "C" void gtamd_spm_destroy(gtamd_spm *sp) { destroy_consumer(sp); }
 
 extern "C" void gtamd_spm_geometry(uint32_t *tile_suffixes, uint64_t *min_capacity) {
   if (tile_suffixes != nullptr) *tile_suffixes = SP_TILE;
@@ -404,11 +301,7 @@ extern "C" void gtamd_spm_geometry(uint32_t *tile_suffixes, uint64_t *min_capaci
 extern "C" int gtamd_spm_set_index(gtamd_spm *sp, const uint8_t *enc, uint64_t n, const void *suf, uint32_t suf_bytes,
                                    const uint8_t *lcp, const uint64_t *llv, uint64_t llv_pairs) {
   GTAMD_ABI_BEGIN
-  TRY(index_arguments(sp, enc, n, suf, suf_bytes, lcp, llv, llv_pairs));
-  HIP_TRY(hipSetDevice(sp->device));
-  drop_index(sp);
-  take_index(sp, enc, n, suf, suf_bytes, lcp, llv, llv_pairs);
-  return 0;
+  return set_index(sp, IndexView{ enc, n, suf, suf_bytes, lcp, llv, llv_pairs }, false);
   GTAMD_ABI_END(-1)
 }
 
@@ -416,48 +309,23 @@ extern "C" int gtamd_spm_set_index_host(gtamd_spm *sp, const uint8_t *enc, uint6
                                         uint32_t suf_bytes, const uint8_t *lcp, const uint64_t *llv,
                                         uint64_t llv_pairs) {
   GTAMD_ABI_BEGIN
-  TRY(index_arguments(sp, enc, n, suf, suf_bytes, lcp, llv, llv_pairs));
-  HIP_TRY(hipSetDevice(sp->device));
-  drop_index(sp);
-  TRY(upload(sp->own_enc, enc, n, "the sequence"));
-  TRY(upload(sp->own_suf, suf, (n + 1) * suf_bytes, "the .suf table"));
-  TRY(upload(sp->own_lcp, lcp, n + 1, "the .lcp table"));
-  TRY(upload(sp->own_llv, llv, llv_pairs * 16, "the .llv table"));
-  take_index(sp, sp->own_enc, n, sp->own_suf.p, suf_bytes, sp->own_lcp, sp->own_llv, llv_pairs);
-  return 0;
+  return set_index(sp, IndexView{ enc, n, suf, suf_bytes, lcp, llv, llv_pairs }, true);
   GTAMD_ABI_END(-1)
 }
 
 extern "C" int gtamd_spm_set_index_esa(gtamd_spm *sp, const gtamd_esa_ctx *esa, const uint8_t *enc, uint64_t n) {
   GTAMD_ABI_BEGIN
   if (sp == nullptr || esa == nullptr) { gtamd_set_error("invalid argument to gtamd_spm_set_index_esa"); return -1; }
-  const void *suf = gtamd_esa_table_device(esa, GTAMD_TAB_SUF);
-  const u8 *lcp = (const u8 *) gtamd_esa_table_device(esa, GTAMD_TAB_LCP);
-  const u64 pairs = gtamd_esa_table_entries(esa, GTAMD_TAB_LLV);
-  const u64 *llv = pairs ? (const u64 *) gtamd_esa_table_device(esa, GTAMD_TAB_LLV) : nullptr;
-  if (suf == nullptr || lcp == nullptr || (pairs && llv == nullptr)) {
-    gtamd_set_error("suffix-prefix matches: the last run did not produce the .suf and .lcp tables");
-    return -1;
-  }
-  if (gtamd_esa_table_offset(esa) != 0 || gtamd_esa_table_entries(esa, GTAMD_TAB_SUF) != n + 1) {
-    gtamd_set_error("suffix-prefix matches: the context holds %llu entries from table index %llu on, not the "
-                    "whole table of %llu symbols; the slices of a build in parts are not searched",
-                    (unsigned long long) gtamd_esa_table_entries(esa, GTAMD_TAB_SUF),
-                    (unsigned long long) gtamd_esa_table_offset(esa), (unsigned long long) n);
-    return -1;
-  }
-  TRY(index_arguments(sp, enc, n, suf, 8, lcp, llv, pairs));
-  HIP_TRY(hipSetDevice(sp->device));
-  drop_index(sp);
-  take_index(sp, enc, n, suf, 8, lcp, llv, pairs);
-  return 0;
+  IndexView v;
+  TRY(engine_tables(FEATURE, esa, enc, n, true, &v));
+  return set_index(sp, v, false);
   GTAMD_ABI_END(-1)
 }
 
 extern "C" int gtamd_spm_prepare(gtamd_spm *sp, uint32_t min_len, gtamd_spm_info *info) {
   GTAMD_ABI_BEGIN
   if (sp == nullptr) { gtamd_set_error("invalid argument to gtamd_spm_prepare"); return -1; }
-  if (!sp->have_index) {
+  if (!sp->index.set) {
     gtamd_set_error("suffix-prefix matches: no index is set (gtamd_spm_set_index)");
     return -1;
   }
@@ -469,7 +337,7 @@ extern "C" int gtamd_spm_prepare(gtamd_spm *sp, uint32_t min_len, gtamd_spm_info
   sp->prepared = false;
   sp->info = gtamd_spm_info();
   sp->M = sp->R = sp->nseps = 0;
-  TRY(sp->suf_bytes == 4 ? prepare<u32>(sp, min_len) : prepare<u64>(sp, min_len));
+  TRY(sp->index.suf_bytes == 4 ? prepare<u32>(sp, min_len) : prepare<u64>(sp, min_len));
   sp->info.device_bytes = held_bytes(sp);
   sp->prepared = true;
   if (info != nullptr) *info = sp->info;
@@ -497,8 +365,6 @@ extern "C" int gtamd_spm_emit(gtamd_spm *sp, uint64_t *cursor, gtamd_spm_record 
 
 extern "C" int gtamd_spm_get_info(const gtamd_spm *sp, gtamd_spm_info *info) {
   GTAMD_ABI_BEGIN
-  if (sp == nullptr || info == nullptr) { gtamd_set_error("invalid argument to gtamd_spm_get_info"); return -1; }
-  *info = sp->info;
-  return 0;
+  return consumer_info(sp, info, "gtamd_spm_get_info");
   GTAMD_ABI_END(-1)
 }

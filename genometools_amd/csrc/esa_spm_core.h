@@ -27,6 +27,7 @@ MST_HD u64 sp_lower_bound(const u32 *a, u64 count, u64 x) {
 template <typename S> MST_HD u32 sp_lcp_value(const SpIndex<S> &x, u64 i) {
   const u32 b = x.lcp[i];
   if (b != 255) return b;
+  // (llv_lower_bound of esa_devutil.h, written out: this header also compiles with g++ alone)
   u64 lo = 0, hi = x.m;
   while (lo < hi) {
     const u64 mid = (lo + hi) >> 1;

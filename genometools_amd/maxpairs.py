@@ -12,87 +12,45 @@ of the info mean).
 Everything here goes through genometools_amd/libgtamd_esa.so (HIP); there is
 no CPU implementation in this package.
 """
-import ctypes
-
 import numpy as np
 
-from . import _lib
-from ._lib import MaxPairsInfo, check
+from ._consumer import Consumer, host_tables, ptr, record_chunks
+from ._lib import MaxPairsInfo
 
 DEFAULT_CAPACITY = 1 << 20        # records of one chunk (24 bytes each)
 
 
-def _ptr(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
-class MaxPairs:
+class MaxPairs(Consumer):
     """enumerator over one index on one device"""
-
-    def __init__(self, device=0):
-        self._lib = _lib.load()
-        self._device = device
-        self._p = self._lib.gtamd_maxpairs_create(device)
-        if not self._p:
-            raise _lib.EsaError(self._lib.gtamd_esa_last_error().decode())
-
-    def close(self):
-        if self._p:
-            self._lib.gtamd_maxpairs_destroy(self._p)
-            self._p = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    NAME, INFO = "maxpairs", MaxPairsInfo
 
     # -- the index: each call replaces the one before -------------------------
     def set_index(self, enc, suf, lcp, llv=None):
         """tables in host memory (numpy): enc uint8, n symbols; suf uint32 or
         uint64, n + 1 entries; lcp uint8, n + 1 bytes; llv uint64 pairs
         (table index, value), any shape of 2 * pairs numbers, or None"""
-        enc = np.ascontiguousarray(enc, dtype=np.uint8)
-        suf = np.ascontiguousarray(suf)
-        lcp = np.ascontiguousarray(lcp, dtype=np.uint8)
-        llv = np.zeros(0, dtype=np.uint64) if llv is None else np.ascontiguousarray(llv, dtype=np.uint64).reshape(-1)
-        if suf.dtype not in (np.dtype(np.uint32), np.dtype(np.uint64)):
-            raise TypeError("suf must be uint32 or uint64, not %s" % suf.dtype)
-        if suf.size != enc.size + 1 or lcp.size != enc.size + 1 or llv.size % 2:
-            raise ValueError("%d symbols need %d entries of suf and lcp (%d, %d given) and whole pairs of llv"
-                             % (enc.size, enc.size + 1, suf.size, lcp.size))
-        check(self._lib.gtamd_maxpairs_set_index_host(self._p, _ptr(enc), enc.size, _ptr(suf), suf.dtype.itemsize,
-                                                      _ptr(lcp), _ptr(llv) if llv.size else None, llv.size // 2))
+        enc, suf, lcp, llv = host_tables(enc, suf, lcp, llv)
+        self._call("set_index_host", ptr(enc), enc.size, ptr(suf), suf.dtype.itemsize, ptr(lcp),
+                   ptr(llv) if llv.size else None, llv.size // 2)
 
     def set_index_device(self, enc_ptr, n, suf_ptr, suf_bytes, lcp_ptr, llv_ptr=None, llv_pairs=0):
         """the same for raw device pointers, which must outlive the calls"""
-        check(self._lib.gtamd_maxpairs_set_index(self._p, enc_ptr, n, suf_ptr, suf_bytes, lcp_ptr, llv_ptr,
-                                                 llv_pairs))
+        self._call("set_index", enc_ptr, n, suf_ptr, suf_bytes, lcp_ptr, llv_ptr, llv_pairs)
 
     def set_index_engine(self, engine, enc_device_ptr, n):
         """the tables an EsaEngine holds after run() with esa.WANT_SUF |
         esa.WANT_LCP (forward read mode); enc_device_ptr: the n symbols, on the
         device.  The engine must outlive the calls."""
-        check(self._lib.gtamd_maxpairs_set_index_esa(self._p, engine._ctx, enc_device_ptr, n))
+        self._call("set_index_esa", engine._ctx, enc_device_ptr, n)
 
     # -- the enumeration ------------------------------------------------------
     def prepare(self, min_len):
         """count the maximal pairs of at least min_len letters; the info as a dict"""
-        info = MaxPairsInfo()
-        check(self._lib.gtamd_maxpairs_prepare(self._p, min_len, ctypes.byref(info)))
-        return {name: getattr(info, name) for name, _ in info._fields_}
+        return self._call_info("prepare", min_len)
 
     def info(self):
         """gtamd_maxpairs_info of the last prepare, as a dict"""
-        info = MaxPairsInfo()
-        check(self._lib.gtamd_maxpairs_get_info(self._p, ctypes.byref(info)))
-        return {name: getattr(info, name) for name, _ in info._fields_}
+        return self._call_info("get_info")
 
     def pairs(self, capacity=None, device=False):
         """the records of the last prepare in table order, in chunks of whole
@@ -102,20 +60,7 @@ class MaxPairs:
         tensors of that shape on the device, which the next chunk overwrites"""
         if capacity is None:
             capacity = max(DEFAULT_CAPACITY, self.info()["max_pairs_of_one_suffix"])
-        cursor, written = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        if device:
-            import torch
-            buf = torch.empty((max(capacity, 1), 3), dtype=torch.int64, device="cuda:%d" % self._device)
-            ptr = buf.data_ptr()
-        else:
-            buf = np.empty((max(capacity, 1), 3), dtype=np.uint64)
-            ptr = buf.ctypes.data
-        while True:
-            check(self._lib.gtamd_maxpairs_emit(self._p, ctypes.byref(cursor), ptr, capacity, int(device),
-                                                ctypes.byref(written)))
-            if written.value == 0:
-                return
-            yield buf[:written.value] if device else buf[:written.value].copy()
+        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device)
 
     def all_pairs(self, capacity=None):
         """every record as one numpy array of shape (pairs, 3)"""

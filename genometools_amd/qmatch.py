@@ -21,14 +21,11 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import QmatchInfo, check
+from ._consumer import Consumer, host_tables, ptr, record_chunks
+from ._lib import QmatchInfo
 
 DEFAULT_CAPACITY = 1 << 20        # records of one emit call (24 bytes each)
 READMODES = ("fwd", "rev", "rcl")
-
-
-def _ptr(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def geometry():
@@ -58,55 +55,26 @@ def transformed(query, readmode):
     return out
 
 
-class QueryMatches:
+class QueryMatches(Consumer):
     """matcher over one index on one device"""
-
-    def __init__(self, device=0):
-        self._lib = _lib.load()
-        self._device = device
-        self._keep = None
-        self._p = self._lib.gtamd_qmatch_create(device)
-        if not self._p:
-            raise _lib.EsaError(self._lib.gtamd_esa_last_error().decode())
-
-    def close(self):
-        if self._p:
-            self._lib.gtamd_qmatch_destroy(self._p)
-            self._p = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    NAME, INFO = "qmatch", QmatchInfo
 
     # -- the index: each call replaces the one before -------------------------
     def set_index(self, enc, suf):
         """tables in host memory (numpy): enc uint8, n symbols; suf uint32 or
         uint64, n + 1 entries"""
-        enc = np.ascontiguousarray(enc, dtype=np.uint8)
-        suf = np.ascontiguousarray(suf)
-        if suf.dtype not in (np.dtype(np.uint32), np.dtype(np.uint64)):
-            raise TypeError("suf must be uint32 or uint64, not %s" % suf.dtype)
-        if suf.size != enc.size + 1:
-            raise ValueError("%d symbols need %d entries of suf (%d given)" % (enc.size, enc.size + 1, suf.size))
-        check(self._lib.gtamd_qmatch_set_index_host(self._p, _ptr(enc), enc.size, _ptr(suf), suf.dtype.itemsize))
+        enc, suf = host_tables(enc, suf)
+        self._call("set_index_host", ptr(enc), enc.size, ptr(suf), suf.dtype.itemsize)
 
     def set_index_device(self, enc_ptr, n, suf_ptr, suf_bytes):
         """the same for raw device pointers, which must outlive the calls"""
-        check(self._lib.gtamd_qmatch_set_index(self._p, enc_ptr, n, suf_ptr, suf_bytes))
+        self._call("set_index", enc_ptr, n, suf_ptr, suf_bytes)
 
     def set_index_engine(self, engine, enc_device_ptr, n):
         """the .suf table an EsaEngine holds after run() with esa.WANT_SUF
         (forward read mode); enc_device_ptr: the n symbols, on the device.  The
         engine must outlive the calls."""
-        check(self._lib.gtamd_qmatch_set_index_esa(self._p, engine._ctx, enc_device_ptr, n))
+        self._call("set_index_esa", engine._ctx, enc_device_ptr, n)
 
     # -- the enumeration ------------------------------------------------------
     def prepare(self, query, min_len):
@@ -114,42 +82,22 @@ class QueryMatches:
         memory (sequences joined by separators) for matches of at least min_len
         letters; the info as a dict"""
         query = np.ascontiguousarray(query, dtype=np.uint8)
-        info = QmatchInfo()
-        check(self._lib.gtamd_qmatch_prepare(self._p, _ptr(query) if query.size else None, query.size, 0, min_len,
-                                             ctypes.byref(info)))
-        return {name: getattr(info, name) for name, _ in info._fields_}
+        return self._call_info("prepare", ptr(query) if query.size else None, query.size, 0, min_len)
 
     def prepare_device(self, query_ptr, m, min_len):
         """the same for m symbols in device memory, which must outlive the emit calls"""
-        info = QmatchInfo()
-        check(self._lib.gtamd_qmatch_prepare(self._p, query_ptr, m, 1, min_len, ctypes.byref(info)))
-        return {name: getattr(info, name) for name, _ in info._fields_}
+        return self._call_info("prepare", query_ptr, m, 1, min_len)
 
     def info(self):
         """gtamd_qmatch_info of the last prepare and the emit calls since, as a dict"""
-        info = QmatchInfo()
-        check(self._lib.gtamd_qmatch_get_info(self._p, ctypes.byref(info)))
-        return {name: getattr(info, name) for name, _ in info._fields_}
+        return self._call_info("get_info")
 
     def emit(self, capacity=DEFAULT_CAPACITY, device=False):
         """the records of the last prepare in order, one array per emit call of
         at most `capacity` records: numpy uint64 arrays of shape (records, 3) --
         dbpos, qpos, len -- or, with device=True, torch int64 tensors of that
         shape on the device, which the next call overwrites"""
-        cursor, written = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        if device:
-            import torch
-            buf = torch.empty((max(capacity, 1), 3), dtype=torch.int64, device="cuda:%d" % self._device)
-            ptr = buf.data_ptr()
-        else:
-            buf = np.empty((max(capacity, 1), 3), dtype=np.uint64)
-            ptr = buf.ctypes.data
-        while True:
-            check(self._lib.gtamd_qmatch_emit(self._p, ctypes.byref(cursor), ptr, capacity, int(device),
-                                              ctypes.byref(written)))
-            if written.value == 0:
-                return
-            yield buf[:written.value] if device else buf[:written.value].copy()
+        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device)
 
     def all_matches(self, query, min_len, readmode="fwd", capacity=DEFAULT_CAPACITY):
         """every record of `query` read in `readmode` ("fwd", "rev": every

@@ -20,9 +20,9 @@ structure, and asserts from info() and the array sizes that it does:
 
 Every record is compared, none sampled, in the stated order; the tables come
 from the engine, in this process.  Matching statistics (mstat) and the index
-check have no second level of their own beyond the upload loop, which the cases
-here drive through three of its copies: they are left out.  Still untested:
-record counts past 2^32 and n near the single-build limit."""
+check have no second level of their own beyond the upload loop, which is the one
+of csrc/esa_index.h for all of them: they are left out.  Still untested: record
+counts past 2^32 and n near the single-build limit."""
 import functools
 
 import numpy as np
@@ -93,6 +93,12 @@ def large_seeds():
 
 
 def test_maxpairs_of_a_large_random_subject(gpu):
+    """The 69 MB of .suf go up in two pieces through the upload of
+    csrc/esa_index.h, and the counts of more than 131,072 run suffixes through
+    the carry loop of offsets_u64 (csrc/esa_prims.hip): the one upload and the
+    one 64-bit scan of every consumer, so this case crosses their second level
+    for the checker, the matching statistics, the query matches and the
+    suffix-prefix matches as well."""
     enc, suf, lcp, llv = _large_tables()
     want = seed.maxpairs(enc, L_SEED, large_seeds())
     in_order = mp.table_order(want, suf)
