@@ -1,0 +1,563 @@
+// esa_tagmatch.hip -- approximate matches of short tags against .suf and the
+// sequence in device memory: `gt tagerator -e K -esa INDEX -q TAGS` (C ABI, the
+// semantics and the order: include/gtamd_tagmatch.h).
+//
+//   a  k_tm_validate      one lane per tag: what is refused
+//   b  k_tm_walk<false>   one WAVE per job (tag, strand): the depth-first walk
+//                         over the intervals of the table, one level per depth in
+//                         LDS; the matches of the job are counted
+//      k_tm_settle        one lane per tag: K' of a tag with a match (with BEST
+//                         step b runs for k = 0..K over the tags without one)
+//   c  offsets_u64 (esa_prims)     64-bit exclusive scan of the counts
+//   d  k_tm_walk<true>    the same walk for the jobs of a window of records,
+//                         which writes those
+//
+// Every working array has one entry per job or per tag, none has N.
+#include <algorithm>
+#include <vector>
+#include "esa_common.h"
+#include "esa_index.h"
+#include "esa_prims.h"
+#include "esa_devutil.h"
+#include "esa_tagmatch_core.h"
+#include "../../include/gtamd_tagmatch.h"
+
+namespace {
+
+constexpr int TM_THREADS = SC_THREADS;
+constexpr u32 TM_WAVES = TM_THREADS / 64;          // jobs of one workgroup: one a wave
+constexpr u32 TM_LEVELS = 128;                     // depths 0 .. m + K - 1 <= 126 have a level
+constexpr u32 TM_BATCH = 64;                       // suffixes the lanes of a wave take at once
+constexpr u64 TM_MIN_CAPACITY = TM_BATCH;
+constexpr u64 TM_MAX_TAGS = 1ull << 30;
+constexpr u32 TM_STRANDS = GTAMD_TAGMATCH_FORWARD | GTAMD_TAGMATCH_REVCOMP;
+constexpr u32 NO_K = GTAMD_TAGMATCH_NO_K;
+
+enum { W_MATCHES = 0, W_MAXJOB, W_LEVELS, W_CHILDREN, W_WALKS, W_BAD, W_WORDS };
+enum { BAD_LENGTH = 1, BAD_SHORT = 2, BAD_SYMBOL = 3 };
+
+struct TmRecord { u64 tag, dbstart, lendist; };
+
+// one level of a walk: the suffixes [lo, end) share as many symbols as the level
+// is deep; cur: the left bound of the next child; the column after those symbols
+struct TmLevel { u32 lo, end, cur, rowval; u64 Pv, Mv; };
+static_assert(sizeof(TmLevel) == 32, "a level is 32 bytes of LDS");
+
+template <typename S> struct TmInput {
+  const u8 *enc; u64 n; const S *suf; u32 N;
+  const u8 *tags; const u64 *toff; u64 T;
+  u32 strands, wild;
+};
+
+__device__ __forceinline__ u32 uni(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// the symbol `d` behind the start of the suffix at table index idx < N; a separator
+// where there is none: behind the end, or for an entry that is no position
+template <typename S> __device__ __forceinline__ u32 tm_symbol(const TmInput<S> &in, u32 idx, u32 d) {
+  const u64 p = in.suf[idx];
+  if (p >= in.n) return TM_SEPARATOR;
+  const u64 x = p + d;
+  return x < in.n ? in.enc[x] : TM_SEPARATOR;
+}
+
+// The right bound of the child of letter s that starts at table index cur of a
+// level that ends at `end`: the first index behind cur whose symbol at depth d
+// is not s.  The symbols at one depth ascend inside an interval, the specials
+// behind all letters, so this is a search: 64 probes a round, spread over the
+// range [lo, hi) that is left; the range behind the last probe that still
+// holds s and in front of the first that does not is what the next round gets.
+// A round leaves fewer than span / 64 + 1 < span entries, whatever the table
+// holds; the result lies in (cur, end].
+template <typename S>
+__device__ __forceinline__ u32 tm_right_bound(const TmInput<S> &in, u32 cur, u32 end, u32 d, u32 s, u32 lane) {
+  u32 lo = cur + 1, hi = end;
+  while (lo < hi) {
+    const u32 span = hi - lo;
+    const u32 step = span <= TM_BATCH ? 1 : (span + TM_BATCH - 1) / TM_BATCH;
+    const u64 q = (u64) lo + (u64) lane * step;
+    const bool differs = q >= hi || tm_symbol(in, (u32) q, d) != s;
+    const u64 mask = __ballot(differs);
+    const u32 f = mask ? (u32) __builtin_ctzll(mask) : TM_BATCH;
+    if (f == 0) return lo;
+    const u64 next = (u64) lo + (u64) f * step;          // the first probe that differs, if there is one
+    if (f < TM_BATCH && next < hi) hi = (u32) next;
+    lo = lo + (f - 1) * step + 1;
+  }
+  return lo;
+}
+
+// what a wave carries through its walk
+struct TmWalk {
+  u64 k;                 // records of the job so far
+  u64 first, stop;       // EMIT: the records [first, stop) of the job are written ...
+  TmRecord *dst;         // ... record `first` here
+  u64 tagword;
+  u32 lane;
+};
+
+// `keep` lanes have a match each, in table order: counted, and written where
+// they fall into the window
+template <bool EMIT> __device__ __forceinline__ void tm_give(TmWalk &wk, bool keep, u64 p, u32 len, u32 dist) {
+  const u64 mask = __ballot(keep);
+  if (EMIT && keep) {
+    const u32 before = __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
+    const u64 place = wk.k + before;
+    if (place >= wk.first && place < wk.stop)
+      wk.dst[place - wk.first] = TmRecord{ wk.tagword, p, (u64) len | (u64) dist << 32 };
+  }
+  wk.k += (u64) __popcll(mask);
+}
+
+// Jobs [j0, j1), one a wave.  EMIT false: cnt[job] = its matches for K = k_pass,
+// for the jobs of the tags whose kbest is still none.  EMIT true: K of a job is
+// kbest of its tag; records [w0, w1) of all are written to out, record w0 first.
+template <typename S, bool EMIT>
+__global__ __launch_bounds__(TM_THREADS) void k_tm_walk(TmInput<S> in, u64 j0, u64 j1, u32 k_pass, const u32 *kbest,
+                                                        u32 *cnt, const u64 *off, u64 w0, u64 w1, TmRecord *out,
+                                                        u64 *w) {
+  __shared__ TmLevel s_level[TM_WAVES][TM_LEVELS];
+  __shared__ u64 s_eq[TM_WAVES][TM_LETTERS];
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u64 j = j0 + (u64) blockIdx.x * TM_WAVES + wave;
+  if (j >= j1) return;                       // (the whole wave: the waves of a workgroup never wait for each other)
+  const bool both = in.strands == TM_STRANDS;
+  const u64 tag = both ? j >> 1 : j;
+  const bool rc = both ? (j & 1) != 0 : in.strands == GTAMD_TAGMATCH_REVCOMP;
+  const u32 K = EMIT ? kbest[tag] : k_pass;
+  if (EMIT ? K == NO_K : kbest[tag] != NO_K) return;
+
+  TmWalk wk = { 0, 0, 0, nullptr, 2 * tag + (rc ? 1 : 0), lane };
+  if (EMIT) {
+    const u64 base = off[j], after = off[j + 1];
+    if (after <= w0 || base >= w1 || after == base) return;
+    wk.first = w0 > base ? w0 - base : 0;
+    wk.stop = (w1 < after ? w1 : after) - base;
+    wk.dst = out + (base + wk.first - w0);
+  }
+
+  // the tag, one letter a lane, as this strand reads it; its Eq words by ballot
+  const u64 t0 = in.toff[tag];
+  const u32 m = (u32) (in.toff[tag + 1] - t0);          // 1 .. 64 (k_tm_validate)
+  u32 letter = TM_SEPARATOR;
+  if (lane < m) letter = rc ? 3u - in.tags[t0 + (m - 1 - lane)] : in.tags[t0 + lane];
+  u64 *eq = s_eq[wave];
+  for (u32 c = 0; c < TM_LETTERS; c++) {
+    const u64 word = __ballot(letter == c);
+    eq[c] = word;                              // (every lane the same word)
+  }
+
+  TmLevel *level = s_level[wave];
+  level[0] = TmLevel{ 0, in.N, 0, K | K << 16, ~0ull, 0 };
+  u32 depth = 0;                               // of the top level, which is its index
+  u32 pushed = 0, children = 0, walks = 0;
+  // Every round moves the cursor of the top level forward by at least one, pops
+  // the level or pushes one of the next depth, which is below m + K: it ends.
+  for (;;) {
+    if (EMIT && wk.k >= wk.stop) break;
+    const u32 cur = uni(level[depth].cur), end = uni(level[depth].end);
+    if (cur >= end) {
+      if (depth == 0) break;
+      depth -= 1;
+      continue;
+    }
+    const u32 s = uni(tm_symbol(in, cur, depth));
+    TmColumn col = { level[depth].Pv, level[depth].Mv, 0, 0 };
+    const u32 rowval = uni(level[depth].rowval);
+    col.row = rowval & 0xffff;
+    col.val = rowval >> 16;
+    if (s >= TM_WILDCARD) {
+      // only specials from here to the end of the level: each goes on alone, if at all
+      if (!in.wild) {
+        if (depth == 0) break;
+        depth -= 1;
+        continue;
+      }
+      const u32 many = end - cur < TM_BATCH ? end - cur : TM_BATCH;
+      level[depth].cur = cur + many;
+      u32 len = 0, dist = 0;
+      u64 p = 0;
+      if (lane < many) {
+        p = in.suf[cur + lane];
+        if (p < in.n) len = tm_walk(col, eq, in.enc, in.n, p, depth, m, K, true, &dist);
+      }
+      walks += many;
+      tm_give<EMIT>(wk, len != 0, p, len, dist);
+      continue;
+    }
+    const u32 e = tm_right_bound(in, cur, end, depth, s, lane);
+    level[depth].cur = e;
+    children += 1;
+    tm_step(col, s < TM_LETTERS ? eq[s] : 0, K);
+    if (tm_dead(col)) continue;
+    if (tm_success(col, m)) {
+      // all suffixes of the child match with depth + 1 symbols
+      for (u32 b = cur; b < e; b += TM_BATCH) {
+        if (EMIT && wk.k >= wk.stop) break;
+        const u32 idx = b + lane;                   // (e <= N <= 2^32 - 4096: no wrap)
+        const u64 p = idx < e ? (u64) in.suf[idx] : in.n;
+        tm_give<EMIT>(wk, p < in.n, p, depth + 1, col.val);
+      }
+      continue;
+    }
+    if (e - cur <= TM_BATCH) {
+      u32 len = 0, dist = 0;
+      u64 p = 0;
+      if (lane < e - cur) {
+        p = in.suf[cur + lane];
+        if (p < in.n) len = tm_walk(col, eq, in.enc, in.n, p, depth + 1, m, K, in.wild != 0, &dist);
+      }
+      walks += e - cur;
+      tm_give<EMIT>(wk, len != 0, p, len, dist);
+      continue;
+    }
+    if (depth + 1 >= TM_LEVELS) continue;          // (cannot be: a column alive at depth m + K has reached row m)
+    depth += 1;
+    level[depth] = TmLevel{ cur, e, cur, col.row | col.val << 16, col.Pv, col.Mv };
+    pushed += 1;
+  }
+  if (!EMIT && lane == 0) {
+    cnt[j] = (u32) wk.k;                          // (at most one match per table entry: below 2^32)
+    if (wk.k) atomicMax((unsigned long long *) &w[W_MAXJOB], (unsigned long long) wk.k);
+    if (pushed) atomicAdd((unsigned long long *) &w[W_LEVELS], (unsigned long long) pushed);
+    if (children) atomicAdd((unsigned long long *) &w[W_CHILDREN], (unsigned long long) children);
+    if (walks) atomicAdd((unsigned long long *) &w[W_WALKS], (unsigned long long) walks);
+  }
+}
+
+// kbest of a tag that had none and whose jobs have a match now: k
+__global__ __launch_bounds__(TM_THREADS) void k_tm_settle(const u32 *cnt, u32 per_tag, u64 T, u32 k, u32 *kbest) {
+  const u64 t = (u64) blockIdx.x * TM_THREADS + threadIdx.x;
+  if (t >= T || kbest[t] != NO_K) return;
+  u32 any = 0;
+  for (u32 s = 0; s < per_tag; s++) any |= cnt[t * per_tag + s];
+  if (any) kbest[t] = k;
+}
+
+// tsum[b] = the sum of the counts of tile b, as offsets_u64 wants it
+__global__ __launch_bounds__(SC_THREADS) void k_tm_tile_sums(const u32 *cnt, u64 count, u64 *tsum) {
+  __shared__ unsigned long long ssum;
+  if (threadIdx.x == 0) ssum = 0;
+  __syncthreads();
+  const u64 i = (u64) blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i < count && cnt[i]) atomicAdd(&ssum, (unsigned long long) cnt[i]);
+  __syncthreads();
+  if (threadIdx.x == 0) tsum[blockIdx.x] = ssum;
+}
+
+// w[W_BAD] = the smallest (tag << 2 | what is wrong with it)
+__global__ __launch_bounds__(TM_THREADS) void k_tm_validate(const u8 *tags, const u64 *toff, u64 T, u32 K, u32 sigma,
+                                                            u64 *w) {
+  const u64 t = (u64) blockIdx.x * TM_THREADS + threadIdx.x;
+  if (t >= T) return;
+  const u64 a = toff[t], b = toff[t + 1];
+  u32 bad = 0;
+  if ((t == 0 && a != 0) || b <= a || b - a > TM_MAX_TAG || b > toff[T]) bad = BAD_LENGTH;
+  else if (b - a <= K) bad = BAD_SHORT;
+  else
+    for (u64 x = a; x < b; x++)
+      if (tags[x] >= sigma) bad = BAD_SYMBOL;
+  if (bad) atomicMin((unsigned long long *) &w[W_BAD], (unsigned long long) (t << 2 | bad));
+}
+
+}  // namespace
+
+struct gtamd_tagmatch : ConsumerBase<> {
+  ResidentIndex index;
+  u32 sigma = 0;
+  bool prepared = false;
+  // what a prepare leaves for the emit calls
+  Dev<u8> own_tags;
+  Dev<u64> own_toff;
+  const u8 *tags = nullptr;
+  const u64 *toff = nullptr;
+  u64 T = 0, jobs = 0;
+  u32 flags = 0;
+  Dev<u32> cnt, kbest;
+  Dev<u64> tsum, off;
+  std::vector<u64> off_host;      // the places of the jobs' first records: which jobs a window needs
+  Dev<u8> out;                    // records on their way to host memory
+  gtamd_tagmatch_info info = gtamd_tagmatch_info();
+};
+
+namespace {
+
+const char FEATURE[] = "tag matches";
+
+// every way of setting an index: what is refused, before anything is touched
+int set_index(gtamd_tagmatch *tm, const IndexView &v, u32 sigma, bool from_host) {
+  if (tm == nullptr || v.suf == nullptr || (v.enc == nullptr && v.n)) {
+    gtamd_set_error("invalid argument to gtamd_tagmatch_set_index");
+    return -1;
+  }
+  TRY(refuse_suf_bytes(FEATURE, v.suf_bytes));
+  TRY(refuse_sizes(FEATURE, v.n, 0));
+  if (sigma == 0 || sigma > TM_LETTERS) {
+    gtamd_set_error("tag matches: an alphabet of %u letters, 1 to %u expected", sigma, TM_LETTERS);
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(tm->device));
+  tm->prepared = false;
+  tm->sigma = sigma;
+  if (from_host) return tm->index.upload_from_host(FEATURE, v);
+  tm->index.borrow(v);
+  return 0;
+}
+
+u64 held_bytes(const gtamd_tagmatch *tm) {
+  return tm->index.bytes() + tm->own_tags.bytes + tm->own_toff.bytes + tm->cnt.bytes + tm->kbest.bytes +
+         tm->tsum.bytes + tm->off.bytes + tm->words.bytes + tm->out.bytes;
+}
+
+int out_of_memory(u64 entries, const char *of) {
+  gtamd_set_error("tag matches: cannot allocate device memory for %llu %s", (unsigned long long) entries, of);
+  return -1;
+}
+
+template <typename S> TmInput<S> input(const gtamd_tagmatch *tm) {
+  return TmInput<S>{ tm->index.enc, tm->index.n, (const S *) tm->index.suf, (u32) (tm->index.n + 1),
+                     tm->tags, tm->toff, tm->T, tm->flags & TM_STRANDS,
+                     (tm->flags & GTAMD_TAGMATCH_WITH_WILDCARDS) ? 1u : 0u };
+}
+
+// the message for what k_tm_validate found
+int refuse_tag(gtamd_tagmatch *tm, u64 found, u32 K) {
+  const u64 t = found >> 2;
+  u64 ab[2] = { 0, 0 };
+  TRY(fetch(tm->st, { { tm->toff + t, ab, sizeof ab } }));
+  const unsigned long long tag = t, len = ab[1] - ab[0];
+  switch (found & 3) {
+    case BAD_LENGTH:
+      if (ab[1] > ab[0] && len > TM_MAX_TAG)
+        gtamd_set_error("tag matches: tag number %llu of length %llu; tags must not be longer than %u", tag, len,
+                        TM_MAX_TAG);
+      else
+        gtamd_set_error("tag matches: tag number %llu is empty, or the offsets do not ascend from 0 to their last", tag);
+      break;
+    case BAD_SHORT:
+      gtamd_set_error("tag matches: tag number %llu of length %llu; tags must be longer than the allowed number "
+                      "of errors (which is %u)", tag, len, K);
+      break;
+    default:
+      gtamd_set_error("tag matches: tag number %llu holds a symbol that is no letter of the alphabet of %u "
+                      "letters (a wildcard in a tag is refused)", tag, tm->sigma);
+  }
+  return -1;
+}
+
+template <typename S> int prepare(gtamd_tagmatch *tm, u32 K) {
+  hipStream_t st = tm->st;
+  const u64 T = tm->T, jobs = tm->jobs;
+  const u32 per_tag = (u32) (jobs / T);
+  HIP_TRY(hipMemsetAsync(tm->words, 0, W_WORDS * sizeof(u64), st));
+  HIP_TRY(hipMemsetAsync(tm->words + W_BAD, 0xff, sizeof(u64), st));
+  HIP_TRY(hipEventRecord(tm->ev[0], st));
+  k_tm_validate<<<(u32) div_up(T, TM_THREADS), TM_THREADS, 0, st>>>(tm->tags, tm->toff, T, K, tm->sigma, tm->words);
+  HIP_TRY(hipGetLastError());
+  u64 found = 0;
+  TRY(fetch(st, { { tm->words + W_BAD, &found, sizeof found } }));
+  if (found != ~0ull) return refuse_tag(tm, found, K);
+  HIP_TRY(hipMemsetAsync(tm->kbest, 0xff, T * sizeof(u32), st));
+  for (u32 k = (tm->flags & GTAMD_TAGMATCH_BEST) ? 0 : K; k <= K; k++) {
+    k_tm_walk<S, false><<<(u32) div_up(jobs, TM_WAVES), TM_THREADS, 0, st>>>(input<S>(tm), 0, jobs, k, tm->kbest, tm->cnt,
+                                                                           nullptr, 0, 0, nullptr, tm->words);
+    HIP_TRY(hipGetLastError());
+    k_tm_settle<<<(u32) div_up(T, TM_THREADS), TM_THREADS, 0, st>>>(tm->cnt, per_tag, T, k, tm->kbest);
+    HIP_TRY(hipGetLastError());
+  }
+  k_tm_tile_sums<<<(u32) div_up(jobs, SC_THREADS), SC_THREADS, 0, st>>>(tm->cnt, jobs, tm->tsum);
+  HIP_TRY(hipGetLastError());
+  TRY(offsets_u64(tm->cnt, jobs, tm->tsum, tm->off, tm->words + W_MATCHES, st));
+  HIP_TRY(hipEventRecord(tm->ev[1], st));
+  u64 h[W_WORDS];
+  tm->off_host.resize(jobs + 1);
+  TRY(fetch(st, { { tm->words, h, sizeof h }, { tm->off, tm->off_host.data(), (jobs + 1) * sizeof(u64) } }));
+  HIP_TRY(hipEventElapsedTime(&tm->info.device_ms, tm->ev[0], tm->ev[1]));
+  tm->info.matches = h[W_MATCHES];
+  tm->info.max_matches_of_one_job = h[W_MAXJOB];
+  tm->info.levels_pushed = h[W_LEVELS];
+  tm->info.children_examined = h[W_CHILDREN];
+  tm->info.single_walks = h[W_WALKS];
+  return 0;
+}
+
+int emit(gtamd_tagmatch *tm, u64 *cursor, gtamd_tagmatch_record *out, u64 capacity, int out_on_device, u64 *written) {
+  *written = 0;
+  const u64 total = tm->info.matches, cur = *cursor;
+  if (cur > total) {
+    gtamd_set_error("tag matches: cursor %llu is not one of this enumeration (%llu records)",
+                    (unsigned long long) cur, (unsigned long long) total);
+    return -1;
+  }
+  if (capacity < TM_MIN_CAPACITY) {
+    gtamd_set_error("tag matches: a capacity of %llu records is too small: a capacity of at least %llu is needed",
+                    (unsigned long long) capacity, (unsigned long long) TM_MIN_CAPACITY);
+    return -1;
+  }
+  if (cur == total) return 0;
+  const u64 w1 = capacity < total - cur ? cur + capacity : total;
+  // the jobs with a record in [cur, w1): from the last whose first record is not
+  // behind cur up to the first whose first record is not in front of w1
+  const std::vector<u64> &off = tm->off_host;
+  const u64 j0 = (u64) (std::upper_bound(off.begin(), off.end(), cur) - off.begin()) - 1;
+  const u64 j1 = (u64) (std::lower_bound(off.begin(), off.end(), w1) - off.begin());
+  RecordStage<TmRecord> stage(out, out_on_device);
+  if (stage.begin(tm->out, w1 - cur) != hipSuccess) return out_of_memory(w1 - cur, "records");
+  const u32 blocks = (u32) div_up(j1 - j0, TM_WAVES);
+  if (tm->index.suf_bytes == 4)
+    k_tm_walk<u32, true><<<blocks, TM_THREADS, 0, tm->st>>>(input<u32>(tm), j0, j1, 0, tm->kbest, nullptr, tm->off, cur,
+                                                             w1, stage.dst, tm->words);
+  else
+    k_tm_walk<u64, true><<<blocks, TM_THREADS, 0, tm->st>>>(input<u64>(tm), j0, j1, 0, tm->kbest, nullptr, tm->off, cur,
+                                                             w1, stage.dst, tm->words);
+  HIP_TRY(hipGetLastError());
+  TRY(stage.finish(w1 - cur, tm->st));
+  tm->info.emitted += w1 - cur;
+  *cursor = w1;
+  *written = w1 - cur;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" gtamd_tagmatch *gtamd_tagmatch_create(int device) {
+  GTAMD_ABI_BEGIN
+  return create_consumer<gtamd_tagmatch>(device, W_WORDS, "the tag matcher");
+  GTAMD_ABI_END(nullptr)
+}
+
+extern "C" void gtamd_tagmatch_destroy(gtamd_tagmatch *tm) { destroy_consumer(tm); }
+
+extern "C" void gtamd_tagmatch_geometry(uint32_t *jobs_per_workgroup, uint64_t *min_capacity, uint32_t *max_levels) {
+  if (jobs_per_workgroup != nullptr) *jobs_per_workgroup = TM_WAVES;
+  if (min_capacity != nullptr) *min_capacity = TM_MIN_CAPACITY;
+  if (max_levels != nullptr) *max_levels = TM_LEVELS;
+}
+
+extern "C" int gtamd_tagmatch_set_index(gtamd_tagmatch *tm, const uint8_t *enc, uint64_t n, const void *suf,
+                                        uint32_t suf_bytes, uint32_t numofchars) {
+  GTAMD_ABI_BEGIN
+  return set_index(tm, IndexView{ enc, n, suf, suf_bytes }, numofchars, false);
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_tagmatch_set_index_host(gtamd_tagmatch *tm, const uint8_t *enc, uint64_t n, const void *suf,
+                                             uint32_t suf_bytes, uint32_t numofchars) {
+  GTAMD_ABI_BEGIN
+  return set_index(tm, IndexView{ enc, n, suf, suf_bytes }, numofchars, true);
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_tagmatch_set_index_esa(gtamd_tagmatch *tm, const gtamd_esa_ctx *esa, const uint8_t *enc,
+                                            uint64_t n, uint32_t numofchars) {
+  GTAMD_ABI_BEGIN
+  if (tm == nullptr || esa == nullptr) { gtamd_set_error("invalid argument to gtamd_tagmatch_set_index_esa"); return -1; }
+  IndexView v;
+  TRY(engine_tables(FEATURE, esa, enc, n, false, &v));
+  return set_index(tm, v, numofchars, false);
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_tagmatch_prepare(gtamd_tagmatch *tm, const uint8_t *tags, const uint64_t *offsets, uint64_t T,
+                                      int is_device, uint32_t K, uint32_t flags, gtamd_tagmatch_info *info) {
+  GTAMD_ABI_BEGIN
+  if (tm == nullptr || (T != 0 && (tags == nullptr || offsets == nullptr))) {
+    gtamd_set_error("invalid argument to gtamd_tagmatch_prepare");
+    return -1;
+  }
+  if (!tm->index.set) {
+    gtamd_set_error("tag matches: no index is set (gtamd_tagmatch_set_index)");
+    return -1;
+  }
+  const u32 known = TM_STRANDS | GTAMD_TAGMATCH_BEST | GTAMD_TAGMATCH_WITH_WILDCARDS;
+  if ((flags & ~known) != 0 || (flags & TM_STRANDS) == 0) {
+    gtamd_set_error("tag matches: flags 0x%x, an OR of GTAMD_TAGMATCH_* with at least one strand expected", flags);
+    return -1;
+  }
+  if ((flags & GTAMD_TAGMATCH_REVCOMP) && tm->sigma != 4) {
+    gtamd_set_error("tag matches: the reverse-complement strand (GTAMD_TAGMATCH_REVCOMP) is defined for an "
+                    "alphabet of 4 letters only, this index has %u", tm->sigma);
+    return -1;
+  }
+  if ((flags & GTAMD_TAGMATCH_WITH_WILDCARDS) && K == 0) {
+    gtamd_set_error("tag matches: GTAMD_TAGMATCH_WITH_WILDCARDS is taken only with K > 0");
+    return -1;
+  }
+  if (K >= TM_MAX_TAG) {
+    gtamd_set_error("tag matches: %u differences, at most %u (tags have at most %u letters)", K, TM_MAX_TAG - 1,
+                    TM_MAX_TAG);
+    return -1;
+  }
+  if (T > TM_MAX_TAGS) {
+    gtamd_set_error("tag matches: %llu tags, at most %llu in one call", (unsigned long long) T,
+                    (unsigned long long) TM_MAX_TAGS);
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(tm->device));
+  tm->prepared = false;
+  tm->info = gtamd_tagmatch_info();
+  tm->T = T;
+  tm->flags = flags;
+  tm->jobs = T * ((flags & TM_STRANDS) == TM_STRANDS ? 2 : 1);
+  tm->info.jobs = tm->jobs;
+  tm->off_host.assign(1, 0);
+  if (T != 0) {
+    const u64 jobs = tm->jobs, tiles = div_up(jobs, SC_THREADS);
+    if (tm->cnt.grow(jobs * 4) != hipSuccess || tm->kbest.grow(T * 4) != hipSuccess ||
+        tm->off.grow((jobs + 1) * 8) != hipSuccess || tm->tsum.grow(tiles * 8) != hipSuccess)
+      return out_of_memory(jobs, "jobs");
+    tm->tags = tags;
+    tm->toff = offsets;
+    if (!is_device) {
+      const u64 symbols = offsets[T];
+      if (tm->own_tags.grow(symbols ? symbols : 1) != hipSuccess || tm->own_toff.grow((T + 1) * 8) != hipSuccess)
+        return out_of_memory(symbols, "tag symbols");
+      if (symbols) HIP_TRY(hipMemcpyAsync(tm->own_tags, tags, symbols, hipMemcpyHostToDevice, tm->st));
+      HIP_TRY(hipMemcpyAsync(tm->own_toff, offsets, (T + 1) * 8, hipMemcpyHostToDevice, tm->st));
+      tm->tags = tm->own_tags;
+      tm->toff = tm->own_toff;
+    }
+    TRY(tm->index.suf_bytes == 4 ? prepare<u32>(tm, K) : prepare<u64>(tm, K));
+  }
+  tm->info.device_bytes = held_bytes(tm);
+  tm->prepared = true;
+  if (info != nullptr) *info = tm->info;
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_tagmatch_emit(gtamd_tagmatch *tm, uint64_t *cursor, gtamd_tagmatch_record *out, uint64_t capacity,
+                                   int out_on_device, uint64_t *written) {
+  GTAMD_ABI_BEGIN
+  if (tm == nullptr || cursor == nullptr || written == nullptr || (out == nullptr && capacity)) {
+    gtamd_set_error("invalid argument to gtamd_tagmatch_emit");
+    return -1;
+  }
+  if (!tm->prepared) {
+    gtamd_set_error("tag matches: nothing is prepared (gtamd_tagmatch_prepare)");
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(tm->device));
+  TRY(emit(tm, cursor, out, capacity, out_on_device, written));
+  tm->info.device_bytes = held_bytes(tm);
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_tagmatch_best_k(gtamd_tagmatch *tm, uint32_t *k_host, uint64_t T) {
+  GTAMD_ABI_BEGIN
+  if (tm == nullptr || (k_host == nullptr && T)) { gtamd_set_error("invalid argument to gtamd_tagmatch_best_k"); return -1; }
+  if (!tm->prepared || T != tm->T) {
+    gtamd_set_error("tag matches: K' of %llu tags asked for, %llu are prepared", (unsigned long long) T,
+                    (unsigned long long) (tm->prepared ? tm->T : 0));
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(tm->device));
+  return fetch(tm->st, { { tm->kbest, k_host, T * sizeof(u32) } });
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_tagmatch_get_info(const gtamd_tagmatch *tm, gtamd_tagmatch_info *info) {
+  GTAMD_ABI_BEGIN
+  return consumer_info(tm, info, "gtamd_tagmatch_get_info");
+  GTAMD_ABI_END(-1)
+}

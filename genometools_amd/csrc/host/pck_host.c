@@ -24,7 +24,7 @@
    show|count` (tool src/tools/gt_encseq2spm.c), all suffix-prefix matches of a
    read set on both strands; the engine builds .suf and .lcp of the mirrored
    reads in this process and hands them to include/gtamd_spm.h. */
-#include "gtamd_host.h"
+#include "host_internal.h"
 #include "gtamd_pck.h"
 #include "gtamd_check.h"
 #include "gtamd_mstat.h"
@@ -1218,3 +1218,10 @@ done:
   free(rec); free(both); free(enc);
   return rc;
 }
+
+/* ---- gt tagerator ----
+   In a file of its own, this one being long enough, but part of this translation
+   unit: the sanitized tool of tests/test_host_sanitized.py is linked from a fixed
+   list of files, of which this is the one with the helpers the tool needs (see the
+   head of tagmatch_host.c). */
+#include "tagmatch_host.c"

@@ -26,6 +26,9 @@
     gtamd_encseq2spm        `gt encseq2spm -l L -ii INDEX -spm show|count`
                             (src/tools/gt_encseq2spm.c), on the device through
                             the engine and include/gtamd_spm.h
+    gtamd_tagerator         `gt tagerator -e K -esa INDEX -q TAGS`
+                            (src/tools/gt_tagerator.c), on the device through
+                            include/gtamd_tagmatch.h
 
   Pure C (gcc); links against libgtamd_esa.so for the hot path.
 */
@@ -410,6 +413,40 @@ int gtamd_querymatch(int argc, const char **argv, char *err, size_t errlen);
    Returns 0, or -1 with the message in err (the caller prints "gt encseq2spm:
    error: <err>" and exits 1). */
 int gtamd_encseq2spm(int argc, const char **argv, char *err, size_t errlen);
+
+/* `gt tagerator -e K -esa INDEX -q FILE...` (tool function
+   src/tools/gt_tagerator.c, gt_runtagerator src/match/tagerator.c:538-773): the
+   matches of short tags with up to K differences against the index's
+   sequences, on the device from .suf and the sequence (semantics and order:
+   include/gtamd_tagmatch.h).  The sub-command `tagerator`.
+     -esa INDEX   reads INDEX.prj, INDEX.esq (+ .ssp) and INDEX.suf (4- or 8-byte
+                  entries, by its size); a read mode other than forward and a
+                  mirrored index are refused
+     -q FILE...   FASTA; the tags are numbered across all files.  At most 64
+                  letters a tag, more than K; no wildcard (but see -rw)
+     -e K         the differences: replacements, insertions, deletions
+     -nod -nop    without the forward, without the reverse-complement strand;
+                  an index that is not DNA needs -nop
+     -best        per tag the matches of the smallest k <= K that gives it one
+     -withwildcards [yes|no]   the reference's switch, which it stores as "no
+                  wildcards" (gt_tagerator.c:170-174): only `-withwildcards no`
+                  lets wildcards of the index be part of a match, with K > 0
+     -rw          a wildcard in a tag becomes the first letter
+     -output tagnum tagseq dblength dbstartpos abspos dbsequence strand edist
+     -v           the figures of gtamd_tagmatch_info as a line starting with
+                  '#', behind the matches
+   Stdout is the reference's byte for byte -- the four '#' lines in front, the
+   `#\ttagnum\ttagseq` line of every tag, the columns and tab rules of
+   tgr_showmatch -- except the order of the match lines of one tag and strand:
+   ascending table index here, the reference's stack there.  The errors of the
+   tags (longer than 64, not longer than K, wildcard, undefined character) come
+   in the reference's words after the blocks of the tags before the failing one.
+   -pck -online -cmp -maxocc -skpp -maxdepth are refused ("option \"-X\" is not
+   supported ..."), and so is a call without -e: the matching statistics belong
+   to -maxocc.
+   Returns 0, or -1 with the message in err (the caller prints "gt tagerator:
+   error: <err>" and exits 1). */
+int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }
