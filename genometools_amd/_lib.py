@@ -14,15 +14,18 @@ LIB_PATH = os.path.join(HERE, "libgtamd_esa.so")
 SOURCES = [os.path.join(HERE, "csrc", f) for f in
            ("esa_prims.hip", "esa_engine.hip", "esa_synth.hip", "esa_encode.hip",
             "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip",
-            "esa_maxpairs.hip", "esa_qmatch.hip", "esa_spm.hip", "esa_tagmatch.hip")]
+            "esa_maxpairs.hip", "esa_qmatch.hip", "esa_spm.hip", "esa_tagmatch.hip",
+            "esa_locali.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_index.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
                                                      "esa_pck_replay.h", "esa_mstat_search.h",
                                                      "esa_maxpairs_walk.h", "esa_qmatch_core.h",
-                                                     "esa_spm_core.h", "esa_tagmatch_core.h")] + \
+                                                     "esa_spm_core.h", "esa_tagmatch_core.h",
+                                                     "esa_locali_core.h")] + \
           [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
                                                        "gtamd_check.h", "gtamd_mstat.h",
                                                        "gtamd_maxpairs.h", "gtamd_qmatch.h",
-                                                       "gtamd_spm.h", "gtamd_tagmatch.h")]
+                                                       "gtamd_spm.h", "gtamd_tagmatch.h",
+                                                       "gtamd_locali.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -148,6 +151,13 @@ class TagmatchInfo(ctypes.Structure):    # gtamd_tagmatch_info, include/gtamd_ta
     _fields_ = [(name, ctypes.c_uint64) for name in
                 ("jobs", "matches", "max_matches_of_one_job", "levels_pushed", "children_examined",
                  "single_walks", "emitted", "device_bytes")] + [("device_ms", ctypes.c_float)]
+
+
+class LocaliInfo(ctypes.Structure):      # gtamd_locali_info, include/gtamd_locali.h
+    _fields_ = [(name, ctypes.c_uint64) for name in
+                ("jobs", "matches", "max_matches_of_one_job", "levels_pushed", "children_examined",
+                 "single_walks", "jobs_finished_alone", "emitted", "device_bytes", "groups")] + \
+               [("cut_depth", ctypes.c_uint32), ("stack_words", ctypes.c_uint32), ("device_ms", ctypes.c_float)]
 
 
 # every symbol include/gtamd_esa.h, gtamd_encode.h and gtamd_pck.h declare:
@@ -313,6 +323,22 @@ TAGMATCH_ABI = {
     "gtamd_tagmatch_get_info": (_INT, [_P, ctypes.POINTER(TagmatchInfo)]),
 }
 
+# every symbol include/gtamd_locali.h declares
+LOCALI_ABI = {
+    "gtamd_locali_create": (_P, [_INT]),
+    "gtamd_locali_destroy": (None, [_P]),
+    "gtamd_locali_geometry": (None, [ctypes.POINTER(_U32), ctypes.POINTER(_U64), ctypes.POINTER(_U32),
+                                     ctypes.POINTER(_U32)]),
+    "gtamd_locali_set_index": (_INT, [_P, _P, _U64, _P, _U32, _U32]),
+    "gtamd_locali_set_index_host": (_INT, [_P, _P, _U64, _P, _U32, _U32]),
+    "gtamd_locali_set_index_esa": (_INT, [_P, _P, _P, _U64, _U32]),
+    "gtamd_locali_set_limits": (_INT, [_P, _U32, _U32]),
+    "gtamd_locali_prepare": (_INT, [_P, _P, _P, _U64, _INT, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _U32,
+                                    ctypes.POINTER(LocaliInfo)]),
+    "gtamd_locali_emit": (_INT, [_P, ctypes.POINTER(_U64), _P, _U64, _INT, ctypes.POINTER(_U64)]),
+    "gtamd_locali_get_info": (_INT, [_P, ctypes.POINTER(LocaliInfo)]),
+}
+
 _lib = None
 
 
@@ -336,7 +362,8 @@ def load():
             pass
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()) + \
-                list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()) + list(SPM_ABI.items()) + list(TAGMATCH_ABI.items()):
+                list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()) + list(SPM_ABI.items()) + list(TAGMATCH_ABI.items()) + \
+                list(LOCALI_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

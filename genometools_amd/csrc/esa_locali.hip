@@ -1,0 +1,666 @@
+// esa_locali.hip -- local alignments of queries against .suf and the sequence in
+// device memory: `gt dev idxlocali -th T -esa INDEX -q FILES` (C ABI, the
+// semantics and the order: include/gtamd_locali.h).
+//
+//   0  k_lc_cuts          one lane per table entry, once per index: where the
+//                         first CUT_MAX symbols of neighbours differ, and at
+//                         which depth; a prepare takes the cuts above its depth q
+//   a  k_lc_validate      one lane per query: what is refused; the longest query
+//   b  k_lc_walk<false>   one WAVE per job (query, group), the waves of the grid
+//                         taking jobs in turn: the depth-first walk over the
+//                         intervals of the group, the column of every level of the
+//                         path as a band of cells on a stack in global memory
+//                         (esa_locali_core.h); the matches of the job are counted
+//   c  offsets_u64 (esa_prims)     64-bit exclusive scan of the counts
+//   d  k_lc_walk<true>    the same walk for the jobs of a window of records,
+//                         which writes those
+//
+// Working memory: one entry per job, the cuts, and per wave of the grid a stack
+// and two columns.
+#include <algorithm>
+#include <vector>
+#include "esa_common.h"
+#include "esa_index.h"
+#include "esa_prims.h"
+#include "esa_devutil.h"
+#include "esa_locali_core.h"
+#include "../../include/gtamd_locali.h"
+
+namespace {
+
+constexpr int LC_THREADS = SC_THREADS;
+constexpr u32 LC_WAVES = LC_THREADS / 64;          // waves of one workgroup: each walks jobs of its own
+constexpr u32 LC_WAVES_PER_CU = 8;                 // waves of the grid per compute unit
+constexpr u32 LC_BATCH = 64;
+constexpr u64 LC_MIN_CAPACITY = LC_BATCH;
+constexpr u64 LC_MAX_QUERIES = 1ull << 24;
+constexpr u64 LC_MAX_JOBS = 1ull << 31;
+constexpr u32 LC_HEADER = 8;                       // words of a level on the stack
+constexpr u32 LC_MAX_STACK = 1u << 28;             // words
+constexpr u32 LC_CUT_GROUPS = 1u << 16;            // sigma ^ CUT_MAX stays below this ...
+constexpr u32 LC_CUT_LIST = 1u << 18;              // ... so a suffix table has fewer cuts than this
+constexpr u64 LC_TARGET_JOBS = 1u << 14;           // q is the smallest depth that gives as many jobs
+constexpr u32 NO_LEVEL = 0xffffffffu;
+
+enum { W_MATCHES = 0, W_MAXJOB, W_LEVELS, W_CHILDREN, W_WALKS, W_OTHER, W_BAD, W_LONGEST, W_CUTS, W_WORDS };
+enum { BAD_LENGTH = 1, BAD_SCORE = 2, BAD_SYMBOL = 3 };
+
+struct LcRecord { u64 query, dbstart, lenscore, qspan; };
+static_assert(sizeof(LcRecord) == sizeof(gtamd_locali_record), "a record is four 64-bit numbers");
+
+template <typename S> struct LcInput {
+  const u8 *enc; u64 n; const S *suf; u32 N;
+  const u8 *queries; const u64 *qoff;
+  const u32 *gstart; u32 groups;                   // group g: table entries [gstart[g], gstart[g + 1])
+  LcScores sc; u32 T;
+  u32 stack_words, col_words;                      // of one wave: its stack, then two columns of col_words
+};
+
+__device__ __forceinline__ u32 uni(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// the symbol `d` behind the start of the suffix at table index idx < N; a separator
+// where there is none: behind the end, or for an entry that is no position
+template <typename S> __device__ __forceinline__ u32 lc_symbol(const u8 *enc, u64 n, const S *suf, u32 idx, u32 d) {
+  const u64 p = suf[idx];
+  if (p >= n) return LC_SEPARATOR;
+  const u64 x = p + d;
+  return x < n ? enc[x] : LC_SEPARATOR;
+}
+
+// The right bound of the child of letter s that starts at table index cur of a
+// level that ends at `end` (the search of esa_tagmatch.hip): 64 probes a round;
+// a round leaves fewer than span / 64 + 1 < span entries whatever the table
+// holds; the result lies in (cur, end].
+template <typename S>
+__device__ __forceinline__ u32 lc_right_bound(const LcInput<S> &in, u32 cur, u32 end, u32 d, u32 s, u32 lane) {
+  u32 lo = cur + 1, hi = end;
+  while (lo < hi) {
+    const u32 span = hi - lo;
+    const u32 step = span <= LC_BATCH ? 1 : (span + LC_BATCH - 1) / LC_BATCH;
+    const u64 q = (u64) lo + (u64) lane * step;
+    const bool differs = q >= hi || lc_symbol(in.enc, in.n, in.suf, (u32) q, d) != s;
+    const u64 mask = __ballot(differs);
+    const u32 f = mask ? (u32) __builtin_ctzll(mask) : LC_BATCH;
+    if (f == 0) return lo;
+    const u64 next = (u64) lo + (u64) f * step;
+    if (f < LC_BATCH && next < hi) hi = (u32) next;
+    lo = lo + (f - 1) * step + 1;
+  }
+  return lo;
+}
+
+struct LcWalk {
+  u64 k;                 // records of the job so far
+  u64 first, stop;       // EMIT: the records [first, stop) of the job are written ...
+  LcRecord *dst;         // ... record `first` here
+  u64 query;
+};
+
+// `keep` lanes have a match each, in table order
+template <bool EMIT>
+__device__ __forceinline__ void lc_give(LcWalk &wk, bool keep, u64 p, u32 dblen, u32 score, u32 e, u32 qstart) {
+  const u64 mask = __ballot(keep);
+  if (EMIT && keep) {
+    const u32 before = __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
+    const u64 place = wk.k + before;
+    if (place >= wk.first && place < wk.stop)
+      wk.dst[place - wk.first] = LcRecord{ wk.query, p, (u64) dblen | (u64) score << 32,
+                                           (u64) qstart | (u64) (e - qstart) << 32 };
+  }
+  wk.k += (u64) __popcll(mask);
+}
+
+// the level on top of the stack, in registers; the others as LC_HEADER words each
+struct LcLevel { u32 lo, end, cur, blo, bhi, cells, below, depth; };
+
+__device__ __forceinline__ void lc_store(u32 *stack, u32 at, const LcLevel &L, u32 lane) {
+  if (lane == 0) {
+    stack[at] = L.lo; stack[at + 1] = L.end; stack[at + 2] = L.cur; stack[at + 3] = L.blo;
+    stack[at + 4] = L.bhi; stack[at + 5] = L.cells; stack[at + 6] = L.below; stack[at + 7] = L.depth;
+  }
+  LC_WAVE_FENCE();
+}
+
+__device__ __forceinline__ LcLevel lc_load(const u32 *stack, u32 at) {
+  return LcLevel{ uni(stack[at]), uni(stack[at + 1]), uni(stack[at + 2]), uni(stack[at + 3]),
+                  uni(stack[at + 4]), uni(stack[at + 5]), uni(stack[at + 6]), uni(stack[at + 7]) };
+}
+
+// One job.  The stack holds, for every level of the path but the top one, its
+// header, and for every level but the root the cells of its band; `at` is where
+// the top level's header goes when a level is pushed above it, `free` the first
+// word behind its cells.
+template <typename S, bool EMIT>
+__device__ void lc_job(const LcInput<S> &in, u64 j, u32 *stack, u32 *cola, u32 *colb, u32 *cnt, const u64 *off, u64 w0,
+                       u64 w1, LcRecord *out, u64 *w, u32 lane) {
+  const u64 query = j / in.groups;
+  const u32 g = (u32) (j % in.groups);
+  LcWalk wk = { 0, 0, 0, nullptr, query };
+  if (EMIT) {
+    const u64 base = off[j], after = off[j + 1];
+    if (after <= w0 || base >= w1 || after == base) return;
+    wk.first = w0 > base ? w0 - base : 0;
+    wk.stop = (w1 < after ? w1 : after) - base;
+    wk.dst = out + (base + wk.first - w0);
+  }
+  const u64 q0 = in.qoff[query];
+  const u32 m = (u32) (in.qoff[query + 1] - q0);          // 1 .. LC_MAX_QUERY (k_lc_validate)
+  const u8 *q = in.queries + q0;
+  const u32 deepest = lc_max_depth(m, in.sc);
+  const u32 glo = uni(in.gstart[g]), ghi = uni(in.gstart[g + 1]);
+
+  LcLevel L = { glo, ghi, glo, 0, 0, 0, NO_LEVEL, 0 };
+  u32 at = 0, free = LC_HEADER;
+  u32 pushed = 0, children = 0, walks = 0;
+  bool other = false;
+  // Every round moves the cursor of the top level forward by at least one, pops
+  // the level or pushes one of the next depth, which is at most `deepest`: it ends.
+  for (;;) {
+    if (EMIT && wk.k >= wk.stop) break;
+    u32 s = LC_SEPARATOR;
+    if (L.cur < L.end) s = uni(lc_symbol(in.enc, in.n, in.suf, L.cur, L.depth));
+    if (s >= LC_WILDCARD) {
+      // the level is done, or only specials are left in it, behind which no column is defined
+      if (L.below == NO_LEVEL) break;
+      free = at;
+      at = L.below;
+      L = lc_load(stack, at);
+      continue;
+    }
+    const u32 cur = L.cur;
+    const u32 e = lc_right_bound(in, cur, L.end, L.depth, s, lane);
+    L.cur = e;
+    children += 1;
+    if (L.depth >= deepest) continue;                 // (cannot be: a column that deep has no cell > 0)
+    const bool first = L.depth == 0;
+    const LcColumn above = { L.blo, L.bhi, 0, 0, 0 };
+    const bool room = (u64) free + LC_HEADER + m <= in.stack_words;
+    if (e - cur == 1 || !room) {
+      // alone in the text, one suffix after the other, in the two columns of the wave
+      if (e - cur > 1) other = true;
+      for (u32 idx = cur; idx < e; idx++) {
+        if (EMIT && wk.k >= wk.stop) break;
+        const u64 raw = in.suf[idx];
+        const u64 p = (u64) uni((u32) (raw >> 32)) << 32 | uni((u32) raw);
+        LcMatch hit = { 0, 0, 0, 0 };
+        if (p < in.n) hit = lc_walk(stack + L.cells, above, L.depth, in.enc, in.n, p, q, m, in.sc, in.T, cola, colb);
+        lc_give<EMIT>(wk, lane == 0 && hit.dblen != 0, p, hit.dblen, hit.score, hit.e, hit.qstart);
+      }
+      walks += e - cur;
+      continue;
+    }
+    u32 *dst = stack + free + LC_HEADER;
+    const LcColumn col = lc_column(stack + L.cells, L.blo, L.bhi, first, s, q, m, in.sc, dst);
+    if (col.M >= in.T) {
+      // all suffixes of the child match with depth + 1 symbols
+      for (u32 b = cur; b < e; b += LC_BATCH) {
+        if (EMIT && wk.k >= wk.stop) break;
+        const u32 idx = b + lane;                     // (e <= N <= 2^32 - 4096: no wrap)
+        const u64 p = idx < e ? (u64) in.suf[idx] : in.n;
+        lc_give<EMIT>(wk, p < in.n, p, L.depth + 1, col.M, col.e, col.qstart);
+      }
+      continue;
+    }
+    if (col.M == 0) continue;
+    lc_store(stack, at, L, lane);
+    const u32 cells = free + LC_HEADER + lc_band_offset(col, first, L.blo);
+    L = LcLevel{ cur, e, cur, col.lo, col.hi, cells, at, L.depth + 1 };
+    at = free;
+    free = cells + (col.hi - col.lo);
+    pushed += 1;
+  }
+  if (!EMIT && lane == 0) {
+    cnt[j] = (u32) wk.k;                              // (at most one match per table entry: below 2^32)
+    if (wk.k) atomicMax((unsigned long long *) &w[W_MAXJOB], (unsigned long long) wk.k);
+    if (pushed) atomicAdd((unsigned long long *) &w[W_LEVELS], (unsigned long long) pushed);
+    if (children) atomicAdd((unsigned long long *) &w[W_CHILDREN], (unsigned long long) children);
+    if (walks) atomicAdd((unsigned long long *) &w[W_WALKS], (unsigned long long) walks);
+    if (other) atomicAdd((unsigned long long *) &w[W_OTHER], 1ull);
+  }
+}
+
+// Jobs [j0, j1), taken in turn by the waves of the grid, each with its own part
+// of `arena`.  EMIT false: cnt[job] = its matches.  EMIT true: records [w0, w1)
+// of all are written to out, record w0 first.
+template <typename S, bool EMIT>
+__global__ __launch_bounds__(LC_THREADS) void k_lc_walk(LcInput<S> in, u64 j0, u64 j1, u32 *cnt, const u64 *off, u64 w0,
+                                                        u64 w1, LcRecord *out, u32 *arena, u64 *w) {
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u64 slot = (u64) blockIdx.x * LC_WAVES + wave, slots = (u64) gridDim.x * LC_WAVES;
+  u32 *stack = arena + slot * ((u64) in.stack_words + 2ull * in.col_words);
+  u32 *cola = stack + in.stack_words, *colb = cola + in.col_words;
+  for (u64 j = j0 + slot; j < j1; j += slots)          // (the whole wave: the waves of a workgroup never wait for each other)
+    lc_job<S, EMIT>(in, j, stack, cola, colb, cnt, off, w0, w1, out, w, lane);
+}
+
+// tsum[b] = the sum of the counts of tile b, as offsets_u64 wants it
+__global__ __launch_bounds__(SC_THREADS) void k_lc_tile_sums(const u32 *cnt, u64 count, u64 *tsum) {
+  __shared__ unsigned long long ssum;
+  if (threadIdx.x == 0) ssum = 0;
+  __syncthreads();
+  const u64 i = (u64) blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i < count && cnt[i]) atomicAdd(&ssum, (unsigned long long) cnt[i]);
+  __syncthreads();
+  if (threadIdx.x == 0) tsum[blockIdx.x] = ssum;
+}
+
+// w[W_BAD] = the smallest (query << 2 | what is wrong with it); w[W_LONGEST]
+__global__ __launch_bounds__(LC_THREADS) void k_lc_validate(const u8 *queries, const u64 *qoff, u64 Q, u32 match,
+                                                            u32 sigma, u64 *w) {
+  const u64 t = (u64) blockIdx.x * LC_THREADS + threadIdx.x;
+  if (t >= Q) return;
+  const u64 a = qoff[t], b = qoff[t + 1];
+  u32 bad = 0;
+  if ((t == 0 && a != 0) || b <= a || b - a > LC_MAX_QUERY || b > qoff[Q]) bad = BAD_LENGTH;
+  else if ((b - a) * match > LC_MAX_SCORE) bad = BAD_SCORE;
+  else {
+    for (u64 x = a; x < b; x++)
+      if (queries[x] >= sigma && queries[x] != LC_WILDCARD) bad = BAD_SYMBOL;
+    atomicMax((unsigned long long *) &w[W_LONGEST], (unsigned long long) (b - a));
+  }
+  if (bad) atomicMin((unsigned long long *) &w[W_BAD], (unsigned long long) (t << 2 | bad));
+}
+
+// Table entry i in [1, N): the first depth k < depth_max at which the symbols of
+// the suffixes i - 1 and i differ, two specials being equal and ending the
+// comparison: cuts[..] = i | k << 32, in no order; w[W_CUTS] = how many there
+// are.  Those beyond `room` are dropped, which joins two groups and loses none.
+template <typename S>
+__global__ __launch_bounds__(LC_THREADS) void k_lc_cuts(const u8 *enc, u64 n, const S *suf, u32 N, u32 depth_max,
+                                                        u64 *cuts, u32 room, u64 *w) {
+  const u64 i = (u64) blockIdx.x * LC_THREADS + threadIdx.x + 1;
+  if (i >= N) return;
+  for (u32 k = 0; k < depth_max; k++) {
+    const u32 a = lc_symbol(enc, n, suf, (u32) i - 1, k), b = lc_symbol(enc, n, suf, (u32) i, k);
+    if (a >= LC_WILDCARD && b >= LC_WILDCARD) return;
+    if (a != b) {
+      const u64 place = atomicAdd((unsigned long long *) &w[W_CUTS], 1ull);
+      if (place < room) cuts[place] = i | (u64) k << 32;
+      return;
+    }
+  }
+}
+
+}  // namespace
+
+struct gtamd_locali : ConsumerBase<> {
+  ResidentIndex index;
+  u32 sigma = 0, cut_max = 0, compute_units = 0;
+  std::vector<u64> cuts;          // of the index, ascending table index: i | depth << 32
+  u32 forced_stack = 0, forced_cut = GTAMD_LOCALI_AUTO;
+  bool prepared = false;
+  // what a prepare leaves for the emit calls
+  Dev<u8> own_queries;
+  Dev<u64> own_qoff;
+  const u8 *queries = nullptr;
+  const u64 *qoff = nullptr;
+  u64 Q = 0, jobs = 0;
+  LcScores sc = { 1, -1, 1 };
+  u32 T = 1, groups = 0, stack_words = 0, col_words = 0, blocks = 0;
+  Dev<u32> cnt, gstart, arena;
+  Dev<u64> tsum, off, cutlist;
+  std::vector<u64> off_host;      // the places of the jobs' first records: which jobs a window needs
+  Dev<u8> out;                    // records on their way to host memory
+  gtamd_locali_info info = gtamd_locali_info();
+};
+
+namespace {
+
+const char FEATURE[] = "local alignments";
+
+int out_of_memory(u64 entries, const char *of) {
+  gtamd_set_error("local alignments: cannot allocate device memory for %llu %s", (unsigned long long) entries, of);
+  return -1;
+}
+
+// the cuts of a new index down to the largest depth q may take
+template <typename S> int find_cuts(gtamd_locali *lc) {
+  const u32 N = (u32) (lc->index.n + 1);
+  if (lc->cutlist.grow((u64) LC_CUT_LIST * 8) != hipSuccess) return out_of_memory(LC_CUT_LIST, "cuts");
+  HIP_TRY(hipMemsetAsync(lc->words + W_CUTS, 0, sizeof(u64), lc->st));
+  if (N > 1)
+    k_lc_cuts<S><<<(u32) div_up(N - 1, LC_THREADS), LC_THREADS, 0, lc->st>>>(
+        lc->index.enc, lc->index.n, (const S *) lc->index.suf, N, lc->cut_max, lc->cutlist, LC_CUT_LIST, lc->words);
+  HIP_TRY(hipGetLastError());
+  u64 found = 0;
+  TRY(fetch(lc->st, { { lc->words + W_CUTS, &found, sizeof found } }));
+  if (found > LC_CUT_LIST) found = LC_CUT_LIST;        // (no suffix table)
+  lc->cuts.resize(found);
+  TRY(fetch(lc->st, { { lc->cutlist, lc->cuts.data(), found * 8 } }));
+  std::sort(lc->cuts.begin(), lc->cuts.end(),
+            [](u64 a, u64 b) { return (a & 0xffffffffull) < (b & 0xffffffffull); });
+  return 0;
+}
+
+// every way of setting an index: what is refused, before anything is touched
+int set_index(gtamd_locali *lc, const IndexView &v, u32 sigma, bool from_host) {
+  if (lc == nullptr || v.suf == nullptr || (v.enc == nullptr && v.n)) {
+    gtamd_set_error("invalid argument to gtamd_locali_set_index");
+    return -1;
+  }
+  TRY(refuse_suf_bytes(FEATURE, v.suf_bytes));
+  TRY(refuse_sizes(FEATURE, v.n, 0));
+  if (sigma == 0 || sigma > LC_LETTERS) {
+    gtamd_set_error("local alignments: an alphabet of %u letters, 1 to %u expected", sigma, LC_LETTERS);
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(lc->device));
+  lc->prepared = false;
+  lc->sigma = sigma;
+  lc->cut_max = 1;
+  for (u64 groups = sigma; sigma > 1 && groups * sigma <= LC_CUT_GROUPS; groups *= sigma) lc->cut_max += 1;
+  if (from_host) TRY(lc->index.upload_from_host(FEATURE, v));
+  else lc->index.borrow(v);
+  const int rc = v.suf_bytes == 4 ? find_cuts<u32>(lc) : find_cuts<u64>(lc);
+  if (rc != 0) lc->index.drop();
+  return rc;
+}
+
+u64 held_bytes(const gtamd_locali *lc) {
+  return lc->index.bytes() + lc->own_queries.bytes + lc->own_qoff.bytes + lc->cnt.bytes + lc->gstart.bytes +
+         lc->arena.bytes + lc->tsum.bytes + lc->off.bytes + lc->cutlist.bytes + lc->words.bytes + lc->out.bytes;
+}
+
+template <typename S> LcInput<S> input(const gtamd_locali *lc) {
+  return LcInput<S>{ lc->index.enc, lc->index.n, (const S *) lc->index.suf, (u32) (lc->index.n + 1),
+                     lc->queries, lc->qoff, lc->gstart, lc->groups, lc->sc, lc->T, lc->stack_words, lc->col_words };
+}
+
+// the message for what k_lc_validate found
+int refuse_query(gtamd_locali *lc, u64 found) {
+  const u64 t = found >> 2;
+  u64 ab[2] = { 0, 0 };
+  TRY(fetch(lc->st, { { lc->qoff + t, ab, sizeof ab } }));
+  const unsigned long long query = t, len = ab[1] - ab[0];
+  switch (found & 3) {
+    case BAD_LENGTH:
+      if (ab[1] > ab[0] && len > LC_MAX_QUERY)
+        gtamd_set_error("local alignments: query number %llu of length %llu; queries must not be longer than %u",
+                        query, len, LC_MAX_QUERY);
+      else
+        gtamd_set_error("local alignments: query number %llu is empty, or the offsets do not ascend from 0 to "
+                        "their last", query);
+      break;
+    case BAD_SCORE:
+      gtamd_set_error("local alignments: query number %llu of length %llu with a match score of %d can reach a "
+                      "score above %u, the largest a cell holds", query, len, lc->sc.match, LC_MAX_SCORE);
+      break;
+    default:
+      gtamd_set_error("local alignments: query number %llu holds a symbol that is neither a letter of the "
+                      "alphabet of %u letters nor the wildcard", query, lc->sigma);
+  }
+  return -1;
+}
+
+// the groups of this prepare: the cuts above depth q, between 0 and N
+int set_groups(gtamd_locali *lc, u64 Q) {
+  const u64 N = lc->index.n + 1;
+  u32 q = lc->forced_cut;
+  if (q == GTAMD_LOCALI_AUTO) {
+    std::vector<u64> upto(lc->cut_max + 1, 1);         // groups with the cuts above depth q
+    for (u64 c : lc->cuts)
+      for (u32 d = (u32) (c >> 32) + 1; d <= lc->cut_max; d++) upto[d] += 1;
+    q = 0;
+    while (q < lc->cut_max && Q * upto[q] < LC_TARGET_JOBS) q += 1;
+  }
+  std::vector<u32> start;
+  start.push_back(0);
+  for (u64 c : lc->cuts)
+    if ((u32) (c >> 32) < q) start.push_back((u32) c);
+  start.push_back((u32) N);
+  lc->groups = (u32) start.size() - 1;
+  lc->info.cut_depth = q < lc->cut_max ? q : lc->cut_max;
+  lc->info.groups = lc->groups;
+  if (lc->gstart.grow(start.size() * 4) != hipSuccess) return out_of_memory(start.size(), "groups");
+  HIP_TRY(hipMemcpy(lc->gstart, start.data(), start.size() * 4, hipMemcpyHostToDevice));
+  return 0;
+}
+
+template <typename S> int prepare(gtamd_locali *lc) {
+  hipStream_t st = lc->st;
+  const u64 Q = lc->Q;
+  HIP_TRY(hipMemsetAsync(lc->words, 0, W_CUTS * sizeof(u64), st));
+  HIP_TRY(hipMemsetAsync(lc->words + W_BAD, 0xff, sizeof(u64), st));
+  HIP_TRY(hipEventRecord(lc->ev[0], st));
+  k_lc_validate<<<(u32) div_up(Q, LC_THREADS), LC_THREADS, 0, st>>>(lc->queries, lc->qoff, Q, (u32) lc->sc.match,
+                                                                   lc->sigma, lc->words);
+  HIP_TRY(hipGetLastError());
+  u64 found[2] = { 0, 0 };
+  TRY(fetch(st, { { lc->words + W_BAD, found, sizeof found } }));
+  if (found[0] != ~0ull) return refuse_query(lc, found[0]);
+  TRY(set_groups(lc, Q));
+  const u64 jobs = Q * lc->groups, tiles = div_up(jobs, SC_THREADS);
+  if (jobs > LC_MAX_JOBS) {
+    gtamd_set_error("local alignments: %llu queries times %u groups of the table are more than %llu jobs",
+                    (unsigned long long) Q, lc->groups, (unsigned long long) LC_MAX_JOBS);
+    return -1;
+  }
+  lc->jobs = jobs;
+  lc->info.jobs = jobs;
+  if (lc->cnt.grow(jobs * 4) != hipSuccess || lc->off.grow((jobs + 1) * 8) != hipSuccess ||
+      lc->tsum.grow(tiles * 8) != hipSuccess)
+    return out_of_memory(jobs, "jobs");
+  // per wave of the grid: the stack, and two columns of the longest query for the suffixes that go on alone
+  const u32 longest = (u32) found[1];
+  lc->col_words = (longest + 63) / 64 * 64;
+  lc->stack_words = lc->forced_stack ? lc->forced_stack : 32 * lc->col_words + 4096;
+  const u64 most = (u64) lc->compute_units * LC_WAVES_PER_CU / LC_WAVES;
+  lc->blocks = (u32) std::min<u64>(div_up(jobs, LC_WAVES), most ? most : 1);
+  const u64 words = (u64) lc->blocks * LC_WAVES * ((u64) lc->stack_words + 2ull * lc->col_words);
+  if (lc->arena.grow(words * 4) != hipSuccess) {
+    gtamd_set_error("local alignments: cannot allocate %llu bytes of device memory for the columns of %u waves "
+                    "(%u words of stack each; gtamd_locali_set_limits)", (unsigned long long) (words * 4),
+                    lc->blocks * LC_WAVES, lc->stack_words);
+    return -1;
+  }
+  k_lc_walk<S, false><<<lc->blocks, LC_THREADS, 0, st>>>(input<S>(lc), 0, jobs, lc->cnt, nullptr, 0, 0, nullptr,
+                                                        lc->arena, lc->words);
+  HIP_TRY(hipGetLastError());
+  k_lc_tile_sums<<<(u32) tiles, SC_THREADS, 0, st>>>(lc->cnt, jobs, lc->tsum);
+  HIP_TRY(hipGetLastError());
+  TRY(offsets_u64(lc->cnt, jobs, lc->tsum, lc->off, lc->words + W_MATCHES, st));
+  HIP_TRY(hipEventRecord(lc->ev[1], st));
+  u64 h[W_WORDS];
+  lc->off_host.resize(jobs + 1);
+  TRY(fetch(st, { { lc->words, h, sizeof h }, { lc->off, lc->off_host.data(), (jobs + 1) * sizeof(u64) } }));
+  HIP_TRY(hipEventElapsedTime(&lc->info.device_ms, lc->ev[0], lc->ev[1]));
+  lc->info.matches = h[W_MATCHES];
+  lc->info.max_matches_of_one_job = h[W_MAXJOB];
+  lc->info.levels_pushed = h[W_LEVELS];
+  lc->info.children_examined = h[W_CHILDREN];
+  lc->info.single_walks = h[W_WALKS];
+  lc->info.jobs_finished_alone = h[W_OTHER];
+  lc->info.stack_words = lc->stack_words;
+  return 0;
+}
+
+int emit(gtamd_locali *lc, u64 *cursor, gtamd_locali_record *out, u64 capacity, int out_on_device, u64 *written) {
+  *written = 0;
+  const u64 total = lc->info.matches, cur = *cursor;
+  if (cur > total) {
+    gtamd_set_error("local alignments: cursor %llu is not one of this enumeration (%llu records)",
+                    (unsigned long long) cur, (unsigned long long) total);
+    return -1;
+  }
+  if (capacity < LC_MIN_CAPACITY) {
+    gtamd_set_error("local alignments: a capacity of %llu records is too small: a capacity of at least %llu is "
+                    "needed", (unsigned long long) capacity, (unsigned long long) LC_MIN_CAPACITY);
+    return -1;
+  }
+  if (cur == total) return 0;
+  const u64 w1 = capacity < total - cur ? cur + capacity : total;
+  // the jobs with a record in [cur, w1): from the last whose first record is not
+  // behind cur up to the first whose first record is not in front of w1
+  const std::vector<u64> &off = lc->off_host;
+  const u64 j0 = (u64) (std::upper_bound(off.begin(), off.end(), cur) - off.begin()) - 1;
+  const u64 j1 = (u64) (std::lower_bound(off.begin(), off.end(), w1) - off.begin());
+  LcRecord *dst = (LcRecord *) out;
+  if (!out_on_device) {
+    if (lc->out.grow((w1 - cur) * sizeof(LcRecord)) != hipSuccess) return out_of_memory(w1 - cur, "records");
+    dst = (LcRecord *) lc->out.p;
+  }
+  const u32 blocks = (u32) std::min<u64>(div_up(j1 - j0, LC_WAVES), lc->blocks);      // (the arena has room for lc->blocks)
+  if (lc->index.suf_bytes == 4)
+    k_lc_walk<u32, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u32>(lc), j0, j1, nullptr, lc->off, cur, w1, dst,
+                                                             lc->arena, lc->words);
+  else
+    k_lc_walk<u64, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u64>(lc), j0, j1, nullptr, lc->off, cur, w1, dst,
+                                                             lc->arena, lc->words);
+  HIP_TRY(hipGetLastError());
+  TRY(fetch(lc->st, { { dst, out, out_on_device ? 0 : (w1 - cur) * sizeof(LcRecord) } }));
+  lc->info.emitted += w1 - cur;
+  *cursor = w1;
+  *written = w1 - cur;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" gtamd_locali *gtamd_locali_create(int device) {
+  GTAMD_ABI_BEGIN
+  gtamd_locali *lc = create_consumer<gtamd_locali>(device, W_WORDS, "the local aligner");
+  if (lc == nullptr) return nullptr;
+  int units = 0;
+  if (hipDeviceGetAttribute(&units, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || units <= 0) {
+    gtamd_set_error("cannot read the number of compute units of device %d", device);
+    destroy_consumer(lc);
+    return nullptr;
+  }
+  lc->compute_units = (u32) units;
+  return lc;
+  GTAMD_ABI_END(nullptr)
+}
+
+extern "C" void gtamd_locali_destroy(gtamd_locali *lc) { destroy_consumer(lc); }
+
+extern "C" void gtamd_locali_geometry(uint32_t *jobs_per_workgroup, uint64_t *min_capacity, uint32_t *max_query,
+                                      uint32_t *min_stack_words) {
+  if (jobs_per_workgroup != nullptr) *jobs_per_workgroup = LC_WAVES;
+  if (min_capacity != nullptr) *min_capacity = LC_MIN_CAPACITY;
+  if (max_query != nullptr) *max_query = LC_MAX_QUERY;
+  if (min_stack_words != nullptr) *min_stack_words = LC_HEADER;
+}
+
+extern "C" int gtamd_locali_set_index(gtamd_locali *lc, const uint8_t *enc, uint64_t n, const void *suf,
+                                      uint32_t suf_bytes, uint32_t numofchars) {
+  GTAMD_ABI_BEGIN
+  return set_index(lc, IndexView{ enc, n, suf, suf_bytes }, numofchars, false);
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_locali_set_index_host(gtamd_locali *lc, const uint8_t *enc, uint64_t n, const void *suf,
+                                           uint32_t suf_bytes, uint32_t numofchars) {
+  GTAMD_ABI_BEGIN
+  return set_index(lc, IndexView{ enc, n, suf, suf_bytes }, numofchars, true);
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_locali_set_index_esa(gtamd_locali *lc, const gtamd_esa_ctx *esa, const uint8_t *enc, uint64_t n,
+                                          uint32_t numofchars) {
+  GTAMD_ABI_BEGIN
+  if (lc == nullptr || esa == nullptr) { gtamd_set_error("invalid argument to gtamd_locali_set_index_esa"); return -1; }
+  IndexView v;
+  TRY(engine_tables(FEATURE, esa, enc, n, false, &v));
+  return set_index(lc, v, numofchars, false);
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_locali_set_limits(gtamd_locali *lc, uint32_t stack_words, uint32_t cut_depth) {
+  GTAMD_ABI_BEGIN
+  if (lc == nullptr) { gtamd_set_error("invalid argument to gtamd_locali_set_limits"); return -1; }
+  if (stack_words != 0 && (stack_words < LC_HEADER || stack_words > LC_MAX_STACK)) {
+    gtamd_set_error("local alignments: a stack of %u words, 0 (chosen from the longest query) or %u to %u expected",
+                    stack_words, LC_HEADER, LC_MAX_STACK);
+    return -1;
+  }
+  if (cut_depth != GTAMD_LOCALI_AUTO && cut_depth > 16) {
+    gtamd_set_error("local alignments: a cut depth of %u, GTAMD_LOCALI_AUTO or 0 to 16 expected (a depth beyond "
+                    "what the alphabet allows is taken as the largest it allows)", cut_depth);
+    return -1;
+  }
+  lc->forced_stack = stack_words;
+  lc->forced_cut = cut_depth;          // (what is prepared keeps the sizes it was prepared with)
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_locali_prepare(gtamd_locali *lc, const uint8_t *queries, const uint64_t *offsets, uint64_t Q,
+                                    int is_device, int32_t match, int32_t mismatch, int32_t gapextend,
+                                    uint32_t threshold, gtamd_locali_info *info) {
+  GTAMD_ABI_BEGIN
+  if (lc == nullptr || (Q != 0 && (queries == nullptr || offsets == nullptr))) {
+    gtamd_set_error("invalid argument to gtamd_locali_prepare");
+    return -1;
+  }
+  if (!lc->index.set) {
+    gtamd_set_error("local alignments: no index is set (gtamd_locali_set_index)");
+    return -1;
+  }
+  if (match <= 0 || mismatch >= 0 || gapextend >= 0 || match > LC_MAX_WEIGHT || mismatch < -LC_MAX_WEIGHT ||
+      gapextend < -LC_MAX_WEIGHT) {
+    gtamd_set_error("local alignments: scores match %d, mismatch %d, gapextend %d; match must be in 1..%d, mismatch "
+                    "and gapextend in -%d..-1 (with other signs the walk need not end)", match, mismatch, gapextend,
+                    LC_MAX_WEIGHT, LC_MAX_WEIGHT);
+    return -1;
+  }
+  if (threshold == 0) {
+    gtamd_set_error("local alignments: a threshold of 0, at least 1 expected");
+    return -1;
+  }
+  if (Q > LC_MAX_QUERIES) {
+    gtamd_set_error("local alignments: %llu queries, at most %llu in one call", (unsigned long long) Q,
+                    (unsigned long long) LC_MAX_QUERIES);
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(lc->device));
+  lc->prepared = false;
+  lc->info = gtamd_locali_info();
+  lc->Q = Q;
+  lc->jobs = 0;
+  lc->sc = LcScores{ match, mismatch, -gapextend };
+  lc->T = threshold;
+  lc->off_host.assign(1, 0);
+  if (Q != 0) {
+    lc->queries = queries;
+    lc->qoff = offsets;
+    if (!is_device) {
+      const u64 symbols = offsets[Q];
+      if (lc->own_queries.grow(symbols ? symbols : 1) != hipSuccess || lc->own_qoff.grow((Q + 1) * 8) != hipSuccess)
+        return out_of_memory(symbols, "query symbols");
+      if (symbols) HIP_TRY(hipMemcpyAsync(lc->own_queries, queries, symbols, hipMemcpyHostToDevice, lc->st));
+      HIP_TRY(hipMemcpyAsync(lc->own_qoff, offsets, (Q + 1) * 8, hipMemcpyHostToDevice, lc->st));
+      lc->queries = lc->own_queries;
+      lc->qoff = lc->own_qoff;
+    }
+    TRY(lc->index.suf_bytes == 4 ? prepare<u32>(lc) : prepare<u64>(lc));
+  }
+  lc->info.device_bytes = held_bytes(lc);
+  lc->prepared = true;
+  if (info != nullptr) *info = lc->info;
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_locali_emit(gtamd_locali *lc, uint64_t *cursor, gtamd_locali_record *out, uint64_t capacity,
+                                 int out_on_device, uint64_t *written) {
+  GTAMD_ABI_BEGIN
+  if (lc == nullptr || cursor == nullptr || written == nullptr || (out == nullptr && capacity)) {
+    gtamd_set_error("invalid argument to gtamd_locali_emit");
+    return -1;
+  }
+  if (!lc->prepared) {
+    gtamd_set_error("local alignments: nothing is prepared (gtamd_locali_prepare)");
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(lc->device));
+  TRY(emit(lc, cursor, out, capacity, out_on_device, written));
+  lc->info.device_bytes = held_bytes(lc);
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_locali_get_info(const gtamd_locali *lc, gtamd_locali_info *info) {
+  GTAMD_ABI_BEGIN
+  return consumer_info(lc, info, "gtamd_locali_get_info");
+  GTAMD_ABI_END(-1)
+}

@@ -1225,3 +1225,8 @@ done:
    list of files, of which this is the one with the helpers the tool needs (see the
    head of tagmatch_host.c). */
 #include "tagmatch_host.c"
+
+/* ---- gt dev idxlocali ----
+   The same arrangement: it reads a project back with the helpers above and takes
+   switch_option from tagmatch_host.c. */
+#include "locali_host.c"

@@ -7,7 +7,8 @@
    `gt-suffixerator-amd repfind ...` is `gt repfind ...`,
    `gt-suffixerator-amd querymatch ...` is `gt repfind ...` with -q, -r or -p,
    `gt-suffixerator-amd encseq2spm ...` is `gt encseq2spm ...`,
-   `gt-suffixerator-amd tagerator ...` is `gt tagerator ...` */
+   `gt-suffixerator-amd tagerator ...` is `gt tagerator ...`,
+   `gt-suffixerator-amd idxlocali ...` is `gt dev idxlocali ...` */
 #include <stdio.h>
 #include <string.h>
 #include "gtamd_host.h"
@@ -61,6 +62,13 @@ int main(int argc, char **argv)
   if (argc > 1 && !strcmp(argv[1], "tagerator")) {
     if (gtamd_tagerator(argc - 1, (const char **) argv + 1, err, sizeof err) != 0) {
       fprintf(stderr, "gt tagerator: error: %s\n", err);
+      return 1;
+    }
+    return 0;
+  }
+  if (argc > 1 && !strcmp(argv[1], "idxlocali")) {
+    if (gtamd_idxlocali(argc - 1, (const char **) argv + 1, err, sizeof err) != 0) {
+      fprintf(stderr, "gt dev idxlocali: error: %s\n", err);
       return 1;
     }
     return 0;

@@ -29,6 +29,9 @@
     gtamd_tagerator         `gt tagerator -e K -esa INDEX -q TAGS`
                             (src/tools/gt_tagerator.c), on the device through
                             include/gtamd_tagmatch.h
+    gtamd_idxlocali         `gt dev idxlocali -th T -esa INDEX -q FILES`
+                            (src/tools/gt_idxlocali.c), on the device through
+                            include/gtamd_locali.h
 
   Pure C (gcc); links against libgtamd_esa.so for the hot path.
 */
@@ -447,6 +450,34 @@ int gtamd_encseq2spm(int argc, const char **argv, char *err, size_t errlen);
    Returns 0, or -1 with the message in err (the caller prints "gt tagerator:
    error: <err>" and exits 1). */
 int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen);
+
+/* `gt dev idxlocali -th T -esa INDEX -q FILE...` (tool function
+   src/tools/gt_idxlocali.c, gt_runidxlocali src/match/idxlocali.c): every local
+   alignment of the queries against the index whose score reaches T, from
+   INDEX.prj, .esq, .ssp and .suf on the device (include/gtamd_locali.h).  The
+   sub-command `idxlocali`.
+     -th T        the threshold, an integer >= 1; mandatory
+     -q FILE...   the queries (FASTA); characters the index's alphabet does not
+                  know end the call with the reference's message, wildcards stay
+                  and equal nothing
+     -match -mismatch -gapextend   the scores (defaults 1, -3, -2); a match score
+                  <= 0 and a mismatch or gap extension score >= 0 are refused,
+                  which the reference does not do (its walk need not end then)
+     -gapstart    parsed and without effect, as in the reference, whose affine
+                  gap model is compiled out
+     -s           the alignment behind each match, 70 columns a block, the query
+                  on top (gt_alignment_show_with_mapped_chars); rebuilt on the
+                  host from the columns of the match
+     -v           the figures of gtamd_locali_info as a line starting with '#'
+                  behind the matches
+   stdout: `# indexname(esa)=`, one `# queryfile=` per file, `# threshold=`, then
+   per query (numbered across the files) `process sequence Q of length m` and
+   per match `seqnum\trelpos\tdblen\t\tQ\tqstart\tqlen\tscore`.  The matches
+   of one query come in the order of the suffix table; the reference's come in
+   the order of its stack.  -pck, -online and -cmp are refused by name.
+   Returns 0, or -1 with the message in err (the caller prints "gt dev
+   idxlocali: error: ..."). */
+int gtamd_idxlocali(int argc, const char **argv, char *err, size_t errlen);
 
 #ifdef __cplusplus
 }
