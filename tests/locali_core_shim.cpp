@@ -17,7 +17,7 @@ uint32_t lc_shim_walk(const uint8_t *q, uint32_t m, const uint8_t *enc, uint64_t
 
 uint32_t lc_shim_max_depth(uint32_t m, int match, int gapextend) { return lc_max_depth(m, LcScores{ match, -1, -gapextend }); }
 
-// figures[13]: the members of lccases::Tally in their order
+// figures[22]: the members of lccases::Tally in their order
 void lc_shim_cases(unsigned long long *figures) {
   const lccases::Tally t = lccases::run();
   memcpy(figures, &t, sizeof t);

@@ -9,9 +9,22 @@ The cases of tests/locali_core_cases.h -- m in {1, 2, 3, 63, 64, 65, 127, 128,
 129}, five sets of scores, sigma in {2, 4}, a wildcard in the query, a
 wildcard, a separator and the end at every distance from the start, a Delete
 run across rows 63, 64, 65, all short queries over two letters against all
-subjects of six symbols for the ties, the deepest walk the bound allows -- run
+subjects of six symbols for the ties, the deepest walk the bound allows; and
+the long queries: m in {191, 192, 193, 1000, 4097, 16384} with two sets of
+scores, walked from where the query's tail aligns (bands in the last chunk,
+every column from an unaligned row) and from where its head does (columns that
+stop long before row m), Delete runs of 200 rows that hang from one letter and
+runs that end on every row of a chunk beyond the last candidate, exact copies
+that score 65504, 65472, 65408, 65534 and 49152 under T equal to that and one
+above it, the last of them with 16384 letters and a gap of 32767, equal
+maxima of which one lies in row 16384 -- run
 twice: inside the library this test loads, and as a program of their own built
-with -fsanitize=address,undefined, started as a child process."""
+with -fsanitize=address,undefined, started as a child process.
+
+The sanitized program ran 8.8 s before the long queries were added and runs
+16.3 s with them (one core of the build machine; 1.5 s and 4.7 s without the
+sanitizers); most of what was added is the plain statement's 16384 full
+columns of the longest exact copy, whose traces take 268 MB in either run."""
 import ctypes
 import os
 import subprocess
@@ -29,7 +42,9 @@ SRC = [os.path.join(ROOT, "tests", f) for f in ("locali_core_shim.cpp", "locali_
 SHIM = os.path.join(ROOT, "oracle", "_build", "liblocali_core_shim.so")
 MAIN = os.path.join(ROOT, "oracle", "_build", "locali_core_main_san")
 TALLY = ("walks", "columns", "matches", "failures", "tie_del_rep", "tie_del_ins", "tie_rep_ins", "delete_across",
-         "two_maxima", "zero_cells", "depth_one", "deepest_reached", "stopped_by_special")
+         "two_maxima", "zero_cells", "depth_one", "deepest_reached", "stopped_by_special", "columns_past_three_chunks",
+         "band_starts_unaligned", "stopped_before_last_row", "delete_across_three", "row_above_16000",
+         "score_above_65000", "chain_dies_on_first_row", "chain_dies_on_last_row", "tie_with_last_row")
 
 
 def _stale(target):
@@ -84,7 +99,8 @@ def _walk(shim, q, enc, p, match, mismatch, gapextend, T):
 
 
 def test_the_depth_bound(shim):
-    for m, match, gap in ((4, 5, -1), (1, 1, -1), (64, 1, -1), (10, 3, -2), (300, 2, -1), (7, 1, -5)):
+    for m, match, gap in ((4, 5, -1), (1, 1, -1), (64, 1, -1), (10, 3, -2), (300, 2, -1), (7, 1, -5), (16384, 3, -1),
+                          (16384, 1, -32767), (1000, 65, -1)):
         d = shim.lc_shim_max_depth(m, match, gap)
         assert d == lr.max_depth(m, match, gap)
         assert match * m + gap * (d - m) > 0 >= match * m + gap * (d + 1 - m)

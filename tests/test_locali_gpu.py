@@ -9,7 +9,15 @@ computed 64 rows a step (queries of 63, 64, 65, 127, 128, 129 letters), the
 shared search probes 64 places a round and a successful child is given 64
 suffixes at a time (children of 1, 2, 64 and 65 suffixes), a workgroup has WAVES
 waves, an emit call takes at least LEAST records, a stack of STACK words holds
-the root of a walk alone."""
+the root of a walk alone.
+
+Beyond 129 letters: queries of 191, 192, 193, 320 and 1000 letters (columns of
+up to sixteen chunks, bands far from row 1); two copies of a piece under
+generous scores, for which the default stack runs out by itself at some
+depth and the rest of the path is finished suffix by suffix; the longest
+query there is, LONGEST letters, with matches that begin in row 0 and above
+row 16000; exact copies that score all but the whole 16 bits of a cell; a
+child of more than 64 * 64 suffixes."""
 import functools
 
 import numpy as np
@@ -25,6 +33,7 @@ WAVES, LEAST, LONGEST, STACK = locali.geometry()
 WIDTHS = [np.uint64, np.uint32]
 ONE = (1, -1, -1)
 STRICT = (1, -2, -2)          # random alignments die early: the reference stays quick
+TAIL = np.array([3, 0, 3, 3, 1, 3, 2, 3, 3, 0, 1, 3], dtype=np.uint8)      # the end of the longest query
 
 
 @pytest.fixture(scope="module")
@@ -70,6 +79,13 @@ def _subject(name):
         enc = np.concatenate(parts).astype(np.uint8)[:-1]
     elif kind == "run":
         enc = np.zeros(int(arg), dtype=np.uint8)
+    elif kind == "twice":                # two copies of one piece of `arg` letters, an a behind one and a c behind the other
+        rng = np.random.default_rng(44)
+        piece = rng.integers(0, 4, int(arg), dtype=np.uint8)
+        enc = np.concatenate([rng.integers(0, 4, 100), piece, [0], rng.integers(0, 4, 100), piece, [1],
+                              rng.integers(0, 4, 50)]).astype(np.uint8)
+    elif kind == "tiny":                 # 28 symbols: TAIL whole in one sequence, its first 7 letters in the other
+        enc = np.concatenate([_random(5, 3, 45), TAIL, [255], TAIL[:7], [1, 3, 3]]).astype(np.uint8)
     elif kind == "specials":
         enc = np.full(int(arg), 254, dtype=np.uint8)
         enc[::7] = 255
@@ -244,6 +260,107 @@ def test_the_deepest_walk(aligner):
         got = aligner.all_records([query], T, 5, -3, -1)
         assert np.array_equal(got, lr.records(enc, suf, [query], 5, -3, -1, T)) and got.shape[0] == count
     assert lr.max_depth(4, 5, -1) == 23
+
+
+# ---- queries beyond 129 letters ----
+
+def _ceil64(m):
+    return (m + 63) // 64 * 64
+
+
+@pytest.mark.parametrize("width", WIDTHS)
+def test_query_lengths_around_the_later_chunks(aligner, width):
+    """queries of 191, 192, 193, 320 and 1000 letters, cut from the subject, with
+    one replacement and one deletion: columns of three to sixteen chunks, bands
+    that lie far from row 1.  The reference takes 0.45 s for a query of 192
+    letters, 0.9 s for 320 and 4.1 s for 1000 (one core of the build machine)."""
+    enc = _subject("random:1500")[0]
+    queries = []
+    for k, m in enumerate((191, 192, 193, 320, 1000)):
+        query = _cut(enc, 40 + 61 * k, m + 1)
+        query[m // 3] = (query[m // 3] + 1) % 4
+        queries.append(np.delete(query, 2 * m // 3))
+    want, info = _agree(aligner, "random:1500", queries, 30, STRICT, width=width)
+    number, _, _, _, qstart, qlen = locali.unpack(want)
+    assert [q.size for q in queries] == [191, 192, 193, 320, 1000] and info["levels_pushed"] > 0
+    assert all((number == k).any() for k in range(5)) and ((number == 4) & (qstart + qlen > 900)).any()
+
+
+@pytest.mark.parametrize("cut_depth", [0, 1])
+@pytest.mark.parametrize("piece,m,scores", [(120, 129, (2, -1, -1)), (120, 192, (2, -1, -1)), (230, 260, ONE)])
+def test_the_default_stack_runs_out_by_itself(aligner, piece, m, scores, cut_depth):
+    """The subject holds a piece twice and the query begins with it; T = 200 is
+    reached 200 / match symbols down the path the two copies share, and with
+    these scores nearly every row of a column is > 0, so a level takes some m
+    words.  The default stack, 32 columns and 4096 words, is full long before:
+    the children from there on are finished suffix by suffix, without any
+    set_limits.  A stack of 2^20 words holds the whole path and gives the same
+    records.  The reference takes 1.7 s, 3.2 s and 6.1 s."""
+    name = "twice:%d" % piece
+    query = np.concatenate([_subject(name)[0][100:100 + piece], _random(m - piece, 4, 46)])
+    want, info = _agree(aligner, name, [query], 200, scores, stack_words=0, cut_depth=cut_depth)
+    assert info["stack_words"] == 32 * _ceil64(m) + 4096
+    assert info["jobs_finished_alone"] > 0
+    assert info["levels_pushed"] > 50
+    _, dbstart, dblen, _, _, _ = locali.unpack(want)
+    for at in (100, 100 + piece + 1 + 100):
+        assert ((dbstart == at) & (dblen == 200 // scores[0])).any()
+    info = _agree(aligner, name, [query], 200, scores, stack_words=1 << 20, cut_depth=cut_depth, set_index=False)[1]
+    assert info["stack_words"] == 1 << 20 and info["jobs_finished_alone"] == 0
+    # the device's own records of the two stacks, one against the other
+    got = []
+    for stack_words in (0, 1 << 20):
+        aligner.set_limits(stack_words, cut_depth)
+        got.append(aligner.all_records([query], 200, *scores))
+    aligner.set_limits()
+    assert np.array_equal(got[0], got[1]) and got[0].shape == want.shape
+
+
+@pytest.mark.parametrize("width", WIDTHS)
+@pytest.mark.parametrize("scores,T,count", [(ONE, 10, 4), ((3, -2, -1), 30, 8), ((3, -2, -2), 20, 13)])
+def test_the_longest_query(aligner, scores, T, count, width):
+    """LONGEST letters over a, c, g with the 12 letters of TAIL at the end and its
+    first five as letters 5 to 9, behind the five letters the subject begins
+    with, so that ten letters are equal and T = 10 is reached from row 0; the subject holds TAIL and its first seven letters, so matches begin in
+    row 0 and in the last rows a cell can name.
+    A second query of 5 letters follows in the same call: the columns are sized
+    from the longest query, not from the last.  The statement finds 4, 8 and 13
+    records, one of each from row 0 (four with the last scores: rows 0 to 3).
+    The reference takes 4.6 to 8.1 s a
+    threshold, shared by the two widths."""
+    query = _random(LONGEST, 3, 47)
+    query[-12:] = TAIL
+    query[:5] = _subject("tiny")[0][:5]           # the subject begins as the query does: ten equal letters
+    query[5:10] = TAIL[:5]
+    queries = [query, TAIL[:5].copy()]
+    want, info = _agree(aligner, "tiny", queries, T, scores, width=width)
+    number, _, _, _, qstart, _ = locali.unpack(want)
+    assert LONGEST == 16384 and info["stack_words"] == 32 * LONGEST + 4096 and want.shape[0] == count
+    assert ((number == 0) & (qstart > 16000)).any() and ((number == 0) & (qstart < 16)).any()
+    _agree(aligner, "tiny", queries, T, scores, capacity=LEAST, set_index=False)
+
+
+@pytest.mark.parametrize("match,m", [(2047, 32), (1023, 64), (511, 128), (32767, 2)])
+def test_the_top_of_a_cell(aligner, match, m):
+    """exact copies that score 65504, 65472, 65408 and 65534, all but the whole
+    16 bits of a cell, under a threshold equal to that, and under one above it,
+    which nothing reaches.  The reference takes 0.03 to 1.6 s a call."""
+    enc = _subject("random:300")[0]
+    query = _cut(enc, 150, m)
+    whole = match * m
+    want, _ = _agree(aligner, "random:300", [query], whole, (match, -1, -1))
+    _, dbstart, dblen, score, qstart, qlen = locali.unpack(want)
+    assert 65400 < whole <= 65535 and want.shape[0] > 0 and (score == whole).all()
+    assert ((dbstart == 150) & (dblen == m) & (qstart == 0) & (qlen == m)).any()
+    assert _agree(aligner, "random:300", [query], whole + 1, (match, -1, -1), set_index=False)[0].shape[0] == 0
+
+
+def test_a_child_wider_than_64_times_64(aligner):
+    """A^4200 as one group: the child of the root has 4200 suffixes, more than two
+    rounds of 64 probes tell apart, so the search for its right bound takes a third"""
+    queries = [np.zeros(12, dtype=np.uint8), np.zeros(5, dtype=np.uint8)]
+    want, info = _agree(aligner, "run:4200", queries, 5, ONE, cut_depth=0)
+    assert info["groups"] == 1 and want.shape[0] == 2 * 4196 and info["max_matches_of_one_job"] == 4196
 
 
 # ---- the width of a child ----

@@ -267,6 +267,16 @@ def test_levels_stay_wide_down_to_the_last_depth(matcher, name):
         assert want.shape[0] > 128 and info["levels_pushed"] >= m - K - 1
 
 
+def test_a_child_wider_than_64_times_64(matcher):
+    """A^4200: the child of the root has more suffixes than two rounds of 64
+    probes tell apart, so the search for its right bound takes a third (the
+    brute force needs 10 ms for this subject)"""
+    tags = [np.zeros(12, dtype=np.uint8), np.zeros(5, dtype=np.uint8)]
+    for K in (0, 1):
+        want = _agree(matcher, "run:4200", tags, K, set_index=K == 0)
+        assert want.shape[0] >= 4189 + 4196 and matcher.info()["max_matches_of_one_job"] >= 4196
+
+
 # ---- ends and specials ----
 
 def test_ends_and_specials(matcher):
