@@ -17,6 +17,7 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in
             "esa_maxpairs.hip", "esa_qmatch.hip", "esa_spm.hip", "esa_tagmatch.hip",
             "esa_locali.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_index.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
+                                                     "esa_jobs.h", "esa_ivwalk.h",
                                                      "esa_pck_replay.h", "esa_mstat_search.h",
                                                      "esa_maxpairs_walk.h", "esa_qmatch_core.h",
                                                      "esa_spm_core.h", "esa_tagmatch_core.h",

@@ -1,10 +1,12 @@
 // esa_index.h -- the host side that the consumers of a resident index share: the
-// checker, the matching statistics, the maximal pairs, the query matches and the
-// suffix-prefix matches (esa_check.hip, esa_mstat.hip, esa_maxpairs.hip,
-// esa_qmatch.hip, esa_spm.hip).  A new consumer starts here: its object is a
-// ConsumerBase with a ResidentIndex, made by create_consumer; what it reads back
-// goes through fetch, the records it hands out through a RecordStage; the 64-bit
-// places of its records are offsets_u64 of esa_prims.h.
+// checker, the matching statistics, the maximal pairs, the query matches, the
+// suffix-prefix matches, the tag matches and the local alignments (esa_check.hip,
+// esa_mstat.hip, esa_maxpairs.hip, esa_qmatch.hip, esa_spm.hip, esa_tagmatch.hip,
+// esa_locali.hip).  A new consumer starts here: its object is a ConsumerBase with
+// a ResidentIndex, made by create_consumer; what it reads back goes through
+// fetch, the records it hands out through a RecordStage, after refuse_window; the
+// 64-bit places of its records are offsets_u64 of esa_prims.h.  One that walks
+// the intervals of .suf job by job goes on in esa_jobs.h.
 //
 // `feature` is what a message starts with ("maximal pairs").  Only .hip files
 // include this header: the *_core.h, *_search.h and *_walk.h lane headers also
@@ -34,7 +36,7 @@ static inline int fetch(hipStream_t st, std::initializer_list<Fetch> items) {
 // written, the caller's device memory or `buf`, grown to hold them.  finish: `count`
 // of them are in the caller's memory and the stream is idle.
 template <typename R> struct RecordStage {
-  static_assert(sizeof(R) == 24, "a record is three 64-bit numbers");
+  static_assert(sizeof(R) % 8 == 0, "a record is a whole number of 64-bit numbers");
   void *out;
   bool on_device;
   R *dst;
@@ -49,6 +51,27 @@ template <typename R> struct RecordStage {
     return fetch(st, { { dst, out, on_device ? 0 : count * sizeof(R) } });
   }
 };
+
+// device memory for `entries` of something (`of`: "records") is not to be had
+static inline int out_of_memory(const char *feature, u64 entries, const char *of) {
+  gtamd_set_error("%s: cannot allocate device memory for %llu %s", feature, (unsigned long long) entries, of);
+  return -1;
+}
+
+// what every emit refuses first: a cursor that is none of `total` `noun`s, a capacity below `least`
+static inline int refuse_window(const char *feature, const char *noun, u64 cur, u64 total, u64 capacity, u64 least) {
+  if (cur > total) {
+    gtamd_set_error("%s: cursor %llu is not one of this enumeration (%llu %s)", feature, (unsigned long long) cur,
+                    (unsigned long long) total, noun);
+    return -1;
+  }
+  if (capacity < least) {
+    gtamd_set_error("%s: a capacity of %llu records is too small: a capacity of at least %llu is needed", feature,
+                    (unsigned long long) capacity, (unsigned long long) least);
+    return -1;
+  }
+  return 0;
+}
 
 // ---- host to device ------------------------------------------------------------
 constexpr u64 UPLOAD_PIECE = 64ull << 20;

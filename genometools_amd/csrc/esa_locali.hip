@@ -11,18 +11,14 @@
 //                         intervals of the group, the column of every level of the
 //                         path as a band of cells on a stack in global memory
 //                         (esa_locali_core.h); the matches of the job are counted
-//   c  offsets_u64 (esa_prims)     64-bit exclusive scan of the counts
+//   c  JobOffsets::scan (esa_jobs) 64-bit exclusive scan of the counts
 //   d  k_lc_walk<true>    the same walk for the jobs of a window of records,
 //                         which writes those
 //
 // Working memory: one entry per job, the cuts, and per wave of the grid a stack
 // and two columns.
-#include <algorithm>
-#include <vector>
 #include "esa_common.h"
-#include "esa_index.h"
-#include "esa_prims.h"
-#include "esa_devutil.h"
+#include "esa_jobs.h"
 #include "esa_locali_core.h"
 #include "../../include/gtamd_locali.h"
 
@@ -31,7 +27,7 @@ namespace {
 constexpr int LC_THREADS = SC_THREADS;
 constexpr u32 LC_WAVES = LC_THREADS / 64;          // waves of one workgroup: each walks jobs of its own
 constexpr u32 LC_WAVES_PER_CU = 8;                 // waves of the grid per compute unit
-constexpr u32 LC_BATCH = 64;
+constexpr u32 LC_BATCH = IV_BATCH;
 constexpr u64 LC_MIN_CAPACITY = LC_BATCH;
 constexpr u64 LC_MAX_QUERIES = 1ull << 24;
 constexpr u64 LC_MAX_JOBS = 1ull << 31;
@@ -42,14 +38,14 @@ constexpr u32 LC_CUT_LIST = 1u << 18;              // ... so a suffix table has 
 constexpr u64 LC_TARGET_JOBS = 1u << 14;           // q is the smallest depth that gives as many jobs
 constexpr u32 NO_LEVEL = 0xffffffffu;
 
-enum { W_MATCHES = 0, W_MAXJOB, W_LEVELS, W_CHILDREN, W_WALKS, W_OTHER, W_BAD, W_LONGEST, W_CUTS, W_WORDS };
+enum { W_OTHER = W_WALK_WORDS, W_BAD, W_LONGEST, W_CUTS, W_WORDS };
 enum { BAD_LENGTH = 1, BAD_SCORE = 2, BAD_SYMBOL = 3 };
 
 struct LcRecord { u64 query, dbstart, lenscore, qspan; };
 static_assert(sizeof(LcRecord) == sizeof(gtamd_locali_record), "a record is four 64-bit numbers");
 
 template <typename S> struct LcInput {
-  const u8 *enc; u64 n; const S *suf; u32 N;
+  IvText<S> text; u32 N;
   const u8 *queries; const u64 *qoff;
   const u32 *gstart; u32 groups;                   // group g: table entries [gstart[g], gstart[g + 1])
   LcScores sc; u32 T;
@@ -58,56 +54,8 @@ template <typename S> struct LcInput {
 
 __device__ __forceinline__ u32 uni(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// the symbol `d` behind the start of the suffix at table index idx < N; a separator
-// where there is none: behind the end, or for an entry that is no position
-template <typename S> __device__ __forceinline__ u32 lc_symbol(const u8 *enc, u64 n, const S *suf, u32 idx, u32 d) {
-  const u64 p = suf[idx];
-  if (p >= n) return LC_SEPARATOR;
-  const u64 x = p + d;
-  return x < n ? enc[x] : LC_SEPARATOR;
-}
-
-// The right bound of the child of letter s that starts at table index cur of a
-// level that ends at `end` (the search of esa_tagmatch.hip): 64 probes a round;
-// a round leaves fewer than span / 64 + 1 < span entries whatever the table
-// holds; the result lies in (cur, end].
-template <typename S>
-__device__ __forceinline__ u32 lc_right_bound(const LcInput<S> &in, u32 cur, u32 end, u32 d, u32 s, u32 lane) {
-  u32 lo = cur + 1, hi = end;
-  while (lo < hi) {
-    const u32 span = hi - lo;
-    const u32 step = span <= LC_BATCH ? 1 : (span + LC_BATCH - 1) / LC_BATCH;
-    const u64 q = (u64) lo + (u64) lane * step;
-    const bool differs = q >= hi || lc_symbol(in.enc, in.n, in.suf, (u32) q, d) != s;
-    const u64 mask = __ballot(differs);
-    const u32 f = mask ? (u32) __builtin_ctzll(mask) : LC_BATCH;
-    if (f == 0) return lo;
-    const u64 next = (u64) lo + (u64) f * step;
-    if (f < LC_BATCH && next < hi) hi = (u32) next;
-    lo = lo + (f - 1) * step + 1;
-  }
-  return lo;
-}
-
-struct LcWalk {
-  u64 k;                 // records of the job so far
-  u64 first, stop;       // EMIT: the records [first, stop) of the job are written ...
-  LcRecord *dst;         // ... record `first` here
-  u64 query;
-};
-
-// `keep` lanes have a match each, in table order
-template <bool EMIT>
-__device__ __forceinline__ void lc_give(LcWalk &wk, bool keep, u64 p, u32 dblen, u32 score, u32 e, u32 qstart) {
-  const u64 mask = __ballot(keep);
-  if (EMIT && keep) {
-    const u32 before = __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
-    const u64 place = wk.k + before;
-    if (place >= wk.first && place < wk.stop)
-      wk.dst[place - wk.first] = LcRecord{ wk.query, p, (u64) dblen | (u64) score << 32,
-                                           (u64) qstart | (u64) (e - qstart) << 32 };
-  }
-  wk.k += (u64) __popcll(mask);
+__device__ __forceinline__ LcRecord lc_record(u64 query, u64 p, u32 dblen, u32 score, u32 e, u32 qstart) {
+  return LcRecord{ query, p, (u64) dblen | (u64) score << 32, (u64) qstart | (u64) (e - qstart) << 32 };
 }
 
 // the level on top of the stack, in registers; the others as LC_HEADER words each
@@ -135,14 +83,9 @@ __device__ void lc_job(const LcInput<S> &in, u64 j, u32 *stack, u32 *cola, u32 *
                        u64 w1, LcRecord *out, u64 *w, u32 lane) {
   const u64 query = j / in.groups;
   const u32 g = (u32) (j % in.groups);
-  LcWalk wk = { 0, 0, 0, nullptr, query };
-  if (EMIT) {
-    const u64 base = off[j], after = off[j + 1];
-    if (after <= w0 || base >= w1 || after == base) return;
-    wk.first = w0 > base ? w0 - base : 0;
-    wk.stop = (w1 < after ? w1 : after) - base;
-    wk.dst = out + (base + wk.first - w0);
-  }
+  const IvText<S> &text = in.text;
+  JobWindow<LcRecord> wk = { 0, 0, 0, nullptr };
+  if (EMIT && !wk.open(off, j, w0, w1, out)) return;
   const u64 q0 = in.qoff[query];
   const u32 m = (u32) (in.qoff[query + 1] - q0);          // 1 .. LC_MAX_QUERY (k_lc_validate)
   const u8 *q = in.queries + q0;
@@ -156,10 +99,10 @@ __device__ void lc_job(const LcInput<S> &in, u64 j, u32 *stack, u32 *cola, u32 *
   // Every round moves the cursor of the top level forward by at least one, pops
   // the level or pushes one of the next depth, which is at most `deepest`: it ends.
   for (;;) {
-    if (EMIT && wk.k >= wk.stop) break;
-    u32 s = LC_SEPARATOR;
-    if (L.cur < L.end) s = uni(lc_symbol(in.enc, in.n, in.suf, L.cur, L.depth));
-    if (s >= LC_WILDCARD) {
+    if (EMIT && wk.full()) break;
+    u32 s = IV_SEPARATOR;
+    if (L.cur < L.end) s = uni(iv_symbol(text, L.cur, L.depth));
+    if (s >= IV_WILDCARD) {
       // the level is done, or only specials are left in it, behind which no column is defined
       if (L.below == NO_LEVEL) break;
       free = at;
@@ -168,7 +111,7 @@ __device__ void lc_job(const LcInput<S> &in, u64 j, u32 *stack, u32 *cola, u32 *
       continue;
     }
     const u32 cur = L.cur;
-    const u32 e = lc_right_bound(in, cur, L.end, L.depth, s, lane);
+    const u32 e = iv_right_bound(text, cur, L.end, L.depth, s);
     L.cur = e;
     children += 1;
     if (L.depth >= deepest) continue;                 // (cannot be: a column that deep has no cell > 0)
@@ -179,12 +122,12 @@ __device__ void lc_job(const LcInput<S> &in, u64 j, u32 *stack, u32 *cola, u32 *
       // alone in the text, one suffix after the other, in the two columns of the wave
       if (e - cur > 1) other = true;
       for (u32 idx = cur; idx < e; idx++) {
-        if (EMIT && wk.k >= wk.stop) break;
-        const u64 raw = in.suf[idx];
+        if (EMIT && wk.full()) break;
+        const u64 raw = text.suf[idx];
         const u64 p = (u64) uni((u32) (raw >> 32)) << 32 | uni((u32) raw);
         LcMatch hit = { 0, 0, 0, 0 };
-        if (p < in.n) hit = lc_walk(stack + L.cells, above, L.depth, in.enc, in.n, p, q, m, in.sc, in.T, cola, colb);
-        lc_give<EMIT>(wk, lane == 0 && hit.dblen != 0, p, hit.dblen, hit.score, hit.e, hit.qstart);
+        if (p < text.n) hit = lc_walk(stack + L.cells, above, L.depth, text.enc, text.n, p, q, m, in.sc, in.T, cola, colb);
+        wk.give<EMIT>(lane == 0 && hit.dblen != 0, lc_record(query, p, hit.dblen, hit.score, hit.e, hit.qstart));
       }
       walks += e - cur;
       continue;
@@ -194,10 +137,10 @@ __device__ void lc_job(const LcInput<S> &in, u64 j, u32 *stack, u32 *cola, u32 *
     if (col.M >= in.T) {
       // all suffixes of the child match with depth + 1 symbols
       for (u32 b = cur; b < e; b += LC_BATCH) {
-        if (EMIT && wk.k >= wk.stop) break;
+        if (EMIT && wk.full()) break;
         const u32 idx = b + lane;                     // (e <= N <= 2^32 - 4096: no wrap)
-        const u64 p = idx < e ? (u64) in.suf[idx] : in.n;
-        lc_give<EMIT>(wk, p < in.n, p, L.depth + 1, col.M, col.e, col.qstart);
+        const u64 p = idx < e ? (u64) text.suf[idx] : text.n;
+        wk.give<EMIT>(p < text.n, lc_record(query, p, L.depth + 1, col.M, col.e, col.qstart));
       }
       continue;
     }
@@ -210,11 +153,7 @@ __device__ void lc_job(const LcInput<S> &in, u64 j, u32 *stack, u32 *cola, u32 *
     pushed += 1;
   }
   if (!EMIT && lane == 0) {
-    cnt[j] = (u32) wk.k;                              // (at most one match per table entry: below 2^32)
-    if (wk.k) atomicMax((unsigned long long *) &w[W_MAXJOB], (unsigned long long) wk.k);
-    if (pushed) atomicAdd((unsigned long long *) &w[W_LEVELS], (unsigned long long) pushed);
-    if (children) atomicAdd((unsigned long long *) &w[W_CHILDREN], (unsigned long long) children);
-    if (walks) atomicAdd((unsigned long long *) &w[W_WALKS], (unsigned long long) walks);
+    report(w, cnt, j, wk.k, pushed, children, walks);
     if (other) atomicAdd((unsigned long long *) &w[W_OTHER], 1ull);
   }
 }
@@ -233,17 +172,6 @@ __global__ __launch_bounds__(LC_THREADS) void k_lc_walk(LcInput<S> in, u64 j0, u
     lc_job<S, EMIT>(in, j, stack, cola, colb, cnt, off, w0, w1, out, w, lane);
 }
 
-// tsum[b] = the sum of the counts of tile b, as offsets_u64 wants it
-__global__ __launch_bounds__(SC_THREADS) void k_lc_tile_sums(const u32 *cnt, u64 count, u64 *tsum) {
-  __shared__ unsigned long long ssum;
-  if (threadIdx.x == 0) ssum = 0;
-  __syncthreads();
-  const u64 i = (u64) blockIdx.x * SC_THREADS + threadIdx.x;
-  if (i < count && cnt[i]) atomicAdd(&ssum, (unsigned long long) cnt[i]);
-  __syncthreads();
-  if (threadIdx.x == 0) tsum[blockIdx.x] = ssum;
-}
-
 // w[W_BAD] = the smallest (query << 2 | what is wrong with it); w[W_LONGEST]
 __global__ __launch_bounds__(LC_THREADS) void k_lc_validate(const u8 *queries, const u64 *qoff, u64 Q, u32 match,
                                                             u32 sigma, u64 *w) {
@@ -255,7 +183,7 @@ __global__ __launch_bounds__(LC_THREADS) void k_lc_validate(const u8 *queries, c
   else if ((b - a) * match > LC_MAX_SCORE) bad = BAD_SCORE;
   else {
     for (u64 x = a; x < b; x++)
-      if (queries[x] >= sigma && queries[x] != LC_WILDCARD) bad = BAD_SYMBOL;
+      if (queries[x] >= sigma && queries[x] != IV_WILDCARD) bad = BAD_SYMBOL;
     atomicMax((unsigned long long *) &w[W_LONGEST], (unsigned long long) (b - a));
   }
   if (bad) atomicMin((unsigned long long *) &w[W_BAD], (unsigned long long) (t << 2 | bad));
@@ -266,13 +194,13 @@ __global__ __launch_bounds__(LC_THREADS) void k_lc_validate(const u8 *queries, c
 // comparison: cuts[..] = i | k << 32, in no order; w[W_CUTS] = how many there
 // are.  Those beyond `room` are dropped, which joins two groups and loses none.
 template <typename S>
-__global__ __launch_bounds__(LC_THREADS) void k_lc_cuts(const u8 *enc, u64 n, const S *suf, u32 N, u32 depth_max,
-                                                        u64 *cuts, u32 room, u64 *w) {
+__global__ __launch_bounds__(LC_THREADS) void k_lc_cuts(IvText<S> text, u32 N, u32 depth_max, u64 *cuts, u32 room,
+                                                        u64 *w) {
   const u64 i = (u64) blockIdx.x * LC_THREADS + threadIdx.x + 1;
   if (i >= N) return;
   for (u32 k = 0; k < depth_max; k++) {
-    const u32 a = lc_symbol(enc, n, suf, (u32) i - 1, k), b = lc_symbol(enc, n, suf, (u32) i, k);
-    if (a >= LC_WILDCARD && b >= LC_WILDCARD) return;
+    const u32 a = iv_symbol(text, (u32) i - 1, k), b = iv_symbol(text, (u32) i, k);
+    if (a >= IV_WILDCARD && b >= IV_WILDCARD) return;
     if (a != b) {
       const u64 place = atomicAdd((unsigned long long *) &w[W_CUTS], 1ull);
       if (place < room) cuts[place] = i | (u64) k << 32;
@@ -290,16 +218,13 @@ struct gtamd_locali : ConsumerBase<> {
   u32 forced_stack = 0, forced_cut = GTAMD_LOCALI_AUTO;
   bool prepared = false;
   // what a prepare leaves for the emit calls
-  Dev<u8> own_queries;
-  Dev<u64> own_qoff;
-  const u8 *queries = nullptr;
-  const u64 *qoff = nullptr;
+  SequenceSet queries;
   u64 Q = 0, jobs = 0;
   LcScores sc = { 1, -1, 1 };
   u32 T = 1, groups = 0, stack_words = 0, col_words = 0, blocks = 0;
-  Dev<u32> cnt, gstart, arena;
-  Dev<u64> tsum, off, cutlist;
-  std::vector<u64> off_host;      // the places of the jobs' first records: which jobs a window needs
+  JobOffsets jo;
+  Dev<u32> gstart, arena;
+  Dev<u64> cutlist;
   Dev<u8> out;                    // records on their way to host memory
   gtamd_locali_info info = gtamd_locali_info();
 };
@@ -308,19 +233,15 @@ namespace {
 
 const char FEATURE[] = "local alignments";
 
-int out_of_memory(u64 entries, const char *of) {
-  gtamd_set_error("local alignments: cannot allocate device memory for %llu %s", (unsigned long long) entries, of);
-  return -1;
-}
-
 // the cuts of a new index down to the largest depth q may take
 template <typename S> int find_cuts(gtamd_locali *lc) {
   const u32 N = (u32) (lc->index.n + 1);
-  if (lc->cutlist.grow((u64) LC_CUT_LIST * 8) != hipSuccess) return out_of_memory(LC_CUT_LIST, "cuts");
+  if (lc->cutlist.grow((u64) LC_CUT_LIST * 8) != hipSuccess) return out_of_memory(FEATURE, LC_CUT_LIST, "cuts");
   HIP_TRY(hipMemsetAsync(lc->words + W_CUTS, 0, sizeof(u64), lc->st));
   if (N > 1)
     k_lc_cuts<S><<<(u32) div_up(N - 1, LC_THREADS), LC_THREADS, 0, lc->st>>>(
-        lc->index.enc, lc->index.n, (const S *) lc->index.suf, N, lc->cut_max, lc->cutlist, LC_CUT_LIST, lc->words);
+        IvText<S>{ lc->index.enc, lc->index.n, (const S *) lc->index.suf }, N, lc->cut_max, lc->cutlist, LC_CUT_LIST,
+        lc->words);
   HIP_TRY(hipGetLastError());
   u64 found = 0;
   TRY(fetch(lc->st, { { lc->words + W_CUTS, &found, sizeof found } }));
@@ -357,20 +278,20 @@ int set_index(gtamd_locali *lc, const IndexView &v, u32 sigma, bool from_host) {
 }
 
 u64 held_bytes(const gtamd_locali *lc) {
-  return lc->index.bytes() + lc->own_queries.bytes + lc->own_qoff.bytes + lc->cnt.bytes + lc->gstart.bytes +
-         lc->arena.bytes + lc->tsum.bytes + lc->off.bytes + lc->cutlist.bytes + lc->words.bytes + lc->out.bytes;
+  return lc->index.bytes() + lc->queries.bytes() + lc->jo.bytes() + lc->gstart.bytes + lc->arena.bytes +
+         lc->cutlist.bytes + lc->words.bytes + lc->out.bytes;
 }
 
 template <typename S> LcInput<S> input(const gtamd_locali *lc) {
-  return LcInput<S>{ lc->index.enc, lc->index.n, (const S *) lc->index.suf, (u32) (lc->index.n + 1),
-                     lc->queries, lc->qoff, lc->gstart, lc->groups, lc->sc, lc->T, lc->stack_words, lc->col_words };
+  return LcInput<S>{ { lc->index.enc, lc->index.n, (const S *) lc->index.suf }, (u32) (lc->index.n + 1),
+                     lc->queries.sym, lc->queries.off, lc->gstart, lc->groups, lc->sc, lc->T, lc->stack_words, lc->col_words };
 }
 
 // the message for what k_lc_validate found
 int refuse_query(gtamd_locali *lc, u64 found) {
   const u64 t = found >> 2;
   u64 ab[2] = { 0, 0 };
-  TRY(fetch(lc->st, { { lc->qoff + t, ab, sizeof ab } }));
+  TRY(fetch(lc->st, { { lc->queries.off + t, ab, sizeof ab } }));
   const unsigned long long query = t, len = ab[1] - ab[0];
   switch (found & 3) {
     case BAD_LENGTH:
@@ -411,7 +332,7 @@ int set_groups(gtamd_locali *lc, u64 Q) {
   lc->groups = (u32) start.size() - 1;
   lc->info.cut_depth = q < lc->cut_max ? q : lc->cut_max;
   lc->info.groups = lc->groups;
-  if (lc->gstart.grow(start.size() * 4) != hipSuccess) return out_of_memory(start.size(), "groups");
+  if (lc->gstart.grow(start.size() * 4) != hipSuccess) return out_of_memory(FEATURE, start.size(), "groups");
   HIP_TRY(hipMemcpy(lc->gstart, start.data(), start.size() * 4, hipMemcpyHostToDevice));
   return 0;
 }
@@ -422,14 +343,14 @@ template <typename S> int prepare(gtamd_locali *lc) {
   HIP_TRY(hipMemsetAsync(lc->words, 0, W_CUTS * sizeof(u64), st));
   HIP_TRY(hipMemsetAsync(lc->words + W_BAD, 0xff, sizeof(u64), st));
   HIP_TRY(hipEventRecord(lc->ev[0], st));
-  k_lc_validate<<<(u32) div_up(Q, LC_THREADS), LC_THREADS, 0, st>>>(lc->queries, lc->qoff, Q, (u32) lc->sc.match,
+  k_lc_validate<<<(u32) div_up(Q, LC_THREADS), LC_THREADS, 0, st>>>(lc->queries.sym, lc->queries.off, Q, (u32) lc->sc.match,
                                                                    lc->sigma, lc->words);
   HIP_TRY(hipGetLastError());
   u64 found[2] = { 0, 0 };
   TRY(fetch(st, { { lc->words + W_BAD, found, sizeof found } }));
   if (found[0] != ~0ull) return refuse_query(lc, found[0]);
   TRY(set_groups(lc, Q));
-  const u64 jobs = Q * lc->groups, tiles = div_up(jobs, SC_THREADS);
+  const u64 jobs = Q * lc->groups;
   if (jobs > LC_MAX_JOBS) {
     gtamd_set_error("local alignments: %llu queries times %u groups of the table are more than %llu jobs",
                     (unsigned long long) Q, lc->groups, (unsigned long long) LC_MAX_JOBS);
@@ -437,9 +358,7 @@ template <typename S> int prepare(gtamd_locali *lc) {
   }
   lc->jobs = jobs;
   lc->info.jobs = jobs;
-  if (lc->cnt.grow(jobs * 4) != hipSuccess || lc->off.grow((jobs + 1) * 8) != hipSuccess ||
-      lc->tsum.grow(tiles * 8) != hipSuccess)
-    return out_of_memory(jobs, "jobs");
+  if (lc->jo.grow(jobs) != hipSuccess) return out_of_memory(FEATURE, jobs, "jobs");
   // per wave of the grid: the stack, and two columns of the longest query for the suffixes that go on alone
   const u32 longest = (u32) found[1];
   lc->col_words = (longest + 63) / 64 * 64;
@@ -453,16 +372,13 @@ template <typename S> int prepare(gtamd_locali *lc) {
                     lc->blocks * LC_WAVES, lc->stack_words);
     return -1;
   }
-  k_lc_walk<S, false><<<lc->blocks, LC_THREADS, 0, st>>>(input<S>(lc), 0, jobs, lc->cnt, nullptr, 0, 0, nullptr,
+  k_lc_walk<S, false><<<lc->blocks, LC_THREADS, 0, st>>>(input<S>(lc), 0, jobs, lc->jo.cnt, nullptr, 0, 0, nullptr,
                                                         lc->arena, lc->words);
   HIP_TRY(hipGetLastError());
-  k_lc_tile_sums<<<(u32) tiles, SC_THREADS, 0, st>>>(lc->cnt, jobs, lc->tsum);
-  HIP_TRY(hipGetLastError());
-  TRY(offsets_u64(lc->cnt, jobs, lc->tsum, lc->off, lc->words + W_MATCHES, st));
+  TRY(lc->jo.scan(jobs, lc->words + W_MATCHES, st));
   HIP_TRY(hipEventRecord(lc->ev[1], st));
   u64 h[W_WORDS];
-  lc->off_host.resize(jobs + 1);
-  TRY(fetch(st, { { lc->words, h, sizeof h }, { lc->off, lc->off_host.data(), (jobs + 1) * sizeof(u64) } }));
+  TRY(fetch(st, { { lc->words, h, sizeof h }, lc->jo.fetch(jobs) }));
   HIP_TRY(hipEventElapsedTime(&lc->info.device_ms, lc->ev[0], lc->ev[1]));
   lc->info.matches = h[W_MATCHES];
   lc->info.max_matches_of_one_job = h[W_MAXJOB];
@@ -477,37 +393,22 @@ template <typename S> int prepare(gtamd_locali *lc) {
 int emit(gtamd_locali *lc, u64 *cursor, gtamd_locali_record *out, u64 capacity, int out_on_device, u64 *written) {
   *written = 0;
   const u64 total = lc->info.matches, cur = *cursor;
-  if (cur > total) {
-    gtamd_set_error("local alignments: cursor %llu is not one of this enumeration (%llu records)",
-                    (unsigned long long) cur, (unsigned long long) total);
-    return -1;
-  }
-  if (capacity < LC_MIN_CAPACITY) {
-    gtamd_set_error("local alignments: a capacity of %llu records is too small: a capacity of at least %llu is "
-                    "needed", (unsigned long long) capacity, (unsigned long long) LC_MIN_CAPACITY);
-    return -1;
-  }
+  TRY(refuse_window(FEATURE, "records", cur, total, capacity, LC_MIN_CAPACITY));
   if (cur == total) return 0;
   const u64 w1 = capacity < total - cur ? cur + capacity : total;
-  // the jobs with a record in [cur, w1): from the last whose first record is not
-  // behind cur up to the first whose first record is not in front of w1
-  const std::vector<u64> &off = lc->off_host;
-  const u64 j0 = (u64) (std::upper_bound(off.begin(), off.end(), cur) - off.begin()) - 1;
-  const u64 j1 = (u64) (std::lower_bound(off.begin(), off.end(), w1) - off.begin());
-  LcRecord *dst = (LcRecord *) out;
-  if (!out_on_device) {
-    if (lc->out.grow((w1 - cur) * sizeof(LcRecord)) != hipSuccess) return out_of_memory(w1 - cur, "records");
-    dst = (LcRecord *) lc->out.p;
-  }
+  u64 j0, j1;
+  lc->jo.jobs_of(cur, w1, &j0, &j1);
+  RecordStage<LcRecord> stage(out, out_on_device);
+  if (stage.begin(lc->out, w1 - cur) != hipSuccess) return out_of_memory(FEATURE, w1 - cur, "records");
   const u32 blocks = (u32) std::min<u64>(div_up(j1 - j0, LC_WAVES), lc->blocks);      // (the arena has room for lc->blocks)
   if (lc->index.suf_bytes == 4)
-    k_lc_walk<u32, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u32>(lc), j0, j1, nullptr, lc->off, cur, w1, dst,
-                                                             lc->arena, lc->words);
+    k_lc_walk<u32, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u32>(lc), j0, j1, nullptr, lc->jo.off, cur, w1,
+                                                             stage.dst, lc->arena, lc->words);
   else
-    k_lc_walk<u64, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u64>(lc), j0, j1, nullptr, lc->off, cur, w1, dst,
-                                                             lc->arena, lc->words);
+    k_lc_walk<u64, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u64>(lc), j0, j1, nullptr, lc->jo.off, cur, w1,
+                                                             stage.dst, lc->arena, lc->words);
   HIP_TRY(hipGetLastError());
-  TRY(fetch(lc->st, { { dst, out, out_on_device ? 0 : (w1 - cur) * sizeof(LcRecord) } }));
+  TRY(stage.finish(w1 - cur, lc->st));
   lc->info.emitted += w1 - cur;
   *cursor = w1;
   *written = w1 - cur;
@@ -619,19 +520,9 @@ extern "C" int gtamd_locali_prepare(gtamd_locali *lc, const uint8_t *queries, co
   lc->jobs = 0;
   lc->sc = LcScores{ match, mismatch, -gapextend };
   lc->T = threshold;
-  lc->off_host.assign(1, 0);
+  lc->jo.off_host.assign(1, 0);
   if (Q != 0) {
-    lc->queries = queries;
-    lc->qoff = offsets;
-    if (!is_device) {
-      const u64 symbols = offsets[Q];
-      if (lc->own_queries.grow(symbols ? symbols : 1) != hipSuccess || lc->own_qoff.grow((Q + 1) * 8) != hipSuccess)
-        return out_of_memory(symbols, "query symbols");
-      if (symbols) HIP_TRY(hipMemcpyAsync(lc->own_queries, queries, symbols, hipMemcpyHostToDevice, lc->st));
-      HIP_TRY(hipMemcpyAsync(lc->own_qoff, offsets, (Q + 1) * 8, hipMemcpyHostToDevice, lc->st));
-      lc->queries = lc->own_queries;
-      lc->qoff = lc->own_qoff;
-    }
+    TRY(lc->queries.set(FEATURE, "query symbols", queries, offsets, Q, is_device, lc->st));
     TRY(lc->index.suf_bytes == 4 ? prepare<u32>(lc) : prepare<u64>(lc));
   }
   lc->info.device_bytes = held_bytes(lc);

@@ -30,11 +30,7 @@
 // match * m - gap * (d - m) > 0, that is d <= lc_max_depth(m) = m +
 // ceil(match * m / gap) - 1.  Every walk stops there whatever the text holds.
 #pragma once
-#include <stdint.h>
-
-typedef uint64_t u64;
-typedef uint32_t u32;
-typedef uint8_t u8;
+#include "esa_ivwalk.h"
 
 #if defined(__HIPCC__)
 #define LC_HD __device__ __forceinline__
@@ -58,7 +54,7 @@ constexpr u32 LC_MAX_QUERY = 16384;      // letters of a query
 constexpr u32 LC_MAX_SCORE = 65535;      // match * m must fit the 16 bits of a cell
 constexpr int LC_MAX_WEIGHT = 32767;     // match, -mismatch, -gapextend
 constexpr u32 LC_LETTERS = 32;
-constexpr u32 LC_WILDCARD = 254, LC_SEPARATOR = 255;
+constexpr u32 LC_WILDCARD = IV_WILDCARD, LC_SEPARATOR = IV_SEPARATOR;      // (as the cases of tests/ name them)
 constexpr u32 LC_NO_ROW = 0xffffffffu;
 
 struct LcScores { int match, mismatch, gap; };      // gap = -gapextend > 0
@@ -205,7 +201,7 @@ LC_HD LcMatch lc_walk(const u32 *src, LcColumn cur, u32 depth, const u8 *enc, u6
   const u32 deepest = lc_max_depth(m, sc);
   while (depth < deepest && p + depth < n) {
     const u32 c = LC_UNI((u32) enc[p + depth]);
-    if (c >= LC_WILDCARD) break;
+    if (c >= IV_WILDCARD) break;
     const bool first = depth == 0;
     const LcColumn next = lc_column(src, cur.lo, cur.hi, first, c, q, m, sc, a);
     depth += 1;

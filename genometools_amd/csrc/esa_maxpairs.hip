@@ -207,11 +207,6 @@ MpSegments view(const gtamd_maxpairs *mp) {
   return MpSegments{ mp->val, mp->tmin, mp->seg_of, mp->seg_first, mp->seg_min, mp->seg_info, mp->nseg };
 }
 
-int out_of_memory(u64 entries, const char *of) {
-  gtamd_set_error("maximal pairs: cannot allocate device memory for %llu %s", (unsigned long long) entries, of);
-  return -1;
-}
-
 // both passes of a selection over `count` items: *selected = their number
 template <typename P>
 int select(gtamd_maxpairs *mp, const P &p, u64 count, u64 *tally, u32 *selected, bool write) {
@@ -236,7 +231,7 @@ template <typename S> int prepare(gtamd_maxpairs *mp, u32 L) {
   const u64 N = x.n + 1, T = div_up(N, MP_TILE);
   if (mp->tiles.grow((T + 1) * sizeof(u32)) != hipSuccess ||
       mp->scanws.grow(scan_workspace_words(T + 1) * sizeof(u32)) != hipSuccess)
-    return out_of_memory(T + 1, "tiles");
+    return out_of_memory(FEATURE, T + 1, "tiles");
   HIP_TRY(hipMemsetAsync(mp->words, 0, W_WORDS * sizeof(u64), st));
   HIP_TRY(hipEventRecord(mp->ev[0], st));
 
@@ -252,7 +247,7 @@ template <typename S> int prepare(gtamd_maxpairs *mp, u32 L) {
         mp->cnt.grow((u64) M * 4) != hipSuccess || mp->cls.grow(M) != hipSuccess ||
         mp->off.grow(((u64) M + 1) * 8) != hipSuccess ||
         mp->tsum.grow(div_up(M, MP_WALK_TILE) * 8) != hipSuccess)
-      return out_of_memory(M, "suffixes in runs");
+      return out_of_memory(FEATURE, M, "suffixes in runs");
     in.idx = mp->idx; in.val = mp->val; in.cls = mp->cls;
     TRY(select(mp, in, N, nullptr, nullptr, true));
 
@@ -261,7 +256,7 @@ template <typename S> int prepare(gtamd_maxpairs *mp, u32 L) {
     TRY(select(mp, seg, M, nullptr, &nseg, false));
     if (mp->seg_first.grow(((u64) nseg + 1) * 4) != hipSuccess || mp->seg_min.grow((u64) nseg * 4) != hipSuccess ||
         mp->seg_info.grow((u64) nseg * 2) != hipSuccess)
-      return out_of_memory(nseg, "segments");
+      return out_of_memory(FEATURE, nseg, "segments");
     seg.seg_first = mp->seg_first;
     TRY(select(mp, seg, M, nullptr, nullptr, true));
     HIP_TRY(hipMemcpyAsync(mp->seg_first + nseg, &mp->M, sizeof(u32), hipMemcpyHostToDevice, st));
@@ -297,11 +292,7 @@ int emit(gtamd_maxpairs *mp, u64 *cursor, gtamd_maxpairs_record *out, u64 capaci
          u64 *written) {
   *written = 0;
   const u64 M = mp->M, z = mp->info.pairs, k0 = *cursor;
-  if (k0 > M) {
-    gtamd_set_error("maximal pairs: cursor %llu is not one of this enumeration (%llu suffixes in runs)",
-                    (unsigned long long) k0, (unsigned long long) M);
-    return -1;
-  }
+  TRY(refuse_window(FEATURE, "suffixes in runs", k0, M, capacity, 0));      // (its least capacity: below, once known)
   if (k0 == M || z == 0) { *cursor = M; return 0; }
   u64 base;
   TRY(offset_at(mp, k0, &base));
@@ -330,7 +321,7 @@ int emit(gtamd_maxpairs *mp, u64 *cursor, gtamd_maxpairs_record *out, u64 capaci
   // (capacity >= the pairs of any one suffix: k1 > k0)
   if (count) {
     RecordStage<MpRecord> stage(out, out_on_device);
-    if (stage.begin(mp->out, count) != hipSuccess) return out_of_memory(count, "records");
+    if (stage.begin(mp->out, count) != hipSuccess) return out_of_memory(FEATURE, count, "records");
     const u32 blocks = (u32) div_up(k1 - k0, MP_WALK_TILE);
     if (mp->index.suf_bytes == 4)
       k_mp_emit<u32><<<blocks, MP_THREADS, 0, mp->st>>>(view(mp), mp->cls, mp->idx, (const u32 *) mp->index.suf,

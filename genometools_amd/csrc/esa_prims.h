@@ -15,6 +15,8 @@ int scan_u32(int op, const u32 *in, u32 *out, u64 n, bool inclusive, u32 *ws,
 // holds their sum when the call is made (the kernel that writes cnt fills it) and
 // the sum of the tiles in front of it afterwards.  Two launches, no wait.
 int offsets_u64(const u32 *cnt, u64 count, u64 *tsum, u64 *off, u64 *total_dev, hipStream_t st);
+// the same for counts whose kernel does not fill tsum: one launch more sums the tiles first
+int offsets_u64_counted(const u32 *cnt, u64 count, u64 *tsum, u64 *off, u64 *total_dev, hipStream_t st);
 
 // workspace (u32 words) for sorting n pairs
 u64 radix_workspace_words(u64 n);

@@ -120,7 +120,24 @@ __global__ __launch_bounds__(SC_THREADS) void k_offsets(const u32 *cnt, const u6
   }
 }
 
+// tsum[b] = the sum of the counts of tile b, as offsets_u64 wants it
+__global__ __launch_bounds__(SC_THREADS) void k_sum_tiles(const u32 *cnt, u64 count, u64 *tsum) {
+  __shared__ unsigned long long ssum;
+  if (threadIdx.x == 0) ssum = 0;
+  __syncthreads();
+  const u64 i = (u64) blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i < count && cnt[i]) atomicAdd(&ssum, (unsigned long long) cnt[i]);
+  __syncthreads();
+  if (threadIdx.x == 0) tsum[blockIdx.x] = ssum;
+}
+
 }  // namespace
+
+int offsets_u64_counted(const u32 *cnt, u64 count, u64 *tsum, u64 *off, u64 *total_dev, hipStream_t st) {
+  k_sum_tiles<<<(u32) div_up(count, SC_THREADS), SC_THREADS, 0, st>>>(cnt, count, tsum);
+  HIP_TRY(hipGetLastError());
+  return offsets_u64(cnt, count, tsum, off, total_dev, st);
+}
 
 int offsets_u64(const u32 *cnt, u64 count, u64 *tsum, u64 *off, u64 *total_dev, hipStream_t st) {
   const u64 tiles = div_up(count, SC_THREADS);

@@ -154,11 +154,6 @@ u64 held_bytes(const gtamd_qmatch *qm) {
          qm->scanws.bytes + qm->tsum.bytes + qm->off.bytes + qm->words.bytes + qm->out.bytes;
 }
 
-int out_of_memory(u64 entries, const char *of) {
-  gtamd_set_error("query matches: cannot allocate device memory for %llu %s", (unsigned long long) entries, of);
-  return -1;
-}
-
 template <typename S> QmInput<S> input(const gtamd_qmatch *qm) {
   return QmInput<S>{ qm->index.enc, qm->index.n, (const S *) qm->index.suf, qm->q, qm->m, qm->L };
 }
@@ -191,7 +186,7 @@ template <typename S> int emit_chunk(gtamd_qmatch *qm, u64 c0, u64 c1, QmRecord 
   const u64 blocks = div_up(c1 - c0, QM_TILE);
   if (qm->tiles.grow((blocks + 1) * sizeof(u32)) != hipSuccess ||
       qm->scanws.grow(scan_workspace_words(blocks + 1) * sizeof(u32)) != hipSuccess)
-    return out_of_memory(blocks + 1, "tiles of candidates");
+    return out_of_memory(FEATURE, blocks + 1, "tiles of candidates");
   HIP_TRY(hipMemsetAsync(qm->tiles, 0, (blocks + 1) * sizeof(u32), st));
   k_qm_emit<S, false><<<(u32) blocks, QM_THREADS, 0, st>>>(input<S>(qm), qm->lo, qm->off, c0, c1, qm->tiles, nullptr,
                                                            qm->words);
@@ -210,20 +205,11 @@ int emit(gtamd_qmatch *qm, u64 *cursor, gtamd_qmatch_record *out, u64 capacity, 
   *written = 0;
   const u64 C = qm->info.candidates;
   u64 cur = *cursor, total = 0;
-  if (cur > C) {
-    gtamd_set_error("query matches: cursor %llu is not one of this enumeration (%llu candidates)",
-                    (unsigned long long) cur, (unsigned long long) C);
-    return -1;
-  }
-  if (capacity < QM_MIN_CHUNK) {
-    gtamd_set_error("query matches: a capacity of %llu records is too small: a capacity of at least %llu is needed",
-                    (unsigned long long) capacity, (unsigned long long) QM_MIN_CHUNK);
-    return -1;
-  }
+  TRY(refuse_window(FEATURE, "candidates", cur, C, capacity, QM_MIN_CHUNK));
   if (cur == C) return 0;
   RecordStage<QmRecord> stage(out, out_on_device);
   const u64 most = capacity < C - cur ? capacity : C - cur;
-  if (stage.begin(qm->out, most) != hipSuccess) return out_of_memory(most, "records");
+  if (stage.begin(qm->out, most) != hipSuccess) return out_of_memory(FEATURE, most, "records");
   QmRecord *dst = stage.dst;
   // a chunk of `room` candidates gives at most `room` records
   while (cur < C && capacity - total >= QM_MIN_CHUNK) {
@@ -305,7 +291,7 @@ extern "C" int gtamd_qmatch_prepare(gtamd_qmatch *qm, const uint8_t *query, uint
   if ((!is_device && qm->own_query.grow(m ? m : 1) != hipSuccess) || qm->lo.grow((m ? m : 1) * 4) != hipSuccess ||
       qm->width.grow((m ? m : 1) * 4) != hipSuccess || qm->off.grow((m + 1) * 8) != hipSuccess ||
       qm->tsum.grow((T ? T : 1) * 8) != hipSuccess)
-    return out_of_memory(m, "query positions");
+    return out_of_memory(FEATURE, m, "query positions");
   qm->q = query;
   if (!is_device) {
     if (m) HIP_TRY(hipMemcpyAsync(qm->own_query, query, m, hipMemcpyHostToDevice, qm->st));

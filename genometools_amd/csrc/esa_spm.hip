@@ -185,11 +185,6 @@ u64 held_bytes(const gtamd_spm *sp) {
          sp->out.bytes;
 }
 
-int out_of_memory(u64 entries, const char *of) {
-  gtamd_set_error("suffix-prefix matches: cannot allocate device memory for %llu %s", (unsigned long long) entries, of);
-  return -1;
-}
-
 template <typename S> SpIndex<S> view(const gtamd_spm *sp) {
   const ResidentIndex &x = sp->index;
   return SpIndex<S>{ x.enc, x.n, (const S *) x.suf, x.lcp, x.llv, x.llv_pairs };
@@ -202,7 +197,7 @@ template <typename S> int prepare(gtamd_spm *sp, u32 L) {
   const u64 N = sp->index.n + 1, T = div_up(N, SP_SEL_TILE), stride = T + 1;
   if (sp->tiles.grow(K_KINDS * stride * sizeof(u32)) != hipSuccess ||
       sp->scanws.grow(scan_workspace_words(stride) * sizeof(u32)) != hipSuccess)
-    return out_of_memory(stride, "tiles");
+    return out_of_memory(FEATURE, stride, "tiles");
   HIP_TRY(hipMemsetAsync(sp->words, 0, W_WORDS * sizeof(u64), st));
   HIP_TRY(hipMemsetAsync(sp->tiles, 0, K_KINDS * stride * sizeof(u32), st));
   HIP_TRY(hipEventRecord(sp->ev[0], st));
@@ -219,9 +214,9 @@ template <typename S> int prepare(gtamd_spm *sp, u32 L) {
   if (sp->idx.grow((M ? (u64) M : 1) * 4) != hipSuccess || sp->len.grow((M ? (u64) M : 1) * 4) != hipSuccess ||
       sp->first.grow((M ? (u64) M : 1) * 4) != hipSuccess || sp->cnt.grow((M ? (u64) M : 1) * 4) != hipSuccess ||
       sp->off.grow(((u64) M + 1) * 8) != hipSuccess || sp->tsum.grow((tiles ? (u64) tiles : 1) * 8) != hipSuccess)
-    return out_of_memory(M, "terminal suffixes");
+    return out_of_memory(FEATURE, M, "terminal suffixes");
   if (sp->starts.grow((R ? (u64) R : 1) * 4) != hipSuccess || sp->seps.grow((nseps ? (u64) nseps : 1) * 4) != hipSuccess)
-    return out_of_memory((u64) R + nseps, "read starts and separators");
+    return out_of_memory(FEATURE, (u64) R + nseps, "read starts and separators");
   sp->M = M; sp->R = R; sp->nseps = nseps;
   k_sp_select<S, true><<<(u32) T, SP_THREADS, 0, st>>>(view<S>(sp), L, sp->tiles, stride, lists(sp));
   HIP_TRY(hipGetLastError());
@@ -261,20 +256,11 @@ template <typename S> int emit_records(gtamd_spm *sp, u64 c0, u64 count, SpRecor
 int emit(gtamd_spm *sp, u64 *cursor, gtamd_spm_record *out, u64 capacity, int out_on_device, u64 *written) {
   *written = 0;
   const u64 Z = sp->info.matches, cur = *cursor;
-  if (cur > Z) {
-    gtamd_set_error("suffix-prefix matches: cursor %llu is not one of this enumeration (%llu matches)",
-                    (unsigned long long) cur, (unsigned long long) Z);
-    return -1;
-  }
-  if (capacity < SP_MIN_CAPACITY) {
-    gtamd_set_error("suffix-prefix matches: a capacity of %llu records is too small: a capacity of at least %llu "
-                    "is needed", (unsigned long long) capacity, (unsigned long long) SP_MIN_CAPACITY);
-    return -1;
-  }
+  TRY(refuse_window(FEATURE, "matches", cur, Z, capacity, SP_MIN_CAPACITY));
   if (cur == Z) return 0;
   const u64 count = capacity < Z - cur ? capacity : Z - cur;
   RecordStage<SpRecord> stage(out, out_on_device);
-  if (stage.begin(sp->out, count) != hipSuccess) return out_of_memory(count, "records");
+  if (stage.begin(sp->out, count) != hipSuccess) return out_of_memory(FEATURE, count, "records");
   TRY(sp->index.suf_bytes == 4 ? emit_records<u32>(sp, cur, count, stage.dst)
                                : emit_records<u64>(sp, cur, count, stage.dst));
   TRY(stage.finish(count, sp->st));

@@ -8,17 +8,13 @@
 //                         LDS; the matches of the job are counted
 //      k_tm_settle        one lane per tag: K' of a tag with a match (with BEST
 //                         step b runs for k = 0..K over the tags without one)
-//   c  offsets_u64 (esa_prims)     64-bit exclusive scan of the counts
+//   c  JobOffsets::scan (esa_jobs) 64-bit exclusive scan of the counts
 //   d  k_tm_walk<true>    the same walk for the jobs of a window of records,
 //                         which writes those
 //
 // Every working array has one entry per job or per tag, none has N.
-#include <algorithm>
-#include <vector>
 #include "esa_common.h"
-#include "esa_index.h"
-#include "esa_prims.h"
-#include "esa_devutil.h"
+#include "esa_jobs.h"
 #include "esa_tagmatch_core.h"
 #include "../../include/gtamd_tagmatch.h"
 
@@ -27,13 +23,13 @@ namespace {
 constexpr int TM_THREADS = SC_THREADS;
 constexpr u32 TM_WAVES = TM_THREADS / 64;          // jobs of one workgroup: one a wave
 constexpr u32 TM_LEVELS = 128;                     // depths 0 .. m + K - 1 <= 126 have a level
-constexpr u32 TM_BATCH = 64;                       // suffixes the lanes of a wave take at once
+constexpr u32 TM_BATCH = IV_BATCH;                 // suffixes the lanes of a wave take at once
 constexpr u64 TM_MIN_CAPACITY = TM_BATCH;
 constexpr u64 TM_MAX_TAGS = 1ull << 30;
 constexpr u32 TM_STRANDS = GTAMD_TAGMATCH_FORWARD | GTAMD_TAGMATCH_REVCOMP;
 constexpr u32 NO_K = GTAMD_TAGMATCH_NO_K;
 
-enum { W_MATCHES = 0, W_MAXJOB, W_LEVELS, W_CHILDREN, W_WALKS, W_BAD, W_WORDS };
+enum { W_BAD = W_WALK_WORDS, W_WORDS };
 enum { BAD_LENGTH = 1, BAD_SHORT = 2, BAD_SYMBOL = 3 };
 
 struct TmRecord { u64 tag, dbstart, lendist; };
@@ -44,69 +40,12 @@ struct TmLevel { u32 lo, end, cur, rowval; u64 Pv, Mv; };
 static_assert(sizeof(TmLevel) == 32, "a level is 32 bytes of LDS");
 
 template <typename S> struct TmInput {
-  const u8 *enc; u64 n; const S *suf; u32 N;
+  IvText<S> text; u32 N;
   const u8 *tags; const u64 *toff; u64 T;
   u32 strands, wild;
 };
 
 __device__ __forceinline__ u32 uni(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// the symbol `d` behind the start of the suffix at table index idx < N; a separator
-// where there is none: behind the end, or for an entry that is no position
-template <typename S> __device__ __forceinline__ u32 tm_symbol(const TmInput<S> &in, u32 idx, u32 d) {
-  const u64 p = in.suf[idx];
-  if (p >= in.n) return TM_SEPARATOR;
-  const u64 x = p + d;
-  return x < in.n ? in.enc[x] : TM_SEPARATOR;
-}
-
-// The right bound of the child of letter s that starts at table index cur of a
-// level that ends at `end`: the first index behind cur whose symbol at depth d
-// is not s.  The symbols at one depth ascend inside an interval, the specials
-// behind all letters, so this is a search: 64 probes a round, spread over the
-// range [lo, hi) that is left; the range behind the last probe that still
-// holds s and in front of the first that does not is what the next round gets.
-// A round leaves fewer than span / 64 + 1 < span entries, whatever the table
-// holds; the result lies in (cur, end].
-template <typename S>
-__device__ __forceinline__ u32 tm_right_bound(const TmInput<S> &in, u32 cur, u32 end, u32 d, u32 s, u32 lane) {
-  u32 lo = cur + 1, hi = end;
-  while (lo < hi) {
-    const u32 span = hi - lo;
-    const u32 step = span <= TM_BATCH ? 1 : (span + TM_BATCH - 1) / TM_BATCH;
-    const u64 q = (u64) lo + (u64) lane * step;
-    const bool differs = q >= hi || tm_symbol(in, (u32) q, d) != s;
-    const u64 mask = __ballot(differs);
-    const u32 f = mask ? (u32) __builtin_ctzll(mask) : TM_BATCH;
-    if (f == 0) return lo;
-    const u64 next = (u64) lo + (u64) f * step;          // the first probe that differs, if there is one
-    if (f < TM_BATCH && next < hi) hi = (u32) next;
-    lo = lo + (f - 1) * step + 1;
-  }
-  return lo;
-}
-
-// what a wave carries through its walk
-struct TmWalk {
-  u64 k;                 // records of the job so far
-  u64 first, stop;       // EMIT: the records [first, stop) of the job are written ...
-  TmRecord *dst;         // ... record `first` here
-  u64 tagword;
-  u32 lane;
-};
-
-// `keep` lanes have a match each, in table order: counted, and written where
-// they fall into the window
-template <bool EMIT> __device__ __forceinline__ void tm_give(TmWalk &wk, bool keep, u64 p, u32 len, u32 dist) {
-  const u64 mask = __ballot(keep);
-  if (EMIT && keep) {
-    const u32 before = __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
-    const u64 place = wk.k + before;
-    if (place >= wk.first && place < wk.stop)
-      wk.dst[place - wk.first] = TmRecord{ wk.tagword, p, (u64) len | (u64) dist << 32 };
-  }
-  wk.k += (u64) __popcll(mask);
-}
 
 // Jobs [j0, j1), one a wave.  EMIT false: cnt[job] = its matches for K = k_pass,
 // for the jobs of the tags whose kbest is still none.  EMIT true: K of a job is
@@ -126,19 +65,15 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk(TmInput<S> in, u64 j0, u
   const u32 K = EMIT ? kbest[tag] : k_pass;
   if (EMIT ? K == NO_K : kbest[tag] != NO_K) return;
 
-  TmWalk wk = { 0, 0, 0, nullptr, 2 * tag + (rc ? 1 : 0), lane };
-  if (EMIT) {
-    const u64 base = off[j], after = off[j + 1];
-    if (after <= w0 || base >= w1 || after == base) return;
-    wk.first = w0 > base ? w0 - base : 0;
-    wk.stop = (w1 < after ? w1 : after) - base;
-    wk.dst = out + (base + wk.first - w0);
-  }
+  const IvText<S> &text = in.text;
+  const u64 tagword = 2 * tag + (rc ? 1 : 0);
+  JobWindow<TmRecord> wk = { 0, 0, 0, nullptr };
+  if (EMIT && !wk.open(off, j, w0, w1, out)) return;
 
   // the tag, one letter a lane, as this strand reads it; its Eq words by ballot
   const u64 t0 = in.toff[tag];
   const u32 m = (u32) (in.toff[tag + 1] - t0);          // 1 .. 64 (k_tm_validate)
-  u32 letter = TM_SEPARATOR;
+  u32 letter = IV_SEPARATOR;
   if (lane < m) letter = rc ? 3u - in.tags[t0 + (m - 1 - lane)] : in.tags[t0 + lane];
   u64 *eq = s_eq[wave];
   for (u32 c = 0; c < TM_LETTERS; c++) {
@@ -153,19 +88,19 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk(TmInput<S> in, u64 j0, u
   // Every round moves the cursor of the top level forward by at least one, pops
   // the level or pushes one of the next depth, which is below m + K: it ends.
   for (;;) {
-    if (EMIT && wk.k >= wk.stop) break;
+    if (EMIT && wk.full()) break;
     const u32 cur = uni(level[depth].cur), end = uni(level[depth].end);
     if (cur >= end) {
       if (depth == 0) break;
       depth -= 1;
       continue;
     }
-    const u32 s = uni(tm_symbol(in, cur, depth));
+    const u32 s = uni(iv_symbol(text, cur, depth));
     TmColumn col = { level[depth].Pv, level[depth].Mv, 0, 0 };
     const u32 rowval = uni(level[depth].rowval);
     col.row = rowval & 0xffff;
     col.val = rowval >> 16;
-    if (s >= TM_WILDCARD) {
+    if (s >= IV_WILDCARD) {
       // only specials from here to the end of the level: each goes on alone, if at all
       if (!in.wild) {
         if (depth == 0) break;
@@ -177,14 +112,14 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk(TmInput<S> in, u64 j0, u
       u32 len = 0, dist = 0;
       u64 p = 0;
       if (lane < many) {
-        p = in.suf[cur + lane];
-        if (p < in.n) len = tm_walk(col, eq, in.enc, in.n, p, depth, m, K, true, &dist);
+        p = text.suf[cur + lane];
+        if (p < text.n) len = tm_walk(col, eq, text.enc, text.n, p, depth, m, K, true, &dist);
       }
       walks += many;
-      tm_give<EMIT>(wk, len != 0, p, len, dist);
+      wk.give<EMIT>(len != 0, TmRecord{ tagword, p, (u64) len | (u64) dist << 32 });
       continue;
     }
-    const u32 e = tm_right_bound(in, cur, end, depth, s, lane);
+    const u32 e = iv_right_bound(text, cur, end, depth, s);
     level[depth].cur = e;
     children += 1;
     tm_step(col, s < TM_LETTERS ? eq[s] : 0, K);
@@ -192,10 +127,10 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk(TmInput<S> in, u64 j0, u
     if (tm_success(col, m)) {
       // all suffixes of the child match with depth + 1 symbols
       for (u32 b = cur; b < e; b += TM_BATCH) {
-        if (EMIT && wk.k >= wk.stop) break;
+        if (EMIT && wk.full()) break;
         const u32 idx = b + lane;                   // (e <= N <= 2^32 - 4096: no wrap)
-        const u64 p = idx < e ? (u64) in.suf[idx] : in.n;
-        tm_give<EMIT>(wk, p < in.n, p, depth + 1, col.val);
+        const u64 p = idx < e ? (u64) text.suf[idx] : text.n;
+        wk.give<EMIT>(p < text.n, TmRecord{ tagword, p, (u64) (depth + 1) | (u64) col.val << 32 });
       }
       continue;
     }
@@ -203,11 +138,11 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk(TmInput<S> in, u64 j0, u
       u32 len = 0, dist = 0;
       u64 p = 0;
       if (lane < e - cur) {
-        p = in.suf[cur + lane];
-        if (p < in.n) len = tm_walk(col, eq, in.enc, in.n, p, depth + 1, m, K, in.wild != 0, &dist);
+        p = text.suf[cur + lane];
+        if (p < text.n) len = tm_walk(col, eq, text.enc, text.n, p, depth + 1, m, K, in.wild != 0, &dist);
       }
       walks += e - cur;
-      tm_give<EMIT>(wk, len != 0, p, len, dist);
+      wk.give<EMIT>(len != 0, TmRecord{ tagword, p, (u64) len | (u64) dist << 32 });
       continue;
     }
     if (depth + 1 >= TM_LEVELS) continue;          // (cannot be: a column alive at depth m + K has reached row m)
@@ -215,13 +150,7 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk(TmInput<S> in, u64 j0, u
     level[depth] = TmLevel{ cur, e, cur, col.row | col.val << 16, col.Pv, col.Mv };
     pushed += 1;
   }
-  if (!EMIT && lane == 0) {
-    cnt[j] = (u32) wk.k;                          // (at most one match per table entry: below 2^32)
-    if (wk.k) atomicMax((unsigned long long *) &w[W_MAXJOB], (unsigned long long) wk.k);
-    if (pushed) atomicAdd((unsigned long long *) &w[W_LEVELS], (unsigned long long) pushed);
-    if (children) atomicAdd((unsigned long long *) &w[W_CHILDREN], (unsigned long long) children);
-    if (walks) atomicAdd((unsigned long long *) &w[W_WALKS], (unsigned long long) walks);
-  }
+  if (!EMIT && lane == 0) report(w, cnt, j, wk.k, pushed, children, walks);
 }
 
 // kbest of a tag that had none and whose jobs have a match now: k
@@ -231,17 +160,6 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_settle(const u32 *cnt, u32 pe
   u32 any = 0;
   for (u32 s = 0; s < per_tag; s++) any |= cnt[t * per_tag + s];
   if (any) kbest[t] = k;
-}
-
-// tsum[b] = the sum of the counts of tile b, as offsets_u64 wants it
-__global__ __launch_bounds__(SC_THREADS) void k_tm_tile_sums(const u32 *cnt, u64 count, u64 *tsum) {
-  __shared__ unsigned long long ssum;
-  if (threadIdx.x == 0) ssum = 0;
-  __syncthreads();
-  const u64 i = (u64) blockIdx.x * SC_THREADS + threadIdx.x;
-  if (i < count && cnt[i]) atomicAdd(&ssum, (unsigned long long) cnt[i]);
-  __syncthreads();
-  if (threadIdx.x == 0) tsum[blockIdx.x] = ssum;
 }
 
 // w[W_BAD] = the smallest (tag << 2 | what is wrong with it)
@@ -266,15 +184,11 @@ struct gtamd_tagmatch : ConsumerBase<> {
   u32 sigma = 0;
   bool prepared = false;
   // what a prepare leaves for the emit calls
-  Dev<u8> own_tags;
-  Dev<u64> own_toff;
-  const u8 *tags = nullptr;
-  const u64 *toff = nullptr;
+  SequenceSet tags;
   u64 T = 0, jobs = 0;
   u32 flags = 0;
-  Dev<u32> cnt, kbest;
-  Dev<u64> tsum, off;
-  std::vector<u64> off_host;      // the places of the jobs' first records: which jobs a window needs
+  JobOffsets jo;
+  Dev<u32> kbest;
   Dev<u8> out;                    // records on their way to host memory
   gtamd_tagmatch_info info = gtamd_tagmatch_info();
 };
@@ -304,18 +218,12 @@ int set_index(gtamd_tagmatch *tm, const IndexView &v, u32 sigma, bool from_host)
 }
 
 u64 held_bytes(const gtamd_tagmatch *tm) {
-  return tm->index.bytes() + tm->own_tags.bytes + tm->own_toff.bytes + tm->cnt.bytes + tm->kbest.bytes +
-         tm->tsum.bytes + tm->off.bytes + tm->words.bytes + tm->out.bytes;
-}
-
-int out_of_memory(u64 entries, const char *of) {
-  gtamd_set_error("tag matches: cannot allocate device memory for %llu %s", (unsigned long long) entries, of);
-  return -1;
+  return tm->index.bytes() + tm->tags.bytes() + tm->jo.bytes() + tm->kbest.bytes + tm->words.bytes + tm->out.bytes;
 }
 
 template <typename S> TmInput<S> input(const gtamd_tagmatch *tm) {
-  return TmInput<S>{ tm->index.enc, tm->index.n, (const S *) tm->index.suf, (u32) (tm->index.n + 1),
-                     tm->tags, tm->toff, tm->T, tm->flags & TM_STRANDS,
+  return TmInput<S>{ { tm->index.enc, tm->index.n, (const S *) tm->index.suf }, (u32) (tm->index.n + 1),
+                     tm->tags.sym, tm->tags.off, tm->T, tm->flags & TM_STRANDS,
                      (tm->flags & GTAMD_TAGMATCH_WITH_WILDCARDS) ? 1u : 0u };
 }
 
@@ -323,7 +231,7 @@ template <typename S> TmInput<S> input(const gtamd_tagmatch *tm) {
 int refuse_tag(gtamd_tagmatch *tm, u64 found, u32 K) {
   const u64 t = found >> 2;
   u64 ab[2] = { 0, 0 };
-  TRY(fetch(tm->st, { { tm->toff + t, ab, sizeof ab } }));
+  TRY(fetch(tm->st, { { tm->tags.off + t, ab, sizeof ab } }));
   const unsigned long long tag = t, len = ab[1] - ab[0];
   switch (found & 3) {
     case BAD_LENGTH:
@@ -351,26 +259,23 @@ template <typename S> int prepare(gtamd_tagmatch *tm, u32 K) {
   HIP_TRY(hipMemsetAsync(tm->words, 0, W_WORDS * sizeof(u64), st));
   HIP_TRY(hipMemsetAsync(tm->words + W_BAD, 0xff, sizeof(u64), st));
   HIP_TRY(hipEventRecord(tm->ev[0], st));
-  k_tm_validate<<<(u32) div_up(T, TM_THREADS), TM_THREADS, 0, st>>>(tm->tags, tm->toff, T, K, tm->sigma, tm->words);
+  k_tm_validate<<<(u32) div_up(T, TM_THREADS), TM_THREADS, 0, st>>>(tm->tags.sym, tm->tags.off, T, K, tm->sigma, tm->words);
   HIP_TRY(hipGetLastError());
   u64 found = 0;
   TRY(fetch(st, { { tm->words + W_BAD, &found, sizeof found } }));
   if (found != ~0ull) return refuse_tag(tm, found, K);
   HIP_TRY(hipMemsetAsync(tm->kbest, 0xff, T * sizeof(u32), st));
   for (u32 k = (tm->flags & GTAMD_TAGMATCH_BEST) ? 0 : K; k <= K; k++) {
-    k_tm_walk<S, false><<<(u32) div_up(jobs, TM_WAVES), TM_THREADS, 0, st>>>(input<S>(tm), 0, jobs, k, tm->kbest, tm->cnt,
+    k_tm_walk<S, false><<<(u32) div_up(jobs, TM_WAVES), TM_THREADS, 0, st>>>(input<S>(tm), 0, jobs, k, tm->kbest, tm->jo.cnt,
                                                                            nullptr, 0, 0, nullptr, tm->words);
     HIP_TRY(hipGetLastError());
-    k_tm_settle<<<(u32) div_up(T, TM_THREADS), TM_THREADS, 0, st>>>(tm->cnt, per_tag, T, k, tm->kbest);
+    k_tm_settle<<<(u32) div_up(T, TM_THREADS), TM_THREADS, 0, st>>>(tm->jo.cnt, per_tag, T, k, tm->kbest);
     HIP_TRY(hipGetLastError());
   }
-  k_tm_tile_sums<<<(u32) div_up(jobs, SC_THREADS), SC_THREADS, 0, st>>>(tm->cnt, jobs, tm->tsum);
-  HIP_TRY(hipGetLastError());
-  TRY(offsets_u64(tm->cnt, jobs, tm->tsum, tm->off, tm->words + W_MATCHES, st));
+  TRY(tm->jo.scan(jobs, tm->words + W_MATCHES, st));
   HIP_TRY(hipEventRecord(tm->ev[1], st));
   u64 h[W_WORDS];
-  tm->off_host.resize(jobs + 1);
-  TRY(fetch(st, { { tm->words, h, sizeof h }, { tm->off, tm->off_host.data(), (jobs + 1) * sizeof(u64) } }));
+  TRY(fetch(st, { { tm->words, h, sizeof h }, tm->jo.fetch(jobs) }));
   HIP_TRY(hipEventElapsedTime(&tm->info.device_ms, tm->ev[0], tm->ev[1]));
   tm->info.matches = h[W_MATCHES];
   tm->info.max_matches_of_one_job = h[W_MAXJOB];
@@ -383,31 +288,19 @@ template <typename S> int prepare(gtamd_tagmatch *tm, u32 K) {
 int emit(gtamd_tagmatch *tm, u64 *cursor, gtamd_tagmatch_record *out, u64 capacity, int out_on_device, u64 *written) {
   *written = 0;
   const u64 total = tm->info.matches, cur = *cursor;
-  if (cur > total) {
-    gtamd_set_error("tag matches: cursor %llu is not one of this enumeration (%llu records)",
-                    (unsigned long long) cur, (unsigned long long) total);
-    return -1;
-  }
-  if (capacity < TM_MIN_CAPACITY) {
-    gtamd_set_error("tag matches: a capacity of %llu records is too small: a capacity of at least %llu is needed",
-                    (unsigned long long) capacity, (unsigned long long) TM_MIN_CAPACITY);
-    return -1;
-  }
+  TRY(refuse_window(FEATURE, "records", cur, total, capacity, TM_MIN_CAPACITY));
   if (cur == total) return 0;
   const u64 w1 = capacity < total - cur ? cur + capacity : total;
-  // the jobs with a record in [cur, w1): from the last whose first record is not
-  // behind cur up to the first whose first record is not in front of w1
-  const std::vector<u64> &off = tm->off_host;
-  const u64 j0 = (u64) (std::upper_bound(off.begin(), off.end(), cur) - off.begin()) - 1;
-  const u64 j1 = (u64) (std::lower_bound(off.begin(), off.end(), w1) - off.begin());
+  u64 j0, j1;
+  tm->jo.jobs_of(cur, w1, &j0, &j1);
   RecordStage<TmRecord> stage(out, out_on_device);
-  if (stage.begin(tm->out, w1 - cur) != hipSuccess) return out_of_memory(w1 - cur, "records");
+  if (stage.begin(tm->out, w1 - cur) != hipSuccess) return out_of_memory(FEATURE, w1 - cur, "records");
   const u32 blocks = (u32) div_up(j1 - j0, TM_WAVES);
   if (tm->index.suf_bytes == 4)
-    k_tm_walk<u32, true><<<blocks, TM_THREADS, 0, tm->st>>>(input<u32>(tm), j0, j1, 0, tm->kbest, nullptr, tm->off, cur,
+    k_tm_walk<u32, true><<<blocks, TM_THREADS, 0, tm->st>>>(input<u32>(tm), j0, j1, 0, tm->kbest, nullptr, tm->jo.off, cur,
                                                              w1, stage.dst, tm->words);
   else
-    k_tm_walk<u64, true><<<blocks, TM_THREADS, 0, tm->st>>>(input<u64>(tm), j0, j1, 0, tm->kbest, nullptr, tm->off, cur,
+    k_tm_walk<u64, true><<<blocks, TM_THREADS, 0, tm->st>>>(input<u64>(tm), j0, j1, 0, tm->kbest, nullptr, tm->jo.off, cur,
                                                              w1, stage.dst, tm->words);
   HIP_TRY(hipGetLastError());
   TRY(stage.finish(w1 - cur, tm->st));
@@ -499,23 +392,11 @@ extern "C" int gtamd_tagmatch_prepare(gtamd_tagmatch *tm, const uint8_t *tags, c
   tm->flags = flags;
   tm->jobs = T * ((flags & TM_STRANDS) == TM_STRANDS ? 2 : 1);
   tm->info.jobs = tm->jobs;
-  tm->off_host.assign(1, 0);
+  tm->jo.off_host.assign(1, 0);
   if (T != 0) {
-    const u64 jobs = tm->jobs, tiles = div_up(jobs, SC_THREADS);
-    if (tm->cnt.grow(jobs * 4) != hipSuccess || tm->kbest.grow(T * 4) != hipSuccess ||
-        tm->off.grow((jobs + 1) * 8) != hipSuccess || tm->tsum.grow(tiles * 8) != hipSuccess)
-      return out_of_memory(jobs, "jobs");
-    tm->tags = tags;
-    tm->toff = offsets;
-    if (!is_device) {
-      const u64 symbols = offsets[T];
-      if (tm->own_tags.grow(symbols ? symbols : 1) != hipSuccess || tm->own_toff.grow((T + 1) * 8) != hipSuccess)
-        return out_of_memory(symbols, "tag symbols");
-      if (symbols) HIP_TRY(hipMemcpyAsync(tm->own_tags, tags, symbols, hipMemcpyHostToDevice, tm->st));
-      HIP_TRY(hipMemcpyAsync(tm->own_toff, offsets, (T + 1) * 8, hipMemcpyHostToDevice, tm->st));
-      tm->tags = tm->own_tags;
-      tm->toff = tm->own_toff;
-    }
+    if (tm->jo.grow(tm->jobs) != hipSuccess || tm->kbest.grow(T * 4) != hipSuccess)
+      return out_of_memory(FEATURE, tm->jobs, "jobs");
+    TRY(tm->tags.set(FEATURE, "tag symbols", tags, offsets, T, is_device, tm->st));
     TRY(tm->index.suf_bytes == 4 ? prepare<u32>(tm, K) : prepare<u64>(tm, K));
   }
   tm->info.device_bytes = held_bytes(tm);

@@ -13,11 +13,7 @@
 // i - 1.  No shift in here has a count of 64: bit m - 1 <= 63 is the highest
 // one that is looked at.
 #pragma once
-#include <stdint.h>
-
-typedef uint64_t u64;
-typedef uint32_t u32;
-typedef uint8_t u8;
+#include "esa_ivwalk.h"
 
 #if defined(__HIPCC__)
 #define TM_HD __device__ __forceinline__
@@ -28,7 +24,7 @@ typedef uint8_t u8;
 constexpr u32 TM_MAX_TAG = 64;           // letters of a tag: the bits of a word
 constexpr u32 TM_LETTERS = 32;           // letters an alphabet may have here: the entries of an Eq table
 constexpr u32 TM_NONE = 0xffffffffu;     // no row of the column is <= K
-constexpr u32 TM_WILDCARD = 254, TM_SEPARATOR = 255;
+constexpr u32 TM_WILDCARD = IV_WILDCARD, TM_SEPARATOR = IV_SEPARATOR;      // (as the cases of tests/ name them)
 
 // row: the largest row whose value is <= K, val: that value.  While row < m the
 // value is K itself (the row above holds K + 1 and rows differ by at most one).
@@ -85,7 +81,7 @@ TM_HD u32 tm_walk(TmColumn c, const u64 *eq, const u8 *enc, u64 n, u64 p, u32 de
                   u32 *dist) {
   while (depth < m + K && p + depth < n) {
     const u32 s = enc[p + depth];
-    if (s == TM_SEPARATOR || (s == TM_WILDCARD && !wild)) return 0;
+    if (s == IV_SEPARATOR || (s == IV_WILDCARD && !wild)) return 0;
     tm_step(c, s < TM_LETTERS ? eq[s] : 0, K);
     depth += 1;
     if (tm_dead(c)) return 0;

@@ -38,7 +38,7 @@ import oracle_util as ou
 ROOT = ou.ROOT
 SRC = [os.path.join(ROOT, "tests", f) for f in ("locali_core_shim.cpp", "locali_core_main.cpp",
                                                  "locali_core_cases.h")] + \
-      [os.path.join(ROOT, "genometools_amd", "csrc", "esa_locali_core.h")]
+      [os.path.join(ROOT, "genometools_amd", "csrc", f) for f in ("esa_locali_core.h", "esa_ivwalk.h")]
 SHIM = os.path.join(ROOT, "oracle", "_build", "liblocali_core_shim.so")
 MAIN = os.path.join(ROOT, "oracle", "_build", "locali_core_main_san")
 TALLY = ("walks", "columns", "matches", "failures", "tie_del_rep", "tie_del_ins", "tie_rep_ins", "delete_across",

@@ -23,7 +23,7 @@ import tagmatch_reference as tr
 ROOT = ou.ROOT
 SRC = [os.path.join(ROOT, "tests", f) for f in ("tagmatch_core_shim.cpp", "tagmatch_core_main.cpp",
                                                  "tagmatch_core_cases.h")] + \
-      [os.path.join(ROOT, "genometools_amd", "csrc", "esa_tagmatch_core.h")]
+      [os.path.join(ROOT, "genometools_amd", "csrc", f) for f in ("esa_tagmatch_core.h", "esa_ivwalk.h")]
 SHIM = os.path.join(ROOT, "oracle", "_build", "libtagmatch_core_shim.so")
 MAIN = os.path.join(ROOT, "oracle", "_build", "tagmatch_core_main_san")
 
