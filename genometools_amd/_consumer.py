@@ -83,18 +83,28 @@ def host_tables(enc, suf, lcp=None, llv=None,
     return enc, suf, lcp, llv
 
 
-def record_chunks(emit_fn, handle, capacity, device, device_index):
-    """the records of an enumeration, one array of shape (records, 3) per call of
-    emit_fn (gtamd_*_emit) with at most `capacity` records, until a call gives
-    none: numpy uint64 copies, or, with `device`, torch int64 views of one
-    buffer on cuda:device_index, which the next call overwrites"""
-    cursor, written = ctypes.c_uint64(0), ctypes.c_uint64(0)
+def record_chunks(emit_fn, handle, capacity, device, device_index, cursor=0, columns=3):
+    """the records of an enumeration, one array of shape (records, columns) per
+    call of emit_fn (gtamd_*_emit) with at most `capacity` records, until a call
+    gives none: numpy uint64 copies, or, with `device`, torch int64 views of one
+    buffer on cuda:device_index, which the next call overwrites.  cursor: where
+    the enumeration starts, in the unit the consumer's header states for its
+    cursor, 0 to its total; a value beyond is refused by the first call.  An
+    int, or a numpy uint64 array of one element, which every call advances in
+    place: what a caller that stops early passes again to resume"""
+    if isinstance(cursor, np.ndarray):
+        if cursor.dtype != np.uint64 or cursor.size != 1 or not cursor.flags.writeable:
+            raise TypeError("a cursor array must be one writable uint64")
+        cursor = ctypes.c_uint64.from_buffer(cursor)
+    else:
+        cursor = ctypes.c_uint64(cursor)
+    written = ctypes.c_uint64(0)
     if device:
         import torch
-        buf = torch.empty((max(capacity, 1), 3), dtype=torch.int64, device="cuda:%d" % device_index)
+        buf = torch.empty((max(capacity, 1), columns), dtype=torch.int64, device="cuda:%d" % device_index)
         address = buf.data_ptr()
     else:
-        buf = np.empty((max(capacity, 1), 3), dtype=np.uint64)
+        buf = np.empty((max(capacity, 1), columns), dtype=np.uint64)
         address = buf.ctypes.data
     while True:
         check(emit_fn(handle, ctypes.byref(cursor), address, capacity, int(device), ctypes.byref(written)))

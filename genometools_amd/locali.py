@@ -19,8 +19,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._consumer import Consumer, host_tables, ptr
-from ._lib import LocaliInfo, check
+from ._consumer import Consumer, host_tables, ptr, record_chunks
+from ._lib import LocaliInfo
 
 DEFAULT_CAPACITY = 1 << 20        # records of one emit call (32 bytes each)
 AUTO = 0xffffffff
@@ -100,26 +100,15 @@ class LocalAlignments(Consumer):
         """gtamd_locali_info of the last prepare and the emit calls since, as a dict"""
         return self._call_info("get_info")
 
-    def records(self, capacity=DEFAULT_CAPACITY, device=False):
+    def records(self, capacity=DEFAULT_CAPACITY, device=False, cursor=0):
         """the records of the last prepare in order, one array per emit call of
         at most `capacity` records: numpy uint64 arrays of shape (records, 4) --
         query, dbstart, dblen | score << 32, qstart | qlen << 32 -- or, with
         device=True, torch int64 tensors of that shape on the device, which the
-        next call overwrites"""
-        cursor, written = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        if device:
-            import torch
-            buf = torch.empty((max(capacity, 1), 4), dtype=torch.int64, device="cuda:%d" % self._device)
-            address = buf.data_ptr()
-        else:
-            buf = np.empty((max(capacity, 1), 4), dtype=np.uint64)
-            address = buf.ctypes.data
-        emit = self._fn("emit")
-        while True:
-            check(emit(self._p, ctypes.byref(cursor), address, capacity, int(device), ctypes.byref(written)))
-            if written.value == 0:
-                return
-            yield buf[:written.value] if device else buf[:written.value].copy()
+        next call overwrites.  cursor: the record number to start from, 0 to
+        info()["matches"] (or a uint64 array of one element that every call
+        advances: _consumer.record_chunks)"""
+        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device, cursor, columns=4)
 
     def all_records(self, queries, T, match=1, mismatch=-1, gapextend=-1, capacity=DEFAULT_CAPACITY):
         """every record of `queries` as one numpy array of shape (matches, 4)"""

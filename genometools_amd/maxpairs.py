@@ -52,15 +52,18 @@ class MaxPairs(Consumer):
         """gtamd_maxpairs_info of the last prepare, as a dict"""
         return self._call_info("get_info")
 
-    def pairs(self, capacity=None, device=False):
+    def pairs(self, capacity=None, device=False, cursor=0):
         """the records of the last prepare in table order, in chunks of whole
         suffixes and at most `capacity` records (default: DEFAULT_CAPACITY, or
         what one suffix needs if that is more): numpy uint64 arrays of shape
         (records, 3) -- pos1, pos2, len -- or, with device=True, torch int64
-        tensors of that shape on the device, which the next chunk overwrites"""
+        tensors of that shape on the device, which the next chunk overwrites.
+        cursor: the suffix in a run to start from, in table order, 0 to
+        info()["run_suffixes"] (or a uint64 array of one element that every call
+        advances: _consumer.record_chunks)"""
         if capacity is None:
             capacity = max(DEFAULT_CAPACITY, self.info()["max_pairs_of_one_suffix"])
-        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device)
+        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device, cursor)
 
     def all_pairs(self, capacity=None):
         """every record as one numpy array of shape (pairs, 3)"""

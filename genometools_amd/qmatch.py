@@ -92,12 +92,14 @@ class QueryMatches(Consumer):
         """gtamd_qmatch_info of the last prepare and the emit calls since, as a dict"""
         return self._call_info("get_info")
 
-    def emit(self, capacity=DEFAULT_CAPACITY, device=False):
+    def emit(self, capacity=DEFAULT_CAPACITY, device=False, cursor=0):
         """the records of the last prepare in order, one array per emit call of
         at most `capacity` records: numpy uint64 arrays of shape (records, 3) --
         dbpos, qpos, len -- or, with device=True, torch int64 tensors of that
-        shape on the device, which the next call overwrites"""
-        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device)
+        shape on the device, which the next call overwrites.  cursor: the
+        candidate number to start from, 0 to info()["candidates"] (or a uint64
+        array of one element that every call advances: _consumer.record_chunks)"""
+        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device, cursor)
 
     def all_matches(self, query, min_len, readmode="fwd", capacity=DEFAULT_CAPACITY):
         """every record of `query` read in `readmode` ("fwd", "rev": every

@@ -76,12 +76,14 @@ class SuffixPrefixMatches(Consumer):
         """gtamd_spm_info of the last prepare, as a dict"""
         return self._call_info("get_info")
 
-    def matches(self, capacity=DEFAULT_CAPACITY, device=False):
+    def matches(self, capacity=DEFAULT_CAPACITY, device=False, cursor=0):
         """the records of the last prepare in order, one array per emit call of
         at most `capacity` records: numpy uint64 arrays of shape (records, 3) --
         suffix_seq, prefix_seq, len -- or, with device=True, torch int64 tensors
-        of that shape on the device, which the next call overwrites"""
-        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device)
+        of that shape on the device, which the next call overwrites.  cursor:
+        the record number to start from, 0 to info()["matches"] (or a uint64 array
+        of one element that every call advances: _consumer.record_chunks)"""
+        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device, cursor)
 
     def all_matches(self, min_len, capacity=DEFAULT_CAPACITY):
         """every record of minimum length min_len as one numpy array of shape (matches, 3)"""

@@ -103,12 +103,14 @@ class TagMatches(Consumer):
         self._call("best_k", ptr(k) if k.size else None, k.size)
         return k
 
-    def records(self, capacity=DEFAULT_CAPACITY, device=False):
+    def records(self, capacity=DEFAULT_CAPACITY, device=False, cursor=0):
         """the records of the last prepare in order, one array per emit call of
         at most `capacity` records: numpy uint64 arrays of shape (records, 3) --
         tag, dbstart, lendist -- or, with device=True, torch int64 tensors of
-        that shape on the device, which the next call overwrites"""
-        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device)
+        that shape on the device, which the next call overwrites.  cursor: the
+        record number to start from, 0 to info()["matches"] (or a uint64 array of
+        one element that every call advances: _consumer.record_chunks)"""
+        yield from record_chunks(self._fn("emit"), self._p, capacity, device, self._device, cursor)
 
     def all_records(self, tags, K, flags=FORWARD | REVCOMP, capacity=DEFAULT_CAPACITY):
         """every record of `tags` as one numpy array of shape (matches, 3)"""

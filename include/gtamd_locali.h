@@ -180,8 +180,12 @@ int gtamd_locali_prepare(gtamd_locali *lc, const uint8_t *queries, const uint64_
                          int is_device, int32_t match, int32_t mismatch, int32_t gapextend,
                          uint32_t threshold, gtamd_locali_info *info);
 
-/* The records of the last prepare in pieces.  *cursor is 0 for the first call
-   after a prepare and is advanced by the call; it is otherwise opaque.  Writes
+/* The records of the last prepare in pieces.  *cursor is the number of the
+   first record to write, counted over the whole enumeration in the order stated
+   above: 0 for the first call after a prepare, advanced by the call to the
+   record behind the last one written.  Any value from 0 to `matches` of the
+   info may be passed, to resume an enumeration or to take a piece out of its
+   middle; a value beyond it is refused with a message.  Writes
    the records whose places are [*cursor, *cursor + capacity) in the order
    stated above to out (device memory when out_on_device, else host memory);
    *written = their number, 0 only when no record is left.  A job whose

@@ -138,8 +138,13 @@ int gtamd_maxpairs_set_index_esa(gtamd_maxpairs *mp, const gtamd_esa_ctx *esa,
    (may be NULL).  Synchronous. */
 int gtamd_maxpairs_prepare(gtamd_maxpairs *mp, uint32_t min_len, gtamd_maxpairs_info *info);
 
-/* Step 4, in pieces.  *cursor is 0 for the first call after a prepare and is
-   advanced by the call; it is otherwise opaque.  Writes the records of whole
+/* Step 4, in pieces.  *cursor is a number of SUFFIXES IN RUNS, not of records:
+   the place, among the M in-run suffixes in table order, of the first suffix
+   whose records are written; 0 for the first call after a prepare, advanced by
+   the call to the suffix behind the last one written, and to M when no record
+   is left.  Any value from 0 to M (`run_suffixes` of the info) may be passed, to
+   resume an enumeration or to start in its middle; a value beyond M is refused
+   with a message.  Writes the records of whole
    suffixes, in table order, from the cursor on, as many as fit `capacity`
    records, to out (device memory when out_on_device, else host memory);
    *written = their number, 0 when all z records have been given.  A capacity

@@ -136,8 +136,12 @@ int gtamd_qmatch_set_index_esa(gtamd_qmatch *qm, const gtamd_esa_ctx *esa,
 int gtamd_qmatch_prepare(gtamd_qmatch *qm, const uint8_t *query, uint64_t m, int is_device,
                          uint32_t min_len, gtamd_qmatch_info *info);
 
-/* Step c, in pieces.  *cursor is 0 for the first call after a prepare and is
-   advanced by the call; it is otherwise opaque.  Goes through the candidates
+/* Step c, in pieces.  *cursor is a number of CANDIDATES, not of records: the
+   place, in the scan of step b, of the first candidate to go through; 0 for
+   the first call after a prepare, advanced by the call to the candidate behind
+   the last one it went through.  Any value from 0 to C (`candidates` of the
+   info) may be passed, to resume an enumeration or to start in its middle; a
+   value beyond C is refused with a message.  Goes through the candidates
    from the cursor on in chunks of at most (capacity - records written so far)
    candidates, and writes the records in the order stated above to out (device
    memory when out_on_device, else host memory).  It stops when that room falls

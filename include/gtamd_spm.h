@@ -157,8 +157,12 @@ int gtamd_spm_set_index_esa(gtamd_spm *sp, const gtamd_esa_ctx *esa,
    (may be NULL).  Synchronous. */
 int gtamd_spm_prepare(gtamd_spm *sp, uint32_t min_len, gtamd_spm_info *info);
 
-/* Step 5, in pieces.  *cursor is 0 for the first call after a prepare and is
-   advanced by the call; it is otherwise opaque.  Writes the next records in the
+/* Step 5, in pieces.  *cursor is the number of the first record to write,
+   counted over all Z records in the order stated above: 0 for the first call
+   after a prepare, advanced by the call to the record behind the last one
+   written.  Any value from 0 to Z (`matches` of the info) may be passed, to
+   resume an enumeration or to take a piece out of its middle; a value beyond Z
+   is refused with a message.  Writes the next records in the
    order stated above, as many as fit `capacity`, to out (device memory when
    out_on_device, else host memory); *written = their number, 0 when all Z
    records have been given.  A capacity below min_capacity is refused with a

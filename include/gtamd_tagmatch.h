@@ -160,8 +160,12 @@ int gtamd_tagmatch_set_index_esa(gtamd_tagmatch *tm, const gtamd_esa_ctx *esa,
 int gtamd_tagmatch_prepare(gtamd_tagmatch *tm, const uint8_t *tags, const uint64_t *offsets, uint64_t T,
                            int is_device, uint32_t K, uint32_t flags, gtamd_tagmatch_info *info);
 
-/* The records of the last prepare in pieces.  *cursor is 0 for the first call
-   after a prepare and is advanced by the call; it is otherwise opaque.  Writes
+/* The records of the last prepare in pieces.  *cursor is the number of the
+   first record to write, counted over the whole enumeration in the order stated
+   above: 0 for the first call after a prepare, advanced by the call to the
+   record behind the last one written.  Any value from 0 to `matches` of the
+   info may be passed, to resume an enumeration or to take a piece out of its
+   middle; a value beyond it is refused with a message.  Writes
    the records whose places are [*cursor, *cursor + capacity) in the order
    stated above to out (device memory when out_on_device, else host memory);
    *written = their number, 0 only when no record is left.  A job whose

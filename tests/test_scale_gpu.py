@@ -21,8 +21,9 @@ structure, and asserts from info() and the array sizes that it does:
 Every record is compared, none sampled, in the stated order; the tables come
 from the engine, in this process.  Matching statistics (mstat) and the index
 check have no second level of their own beyond the upload loop, which is the one
-of csrc/esa_index.h for all of them: they are left out.  Still untested: record
-counts past 2^32 and n near the single-build limit."""
+of csrc/esa_index.h for all of them: they are left out.  Record places past 2^32
+are tests/test_wide_places_gpu.py; still untested: n near the single-build
+limit."""
 import functools
 
 import numpy as np
