@@ -15,18 +15,19 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in
            ("esa_prims.hip", "esa_engine.hip", "esa_synth.hip", "esa_encode.hip",
             "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip",
             "esa_maxpairs.hip", "esa_qmatch.hip", "esa_spm.hip", "esa_tagmatch.hip",
-            "esa_locali.hip")]
+            "esa_locali.hip", "esa_pckidx.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_index.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
                                                      "esa_jobs.h", "esa_ivwalk.h",
                                                      "esa_pck_replay.h", "esa_mstat_search.h",
                                                      "esa_maxpairs_walk.h", "esa_qmatch_core.h",
                                                      "esa_spm_core.h", "esa_tagmatch_core.h",
-                                                     "esa_locali_core.h")] + \
+                                                     "esa_locali_core.h", "esa_pckidx_core.h",
+                                                     "esa_pckidx.h")] + \
           [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
                                                        "gtamd_check.h", "gtamd_mstat.h",
                                                        "gtamd_maxpairs.h", "gtamd_qmatch.h",
                                                        "gtamd_spm.h", "gtamd_tagmatch.h",
-                                                       "gtamd_locali.h")]
+                                                       "gtamd_locali.h", "gtamd_pckidx.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -340,6 +341,31 @@ LOCALI_ABI = {
     "gtamd_locali_get_info": (_INT, [_P, ctypes.POINTER(LocaliInfo)]),
 }
 
+class PckidxInfo(ctypes.Structure):      # gtamd_pckidx_info, include/gtamd_pckidx.h
+    _fields_ = [(name, ctypes.c_uint64) for name in
+                ("rows", "buckets", "regions", "special_rows", "marks", "rot0_row", "image_bytes",
+                 "decoded_bytes")] + \
+               [(name, ctypes.c_uint32) for name in
+                ("numofchars", "block_size", "bucket_blocks", "locate_interval", "feature_toggles",
+                 "two_bit")] + [("decode_ms", ctypes.c_float), ("line_rows", ctypes.c_uint32)]
+
+
+# every symbol include/gtamd_pckidx.h declares
+PCKIDX_ABI = {
+    "gtamd_pckidx_check_image": (_INT, [_P, _U64]),
+    "gtamd_pckidx_create": (_P, [_INT]),
+    "gtamd_pckidx_destroy": (None, [_P]),
+    "gtamd_pckidx_open_host": (_INT, [_P, _P, _U64]),
+    "gtamd_pckidx_open_device": (_INT, [_P, _P, _U64]),
+    "gtamd_pckidx_open_builder": (_INT, [_P, _P]),
+    "gtamd_pckidx_get_info": (_INT, [_P, ctypes.POINTER(PckidxInfo)]),
+    "gtamd_pckidx_decoded_copy": (_INT, [_P, _U32, _P, _U64, ctypes.POINTER(_U64)]),
+    "gtamd_pckidx_bwt": (_INT, [_P, _U64, _U64, _P, _INT]),
+    "gtamd_pckidx_rank": (_INT, [_P, _P, _P, _U64, _P, _INT]),
+    "gtamd_pckidx_locate": (_INT, [_P, _P, _U64, _P, _INT]),
+    "gtamd_mstat_set_index_pckidx": (_INT, [_P, _P]),
+}
+
 _lib = None
 
 
@@ -364,7 +390,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()) + \
                 list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()) + list(SPM_ABI.items()) + list(TAGMATCH_ABI.items()) + \
-                list(LOCALI_ABI.items()):
+                list(LOCALI_ABI.items()) + list(PCKIDX_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

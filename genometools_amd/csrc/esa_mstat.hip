@@ -7,10 +7,16 @@
 // carries the letters shared with both borders, then at most one more search
 // (the witness) or one more comparison (the second neighbour, for uniqueness):
 // esa_mstat_search.h.  Letters are compared MST_WORD at a time through 4-byte words.
+//
+// With a reader of the packed index as the index (gtamd_mstat_set_index_pckidx,
+// include/gtamd_pckidx.h) the same two calls run the backward search of
+// esa_pckidx.hip instead.
 #include "esa_common.h"
 #include "esa_index.h"
 #include "esa_mstat_search.h"
+#include "esa_pckidx.h"
 #include "../../include/gtamd_mstat.h"
+#include "../../include/gtamd_pckidx.h"
 
 namespace {
 
@@ -18,7 +24,7 @@ constexpr int MST_THREADS = 256;
 constexpr u32 MST_TILE = 256;            // query positions per workgroup, one a lane
 constexpr u64 MST_MAX_QUERY = (1ull << 32) - 1;
 
-enum { W_COMPARED = 0, W_RERUNS, W_WORDS };
+enum { W_COMPARED = 0, W_RERUNS, W_ERROR, W_WORDS };   // W_ERROR: the error word of a packed-index search
 
 // one lane per query position: mst_position of esa_mstat_search.h
 template <typename S, bool MATSTAT>
@@ -51,6 +57,7 @@ __global__ __launch_bounds__(MST_THREADS) void k_mstat(const u8 *enc, u64 n, con
 
 struct gtamd_mstat : ConsumerBase<> {
   ResidentIndex index;
+  const gtamd_pckidx *pck = nullptr;     // the index is a reader of the packed index
   u32 numofchars = 0;
   Dev<u8> query;
   Dev<u32> len;
@@ -75,6 +82,7 @@ int set_index(gtamd_mstat *ms, const IndexView &v, u32 numofchars, bool from_hos
   }
   TRY(refuse_sizes(FEATURE, v.n, 0));
   HIP_TRY(hipSetDevice(ms->device));
+  ms->pck = nullptr;
   ms->numofchars = numofchars;
   if (from_host) return ms->index.upload_from_host(FEATURE, v);
   ms->index.borrow(v);
@@ -82,7 +90,7 @@ int set_index(gtamd_mstat *ms, const IndexView &v, u32 numofchars, bool from_hos
 }
 
 u64 held_bytes(const gtamd_mstat *ms) {
-  return ms->index.bytes() + ms->query.bytes + ms->len.bytes + ms->pos.bytes + ms->words.bytes;
+  return ms->index.bytes() + (ms->pck != nullptr ? pckidx_decoded_bytes(ms->pck) : 0) + ms->query.bytes + ms->len.bytes + ms->pos.bytes + ms->words.bytes;
 }
 
 template <typename S, bool MATSTAT>
@@ -97,8 +105,13 @@ int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_devi
     gtamd_set_error("invalid argument to gtamd_mstat_%s", matstat ? "matstat" : "uniquesub");
     return -1;
   }
-  if (!ms->index.set) {
+  if (!ms->index.set && ms->pck == nullptr) {
     gtamd_set_error("matching statistics: no index is set (gtamd_mstat_set_index)");
+    return -1;
+  }
+  if (ms->pck != nullptr && !pckidx_is_open(ms->pck)) {
+    gtamd_set_error("matching statistics: the packed index reader that is the index has no image open any more "
+                    "(its last gtamd_pckidx_open_* failed)");
     return -1;
   }
   if (m > MST_MAX_QUERY) {
@@ -112,6 +125,11 @@ int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_devi
   if (m == 0) return 0;
   HIP_TRY(hipSetDevice(ms->device));
   const bool want_pos = matstat && subjectpos_out != nullptr;
+  if (ms->pck != nullptr && want_pos && !pckidx_can_locate(ms->pck)) {
+    gtamd_set_error("matching statistics: the packed index holds no locate information (locate interval 0): "
+                    "subject positions cannot be had from it");
+    return -1;
+  }
   if ((!is_device && ms->query.grow(m) != hipSuccess) ||
       (!out_is_device && (ms->len.grow(m * sizeof(u32)) != hipSuccess ||
                           (want_pos && ms->pos.grow(m * sizeof(u64)) != hipSuccess)))) {
@@ -130,7 +148,9 @@ int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_devi
   const u32 limit = max_len == 0 || max_len >= MST_MAX_QUERY ? (u32) MST_MAX_QUERY : max_len + 1;
   HIP_TRY(hipMemsetAsync(ms->words, 0, W_WORDS * sizeof(u64), st));
   HIP_TRY(hipEventRecord(ms->ev[0], st));
-  if (ms->index.suf_bytes == 4) {
+  if (ms->pck != nullptr) {
+    TRY(pckidx_search(ms->pck, st, matstat, q, m, limit, len, pos, &ms->words[W_COMPARED], &ms->words[W_ERROR]));
+  } else if (ms->index.suf_bytes == 4) {
     if (matstat) launch<u32, true>(ms, q, m, limit, len, pos); else launch<u32, false>(ms, q, m, limit, len, pos);
   } else {
     if (matstat) launch<u64, true>(ms, q, m, limit, len, pos); else launch<u64, false>(ms, q, m, limit, len, pos);
@@ -141,6 +161,7 @@ int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_devi
   TRY(fetch(st, { { len, length_out, out_is_device ? 0 : m * sizeof(u32) },
                   { pos, subjectpos_out, out_is_device || !want_pos ? 0 : m * sizeof(u64) },
                   { ms->words, h, sizeof h } }));
+  if (h[W_ERROR]) { pckidx_set_search_error(h[W_ERROR]); return -1; }
   HIP_TRY(hipEventElapsedTime(&ms->info.device_ms, ms->ev[0], ms->ev[1]));
   ms->info.symbols_compared = h[W_COMPARED];
   ms->info.reruns = (u32) h[W_RERUNS];
@@ -185,6 +206,21 @@ extern "C" int gtamd_mstat_set_index_esa(gtamd_mstat *ms, const gtamd_esa_ctx *e
   IndexView v;
   TRY(engine_tables(FEATURE, esa, enc, n, false, &v));
   return set_index(ms, v, numofchars, false);
+  GTAMD_ABI_END(-1)
+}
+
+extern "C" int gtamd_mstat_set_index_pckidx(gtamd_mstat *ms, const gtamd_pckidx *px) {
+  GTAMD_ABI_BEGIN
+  if (ms == nullptr || px == nullptr) { gtamd_set_error("invalid argument to gtamd_mstat_set_index_pckidx"); return -1; }
+  if (!pckidx_is_open(px)) { gtamd_set_error("matching statistics: the packed index reader has no image open"); return -1; }
+  if (pckidx_device(px) != ms->device) {
+    gtamd_set_error("matching statistics: the packed index lives on device %d, the searcher on %d", pckidx_device(px), ms->device);
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(ms->device));
+  ms->index.drop();
+  ms->pck = px;
+  return 0;
   GTAMD_ABI_END(-1)
 }
 

@@ -1,0 +1,22 @@
+// esa_pckidx.h -- what esa_mstat.hip needs of the reader of the packed index
+// (esa_pckidx.hip): the search through a reader's decoded form.
+#pragma once
+#include "esa_common.h"
+
+struct gtamd_pckidx;
+
+// device of the reader, does it hold an open image, can it locate
+int pckidx_device(const gtamd_pckidx *px);
+bool pckidx_is_open(const gtamd_pckidx *px);
+bool pckidx_can_locate(const gtamd_pckidx *px);
+u64 pckidx_decoded_bytes(const gtamd_pckidx *px);
+
+// Launches the search of the m query positions at q on stream st: lengths to len,
+// witnesses to pos (matstat, may be nullptr).  limit: letters of a query suffix
+// that count, max_len + 1 or 2^32 - 1.  *pairs gets the rank pairs, *error is set
+// to the error word (esa_pckidx_core.h) of a lane that met one; both are device
+// memory the caller zeroed.
+int pckidx_search(const gtamd_pckidx *px, hipStream_t st, bool matstat, const u8 *q, u64 m, u32 limit, u32 *len,
+                  u64 *pos, u64 *pairs, u64 *error);
+// the message for an error word a search left
+void pckidx_set_search_error(u64 error);

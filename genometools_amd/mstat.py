@@ -53,6 +53,14 @@ class MatchStats(Consumer):
         mode reads them), on the device.  The engine must outlive the searches."""
         self._call("set_index_esa", engine._ctx, enc_device_ptr, n, engine.numofchars)
 
+    def set_index_packed(self, reader):
+        """a `pck.PackedIndexReader` with an open image (include/gtamd_pckidx.h):
+        lengths are those of the text the index was built from read backwards --
+        an index of the reversed subject answers for the subject -- and
+        subjectpos is the reference's witness.  The reader must outlive the
+        searches."""
+        _lib.check(self._lib.gtamd_mstat_set_index_pckidx(self._p, reader._p))
+
     # -- the questions --------------------------------------------------------
     def matstat(self, query, max_len=0):
         """(length, subjectpos) for every position of the encoded query (numpy
