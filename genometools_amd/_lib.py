@@ -22,12 +22,13 @@ HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", 
                                                      "esa_maxpairs_walk.h", "esa_qmatch_core.h",
                                                      "esa_spm_core.h", "esa_tagmatch_core.h",
                                                      "esa_locali_core.h", "esa_pckidx_core.h",
-                                                     "esa_pckidx.h")] + \
+                                                     "esa_pckidx.h", "esa_pckidx_dec.h")] + \
           [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
                                                        "gtamd_check.h", "gtamd_mstat.h",
                                                        "gtamd_maxpairs.h", "gtamd_qmatch.h",
                                                        "gtamd_spm.h", "gtamd_tagmatch.h",
-                                                       "gtamd_locali.h", "gtamd_pckidx.h")]
+                                                       "gtamd_locali.h", "gtamd_pckidx.h",
+                                                       "gtamd_pcktag.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -366,6 +367,11 @@ PCKIDX_ABI = {
     "gtamd_mstat_set_index_pckidx": (_INT, [_P, _P]),
 }
 
+# every symbol include/gtamd_pcktag.h declares
+PCKTAG_ABI = {
+    "gtamd_tagmatch_set_index_pckidx": (_INT, [_P, _P]),
+}
+
 _lib = None
 
 
@@ -390,7 +396,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()) + \
                 list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()) + list(SPM_ABI.items()) + list(TAGMATCH_ABI.items()) + \
-                list(LOCALI_ABI.items()) + list(PCKIDX_ABI.items()):
+                list(LOCALI_ABI.items()) + list(PCKIDX_ABI.items()) + list(PCKTAG_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

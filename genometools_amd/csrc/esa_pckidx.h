@@ -1,5 +1,7 @@
-// esa_pckidx.h -- what esa_mstat.hip needs of the reader of the packed index
-// (esa_pckidx.hip): the search through a reader's decoded form.
+// esa_pckidx.h -- what esa_mstat.hip and esa_tagmatch.hip need of the reader of
+// the packed index (esa_pckidx.hip): the search through a reader's decoded form.
+// A kernel of another file that walks the decoded form itself takes it from
+// pckidx_dec (esa_pckidx_dec.h, which has the lane functions too).
 #pragma once
 #include "esa_common.h"
 

@@ -13,10 +13,19 @@
 //                         which writes those
 //
 // Every working array has one entry per job or per tag, none has N.
+//
+// With a reader of the packed index as the index (gtamd_tagmatch_set_index_pckidx,
+// include/gtamd_pcktag.h) steps b and d are k_tm_walk_pck: the same
+// jobs, windows and records, the levels intervals of rows of the decoded form
+// (esa_pckidx_dec.h), all children of a level from one rank pair a letter.
+#include <type_traits>
 #include "esa_common.h"
 #include "esa_jobs.h"
 #include "esa_tagmatch_core.h"
+#include "esa_pckidx.h"
+#include "esa_pckidx_dec.h"
 #include "../../include/gtamd_tagmatch.h"
+#include "../../include/gtamd_pcktag.h"
 
 namespace {
 
@@ -29,7 +38,7 @@ constexpr u64 TM_MAX_TAGS = 1ull << 30;
 constexpr u32 TM_STRANDS = GTAMD_TAGMATCH_FORWARD | GTAMD_TAGMATCH_REVCOMP;
 constexpr u32 NO_K = GTAMD_TAGMATCH_NO_K;
 
-enum { W_BAD = W_WALK_WORDS, W_WORDS };
+enum { W_BAD = W_WALK_WORDS, W_ERROR, W_WORDS };   // W_ERROR: the error word of a walk over a packed index
 enum { BAD_LENGTH = 1, BAD_SHORT = 2, BAD_SYMBOL = 3 };
 
 struct TmRecord { u64 tag, dbstart, lendist; };
@@ -47,6 +56,31 @@ template <typename S> struct TmInput {
 
 __device__ __forceinline__ u32 uni(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// what job j is: its tag, its strand and its K; false if this pass has nothing to
+// do for it (EMIT: its tag has no K'; else: its tag has one already)
+struct TmJob { u64 tag, tagword; u32 K; bool rc; };
+template <bool EMIT> __device__ __forceinline__ bool tm_job(u32 strands, u64 j, u32 k_pass, const u32 *kbest, TmJob *job) {
+  const bool both = strands == TM_STRANDS;
+  job->tag = both ? j >> 1 : j;
+  job->rc = both ? (j & 1) != 0 : strands == GTAMD_TAGMATCH_REVCOMP;
+  job->K = EMIT ? kbest[job->tag] : k_pass;
+  job->tagword = 2 * job->tag + (job->rc ? 1 : 0);
+  return EMIT ? job->K != NO_K : kbest[job->tag] == NO_K;
+}
+
+// the tag, one letter a lane, as the strand reads it; its Eq words by ballot; its length
+__device__ __forceinline__ u32 tm_tag_eq(const u8 *tags, const u64 *toff, u64 tag, bool rc, u32 lane, u64 *eq) {
+  const u64 t0 = toff[tag];
+  const u32 m = (u32) (toff[tag + 1] - t0);             // 1 .. 64 (k_tm_validate)
+  u32 letter = IV_SEPARATOR;
+  if (lane < m) letter = rc ? 3u - tags[t0 + (m - 1 - lane)] : tags[t0 + lane];
+  for (u32 c = 0; c < TM_LETTERS; c++) {
+    const u64 word = __ballot(letter == c);
+    eq[c] = word;                              // (every lane the same word)
+  }
+  return m;
+}
+
 // Jobs [j0, j1), one a wave.  EMIT false: cnt[job] = its matches for K = k_pass,
 // for the jobs of the tags whose kbest is still none.  EMIT true: K of a job is
 // kbest of its tag; records [w0, w1) of all are written to out, record w0 first.
@@ -59,27 +93,17 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk(TmInput<S> in, u64 j0, u
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const u64 j = j0 + (u64) blockIdx.x * TM_WAVES + wave;
   if (j >= j1) return;                       // (the whole wave: the waves of a workgroup never wait for each other)
-  const bool both = in.strands == TM_STRANDS;
-  const u64 tag = both ? j >> 1 : j;
-  const bool rc = both ? (j & 1) != 0 : in.strands == GTAMD_TAGMATCH_REVCOMP;
-  const u32 K = EMIT ? kbest[tag] : k_pass;
-  if (EMIT ? K == NO_K : kbest[tag] != NO_K) return;
+  TmJob job;
+  if (!tm_job<EMIT>(in.strands, j, k_pass, kbest, &job)) return;
+  const u32 K = job.K;
 
   const IvText<S> &text = in.text;
-  const u64 tagword = 2 * tag + (rc ? 1 : 0);
+  const u64 tagword = job.tagword;
   JobWindow<TmRecord> wk = { 0, 0, 0, nullptr };
   if (EMIT && !wk.open(off, j, w0, w1, out)) return;
 
-  // the tag, one letter a lane, as this strand reads it; its Eq words by ballot
-  const u64 t0 = in.toff[tag];
-  const u32 m = (u32) (in.toff[tag + 1] - t0);          // 1 .. 64 (k_tm_validate)
-  u32 letter = IV_SEPARATOR;
-  if (lane < m) letter = rc ? 3u - in.tags[t0 + (m - 1 - lane)] : in.tags[t0 + lane];
   u64 *eq = s_eq[wave];
-  for (u32 c = 0; c < TM_LETTERS; c++) {
-    const u64 word = __ballot(letter == c);
-    eq[c] = word;                              // (every lane the same word)
-  }
+  const u32 m = tm_tag_eq(in.tags, in.toff, job.tag, job.rc, lane, eq);
 
   TmLevel *level = s_level[wave];
   level[0] = TmLevel{ 0, in.N, 0, K | K << 16, ~0ull, 0 };
@@ -153,6 +177,187 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk(TmInput<S> in, u64 j0, u
   if (!EMIT && lane == 0) report(w, cnt, j, wk.k, pushed, children, walks);
 }
 
+// ---- the same walk over a packed index (include/gtamd_pcktag.h) ----
+// A level is an interval [lo, end) of rows of the decoded form: the rows whose
+// suffixes, in the text of the index, begin with the letters taken so far, last
+// letter first.  In TmLevel, cur is the set of letters whose children are still
+// to be taken when the walk comes back to the level.
+struct PkInput {
+  PkxDec d;
+  const u8 *tags; const u64 *toff; u64 T;
+  u32 strands;
+};
+
+__device__ __forceinline__ u32 lanes_before(u64 mask) {
+  return __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
+}
+
+// The children step, one letter a lane: lane c of `todo` gets the rows [*clo, *chi)
+// of the child of letter c of the interval [lo, hi) -- one rank pair, all lanes
+// in the same one or two lines -- and, where the child is not empty, *ccol = col
+// after letter c.  An empty child, and every other lane, has *clo == *chi.
+// count: count[] of the index, eq: the Eq words of the tag.  Bounds that are none
+// (the decoded form is inconsistent) leave the error word and an empty child.
+__device__ __forceinline__ void pk_children(const PkxDec &d, const u32 *count, const u64 *eq, u32 lo, u32 hi,
+                                            const TmColumn &col, u32 K, u32 todo, u32 lane, u32 *clo, u32 *chi,
+                                            TmColumn *ccol, u32 *err) {
+  *clo = *chi = 0;
+  *ccol = col;
+  if (lane < d.sigma && lane < TM_LETTERS && ((todo >> lane) & 1u)) {
+    u32 a, b;
+    dec_rank_pair(d, lane, lo, hi, &a, &b);
+    const u64 l = (u64) count[lane] + a, h = (u64) count[lane] + b;
+    if (l > h || h > d.N) dev_fail(err, PKX_E_WALK);
+    else if (l < h) {
+      *clo = (u32) l; *chi = (u32) h;
+      tm_step(*ccol, eq[lane], K);
+    }
+  }
+}
+
+// Row `row`, whose `depth` letters gave column c (alive, no success yet), goes on
+// alone: the next letter is the BWT symbol of the row, the next row its LF
+// (pck_overcontext of the reference, one row a lane).  The length of its match,
+// *dist = its distance, *at = the row the match was found at; 0 if it has none.  A
+// special ends it: so does the row of suffix 0, whose symbol is one.  At most
+// m + K letters are part of a match, and every row is checked against the rows.
+__device__ __forceinline__ u32 pk_walk(const PkxDec &d, const u32 *count, const u64 *eq, TmColumn c, u32 row, u32 depth,
+                                       u32 m, u32 K, u32 *dist, u32 *at, u32 *err) {
+  while (depth < m + K) {
+    const u32 s = dec_symbol(d, row);
+    if (s >= d.sigma || s >= TM_LETTERS) return 0;
+    tm_step(c, eq[s], K);
+    depth += 1;
+    if (tm_dead(c)) return 0;
+    const u64 next = (u64) count[s] + dec_rank(d, s, row);
+    if (next >= d.N) { dev_fail(err, PKX_E_WALK); return 0; }
+    row = (u32) next;
+    if (tm_success(c, m)) { *dist = c.val; *at = row; return depth; }
+  }
+  return 0;
+}
+
+// dbstart of the match of `len` letters found at `row`: the suffix of the row
+// begins with them, last letter first (gen_pck_overinterval, pck_overcontext)
+__device__ __forceinline__ u64 pk_dbstart(const PkxDec &d, u32 row, u32 len, u32 *err) {
+  const u64 end = dec_locate(d, row, err) + len;
+  if (end > d.N - 1) { dev_fail(err, PKX_E_WALK); return 0; }
+  return d.N - 1 - end;
+}
+
+// k_tm_walk for a packed index: the same jobs, counts, windows and records.
+template <bool EMIT>
+__global__ __launch_bounds__(TM_THREADS) void k_tm_walk_pck(PkInput in, u64 j0, u64 j1, u32 k_pass, const u32 *kbest,
+                                                            u32 *cnt, const u64 *off, u64 w0, u64 w1, TmRecord *out,
+                                                            u64 *w) {
+  __shared__ TmLevel s_level[TM_WAVES][TM_LEVELS];
+  __shared__ u64 s_eq[TM_WAVES][TM_LETTERS];
+  __shared__ u32 s_count[TM_WAVES][TM_LETTERS + 1];
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u64 j = j0 + (u64) blockIdx.x * TM_WAVES + wave;
+  if (j >= j1) return;                       // (the whole wave: the waves of a workgroup never wait for each other)
+  TmJob job;
+  if (!tm_job<EMIT>(in.strands, j, k_pass, kbest, &job)) return;
+  const u32 K = job.K;
+  const u64 tagword = job.tagword;
+  JobWindow<TmRecord> wk = { 0, 0, 0, nullptr };
+  if (EMIT && !wk.open(off, j, w0, w1, out)) return;
+
+  const PkxDec &d = in.d;
+  u32 *err = reinterpret_cast<u32 *>(&w[W_ERROR]);
+  u64 *eq = s_eq[wave];
+  const u32 m = tm_tag_eq(in.tags, in.toff, job.tag, job.rc, lane, eq);
+  u32 *count = s_count[wave];
+  const u32 sigma = d.sigma < TM_LETTERS ? d.sigma : TM_LETTERS;
+  for (u32 c = 0; c <= sigma; c++) count[c] = d.count[c];       // (every lane the same word)
+
+  TmLevel *level = s_level[wave];
+  level[0] = TmLevel{ 0, (u32) d.N, 0, K | K << 16, ~0ull, 0 };
+  u32 depth = 0;                               // of the top level, which is its index
+  bool fresh = true;                           // the top level has not been expanded yet
+  u32 pushed = 0, children = 0, walks = 0;
+  // Every round expands the top level: for the first time, with all letters, or
+  // again after a child of it has been walked, with the letters behind that
+  // child, which are fewer each time.  A round ends with a push to the next
+  // depth, which is below m + K, or with a pop: the walk ends.
+  for (;;) {
+    if (EMIT && wk.full()) break;
+    const u32 lo = uni(level[depth].lo), hi = uni(level[depth].end);
+    const u32 todo = fresh ? (sigma >= 32 ? ~0u : (1u << sigma) - 1u) : uni(level[depth].cur);
+    if (todo == 0) {
+      if (depth == 0) break;
+      depth -= 1;
+      fresh = false;
+      continue;
+    }
+    TmColumn col = { level[depth].Pv, level[depth].Mv, 0, 0 };
+    const u32 rowval = uni(level[depth].rowval);
+    col.row = rowval & 0xffff;
+    col.val = rowval >> 16;
+    u32 my_lo, my_hi;
+    TmColumn my_col;
+    pk_children(d, count, eq, lo, hi, col, K, todo, lane, &my_lo, &my_hi, &my_col, err);
+    const bool nonempty = my_lo < my_hi;
+    if (fresh) children += (u32) __popcll(__ballot(nonempty));
+    u32 work = (u32) __ballot(nonempty && !tm_dead(my_col));          // (letters are lanes 0 .. 31)
+    const u32 success = (u32) __ballot(nonempty && tm_success(my_col, m));
+    bool down = false;
+    while (work && !(EMIT && wk.full())) {
+      const u32 c = uni((u32) __builtin_ctz(work));
+      work &= work - 1;
+      const u32 clo = __builtin_amdgcn_readlane(my_lo, c), chi = __builtin_amdgcn_readlane(my_hi, c);
+      TmColumn ccol;
+      ccol.Pv = (u64) __builtin_amdgcn_readlane((u32) my_col.Pv, c) | (u64) __builtin_amdgcn_readlane((u32) (my_col.Pv >> 32), c) << 32;
+      ccol.Mv = (u64) __builtin_amdgcn_readlane((u32) my_col.Mv, c) | (u64) __builtin_amdgcn_readlane((u32) (my_col.Mv >> 32), c) << 32;
+      ccol.row = __builtin_amdgcn_readlane(my_col.row, c);
+      ccol.val = __builtin_amdgcn_readlane(my_col.val, c);
+      if ((success >> c) & 1u) {
+        // all rows of the child match with depth + 1 letters
+        if (!EMIT) { wk.k += chi - clo; continue; }
+        u32 b = clo;
+        if (wk.k < wk.first) {                      // rows whose records lie in front of the window
+          const u64 skip = wk.first - wk.k < chi - clo ? wk.first - wk.k : chi - clo;
+          b += (u32) skip;
+          wk.k += skip;
+        }
+        for (; b < chi; b += TM_BATCH) {
+          if (wk.full()) break;
+          const u32 row = b + lane;                  // (chi <= N <= 2^32 - 4096: no wrap)
+          const u64 place = wk.k + lane;
+          u64 p = 0;
+          if (row < chi && place >= wk.first && place < wk.stop) p = pk_dbstart(d, row, depth + 1, err);
+          wk.give<EMIT>(row < chi, TmRecord{ tagword, p, (u64) (depth + 1) | (u64) ccol.val << 32 });
+        }
+        continue;
+      }
+      if (chi - clo <= TM_BATCH) {
+        u32 len = 0, dist = 0, at = 0;
+        if (lane < chi - clo) len = pk_walk(d, count, eq, ccol, clo + lane, depth + 1, m, K, &dist, &at, err);
+        walks += chi - clo;
+        u64 p = 0;
+        if (EMIT) {
+          const u64 place = wk.k + lanes_before(__ballot(len != 0));
+          if (len != 0 && place >= wk.first && place < wk.stop) p = pk_dbstart(d, at, len, err);
+        }
+        wk.give<EMIT>(len != 0, TmRecord{ tagword, p, (u64) len | (u64) dist << 32 });
+        continue;
+      }
+      if (depth + 1 >= TM_LEVELS) continue;          // (cannot be: a column alive at depth m + K has reached row m)
+      level[depth].cur = work;
+      depth += 1;
+      level[depth] = TmLevel{ clo, chi, 0, ccol.row | ccol.val << 16, ccol.Pv, ccol.Mv };
+      pushed += 1;
+      down = true;
+      break;
+    }
+    if (down) { fresh = true; continue; }
+    if (depth == 0) break;
+    depth -= 1;
+    fresh = false;
+  }
+  if (!EMIT && lane == 0) report(w, cnt, j, wk.k, pushed, children, walks);
+}
+
 // kbest of a tag that had none and whose jobs have a match now: k
 __global__ __launch_bounds__(TM_THREADS) void k_tm_settle(const u32 *cnt, u32 per_tag, u64 T, u32 k, u32 *kbest) {
   const u64 t = (u64) blockIdx.x * TM_THREADS + threadIdx.x;
@@ -181,6 +386,7 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_validate(const u8 *tags, cons
 
 struct gtamd_tagmatch : ConsumerBase<> {
   ResidentIndex index;
+  const gtamd_pckidx *pck = nullptr;     // the index is a reader of the packed index
   u32 sigma = 0;
   bool prepared = false;
   // what a prepare leaves for the emit calls
@@ -211,14 +417,23 @@ int set_index(gtamd_tagmatch *tm, const IndexView &v, u32 sigma, bool from_host)
   }
   HIP_TRY(hipSetDevice(tm->device));
   tm->prepared = false;
+  tm->pck = nullptr;
   tm->sigma = sigma;
   if (from_host) return tm->index.upload_from_host(FEATURE, v);
   tm->index.borrow(v);
   return 0;
 }
 
+// the reader that is the index must still hold the image it held when it was set
+int refuse_lost_reader(const gtamd_tagmatch *tm) {
+  if (pckidx_is_open(tm->pck)) return 0;
+  gtamd_set_error("tag matches: the packed index reader that is the index has no image open any more "
+                  "(its last gtamd_pckidx_open_* failed)");
+  return -1;
+}
+
 u64 held_bytes(const gtamd_tagmatch *tm) {
-  return tm->index.bytes() + tm->tags.bytes() + tm->jo.bytes() + tm->kbest.bytes + tm->words.bytes + tm->out.bytes;
+  return tm->index.bytes() + (tm->pck != nullptr ? pckidx_decoded_bytes(tm->pck) : 0) + tm->tags.bytes() + tm->jo.bytes() + tm->kbest.bytes + tm->words.bytes + tm->out.bytes;
 }
 
 template <typename S> TmInput<S> input(const gtamd_tagmatch *tm) {
@@ -252,6 +467,11 @@ int refuse_tag(gtamd_tagmatch *tm, u64 found, u32 K) {
   return -1;
 }
 
+PkInput input_pck(const gtamd_tagmatch *tm) {
+  return PkInput{ pckidx_dec(tm->pck), tm->tags.sym, tm->tags.off, tm->T, tm->flags & TM_STRANDS };
+}
+
+// S: the entries of .suf; void: the index is a reader of the packed index
 template <typename S> int prepare(gtamd_tagmatch *tm, u32 K) {
   hipStream_t st = tm->st;
   const u64 T = tm->T, jobs = tm->jobs;
@@ -266,8 +486,12 @@ template <typename S> int prepare(gtamd_tagmatch *tm, u32 K) {
   if (found != ~0ull) return refuse_tag(tm, found, K);
   HIP_TRY(hipMemsetAsync(tm->kbest, 0xff, T * sizeof(u32), st));
   for (u32 k = (tm->flags & GTAMD_TAGMATCH_BEST) ? 0 : K; k <= K; k++) {
-    k_tm_walk<S, false><<<(u32) div_up(jobs, TM_WAVES), TM_THREADS, 0, st>>>(input<S>(tm), 0, jobs, k, tm->kbest, tm->jo.cnt,
-                                                                           nullptr, 0, 0, nullptr, tm->words);
+    if constexpr (std::is_void<S>::value)
+      k_tm_walk_pck<false><<<(u32) div_up(jobs, TM_WAVES), TM_THREADS, 0, st>>>(input_pck(tm), 0, jobs, k, tm->kbest, tm->jo.cnt,
+                                                                              nullptr, 0, 0, nullptr, tm->words);
+    else
+      k_tm_walk<S, false><<<(u32) div_up(jobs, TM_WAVES), TM_THREADS, 0, st>>>(input<S>(tm), 0, jobs, k, tm->kbest, tm->jo.cnt,
+                                                                             nullptr, 0, 0, nullptr, tm->words);
     HIP_TRY(hipGetLastError());
     k_tm_settle<<<(u32) div_up(T, TM_THREADS), TM_THREADS, 0, st>>>(tm->jo.cnt, per_tag, T, k, tm->kbest);
     HIP_TRY(hipGetLastError());
@@ -276,6 +500,7 @@ template <typename S> int prepare(gtamd_tagmatch *tm, u32 K) {
   HIP_TRY(hipEventRecord(tm->ev[1], st));
   u64 h[W_WORDS];
   TRY(fetch(st, { { tm->words, h, sizeof h }, tm->jo.fetch(jobs) }));
+  if (h[W_ERROR]) { pckidx_set_search_error(h[W_ERROR]); return -1; }
   HIP_TRY(hipEventElapsedTime(&tm->info.device_ms, tm->ev[0], tm->ev[1]));
   tm->info.matches = h[W_MATCHES];
   tm->info.max_matches_of_one_job = h[W_MAXJOB];
@@ -288,6 +513,14 @@ template <typename S> int prepare(gtamd_tagmatch *tm, u32 K) {
 int emit(gtamd_tagmatch *tm, u64 *cursor, gtamd_tagmatch_record *out, u64 capacity, int out_on_device, u64 *written) {
   *written = 0;
   const u64 total = tm->info.matches, cur = *cursor;
+  if (tm->pck != nullptr) {
+    TRY(refuse_lost_reader(tm));
+    if (!pckidx_can_locate(tm->pck)) {
+      gtamd_set_error("tag matches: the packed index holds no locate information (locate interval 0): positions "
+                      "cannot be had from it, only the counts of gtamd_tagmatch_prepare");
+      return -1;
+    }
+  }
   TRY(refuse_window(FEATURE, "records", cur, total, capacity, TM_MIN_CAPACITY));
   if (cur == total) return 0;
   const u64 w1 = capacity < total - cur ? cur + capacity : total;
@@ -296,7 +529,11 @@ int emit(gtamd_tagmatch *tm, u64 *cursor, gtamd_tagmatch_record *out, u64 capaci
   RecordStage<TmRecord> stage(out, out_on_device);
   if (stage.begin(tm->out, w1 - cur) != hipSuccess) return out_of_memory(FEATURE, w1 - cur, "records");
   const u32 blocks = (u32) div_up(j1 - j0, TM_WAVES);
-  if (tm->index.suf_bytes == 4)
+  if (tm->pck != nullptr) {
+    HIP_TRY(hipMemsetAsync(tm->words + W_ERROR, 0, sizeof(u64), tm->st));
+    k_tm_walk_pck<true><<<blocks, TM_THREADS, 0, tm->st>>>(input_pck(tm), j0, j1, 0, tm->kbest, nullptr, tm->jo.off, cur, w1,
+                                                           stage.dst, tm->words);
+  } else if (tm->index.suf_bytes == 4)
     k_tm_walk<u32, true><<<blocks, TM_THREADS, 0, tm->st>>>(input<u32>(tm), j0, j1, 0, tm->kbest, nullptr, tm->jo.off, cur,
                                                              w1, stage.dst, tm->words);
   else
@@ -304,6 +541,11 @@ int emit(gtamd_tagmatch *tm, u64 *cursor, gtamd_tagmatch_record *out, u64 capaci
                                                              w1, stage.dst, tm->words);
   HIP_TRY(hipGetLastError());
   TRY(stage.finish(w1 - cur, tm->st));
+  if (tm->pck != nullptr) {
+    u64 error = 0;
+    TRY(fetch(tm->st, { { tm->words + W_ERROR, &error, sizeof error } }));
+    if (error) { pckidx_set_search_error(error); return -1; }
+  }
   tm->info.emitted += w1 - cur;
   *cursor = w1;
   *written = w1 - cur;
@@ -350,6 +592,28 @@ extern "C" int gtamd_tagmatch_set_index_esa(gtamd_tagmatch *tm, const gtamd_esa_
   GTAMD_ABI_END(-1)
 }
 
+extern "C" int gtamd_tagmatch_set_index_pckidx(gtamd_tagmatch *tm, const gtamd_pckidx *px) {
+  GTAMD_ABI_BEGIN
+  if (tm == nullptr || px == nullptr) { gtamd_set_error("invalid argument to gtamd_tagmatch_set_index_pckidx"); return -1; }
+  if (!pckidx_is_open(px)) { gtamd_set_error("tag matches: the packed index reader has no image open"); return -1; }
+  if (pckidx_device(px) != tm->device) {
+    gtamd_set_error("tag matches: the packed index lives on device %d, the matcher on %d", pckidx_device(px), tm->device);
+    return -1;
+  }
+  const u32 sigma = pckidx_dec(px).sigma;
+  if (sigma == 0 || sigma > TM_LETTERS) {
+    gtamd_set_error("tag matches: an alphabet of %u letters, 1 to %u expected", sigma, TM_LETTERS);
+    return -1;
+  }
+  HIP_TRY(hipSetDevice(tm->device));
+  tm->prepared = false;
+  tm->index.drop();
+  tm->pck = px;
+  tm->sigma = sigma;
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
 extern "C" int gtamd_tagmatch_prepare(gtamd_tagmatch *tm, const uint8_t *tags, const uint64_t *offsets, uint64_t T,
                                       int is_device, uint32_t K, uint32_t flags, gtamd_tagmatch_info *info) {
   GTAMD_ABI_BEGIN
@@ -357,9 +621,17 @@ extern "C" int gtamd_tagmatch_prepare(gtamd_tagmatch *tm, const uint8_t *tags, c
     gtamd_set_error("invalid argument to gtamd_tagmatch_prepare");
     return -1;
   }
-  if (!tm->index.set) {
+  if (!tm->index.set && tm->pck == nullptr) {
     gtamd_set_error("tag matches: no index is set (gtamd_tagmatch_set_index)");
     return -1;
+  }
+  if (tm->pck != nullptr) {
+    TRY(refuse_lost_reader(tm));
+    if (flags & GTAMD_TAGMATCH_WITH_WILDCARDS) {
+      gtamd_set_error("tag matches: GTAMD_TAGMATCH_WITH_WILDCARDS is not taken with a packed index as the index "
+                      "(include/gtamd_pcktag.h)");
+      return -1;
+    }
   }
   const u32 known = TM_STRANDS | GTAMD_TAGMATCH_BEST | GTAMD_TAGMATCH_WITH_WILDCARDS;
   if ((flags & ~known) != 0 || (flags & TM_STRANDS) == 0) {
@@ -397,7 +669,7 @@ extern "C" int gtamd_tagmatch_prepare(gtamd_tagmatch *tm, const uint8_t *tags, c
     if (tm->jo.grow(tm->jobs) != hipSuccess || tm->kbest.grow(T * 4) != hipSuccess)
       return out_of_memory(FEATURE, tm->jobs, "jobs");
     TRY(tm->tags.set(FEATURE, "tag symbols", tags, offsets, T, is_device, tm->st));
-    TRY(tm->index.suf_bytes == 4 ? prepare<u32>(tm, K) : prepare<u64>(tm, K));
+    TRY(tm->pck != nullptr ? prepare<void>(tm, K) : tm->index.suf_bytes == 4 ? prepare<u32>(tm, K) : prepare<u64>(tm, K));
   }
   tm->info.device_bytes = held_bytes(tm);
   tm->prepared = true;

@@ -9,7 +9,8 @@ matches, `TagMatches.records()` yields the records (tag, dbstart, lendist) in
 the order of include/gtamd_tagmatch.h -- tag, strand, table index -- in pieces,
 so that a result larger than memory is streamed.  The index is the encoded
 sequence with its .suf table: in host memory, in device memory or resident in
-an `EsaEngine`.
+an `EsaEngine`; or a `pck.PackedIndexReader` (`gt tagerator -pck`,
+include/gtamd_pcktag.h).
 
 Everything here goes through genometools_amd/libgtamd_esa.so (HIP); there is
 no CPU implementation in this package.
@@ -75,6 +76,15 @@ class TagMatches(Consumer):
         (forward read mode); enc_device_ptr: the n symbols, on the device.  The
         engine must outlive the calls."""
         self._call("set_index_esa", engine._ctx, enc_device_ptr, n, numofchars)
+
+    def set_index_packed(self, reader):
+        """a `pck.PackedIndexReader` with an open image (include/gtamd_pcktag.h):
+        the matches are those of the text the index was built from read
+        backwards -- an index of the reversed subject answers for the subject --
+        in the order of that header, which inside one (tag, strand) is not the
+        order of the suffix table; WITH_WILDCARDS is refused.  The reader must
+        outlive the calls."""
+        _lib.check(self._lib.gtamd_tagmatch_set_index_pckidx(self._p, reader._p))
 
     # -- the enumeration ------------------------------------------------------
     def prepare(self, tags, K, flags=FORWARD | REVCOMP):

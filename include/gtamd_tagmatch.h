@@ -56,7 +56,9 @@
   the children of an interval from left to right gives this order without a
   sort; it is deterministic.  (The reference's order inside one tag and strand
   is that of its stack, a by-product: outputs are compared with the lines of
-  one tag sorted.)
+  one tag sorted.)  With a reader of the packed index as the index
+  (include/gtamd_pcktag.h) the order inside one tag and strand is another one,
+  stated there: that of the rows of the index.
 
   RECORD.  { tag = 2 * tagnumber + (1 for the reverse complement), dbstart = p,
   lendist = len | dist << 32 }, three uint64.
