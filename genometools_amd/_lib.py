@@ -28,7 +28,7 @@ HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", 
                                                        "gtamd_maxpairs.h", "gtamd_qmatch.h",
                                                        "gtamd_spm.h", "gtamd_tagmatch.h",
                                                        "gtamd_locali.h", "gtamd_pckidx.h",
-                                                       "gtamd_pcktag.h")]
+                                                       "gtamd_pcktag.h", "gtamd_pcklocali.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -372,6 +372,11 @@ PCKTAG_ABI = {
     "gtamd_tagmatch_set_index_pckidx": (_INT, [_P, _P]),
 }
 
+# every symbol include/gtamd_pcklocali.h declares
+PCKLOCALI_ABI = {
+    "gtamd_locali_set_index_pckidx": (_INT, [_P, _P]),
+}
+
 _lib = None
 
 
@@ -396,7 +401,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()) + \
                 list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()) + list(SPM_ABI.items()) + list(TAGMATCH_ABI.items()) + \
-                list(LOCALI_ABI.items()) + list(PCKIDX_ABI.items()) + list(PCKTAG_ABI.items()):
+                list(LOCALI_ABI.items()) + list(PCKIDX_ABI.items()) + list(PCKTAG_ABI.items()) + \
+                list(PCKLOCALI_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

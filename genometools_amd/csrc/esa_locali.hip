@@ -15,12 +15,22 @@
 //   d  k_lc_walk<true>    the same walk for the jobs of a window of records,
 //                         which writes those
 //
+// With a reader of the packed index as the index (gtamd_locali_set_index_pckidx,
+// include/gtamd_pcklocali.h) there is no step 0, a job is (query,
+// code of q letters), and steps b and d are k_lc_walk_pck: the same walk over
+// intervals of rows of the decoded form (esa_pckidx_dec.h), all children of a level
+// from one rank pair a letter, the column of each computed by the whole wave.
+//
 // Working memory: one entry per job, the cuts, and per wave of the grid a stack
-// and two columns.
+// and two columns (three with a packed index).
+#include <type_traits>
 #include "esa_common.h"
 #include "esa_jobs.h"
 #include "esa_locali_core.h"
+#include "esa_pckidx.h"
+#include "esa_pckidx_dec.h"
 #include "../../include/gtamd_locali.h"
+#include "../../include/gtamd_pcklocali.h"
 
 namespace {
 
@@ -38,7 +48,7 @@ constexpr u32 LC_CUT_LIST = 1u << 18;              // ... so a suffix table has 
 constexpr u64 LC_TARGET_JOBS = 1u << 14;           // q is the smallest depth that gives as many jobs
 constexpr u32 NO_LEVEL = 0xffffffffu;
 
-enum { W_OTHER = W_WALK_WORDS, W_BAD, W_LONGEST, W_CUTS, W_WORDS };
+enum { W_OTHER = W_WALK_WORDS, W_BAD, W_LONGEST, W_CUTS, W_ERROR, W_WORDS };
 enum { BAD_LENGTH = 1, BAD_SCORE = 2, BAD_SYMBOL = 3 };
 
 struct LcRecord { u64 query, dbstart, lenscore, qspan; };
@@ -172,6 +182,222 @@ __global__ __launch_bounds__(LC_THREADS) void k_lc_walk(LcInput<S> in, u64 j0, u
     lc_job<S, EMIT>(in, j, stack, cola, colb, cnt, off, w0, w1, out, w, lane);
 }
 
+// ---- the same walk over a packed index (include/gtamd_pcklocali.h) ----
+// A level is an interval [lo, end) of rows of the decoded form: the rows whose
+// suffixes, in the text of the index, begin with the letters taken so far, last
+// letter first.  In LcLevel, cur is the set of letters whose children are still
+// to be taken when the walk comes back to the level.  A job is (query, code of q
+// letters): it walks the path of its code first, then the interval it reaches.
+struct LcPkInput {
+  PkxDec d;
+  const u8 *queries; const u64 *qoff;
+  u32 groups, q;                                   // sigma ^ q codes of q letters, the first letter the highest digit
+  LcScores sc; u32 T;
+  u32 stack_words, col_words;                      // of one wave: its stack, then three columns of col_words
+};
+
+// dbstart of the match of `len` letters found at `row`: the suffix of the row
+// begins with them, last letter first (gen_pck_overinterval, pck_overcontext)
+__device__ __forceinline__ u64 lc_pck_dbstart(const PkxDec &d, u32 row, u32 len, u32 *err) {
+  const u64 end = dec_locate(d, row, err) + len;
+  if (end > d.N - 1) { dev_fail(err, PKX_E_WALK); return 0; }
+  return d.N - 1 - end;
+}
+
+// all rows [clo, chi) of a child whose column reached T after dblen letters: counted,
+// and in emit located 64 at a time, those in front of the window skipped by arithmetic
+template <bool EMIT>
+__device__ __forceinline__ void lc_pck_rows(const PkxDec &d, JobWindow<LcRecord> &wk, u64 query, u32 clo, u32 chi,
+                                            u32 dblen, const LcColumn &col, u32 lane, u32 *err) {
+  if (!EMIT) { wk.k += chi - clo; return; }
+  u32 b = clo;
+  if (wk.k < wk.first) {
+    const u64 skip = wk.first - wk.k < chi - clo ? wk.first - wk.k : chi - clo;
+    b += (u32) skip;
+    wk.k += skip;
+  }
+  for (; b < chi; b += LC_BATCH) {
+    if (wk.full()) break;
+    const u32 row = b + lane;                         // (chi <= N <= 2^32 - 4096: no wrap)
+    const u64 place = wk.k + lane;
+    u64 p = 0;
+    if (row < chi && place >= wk.first && place < wk.stop) p = lc_pck_dbstart(d, row, dblen, err);
+    wk.give<EMIT>(row < chi, lc_record(query, p, dblen, col.M, col.e, col.qstart));
+  }
+}
+
+// Row `row` < N, reached by the letter s from a row whose `depth` letters gave the
+// column `cur` in src (depth 0: none yet), goes on alone (lc_walk with the text
+// read replaced): the next letter is the BWT symbol of the row, the next row its
+// LF, both asked for before the column of s is computed.  A special ends it; so
+// does the row of suffix 0, whose symbol is one, and lc_max_depth.  *at = the row
+// the match was found at.  a and b: two buffers of m cells each, neither of them
+// src.  The whole wave calls this with the same arguments.
+__device__ __forceinline__ LcMatch lc_walk_pck(const PkxDec &d, const u32 *count, u32 sigma, const u32 *src,
+                                               LcColumn cur, u32 depth, u32 s, u32 row, const u8 *q, u32 m,
+                                               LcScores sc, u32 T, u32 *a, u32 *b, u32 *at, u32 *err) {
+  const u32 deepest = lc_max_depth(m, sc);
+  while (depth < deepest) {
+    const u32 s2 = uni(dec_symbol(d, row));
+    u64 next = d.N;
+    if (s2 < sigma) next = (u64) count[s2] + uni(dec_rank(d, s2, row));
+    const bool first = depth == 0;
+    const LcColumn col = lc_column(src, cur.lo, cur.hi, first, s, q, m, sc, a);
+    depth += 1;
+    if (col.M >= T) { *at = row; return LcMatch{ depth, col.M, col.e, col.qstart }; }
+    if (col.M == 0 || s2 >= sigma) break;
+    if (next >= d.N) { dev_fail(err, PKX_E_WALK); break; }
+    src = a + lc_band_offset(col, first, cur.lo);
+    cur = col;
+    u32 *t = a; a = b; b = t;
+    s = s2;
+    row = (u32) next;
+  }
+  return LcMatch{ 0, 0, 0, 0 };
+}
+
+// the record of a row that went on alone, if it has one: lane 0 locates it, in emit
+// and where it falls into the window
+template <bool EMIT>
+__device__ __forceinline__ void lc_pck_one(const PkxDec &d, JobWindow<LcRecord> &wk, u64 query, const LcMatch &hit,
+                                           u32 at, u32 lane, u32 *err) {
+  u64 p = 0;
+  if (EMIT && lane == 0 && hit.dblen != 0 && wk.k >= wk.first && wk.k < wk.stop) p = lc_pck_dbstart(d, at, hit.dblen, err);
+  wk.give<EMIT>(lane == 0 && hit.dblen != 0, lc_record(query, p, hit.dblen, hit.score, hit.e, hit.qstart));
+}
+
+// One job.  The columns of the path of the code go in turn to the third column
+// of the wave and to its first, the last of them to the third, where it stays as
+// the band of the root of the walk; the stack is that of lc_job, with the root's
+// header at 0, and the first two columns are those of the rows that go on alone.
+template <bool EMIT>
+__device__ void lc_job_pck(const LcPkInput &in, const u32 *count, u32 sigma, u64 j, u32 *stack, u32 *cnt,
+                           const u64 *off, u64 w0, u64 w1, LcRecord *out, u64 *w, u32 lane) {
+  const PkxDec &d = in.d;
+  u32 *err = reinterpret_cast<u32 *>(&w[W_ERROR]);
+  const u64 query = j / in.groups;
+  u32 code = (u32) (j % in.groups);
+  JobWindow<LcRecord> wk = { 0, 0, 0, nullptr };
+  if (EMIT && !wk.open(off, j, w0, w1, out)) return;
+  const u64 q0 = in.qoff[query];
+  const u32 m = (u32) (in.qoff[query + 1] - q0);          // 1 .. LC_MAX_QUERY (k_lc_validate)
+  const u8 *q = in.queries + q0;
+  const u32 deepest = lc_max_depth(m, in.sc);
+  u32 *cola = stack + in.stack_words, *colb = cola + in.col_words, *colr = colb + in.col_words;
+  const u32 all = sigma >= 32 ? ~0u : (1u << sigma) - 1u;
+  u32 pushed = 0, children = 0, walks = 0;
+  bool other = false;
+
+  // the path of the code: one letter, one rank pair and one column a depth
+  u32 lo = 0, hi = (u32) d.N, depth = 0, div = in.groups;
+  LcColumn band = { 0, 0, 0, 0, 0 };
+  const u32 *src = colr;
+  bool live = true;
+  for (u32 i = 0; i < in.q && live; i++) {
+    div /= sigma;
+    const u32 c = code / div;                           // (code < div * sigma: a letter)
+    code -= c * div;                                    // the letters behind this one
+    live = false;
+    if (depth >= deepest) break;                        // (cannot be: a column that deep has no cell > 0)
+    u32 ra, rb;
+    dec_rank_pair(d, c, lo, hi, &ra, &rb);
+    const u64 l = (u64) count[c] + uni(ra), h = (u64) count[c] + uni(rb);
+    if (l > h || h > d.N) { dev_fail(err, PKX_E_WALK); break; }
+    if (l == h) break;
+    children += 1;
+    u32 *dst = ((in.q - 1 - i) & 1u) ? cola : colr;
+    const bool first = depth == 0;
+    const LcColumn col = lc_column(src, band.lo, band.hi, first, c, q, m, in.sc, dst);
+    lo = (u32) l; hi = (u32) h; depth += 1;
+    if (col.M >= in.T) {
+      // every job whose code begins with these letters finds this; the one whose other letters are 0 gives it
+      if (code == 0) lc_pck_rows<EMIT>(d, wk, query, lo, hi, depth, col, lane, err);
+      break;
+    }
+    if (col.M == 0) break;
+    src = dst + lc_band_offset(col, first, band.lo);
+    band = col;
+    live = true;
+  }
+
+  // (a root of one row needs nothing of its own: the children step gives the one child its LF leads to)
+  LcLevel L = { lo, hi, all, band.lo, band.hi, (u32) (src - stack), NO_LEVEL, depth };
+  u32 at = 0, free = LC_HEADER;
+  // Every round expands the top level for the letters left in it, which are fewer
+  // each time, and ends with a push to the next depth, which is at most `deepest`,
+  // or with a pop: the walk ends.
+  while (live) {
+    if (EMIT && wk.full()) break;
+    u32 my_lo = 0, my_hi = 0;
+    bool nonempty = false;
+    if (L.cur != 0 && L.depth < deepest)
+      nonempty = dec_children(d, count, L.lo, L.end, LC_LETTERS, L.cur, lane, &my_lo, &my_hi, err);
+    u32 work = (u32) __ballot(nonempty);                   // (letters are lanes 0 .. 31)
+    if (L.cur == all) children += (u32) __popc(work);
+    const bool first = L.depth == 0;
+    const LcColumn above = { L.blo, L.bhi, 0, 0, 0 };
+    bool down = false;
+    while (work && !(EMIT && wk.full())) {
+      const u32 c = uni((u32) __builtin_ctz(work));
+      work &= work - 1;
+      const u32 clo = __builtin_amdgcn_readlane(my_lo, c), chi = __builtin_amdgcn_readlane(my_hi, c);
+      const bool room = (u64) free + LC_HEADER + m <= in.stack_words;
+      if (chi - clo == 1 || !room) {
+        // alone, one row after the other, in the two columns of the wave
+        if (chi - clo > 1) other = true;
+        for (u32 row = clo; row < chi; row++) {
+          if (EMIT && wk.full()) break;
+          u32 found = 0;
+          const LcMatch hit = lc_walk_pck(d, count, sigma, stack + L.cells, above, L.depth, c, row, q, m, in.sc, in.T, cola, colb, &found, err);
+          lc_pck_one<EMIT>(d, wk, query, hit, found, lane, err);
+        }
+        walks += chi - clo;
+        continue;
+      }
+      u32 *dst = stack + free + LC_HEADER;
+      const LcColumn col = lc_column(stack + L.cells, L.blo, L.bhi, first, c, q, m, in.sc, dst);
+      if (col.M >= in.T) {
+        lc_pck_rows<EMIT>(d, wk, query, clo, chi, L.depth + 1, col, lane, err);
+        continue;
+      }
+      if (col.M == 0) continue;
+      L.cur = work;
+      lc_store(stack, at, L, lane);
+      const u32 cells = free + LC_HEADER + lc_band_offset(col, first, L.blo);
+      L = LcLevel{ clo, chi, all, col.lo, col.hi, cells, at, L.depth + 1 };
+      at = free;
+      free = cells + (col.hi - col.lo);
+      pushed += 1;
+      down = true;
+      break;
+    }
+    if (down) continue;
+    if (L.below == NO_LEVEL) break;
+    free = at;
+    at = L.below;
+    L = lc_load(stack, at);
+  }
+  if (!EMIT && lane == 0) {
+    report(w, cnt, j, wk.k, pushed, children, walks);
+    if (other) atomicAdd((unsigned long long *) &w[W_OTHER], 1ull);
+  }
+}
+
+// k_lc_walk for a packed index: the same counts, windows and records
+template <bool EMIT>
+__global__ __launch_bounds__(LC_THREADS) void k_lc_walk_pck(LcPkInput in, u64 j0, u64 j1, u32 *cnt, const u64 *off, u64 w0,
+                                                            u64 w1, LcRecord *out, u32 *arena, u64 *w) {
+  __shared__ u32 s_count[LC_WAVES][LC_LETTERS + 1];
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u64 slot = (u64) blockIdx.x * LC_WAVES + wave, slots = (u64) gridDim.x * LC_WAVES;
+  u32 *stack = arena + slot * ((u64) in.stack_words + 3ull * in.col_words);
+  u32 *count = s_count[wave];
+  const u32 sigma = in.d.sigma < LC_LETTERS ? in.d.sigma : LC_LETTERS;
+  for (u32 c = 0; c <= sigma; c++) count[c] = in.d.count[c];       // (every lane the same word)
+  for (u64 j = j0 + slot; j < j1; j += slots)          // (the whole wave: the waves of a workgroup never wait for each other)
+    lc_job_pck<EMIT>(in, count, sigma, j, stack, cnt, off, w0, w1, out, w, lane);
+}
+
 // w[W_BAD] = the smallest (query << 2 | what is wrong with it); w[W_LONGEST]
 __global__ __launch_bounds__(LC_THREADS) void k_lc_validate(const u8 *queries, const u64 *qoff, u64 Q, u32 match,
                                                             u32 sigma, u64 *w) {
@@ -213,6 +439,8 @@ __global__ __launch_bounds__(LC_THREADS) void k_lc_cuts(IvText<S> text, u32 N, u
 
 struct gtamd_locali : ConsumerBase<> {
   ResidentIndex index;
+  const gtamd_pckidx *pck = nullptr;     // the index is a reader of the packed index
+  u64 pck_opens = 0;                     // ... and the image of it that the last prepare counted
   u32 sigma = 0, cut_max = 0, compute_units = 0;
   std::vector<u64> cuts;          // of the index, ascending table index: i | depth << 32
   u32 forced_stack = 0, forced_cut = GTAMD_LOCALI_AUTO;
@@ -221,7 +449,7 @@ struct gtamd_locali : ConsumerBase<> {
   SequenceSet queries;
   u64 Q = 0, jobs = 0;
   LcScores sc = { 1, -1, 1 };
-  u32 T = 1, groups = 0, stack_words = 0, col_words = 0, blocks = 0;
+  u32 T = 1, groups = 0, q = 0, stack_words = 0, col_words = 0, blocks = 0;
   JobOffsets jo;
   Dev<u32> gstart, arena;
   Dev<u64> cutlist;
@@ -253,6 +481,40 @@ template <typename S> int find_cuts(gtamd_locali *lc) {
   return 0;
 }
 
+// the letters and the largest depth q may take: at most 2^16 groups
+void set_alphabet(gtamd_locali *lc, u32 sigma) {
+  lc->sigma = sigma;
+  lc->cut_max = 1;
+  for (u64 groups = sigma; sigma > 1 && groups * sigma <= LC_CUT_GROUPS; groups *= sigma) lc->cut_max += 1;
+}
+
+// the reader that is the index must still hold the image it held when it was set
+int refuse_lost_reader(const gtamd_locali *lc) {
+  if (pckidx_is_open(lc->pck)) return 0;
+  gtamd_set_error("local alignments: the packed index reader that is the index has no image open any more "
+                  "(its last gtamd_pckidx_open_* failed)");
+  return -1;
+}
+
+// what an image must be like to be the index
+int refuse_image(const PkxDec &d) {
+  if (d.sigma == 0 || d.sigma > LC_LETTERS) {
+    gtamd_set_error("local alignments: an alphabet of %u letters, 1 to %u expected", d.sigma, LC_LETTERS);
+    return -1;
+  }
+  if (d.N == 0) { gtamd_set_error("local alignments: a packed index without a row"); return -1; }
+  return refuse_sizes(FEATURE, d.N - 1, 0);               // rows <= 2^32 - 4096
+}
+
+// emit gives the records of the image that prepare counted: a reader opened
+// again since then holds another one, and the places of the jobs are not its
+int refuse_other_image(const gtamd_locali *lc) {
+  if (pckidx_opens(lc->pck) == lc->pck_opens) return 0;
+  gtamd_set_error("local alignments: the packed index reader was opened again since gtamd_locali_prepare: what "
+                  "was prepared is of the image before (prepare again)");
+  return -1;
+}
+
 // every way of setting an index: what is refused, before anything is touched
 int set_index(gtamd_locali *lc, const IndexView &v, u32 sigma, bool from_host) {
   if (lc == nullptr || v.suf == nullptr || (v.enc == nullptr && v.n)) {
@@ -267,9 +529,8 @@ int set_index(gtamd_locali *lc, const IndexView &v, u32 sigma, bool from_host) {
   }
   HIP_TRY(hipSetDevice(lc->device));
   lc->prepared = false;
-  lc->sigma = sigma;
-  lc->cut_max = 1;
-  for (u64 groups = sigma; sigma > 1 && groups * sigma <= LC_CUT_GROUPS; groups *= sigma) lc->cut_max += 1;
+  lc->pck = nullptr;
+  set_alphabet(lc, sigma);
   if (from_host) TRY(lc->index.upload_from_host(FEATURE, v));
   else lc->index.borrow(v);
   const int rc = v.suf_bytes == 4 ? find_cuts<u32>(lc) : find_cuts<u64>(lc);
@@ -278,13 +539,18 @@ int set_index(gtamd_locali *lc, const IndexView &v, u32 sigma, bool from_host) {
 }
 
 u64 held_bytes(const gtamd_locali *lc) {
-  return lc->index.bytes() + lc->queries.bytes() + lc->jo.bytes() + lc->gstart.bytes + lc->arena.bytes +
+  return lc->index.bytes() + (lc->pck != nullptr ? pckidx_decoded_bytes(lc->pck) : 0) + lc->queries.bytes() + lc->jo.bytes() + lc->gstart.bytes + lc->arena.bytes +
          lc->cutlist.bytes + lc->words.bytes + lc->out.bytes;
 }
 
 template <typename S> LcInput<S> input(const gtamd_locali *lc) {
   return LcInput<S>{ { lc->index.enc, lc->index.n, (const S *) lc->index.suf }, (u32) (lc->index.n + 1),
                      lc->queries.sym, lc->queries.off, lc->gstart, lc->groups, lc->sc, lc->T, lc->stack_words, lc->col_words };
+}
+
+LcPkInput input_pck(const gtamd_locali *lc) {
+  return LcPkInput{ pckidx_dec(lc->pck), lc->queries.sym, lc->queries.off, lc->groups, lc->q, lc->sc, lc->T,
+                    lc->stack_words, lc->col_words };
 }
 
 // the message for what k_lc_validate found
@@ -337,11 +603,31 @@ int set_groups(gtamd_locali *lc, u64 Q) {
   return 0;
 }
 
+// the codes of this prepare with a packed index: every string of q letters
+void set_codes(gtamd_locali *lc, u64 Q) {
+  u32 q = lc->forced_cut;
+  u64 codes = 1;
+  if (q == GTAMD_LOCALI_AUTO) {
+    q = 0;
+    while (q < lc->cut_max && Q * codes < LC_TARGET_JOBS) { q += 1; codes *= lc->sigma; }
+  } else {
+    if (q > lc->cut_max) q = lc->cut_max;
+    for (u32 d = 0; d < q; d++) codes *= lc->sigma;
+  }
+  lc->q = q;
+  lc->groups = (u32) codes;                          // (at most LC_CUT_GROUPS)
+  lc->info.cut_depth = q;
+  lc->info.groups = lc->groups;
+}
+
+// S: the entries of .suf; void: the index is a reader of the packed index
 template <typename S> int prepare(gtamd_locali *lc) {
+  constexpr bool PCK = std::is_void<S>::value;
   hipStream_t st = lc->st;
   const u64 Q = lc->Q;
   HIP_TRY(hipMemsetAsync(lc->words, 0, W_CUTS * sizeof(u64), st));
   HIP_TRY(hipMemsetAsync(lc->words + W_BAD, 0xff, sizeof(u64), st));
+  HIP_TRY(hipMemsetAsync(lc->words + W_ERROR, 0, sizeof(u64), st));
   HIP_TRY(hipEventRecord(lc->ev[0], st));
   k_lc_validate<<<(u32) div_up(Q, LC_THREADS), LC_THREADS, 0, st>>>(lc->queries.sym, lc->queries.off, Q, (u32) lc->sc.match,
                                                                    lc->sigma, lc->words);
@@ -349,7 +635,8 @@ template <typename S> int prepare(gtamd_locali *lc) {
   u64 found[2] = { 0, 0 };
   TRY(fetch(st, { { lc->words + W_BAD, found, sizeof found } }));
   if (found[0] != ~0ull) return refuse_query(lc, found[0]);
-  TRY(set_groups(lc, Q));
+  if constexpr (PCK) set_codes(lc, Q);
+  else TRY(set_groups(lc, Q));
   const u64 jobs = Q * lc->groups;
   if (jobs > LC_MAX_JOBS) {
     gtamd_set_error("local alignments: %llu queries times %u groups of the table are more than %llu jobs",
@@ -359,26 +646,32 @@ template <typename S> int prepare(gtamd_locali *lc) {
   lc->jobs = jobs;
   lc->info.jobs = jobs;
   if (lc->jo.grow(jobs) != hipSuccess) return out_of_memory(FEATURE, jobs, "jobs");
-  // per wave of the grid: the stack, and two columns of the longest query for the suffixes that go on alone
+  // per wave of the grid: the stack, and two columns of the longest query for the suffixes that go on alone;
+  // with a packed index a third, for the column the path of a code ends with
   const u32 longest = (u32) found[1];
   lc->col_words = (longest + 63) / 64 * 64;
   lc->stack_words = lc->forced_stack ? lc->forced_stack : 32 * lc->col_words + 4096;
   const u64 most = (u64) lc->compute_units * LC_WAVES_PER_CU / LC_WAVES;
   lc->blocks = (u32) std::min<u64>(div_up(jobs, LC_WAVES), most ? most : 1);
-  const u64 words = (u64) lc->blocks * LC_WAVES * ((u64) lc->stack_words + 2ull * lc->col_words);
+  const u64 words = (u64) lc->blocks * LC_WAVES * ((u64) lc->stack_words + (PCK ? 3ull : 2ull) * lc->col_words);
   if (lc->arena.grow(words * 4) != hipSuccess) {
     gtamd_set_error("local alignments: cannot allocate %llu bytes of device memory for the columns of %u waves "
                     "(%u words of stack each; gtamd_locali_set_limits)", (unsigned long long) (words * 4),
                     lc->blocks * LC_WAVES, lc->stack_words);
     return -1;
   }
-  k_lc_walk<S, false><<<lc->blocks, LC_THREADS, 0, st>>>(input<S>(lc), 0, jobs, lc->jo.cnt, nullptr, 0, 0, nullptr,
-                                                        lc->arena, lc->words);
+  if constexpr (PCK)
+    k_lc_walk_pck<false><<<lc->blocks, LC_THREADS, 0, st>>>(input_pck(lc), 0, jobs, lc->jo.cnt, nullptr, 0, 0, nullptr,
+                                                           lc->arena, lc->words);
+  else
+    k_lc_walk<S, false><<<lc->blocks, LC_THREADS, 0, st>>>(input<S>(lc), 0, jobs, lc->jo.cnt, nullptr, 0, 0, nullptr,
+                                                          lc->arena, lc->words);
   HIP_TRY(hipGetLastError());
   TRY(lc->jo.scan(jobs, lc->words + W_MATCHES, st));
   HIP_TRY(hipEventRecord(lc->ev[1], st));
   u64 h[W_WORDS];
   TRY(fetch(st, { { lc->words, h, sizeof h }, lc->jo.fetch(jobs) }));
+  if (PCK && h[W_ERROR]) { pckidx_set_search_error(h[W_ERROR]); return -1; }
   HIP_TRY(hipEventElapsedTime(&lc->info.device_ms, lc->ev[0], lc->ev[1]));
   lc->info.matches = h[W_MATCHES];
   lc->info.max_matches_of_one_job = h[W_MAXJOB];
@@ -393,6 +686,15 @@ template <typename S> int prepare(gtamd_locali *lc) {
 int emit(gtamd_locali *lc, u64 *cursor, gtamd_locali_record *out, u64 capacity, int out_on_device, u64 *written) {
   *written = 0;
   const u64 total = lc->info.matches, cur = *cursor;
+  if (lc->pck != nullptr) {
+    TRY(refuse_lost_reader(lc));
+    TRY(refuse_other_image(lc));
+    if (!pckidx_can_locate(lc->pck)) {
+      gtamd_set_error("local alignments: the packed index holds no locate information (locate interval 0): "
+                      "positions cannot be had from it, only the counts of gtamd_locali_prepare");
+      return -1;
+    }
+  }
   TRY(refuse_window(FEATURE, "records", cur, total, capacity, LC_MIN_CAPACITY));
   if (cur == total) return 0;
   const u64 w1 = capacity < total - cur ? cur + capacity : total;
@@ -401,7 +703,11 @@ int emit(gtamd_locali *lc, u64 *cursor, gtamd_locali_record *out, u64 capacity, 
   RecordStage<LcRecord> stage(out, out_on_device);
   if (stage.begin(lc->out, w1 - cur) != hipSuccess) return out_of_memory(FEATURE, w1 - cur, "records");
   const u32 blocks = (u32) std::min<u64>(div_up(j1 - j0, LC_WAVES), lc->blocks);      // (the arena has room for lc->blocks)
-  if (lc->index.suf_bytes == 4)
+  if (lc->pck != nullptr) {
+    HIP_TRY(hipMemsetAsync(lc->words + W_ERROR, 0, sizeof(u64), lc->st));
+    k_lc_walk_pck<true><<<blocks, LC_THREADS, 0, lc->st>>>(input_pck(lc), j0, j1, nullptr, lc->jo.off, cur, w1, stage.dst,
+                                                          lc->arena, lc->words);
+  } else if (lc->index.suf_bytes == 4)
     k_lc_walk<u32, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u32>(lc), j0, j1, nullptr, lc->jo.off, cur, w1,
                                                              stage.dst, lc->arena, lc->words);
   else
@@ -409,6 +715,11 @@ int emit(gtamd_locali *lc, u64 *cursor, gtamd_locali_record *out, u64 capacity, 
                                                              stage.dst, lc->arena, lc->words);
   HIP_TRY(hipGetLastError());
   TRY(stage.finish(w1 - cur, lc->st));
+  if (lc->pck != nullptr) {
+    u64 error = 0;
+    TRY(fetch(lc->st, { { lc->words + W_ERROR, &error, sizeof error } }));
+    if (error) { pckidx_set_search_error(error); return -1; }
+  }
   lc->info.emitted += w1 - cur;
   *cursor = w1;
   *written = w1 - cur;
@@ -466,6 +777,27 @@ extern "C" int gtamd_locali_set_index_esa(gtamd_locali *lc, const gtamd_esa_ctx 
   GTAMD_ABI_END(-1)
 }
 
+extern "C" int gtamd_locali_set_index_pckidx(gtamd_locali *lc, const gtamd_pckidx *px) {
+  GTAMD_ABI_BEGIN
+  if (lc == nullptr || px == nullptr) { gtamd_set_error("invalid argument to gtamd_locali_set_index_pckidx"); return -1; }
+  if (!pckidx_is_open(px)) { gtamd_set_error("local alignments: the packed index reader has no image open"); return -1; }
+  if (pckidx_device(px) != lc->device) {
+    gtamd_set_error("local alignments: the packed index lives on device %d, the aligner on %d", pckidx_device(px),
+                    lc->device);
+    return -1;
+  }
+  const PkxDec &d = pckidx_dec(px);
+  TRY(refuse_image(d));
+  HIP_TRY(hipSetDevice(lc->device));
+  lc->prepared = false;
+  lc->index.drop();
+  lc->cuts.clear();
+  lc->pck = px;
+  set_alphabet(lc, d.sigma);
+  return 0;
+  GTAMD_ABI_END(-1)
+}
+
 extern "C" int gtamd_locali_set_limits(gtamd_locali *lc, uint32_t stack_words, uint32_t cut_depth) {
   GTAMD_ABI_BEGIN
   if (lc == nullptr) { gtamd_set_error("invalid argument to gtamd_locali_set_limits"); return -1; }
@@ -493,9 +825,14 @@ extern "C" int gtamd_locali_prepare(gtamd_locali *lc, const uint8_t *queries, co
     gtamd_set_error("invalid argument to gtamd_locali_prepare");
     return -1;
   }
-  if (!lc->index.set) {
+  if (!lc->index.set && lc->pck == nullptr) {
     gtamd_set_error("local alignments: no index is set (gtamd_locali_set_index)");
     return -1;
+  }
+  if (lc->pck != nullptr) {
+    // the reader may hold another image than when it was set: this prepare is of the one it holds now
+    TRY(refuse_lost_reader(lc));
+    TRY(refuse_image(pckidx_dec(lc->pck)));
   }
   if (match <= 0 || mismatch >= 0 || gapextend >= 0 || match > LC_MAX_WEIGHT || mismatch < -LC_MAX_WEIGHT ||
       gapextend < -LC_MAX_WEIGHT) {
@@ -515,6 +852,10 @@ extern "C" int gtamd_locali_prepare(gtamd_locali *lc, const uint8_t *queries, co
   }
   HIP_TRY(hipSetDevice(lc->device));
   lc->prepared = false;
+  if (lc->pck != nullptr) {
+    set_alphabet(lc, pckidx_dec(lc->pck).sigma);
+    lc->pck_opens = pckidx_opens(lc->pck);
+  }
   lc->info = gtamd_locali_info();
   lc->Q = Q;
   lc->jobs = 0;
@@ -523,7 +864,7 @@ extern "C" int gtamd_locali_prepare(gtamd_locali *lc, const uint8_t *queries, co
   lc->jo.off_host.assign(1, 0);
   if (Q != 0) {
     TRY(lc->queries.set(FEATURE, "query symbols", queries, offsets, Q, is_device, lc->st));
-    TRY(lc->index.suf_bytes == 4 ? prepare<u32>(lc) : prepare<u64>(lc));
+    TRY(lc->pck != nullptr ? prepare<void>(lc) : lc->index.suf_bytes == 4 ? prepare<u32>(lc) : prepare<u64>(lc));
   }
   lc->info.device_bytes = held_bytes(lc);
   lc->prepared = true;

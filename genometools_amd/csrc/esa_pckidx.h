@@ -10,6 +10,8 @@ struct gtamd_pckidx;
 // device of the reader, does it hold an open image, can it locate
 int pckidx_device(const gtamd_pckidx *px);
 bool pckidx_is_open(const gtamd_pckidx *px);
+// the open calls of the reader so far, failed ones included: two values that differ are two images
+u64 pckidx_opens(const gtamd_pckidx *px);
 bool pckidx_can_locate(const gtamd_pckidx *px);
 u64 pckidx_decoded_bytes(const gtamd_pckidx *px);
 

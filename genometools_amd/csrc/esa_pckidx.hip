@@ -202,6 +202,7 @@ struct gtamd_pckidx : ConsumerBase<> {
   PkxGeom g = PkxGeom();
   PkxDec d = PkxDec();
   bool open = false;
+  u64 opens = 0;                // open calls so far: which image a consumer saw
   Dev<u8> image;               // a host image on its way through the decode
   Dev<u8> comp_tab; u32 tab_sigma = 0, tab_B = 0;
   Dev<u32> rows, aux, count, mkpre, mkpos, sprank, rg_start, rg_pre, totals, ws;
@@ -251,6 +252,7 @@ int open_image(gtamd_pckidx *px, const u8 *host, const u8 *dev, u64 bytes) {
   // (a searcher may still point here: whatever happens below, it finds no image
   // and no pointer of the one before)
   px->open = false;
+  px->opens += 1;
   px->d = PkxDec();
   px->g = PkxGeom();
   HIP_TRY(hipSetDevice(px->device));
@@ -414,6 +416,7 @@ int finish(gtamd_pckidx *px, const Staged &s, void *out, u64 out_bytes, int is_d
 
 int pckidx_device(const gtamd_pckidx *px) { return px->device; }
 bool pckidx_is_open(const gtamd_pckidx *px) { return px->open; }
+u64 pckidx_opens(const gtamd_pckidx *px) { return px->opens; }
 bool pckidx_can_locate(const gtamd_pckidx *px) { return px->g.locint != 0; }
 u64 pckidx_decoded_bytes(const gtamd_pckidx *px) { return px->info.decoded_bytes; }
 const PkxDec &pckidx_dec(const gtamd_pckidx *px) { return px->d; }

@@ -123,6 +123,28 @@ __device__ __forceinline__ void dec_rank_pair(const PkxDec &d, u32 s, u64 lo, u6
   }
   *a = ca; *b = cb;
 }
+// The rank part of the children step of a walk over intervals of rows, one letter
+// a lane: lane c of `todo`, c < sigma and c < letters, gets the rows [*clo, *chi)
+// of the child of letter c of the interval [lo, hi) -- one rank pair, all lanes in
+// the same one or two lines.  True where the child is not empty; an empty child,
+// and every other lane, has *clo == *chi.  count: count[] of the index.  Bounds
+// that are none (the decoded form is inconsistent) leave the error word and an
+// empty child.
+__device__ __forceinline__ bool dec_children(const PkxDec &d, const u32 *count, u32 lo, u32 hi, u32 letters, u32 todo,
+                                             u32 lane, u32 *clo, u32 *chi, u32 *err) {
+  *clo = *chi = 0;
+  if (lane < d.sigma && lane < letters && ((todo >> lane) & 1u)) {
+    u32 a, b;
+    dec_rank_pair(d, lane, lo, hi, &a, &b);
+    const u64 l = (u64) count[lane] + a, h = (u64) count[lane] + b;
+    if (l > h || h > d.N) dev_fail(err, PKX_E_WALK);
+    else if (l < h) {
+      *clo = (u32) l; *chi = (u32) h;
+      return true;
+    }
+  }
+  return false;
+}
 // BWT symbol of row < N: 0..sigma-1, 254, 255
 __device__ __forceinline__ u32 dec_symbol(const PkxDec &d, u64 row) {
   if (!d.two_bit) return d.sym[row];

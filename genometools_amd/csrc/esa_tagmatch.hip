@@ -201,18 +201,8 @@ __device__ __forceinline__ u32 lanes_before(u64 mask) {
 __device__ __forceinline__ void pk_children(const PkxDec &d, const u32 *count, const u64 *eq, u32 lo, u32 hi,
                                             const TmColumn &col, u32 K, u32 todo, u32 lane, u32 *clo, u32 *chi,
                                             TmColumn *ccol, u32 *err) {
-  *clo = *chi = 0;
   *ccol = col;
-  if (lane < d.sigma && lane < TM_LETTERS && ((todo >> lane) & 1u)) {
-    u32 a, b;
-    dec_rank_pair(d, lane, lo, hi, &a, &b);
-    const u64 l = (u64) count[lane] + a, h = (u64) count[lane] + b;
-    if (l > h || h > d.N) dev_fail(err, PKX_E_WALK);
-    else if (l < h) {
-      *clo = (u32) l; *chi = (u32) h;
-      tm_step(*ccol, eq[lane], K);
-    }
-  }
+  if (dec_children(d, count, lo, hi, TM_LETTERS, todo, lane, clo, chi, err)) tm_step(*ccol, eq[lane], K);
 }
 
 // Row `row`, whose `depth` letters gave column c (alive, no success yet), goes on

@@ -9,7 +9,8 @@ once and counts its matches, `LocalAlignments.records()` yields the records
 (query, dbstart, dblen | score << 32, qstart | qlen << 32) in the order of
 include/gtamd_locali.h -- query, table index -- in pieces, so that a result
 larger than memory is streamed.  The index is the encoded sequence with its
-.suf table: in host memory, in device memory or resident in an `EsaEngine`.
+.suf table: in host memory, in device memory or resident in an `EsaEngine`; or
+a `pck.PackedIndexReader` (`gt dev idxlocali -pck`, include/gtamd_pcklocali.h).
 
 Everything here goes through genometools_amd/libgtamd_esa.so (HIP); there is
 no CPU implementation in this package.
@@ -75,6 +76,15 @@ class LocalAlignments(Consumer):
         (forward read mode); enc_device_ptr: the n symbols, on the device.  The
         engine must outlive the calls."""
         self._call("set_index_esa", engine._ctx, enc_device_ptr, n, numofchars)
+
+    def set_index_packed(self, reader):
+        """a `pck.PackedIndexReader` with an open image
+        (include/gtamd_pcklocali.h): the matches are those of the text the index
+        was built from read backwards -- an index of the reversed subject answers
+        for the subject -- in the order of that header, which inside one query
+        is not the order of the suffix table.  The reader must outlive the
+        calls."""
+        _lib.check(self._lib.gtamd_locali_set_index_pckidx(self._p, reader._p))
 
     def set_limits(self, stack_words=0, cut_depth=AUTO):
         """what the next prepare sizes itself by: the words of one wave's stack
