@@ -15,20 +15,22 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in
            ("esa_prims.hip", "esa_engine.hip", "esa_synth.hip", "esa_encode.hip",
             "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip",
             "esa_maxpairs.hip", "esa_qmatch.hip", "esa_spm.hip", "esa_tagmatch.hip",
-            "esa_locali.hip", "esa_pckidx.hip")]
+            "esa_locali.hip", "esa_pckidx.hip", "esa_spmred.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_index.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
                                                      "esa_jobs.h", "esa_ivwalk.h",
                                                      "esa_pck_replay.h", "esa_mstat_search.h",
                                                      "esa_maxpairs_walk.h", "esa_qmatch_core.h",
                                                      "esa_spm_core.h", "esa_tagmatch_core.h",
                                                      "esa_locali_core.h", "esa_pckidx_core.h",
-                                                     "esa_pckidx.h", "esa_pckidx_dec.h")] + \
+                                                     "esa_pckidx.h", "esa_pckidx_dec.h",
+                                                     "esa_spm_state.h", "esa_spmred_core.h")] + \
           [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
                                                        "gtamd_check.h", "gtamd_mstat.h",
                                                        "gtamd_maxpairs.h", "gtamd_qmatch.h",
                                                        "gtamd_spm.h", "gtamd_tagmatch.h",
                                                        "gtamd_locali.h", "gtamd_pckidx.h",
-                                                       "gtamd_pcktag.h", "gtamd_pcklocali.h")]
+                                                       "gtamd_pcktag.h", "gtamd_pcklocali.h",
+                                                       "gtamd_spmred.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -148,6 +150,15 @@ class SpmInfo(ctypes.Structure):         # gtamd_spm_info, include/gtamd_spm.h
     _fields_ = [(name, ctypes.c_uint64) for name in
                 ("table_entries", "terminal_suffixes", "read_starts", "matches", "max_width",
                  "max_matches_of_one_suffix", "search_symbols", "device_bytes")] + [("device_ms", ctypes.c_float)]
+
+
+class SpmredInfo(ctypes.Structure):      # gtamd_spmred_info, include/gtamd_spmred.h
+    _fields_ = [(name, ctypes.c_uint64) for name in
+                ("table_entries", "terminal_suffixes", "read_starts", "matches", "max_width",
+                 "max_matches_of_one_suffix", "search_symbols", "kept", "transitive_same_read",
+                 "transitive_other", "contained_sequences", "candidates_examined",
+                 "max_candidates_of_one_pair", "letters_compared", "device_bytes")] + \
+               [(name, ctypes.c_float) for name in ("device_ms", "spm_ms", "decide_ms")]
 
 
 class TagmatchInfo(ctypes.Structure):    # gtamd_tagmatch_info, include/gtamd_tagmatch.h
@@ -377,6 +388,19 @@ PCKLOCALI_ABI = {
     "gtamd_locali_set_index_pckidx": (_INT, [_P, _P]),
 }
 
+# every symbol include/gtamd_spmred.h declares
+SPMRED_ABI = {
+    "gtamd_spmred_create": (_P, [_INT]),
+    "gtamd_spmred_destroy": (None, [_P]),
+    "gtamd_spmred_geometry": (None, [ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "gtamd_spmred_set_index": (_INT, [_P, _P, _U64, _P, _U32, _P, _P, _U64]),
+    "gtamd_spmred_set_index_host": (_INT, [_P, _P, _U64, _P, _U32, _P, _P, _U64]),
+    "gtamd_spmred_set_index_esa": (_INT, [_P, _P, _P, _U64]),
+    "gtamd_spmred_prepare": (_INT, [_P, _U32, _U32, ctypes.POINTER(SpmredInfo)]),
+    "gtamd_spmred_emit": (_INT, [_P, ctypes.POINTER(_U64), _P, _U64, _INT, ctypes.POINTER(_U64)]),
+    "gtamd_spmred_get_info": (_INT, [_P, ctypes.POINTER(SpmredInfo)]),
+}
+
 _lib = None
 
 
@@ -402,7 +426,7 @@ def load():
         for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()) + \
                 list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()) + list(SPM_ABI.items()) + list(TAGMATCH_ABI.items()) + \
                 list(LOCALI_ABI.items()) + list(PCKIDX_ABI.items()) + list(PCKTAG_ABI.items()) + \
-                list(PCKLOCALI_ABI.items()):
+                list(PCKLOCALI_ABI.items()) + list(SPMRED_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -19,7 +19,7 @@
 #include "esa_prims.h"
 #include "esa_devutil.h"
 #include "esa_spm_core.h"
-#include "../../include/gtamd_spm.h"
+#include "esa_spm_state.h"
 
 namespace {
 
@@ -33,13 +33,6 @@ constexpr u64 SP_MAX_CHUNK = 1ull << 24;          // candidates of one launch: 6
 
 enum { K_TERMINAL = 0, K_START, K_SEPARATOR, K_KINDS };
 enum { W_MATCHES = 0, W_MAXWIDTH, W_MAXCOUNT, W_SEARCH, W_WORDS };
-
-// the three lists of steps 1 and 2
-struct SpLists {
-  u32 *idx, *len;        // terminal suffixes: table index, letters
-  u32 *starts;           // read starts: table index
-  u32 *seps;             // separators: position
-};
 
 // ---- steps 1 and 2 -------------------------------------------------------------
 // Item blockIdx.x * SP_SEL_TILE + e * SP_THREADS + threadIdx.x, e < SP_PER, is a
@@ -144,17 +137,6 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_emit(SpIndex<S> x, SpLists l,
 }
 
 }  // namespace
-
-struct gtamd_spm : ConsumerBase<> {
-  ResidentIndex index;
-  bool prepared = false;
-  // what a prepare leaves for the emit calls
-  Dev<u32> tiles, scanws, idx, len, starts, seps, first, cnt;
-  Dev<u64> tsum, off;
-  Dev<u8> out;                         // records on their way to host memory
-  u32 M = 0, R = 0, nseps = 0;
-  gtamd_spm_info info = gtamd_spm_info();
-};
 
 namespace {
 

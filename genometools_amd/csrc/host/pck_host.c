@@ -23,7 +23,8 @@
    And the one that needs no table on disk: `gt encseq2spm -l L -ii INDEX -spm
    show|count` (tool src/tools/gt_encseq2spm.c), all suffix-prefix matches of a
    read set on both strands; the engine builds .suf and .lcp of the mirrored
-   reads in this process and hands them to include/gtamd_spm.h. */
+   reads in this process and hands them to include/gtamd_spm.h.  Its consumer,
+   `gt readjoiner overlap`, the irreducible ones of them, is in rdj_host.c. */
 #include "host_internal.h"
 #include "gtamd_pck.h"
 #include "gtamd_check.h"
@@ -1230,3 +1231,8 @@ done:
    The same arrangement: it reads a project back with the helpers above and takes
    switch_option from tagmatch_host.c. */
 #include "locali_host.c"
+
+/* ---- gt readjoiner overlap ----
+   The same arrangement: it takes pfail from above and switch_option from
+   tagmatch_host.c. */
+#include "rdj_host.c"

@@ -7,6 +7,7 @@
    `gt-suffixerator-amd repfind ...` is `gt repfind ...`,
    `gt-suffixerator-amd querymatch ...` is `gt repfind ...` with -q, -r or -p,
    `gt-suffixerator-amd encseq2spm ...` is `gt encseq2spm ...`,
+   `gt-suffixerator-amd readjoiner overlap ...` is `gt readjoiner overlap ...`,
    `gt-suffixerator-amd tagerator ...` is `gt tagerator ...`,
    `gt-suffixerator-amd idxlocali ...` is `gt dev idxlocali ...` */
 #include <stdio.h>
@@ -55,6 +56,17 @@ int main(int argc, char **argv)
   if (argc > 1 && !strcmp(argv[1], "encseq2spm")) {
     if (gtamd_encseq2spm(argc - 1, (const char **) argv + 1, err, sizeof err) != 0) {
       fprintf(stderr, "gt encseq2spm: error: %s\n", err);
+      return 1;
+    }
+    return 0;
+  }
+  if (argc > 1 && !strcmp(argv[1], "readjoiner")) {
+    if (argc < 3 || strcmp(argv[2], "overlap")) {
+      fprintf(stderr, "gt readjoiner: error: tool overlap expected\n");
+      return 1;
+    }
+    if (gtamd_readjoiner_overlap(argc - 2, (const char **) argv + 2, err, sizeof err) != 0) {
+      fprintf(stderr, "gt readjoiner overlap: error: %s\n", err);
       return 1;
     }
     return 0;

@@ -26,6 +26,9 @@
     gtamd_encseq2spm        `gt encseq2spm -l L -ii INDEX -spm show|count`
                             (src/tools/gt_encseq2spm.c), on the device through
                             the engine and include/gtamd_spm.h
+    gtamd_readjoiner_overlap  `gt readjoiner overlap -readset X -l L`
+                            (src/tools/gt_readjoiner_overlap.c), on the device
+                            through the engine and include/gtamd_spmred.h
     gtamd_tagerator         `gt tagerator -e K -esa INDEX -q TAGS`
                             (src/tools/gt_tagerator.c), on the device through
                             include/gtamd_tagmatch.h
@@ -40,8 +43,10 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 #include "gtamd_esa.h"
 #include "gtamd_encode.h"
+#include "gtamd_spmred.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -416,6 +421,46 @@ int gtamd_querymatch(int argc, const char **argv, char *err, size_t errlen);
    Returns 0, or -1 with the message in err (the caller prints "gt encseq2spm:
    error: <err>" and exits 1). */
 int gtamd_encseq2spm(int argc, const char **argv, char *err, size_t errlen);
+
+/* `gt readjoiner overlap -readset X -l L [-elimtrans yes|no] [-showspm] [-q] [-v]`
+   (tool function src/tools/gt_readjoiner_overlap.c; the traversal it replaces:
+   src/match/rdj-spmfind.c): the irreducible suffix-prefix matches of at least L
+   letters of the reads of X, on both strands (definition, filter and order:
+   include/gtamd_spmred.h).  The sub-command `readjoiner overlap`.
+     -readset X  reads X.esq (+ .ssp) and no table, as encseq2spm does; a protein
+                 readset is refused with the reference's message
+     -l L        2 or more, as the reference's parser has it
+     -elimtrans  yes (default) or no: all matches, none tested
+     -showspm    the lines `sn +|- pn +|- len`, in TABLE ORDER; the reference
+                 prints the same lines in the order of its traversal.  Without it
+                 no line is written and the matches go to X.0.spm in the bin32
+                 list format (below), which `gt readjoiner assembly` opens
+     -q          no '#' lines;  -v  '#' lines of the tool's own (the reference's
+                 are the figures of its k-mer sort); the two exclude each other
+   Stdout is the reference's byte for byte, the match lines sorted: the two
+   opening '#' lines, the matches, then `number of irreducible suffix-prefix
+   matches`, `average irreducible SPM/read`, `number of transitive suffix-prefix
+   matches` (without reduction `number of suffix-prefix matches`, `average
+   SPM/read`).
+   A readset in which a read occurs whole at another place -- a duplicate, a
+   contained read, a read equal to its own reverse complement -- is refused with
+   their number and a pointer to `gt readjoiner prefilter`: there the reference's
+   result depends on its traversal.  -singlestrand is answered "not implemented"
+   (it aborts the reference).  -parts -memlimit -wmax -phase2extra -radixparts
+   -radixsmall -onlyallfirstcodes steer the reference's own sort and its w sets
+   and are refused ("option \"-X\" is not supported ...").
+   Returns 0, or -1 with the message in err (the caller prints "gt readjoiner
+   overlap: error: <err>" and exits 1). */
+int gtamd_readjoiner_overlap(int argc, const char **argv, char *err, size_t errlen);
+
+/* Readjoiner's bin32 list of matches (src/match/rdj-spmlist.c:45-124): one
+   header byte, then three uint32 a match in host byte order: suffix_read,
+   prefix_read, len << 2 | suffix_direct << 1 | prefix_direct.  A record that does
+   not fit (a read number of 2^32 or more, a length of 2^30 or more) is refused by
+   name: the bin64 format is not written.  0, or -1 (the second with a message). */
+int gtamd_spmlist_bin32_header(FILE *fp);
+int gtamd_spmlist_bin32_records(FILE *fp, const gtamd_spmred_record *rec, uint64_t count, char *err,
+                                size_t errlen);
 
 /* `gt tagerator -e K -esa INDEX -q FILE...` (tool function
    src/tools/gt_tagerator.c, gt_runtagerator src/match/tagerator.c:538-773): the
