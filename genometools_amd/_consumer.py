@@ -1,7 +1,9 @@
 """What the wrappers of the index consumers share (check.py, mstat.py,
-maxpairs.py, qmatch.py, spm.py): the life of the object behind the C ABI, its
-info struct as a dict, the checks of tables in host memory and the generator
-over the records of an enumeration."""
+maxpairs.py, qmatch.py, spm.py, spmred.py, tagmatch.py, locali.py, and the
+reader and the builder of pck.py): the life of the object behind the C ABI, its
+info struct as a dict, the checks of tables in host memory, the setters of an
+index of .suf with its alphabet, the sequences of a job walker, and the
+generator over the records of an enumeration with their gathering."""
 import ctypes
 
 import numpy as np
@@ -81,6 +83,46 @@ def host_tables(enc, suf, lcp=None, llv=None,
         raise ValueError("%d symbols need %d entries of suf and lcp (%d, %d given) and whole pairs of llv"
                          % (enc.size, enc.size + 1, suf.size, lcp.size))
     return enc, suf, lcp, llv
+
+
+class SufIndexSetters:
+    """the index of a Consumer that reads the sequence and .suf and is told the
+    letters of the alphabet (tagmatch.py, locali.py): each call replaces the
+    index before.  Their set_index_packed is their own: what a packed index
+    answers differs."""
+
+    def set_index(self, enc, suf, numofchars=4):
+        """tables in host memory (numpy): enc uint8, n symbols; suf uint32 or
+        uint64, n + 1 entries; numofchars: letters of the alphabet"""
+        enc, suf = host_tables(enc, suf)
+        self._call("set_index_host", ptr(enc), enc.size, ptr(suf), suf.dtype.itemsize, numofchars)
+
+    def set_index_device(self, enc_ptr, n, suf_ptr, suf_bytes, numofchars=4):
+        """the same for raw device pointers, which must outlive the calls"""
+        self._call("set_index", enc_ptr, n, suf_ptr, suf_bytes, numofchars)
+
+    def set_index_engine(self, engine, enc_device_ptr, n, numofchars=4):
+        """the .suf table an EsaEngine holds after run() with esa.WANT_SUF
+        (forward read mode); enc_device_ptr: the n symbols, on the device.  The
+        engine must outlive the calls."""
+        self._call("set_index_esa", engine._ctx, enc_device_ptr, n, numofchars)
+
+
+def pack_sequences(sequences):
+    """(symbols, offsets) of a list of encoded sequences (tags, queries): one
+    uint8 array and the len(sequences) + 1 uint64 offsets into it"""
+    sequences = [np.ascontiguousarray(s, dtype=np.uint8).reshape(-1) for s in sequences]
+    offsets = np.zeros(len(sequences) + 1, dtype=np.uint64)
+    if sequences:
+        offsets[1:] = np.cumsum([s.size for s in sequences])
+    symbols = np.concatenate(sequences) if sequences else np.zeros(0, dtype=np.uint8)
+    return symbols, offsets
+
+
+def gathered(chunks, columns=3):
+    """the arrays of record_chunks as one numpy array of shape (records, columns)"""
+    chunks = list(chunks)
+    return np.concatenate(chunks) if chunks else np.zeros((0, columns), dtype=np.uint64)
 
 
 def record_chunks(emit_fn, handle, capacity, device, device_index, cursor=0, columns=3):

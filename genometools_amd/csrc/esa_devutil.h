@@ -5,6 +5,14 @@
 
 constexpr int SC_THREADS = 256;
 
+// v of the first active lane, in a scalar register: for what every lane of the wave has alike
+__device__ __forceinline__ u32 uni(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// the lanes of `mask` (a __ballot) below this one
+__device__ __forceinline__ u32 lanes_before(u64 mask) {
+  return __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
+}
+
 template <int OP> __device__ __forceinline__ u32 sc_op(u32 a, u32 b) {
   return OP == SCAN_SUM ? a + b : (a > b ? a : b);
 }

@@ -1,12 +1,14 @@
 // esa_index.h -- the host side that the consumers of a resident index share: the
 // checker, the matching statistics, the maximal pairs, the query matches, the
-// suffix-prefix matches, the tag matches and the local alignments (esa_check.hip,
-// esa_mstat.hip, esa_maxpairs.hip, esa_qmatch.hip, esa_spm.hip, esa_tagmatch.hip,
-// esa_locali.hip).  A new consumer starts here: its object is a ConsumerBase with
-// a ResidentIndex, made by create_consumer; what it reads back goes through
-// fetch, the records it hands out through a RecordStage, after refuse_window; the
-// 64-bit places of its records are offsets_u64 of esa_prims.h.  One that walks
-// the intervals of .suf job by job goes on in esa_jobs.h.
+// suffix-prefix matches (all and irreducible), the tag matches and the local
+// alignments (esa_check.hip, esa_mstat.hip, esa_maxpairs.hip, esa_qmatch.hip,
+// esa_spm.hip, esa_spmred.hip, esa_tagmatch.hip, esa_locali.hip).  A new consumer
+// starts here: its object is a ConsumerBase with a ResidentIndex -- an IndexSlot
+// if a reader of the packed index may be its index too -- made by
+// create_consumer; what it reads back goes through fetch, the records it hands
+// out through a RecordStage, after refuse_window; the 64-bit places of its
+// records are offsets_u64 of esa_prims.h.  One that walks the intervals of .suf,
+// or of the rows of a packed index, job by job goes on in esa_jobs.h.
 //
 // `feature` is what a message starts with ("maximal pairs").  Only .hip files
 // include this header: the *_core.h, *_search.h and *_walk.h lane headers also
@@ -14,6 +16,7 @@
 #pragma once
 #include <initializer_list>
 #include "esa_own.h"
+#include "esa_pckidx.h"
 #include "../../include/gtamd_esa.h"
 
 // ---- device to host ------------------------------------------------------------
@@ -186,6 +189,70 @@ struct ResidentIndex : IndexView {
     return 0;
   }
   u64 bytes() const { return own.enc.bytes + own.suf.bytes + own.lcp.bytes + own.llv.bytes; }
+};
+
+// The index of a consumer that a reader of the packed index may be as well: the
+// tables, or the reader, never both.  `name` is the consumer's in its entry points
+// (gtamd_<name>_...), `noun` what a message calls its object ("the matcher").
+struct IndexSlot {
+  ResidentIndex tab;
+  const gtamd_pckidx *pck = nullptr;     // the index is a reader of the packed index ...
+  u64 opens = 0;                         // ... and the image of it that stamp() saw
+
+  bool is_set() const { return tab.set || pck != nullptr; }
+  int refuse_unset(const char *feature, const char *name) const {
+    if (is_set()) return 0;
+    gtamd_set_error("%s: no index is set (gtamd_%s_set_index)", feature, name);
+    return -1;
+  }
+  // tables: device memory that outlives the calls, or host memory
+  int set_tables(const char *feature, const IndexView &v, bool from_host) {
+    pck = nullptr;
+    if (from_host) return tab.upload_from_host(feature, v);
+    tab.borrow(v);
+    return 0;
+  }
+  // a reader, in two steps, between which a consumer looks at the image: what
+  // every consumer refuses of the reader px as the index of its object c ...
+  template <typename T> static int refuse_reader(const char *feature, const char *name, const char *noun, const T *c,
+                                                 const gtamd_pckidx *px) {
+    if (c == nullptr || px == nullptr) { gtamd_set_error("invalid argument to gtamd_%s_set_index_pckidx", name); return -1; }
+    if (!pckidx_is_open(px)) { gtamd_set_error("%s: the packed index reader has no image open", feature); return -1; }
+    if (pckidx_device(px) != c->device) {
+      gtamd_set_error("%s: the packed index lives on device %d, %s on %d", feature, pckidx_device(px), noun, c->device);
+      return -1;
+    }
+    return 0;
+  }
+  // ... and px is the index
+  void set_reader(const gtamd_pckidx *px) {
+    tab.drop();
+    pck = px;
+  }
+  // the reader that is the index must still hold the image it held when it was set
+  int refuse_lost_reader(const char *feature) const {
+    if (pckidx_is_open(pck)) return 0;
+    gtamd_set_error("%s: the packed index reader that is the index has no image open any more "
+                    "(its last gtamd_pckidx_open_* failed)", feature);
+    return -1;
+  }
+  // positions come from the locate information of the image; tail, with what it ends in: what the caller cannot have
+  int refuse_no_locate(const char *feature, const char *tail, const char *tail_end = "") const {
+    if (pckidx_can_locate(pck)) return 0;
+    gtamd_set_error("%s: the packed index holds no locate information (locate interval 0): %s%s", feature, tail,
+                    tail_end);
+    return -1;
+  }
+  // What a prepare leaves for later calls is of the image the reader held then:
+  // stamp() at prepare, and a reader opened again since holds another one.
+  void stamp() { opens = pckidx_opens(pck); }
+  int refuse_other_image(const char *feature, const char *prepare_fn) const {
+    if (pckidx_opens(pck) == opens) return 0;
+    gtamd_set_error("%s: the packed index reader was opened again since %s: what was prepared is of the image "
+                    "before (prepare again)", feature, prepare_fn);
+    return -1;
+  }
+  u64 bytes() const { return tab.bytes() + (pck != nullptr ? pckidx_decoded_bytes(pck) : 0); }
 };
 
 // ---- the object ----------------------------------------------------------------

@@ -1,18 +1,23 @@
-// esa_jobs.h -- what the consumers share that walk the intervals of .suf job by
-// job, one wave a job (esa_tagmatch.hip, esa_locali.hip): what a
-// counting walk reports, the 64-bit places of the jobs' records, the window of
-// records of an emit pass, the sequences the jobs are made of.  The lane code of
-// the walk is esa_ivwalk.h.  Beside esa_index.h, which is host code for every
-// consumer: this has device code, for those with jobs.  Only .hip files include it.
+// esa_jobs.h -- what the consumers share that walk an index job by job, one wave
+// a job (esa_tagmatch.hip, esa_locali.hip): what a counting walk
+// reports and the tail of its pass, the 64-bit places of the jobs' records, the
+// window of records of an emit pass and the pass itself, the sequences the jobs
+// are made of.  The lane code of the walk over the intervals of .suf is
+// esa_ivwalk.h, that of the walk over intervals of rows of a packed index
+// esa_pckidx_dec.h, with the step that needs the window here.  Beside esa_index.h,
+// which is host code for every consumer: this has device code, for those with
+// jobs.  Only .hip files include it.
 #pragma once
 #include <algorithm>
 #include <vector>
 #include "esa_index.h"
 #include "esa_prims.h"
 #include "esa_devutil.h"
+#include "esa_pckidx_dec.h"
 
 // ---- the kernels' side ---------------------------------------------------------
-// the words every walk reports through; a consumer's own words follow
+// the words every walk reports through; a consumer's own words follow, one of
+// them the error word of a walk over a packed index (esa_pckidx_core.h)
 enum { W_MATCHES = 0, W_MAXJOB, W_LEVELS, W_CHILDREN, W_WALKS, W_WALK_WORDS };
 
 // lane 0 of a counting walk: the k matches of job j, and what the walk took
@@ -45,13 +50,38 @@ template <typename R> struct JobWindow {
   template <bool EMIT> __device__ __forceinline__ void give(bool keep, const R &record) {
     const u64 mask = __ballot(keep);
     if (EMIT && keep) {
-      const u32 before = __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
-      const u64 place = k + before;
+      const u64 place = k + lanes_before(mask);
       if (place >= first && place < stop) dst[place - first] = record;
     }
     k += (u64) __popcll(mask);
   }
 };
+
+// rows of a packed index a wave locates at once, one a lane
+constexpr u32 DEC_BATCH = 64;
+
+// All rows [clo, chi) of a child match with `len` letters: counted, and in emit
+// located DEC_BATCH at a time, those whose records lie in front of the window
+// skipped by arithmetic.  make(p): the record of a row with dbstart p.
+template <bool EMIT, typename R, typename Make>
+__device__ __forceinline__ void dec_rows(const PkxDec &d, JobWindow<R> &wk, u32 clo, u32 chi, u32 len, u32 lane,
+                                         u32 *err, Make make) {
+  if (!EMIT) { wk.k += chi - clo; return; }
+  u32 b = clo;
+  if (wk.k < wk.first) {
+    const u64 skip = wk.first - wk.k < chi - clo ? wk.first - wk.k : chi - clo;
+    b += (u32) skip;
+    wk.k += skip;
+  }
+  for (; b < chi; b += DEC_BATCH) {
+    if (wk.full()) break;
+    const u32 row = b + lane;                         // (chi <= N <= 2^32 - 4096: no wrap)
+    const u64 place = wk.k + lane;
+    u64 p = 0;
+    if (row < chi && place >= wk.first && place < wk.stop) p = dec_dbstart(d, row, len, err);
+    wk.template give<EMIT>(row < chi, make(p));
+  }
+}
 
 // ---- the host side -------------------------------------------------------------
 // the counts of the jobs and the places of their first records
@@ -100,3 +130,60 @@ struct SequenceSet {
   }
   u64 bytes() const { return own_sym.bytes + own_off.bytes; }
 };
+
+// The tail of a counting pass over `jobs` jobs of consumer c, whose walks have been
+// launched behind ev[0]: the places of the jobs' records, h = the words, with one
+// wait, and what every walk reports to the fields every job walker's info has.
+// w_error: which word is the error word of a walk over a packed index.
+template <typename C, size_t WORDS, typename I>
+int finish_count(C *c, JobOffsets &jo, u64 jobs, u64 (&h)[WORDS], u32 w_error, I *info) {
+  TRY(jo.scan(jobs, c->words + W_MATCHES, c->st));
+  HIP_TRY(hipEventRecord(c->ev[1], c->st));
+  TRY(fetch(c->st, { { c->words, h, sizeof h }, jo.fetch(jobs) }));
+  if (h[w_error]) { pckidx_set_search_error(h[w_error]); return -1; }
+  HIP_TRY(hipEventElapsedTime(&info->device_ms, c->ev[0], c->ev[1]));
+  info->matches = h[W_MATCHES];
+  info->max_matches_of_one_job = h[W_MAXJOB];
+  info->levels_pushed = h[W_LEVELS];
+  info->children_examined = h[W_CHILDREN];
+  info->single_walks = h[W_WALKS];
+  return 0;
+}
+
+// One emit call of a job walker: the records [*cursor, *cursor + *written) of the
+// `total` that `prepare_fn` (its name, for the messages) counted, at most
+// `capacity`, which is at least `least`, to `out` -- through `buf` where that is
+// host memory.  launch(j0, j1, cur, w1, dst) launches the walk of the jobs
+// [j0, j1) that writes the records [cur, w1) to dst.  `error`: the error word of a
+// walk over a packed index, device memory.
+template <typename R, typename Launch>
+int emit_jobs(const char *feature, const char *prepare_fn, const IndexSlot &index, const JobOffsets &jo, u64 total,
+              u64 *cursor, u64 capacity, u64 least, void *out, int out_on_device, Dev<u8> &buf, hipStream_t st,
+              u64 *error, u64 *written, Launch launch) {
+  *written = 0;
+  const u64 cur = *cursor;
+  if (index.pck != nullptr) {
+    TRY(index.refuse_lost_reader(feature));
+    TRY(index.refuse_other_image(feature, prepare_fn));
+    TRY(index.refuse_no_locate(feature, "positions cannot be had from it, only the counts of ", prepare_fn));
+  }
+  TRY(refuse_window(feature, "records", cur, total, capacity, least));
+  if (cur == total) return 0;
+  const u64 w1 = capacity < total - cur ? cur + capacity : total;
+  u64 j0, j1;
+  jo.jobs_of(cur, w1, &j0, &j1);
+  RecordStage<R> stage(out, out_on_device);
+  if (stage.begin(buf, w1 - cur) != hipSuccess) return out_of_memory(feature, w1 - cur, "records");
+  if (index.pck != nullptr) HIP_TRY(hipMemsetAsync(error, 0, sizeof(u64), st));
+  launch(j0, j1, cur, w1, stage.dst);
+  HIP_TRY(hipGetLastError());
+  TRY(stage.finish(w1 - cur, st));
+  if (index.pck != nullptr) {
+    u64 found = 0;
+    TRY(fetch(st, { { error, &found, sizeof found } }));
+    if (found) { pckidx_set_search_error(found); return -1; }
+  }
+  *cursor = w1;
+  *written = w1 - cur;
+  return 0;
+}

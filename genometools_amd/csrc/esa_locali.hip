@@ -27,8 +27,6 @@
 #include "esa_common.h"
 #include "esa_jobs.h"
 #include "esa_locali_core.h"
-#include "esa_pckidx.h"
-#include "esa_pckidx_dec.h"
 #include "../../include/gtamd_locali.h"
 #include "../../include/gtamd_pcklocali.h"
 
@@ -38,6 +36,7 @@ constexpr int LC_THREADS = SC_THREADS;
 constexpr u32 LC_WAVES = LC_THREADS / 64;          // waves of one workgroup: each walks jobs of its own
 constexpr u32 LC_WAVES_PER_CU = 8;                 // waves of the grid per compute unit
 constexpr u32 LC_BATCH = IV_BATCH;
+static_assert(LC_BATCH == DEC_BATCH, "suffixes of a table, rows of a packed index: as many at once");
 constexpr u64 LC_MIN_CAPACITY = LC_BATCH;
 constexpr u64 LC_MAX_QUERIES = 1ull << 24;
 constexpr u64 LC_MAX_JOBS = 1ull << 31;
@@ -61,8 +60,6 @@ template <typename S> struct LcInput {
   LcScores sc; u32 T;
   u32 stack_words, col_words;                      // of one wave: its stack, then two columns of col_words
 };
-
-__device__ __forceinline__ u32 uni(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
 
 __device__ __forceinline__ LcRecord lc_record(u64 query, u64 p, u32 dblen, u32 score, u32 e, u32 qstart) {
   return LcRecord{ query, p, (u64) dblen | (u64) score << 32, (u64) qstart | (u64) (e - qstart) << 32 };
@@ -196,34 +193,12 @@ struct LcPkInput {
   u32 stack_words, col_words;                      // of one wave: its stack, then three columns of col_words
 };
 
-// dbstart of the match of `len` letters found at `row`: the suffix of the row
-// begins with them, last letter first (gen_pck_overinterval, pck_overcontext)
-__device__ __forceinline__ u64 lc_pck_dbstart(const PkxDec &d, u32 row, u32 len, u32 *err) {
-  const u64 end = dec_locate(d, row, err) + len;
-  if (end > d.N - 1) { dev_fail(err, PKX_E_WALK); return 0; }
-  return d.N - 1 - end;
-}
-
-// all rows [clo, chi) of a child whose column reached T after dblen letters: counted,
-// and in emit located 64 at a time, those in front of the window skipped by arithmetic
+// all rows [clo, chi) of a child whose column reached T after dblen letters
 template <bool EMIT>
 __device__ __forceinline__ void lc_pck_rows(const PkxDec &d, JobWindow<LcRecord> &wk, u64 query, u32 clo, u32 chi,
                                             u32 dblen, const LcColumn &col, u32 lane, u32 *err) {
-  if (!EMIT) { wk.k += chi - clo; return; }
-  u32 b = clo;
-  if (wk.k < wk.first) {
-    const u64 skip = wk.first - wk.k < chi - clo ? wk.first - wk.k : chi - clo;
-    b += (u32) skip;
-    wk.k += skip;
-  }
-  for (; b < chi; b += LC_BATCH) {
-    if (wk.full()) break;
-    const u32 row = b + lane;                         // (chi <= N <= 2^32 - 4096: no wrap)
-    const u64 place = wk.k + lane;
-    u64 p = 0;
-    if (row < chi && place >= wk.first && place < wk.stop) p = lc_pck_dbstart(d, row, dblen, err);
-    wk.give<EMIT>(row < chi, lc_record(query, p, dblen, col.M, col.e, col.qstart));
-  }
+  dec_rows<EMIT>(d, wk, clo, chi, dblen, lane, err,
+                 [=](u64 p) { return lc_record(query, p, dblen, col.M, col.e, col.qstart); });
 }
 
 // Row `row` < N, reached by the letter s from a row whose `depth` letters gave the
@@ -262,7 +237,7 @@ template <bool EMIT>
 __device__ __forceinline__ void lc_pck_one(const PkxDec &d, JobWindow<LcRecord> &wk, u64 query, const LcMatch &hit,
                                            u32 at, u32 lane, u32 *err) {
   u64 p = 0;
-  if (EMIT && lane == 0 && hit.dblen != 0 && wk.k >= wk.first && wk.k < wk.stop) p = lc_pck_dbstart(d, at, hit.dblen, err);
+  if (EMIT && lane == 0 && hit.dblen != 0 && wk.k >= wk.first && wk.k < wk.stop) p = dec_dbstart(d, at, hit.dblen, err);
   wk.give<EMIT>(lane == 0 && hit.dblen != 0, lc_record(query, p, hit.dblen, hit.score, hit.e, hit.qstart));
 }
 
@@ -284,7 +259,7 @@ __device__ void lc_job_pck(const LcPkInput &in, const u32 *count, u32 sigma, u64
   const u8 *q = in.queries + q0;
   const u32 deepest = lc_max_depth(m, in.sc);
   u32 *cola = stack + in.stack_words, *colb = cola + in.col_words, *colr = colb + in.col_words;
-  const u32 all = sigma >= 32 ? ~0u : (1u << sigma) - 1u;
+  const u32 all = dec_all_letters(sigma);
   u32 pushed = 0, children = 0, walks = 0;
   bool other = false;
 
@@ -392,8 +367,7 @@ __global__ __launch_bounds__(LC_THREADS) void k_lc_walk_pck(LcPkInput in, u64 j0
   const u64 slot = (u64) blockIdx.x * LC_WAVES + wave, slots = (u64) gridDim.x * LC_WAVES;
   u32 *stack = arena + slot * ((u64) in.stack_words + 3ull * in.col_words);
   u32 *count = s_count[wave];
-  const u32 sigma = in.d.sigma < LC_LETTERS ? in.d.sigma : LC_LETTERS;
-  for (u32 c = 0; c <= sigma; c++) count[c] = in.d.count[c];       // (every lane the same word)
+  const u32 sigma = dec_count_to_lds(in.d, count, LC_LETTERS);
   for (u64 j = j0 + slot; j < j1; j += slots)          // (the whole wave: the waves of a workgroup never wait for each other)
     lc_job_pck<EMIT>(in, count, sigma, j, stack, cnt, off, w0, w1, out, w, lane);
 }
@@ -438,9 +412,7 @@ __global__ __launch_bounds__(LC_THREADS) void k_lc_cuts(IvText<S> text, u32 N, u
 }  // namespace
 
 struct gtamd_locali : ConsumerBase<> {
-  ResidentIndex index;
-  const gtamd_pckidx *pck = nullptr;     // the index is a reader of the packed index
-  u64 pck_opens = 0;                     // ... and the image of it that the last prepare counted
+  IndexSlot index;
   u32 sigma = 0, cut_max = 0, compute_units = 0;
   std::vector<u64> cuts;          // of the index, ascending table index: i | depth << 32
   u32 forced_stack = 0, forced_cut = GTAMD_LOCALI_AUTO;
@@ -463,12 +435,13 @@ const char FEATURE[] = "local alignments";
 
 // the cuts of a new index down to the largest depth q may take
 template <typename S> int find_cuts(gtamd_locali *lc) {
-  const u32 N = (u32) (lc->index.n + 1);
+  const IndexView &v = lc->index.tab;
+  const u32 N = (u32) (v.n + 1);
   if (lc->cutlist.grow((u64) LC_CUT_LIST * 8) != hipSuccess) return out_of_memory(FEATURE, LC_CUT_LIST, "cuts");
   HIP_TRY(hipMemsetAsync(lc->words + W_CUTS, 0, sizeof(u64), lc->st));
   if (N > 1)
     k_lc_cuts<S><<<(u32) div_up(N - 1, LC_THREADS), LC_THREADS, 0, lc->st>>>(
-        IvText<S>{ lc->index.enc, lc->index.n, (const S *) lc->index.suf }, N, lc->cut_max, lc->cutlist, LC_CUT_LIST,
+        IvText<S>{ v.enc, v.n, (const S *) v.suf }, N, lc->cut_max, lc->cutlist, LC_CUT_LIST,
         lc->words);
   HIP_TRY(hipGetLastError());
   u64 found = 0;
@@ -488,14 +461,6 @@ void set_alphabet(gtamd_locali *lc, u32 sigma) {
   for (u64 groups = sigma; sigma > 1 && groups * sigma <= LC_CUT_GROUPS; groups *= sigma) lc->cut_max += 1;
 }
 
-// the reader that is the index must still hold the image it held when it was set
-int refuse_lost_reader(const gtamd_locali *lc) {
-  if (pckidx_is_open(lc->pck)) return 0;
-  gtamd_set_error("local alignments: the packed index reader that is the index has no image open any more "
-                  "(its last gtamd_pckidx_open_* failed)");
-  return -1;
-}
-
 // what an image must be like to be the index
 int refuse_image(const PkxDec &d) {
   if (d.sigma == 0 || d.sigma > LC_LETTERS) {
@@ -504,15 +469,6 @@ int refuse_image(const PkxDec &d) {
   }
   if (d.N == 0) { gtamd_set_error("local alignments: a packed index without a row"); return -1; }
   return refuse_sizes(FEATURE, d.N - 1, 0);               // rows <= 2^32 - 4096
-}
-
-// emit gives the records of the image that prepare counted: a reader opened
-// again since then holds another one, and the places of the jobs are not its
-int refuse_other_image(const gtamd_locali *lc) {
-  if (pckidx_opens(lc->pck) == lc->pck_opens) return 0;
-  gtamd_set_error("local alignments: the packed index reader was opened again since gtamd_locali_prepare: what "
-                  "was prepared is of the image before (prepare again)");
-  return -1;
 }
 
 // every way of setting an index: what is refused, before anything is touched
@@ -529,27 +485,26 @@ int set_index(gtamd_locali *lc, const IndexView &v, u32 sigma, bool from_host) {
   }
   HIP_TRY(hipSetDevice(lc->device));
   lc->prepared = false;
-  lc->pck = nullptr;
   set_alphabet(lc, sigma);
-  if (from_host) TRY(lc->index.upload_from_host(FEATURE, v));
-  else lc->index.borrow(v);
+  TRY(lc->index.set_tables(FEATURE, v, from_host));
   const int rc = v.suf_bytes == 4 ? find_cuts<u32>(lc) : find_cuts<u64>(lc);
-  if (rc != 0) lc->index.drop();
+  if (rc != 0) lc->index.tab.drop();
   return rc;
 }
 
 u64 held_bytes(const gtamd_locali *lc) {
-  return lc->index.bytes() + (lc->pck != nullptr ? pckidx_decoded_bytes(lc->pck) : 0) + lc->queries.bytes() + lc->jo.bytes() + lc->gstart.bytes + lc->arena.bytes +
+  return lc->index.bytes() + lc->queries.bytes() + lc->jo.bytes() + lc->gstart.bytes + lc->arena.bytes +
          lc->cutlist.bytes + lc->words.bytes + lc->out.bytes;
 }
 
 template <typename S> LcInput<S> input(const gtamd_locali *lc) {
-  return LcInput<S>{ { lc->index.enc, lc->index.n, (const S *) lc->index.suf }, (u32) (lc->index.n + 1),
+  const IndexView &v = lc->index.tab;
+  return LcInput<S>{ { v.enc, v.n, (const S *) v.suf }, (u32) (v.n + 1),
                      lc->queries.sym, lc->queries.off, lc->gstart, lc->groups, lc->sc, lc->T, lc->stack_words, lc->col_words };
 }
 
 LcPkInput input_pck(const gtamd_locali *lc) {
-  return LcPkInput{ pckidx_dec(lc->pck), lc->queries.sym, lc->queries.off, lc->groups, lc->q, lc->sc, lc->T,
+  return LcPkInput{ pckidx_dec(lc->index.pck), lc->queries.sym, lc->queries.off, lc->groups, lc->q, lc->sc, lc->T,
                     lc->stack_words, lc->col_words };
 }
 
@@ -581,7 +536,7 @@ int refuse_query(gtamd_locali *lc, u64 found) {
 
 // the groups of this prepare: the cuts above depth q, between 0 and N
 int set_groups(gtamd_locali *lc, u64 Q) {
-  const u64 N = lc->index.n + 1;
+  const u64 N = lc->index.tab.n + 1;
   u32 q = lc->forced_cut;
   if (q == GTAMD_LOCALI_AUTO) {
     std::vector<u64> upto(lc->cut_max + 1, 1);         // groups with the cuts above depth q
@@ -667,63 +622,25 @@ template <typename S> int prepare(gtamd_locali *lc) {
     k_lc_walk<S, false><<<lc->blocks, LC_THREADS, 0, st>>>(input<S>(lc), 0, jobs, lc->jo.cnt, nullptr, 0, 0, nullptr,
                                                           lc->arena, lc->words);
   HIP_TRY(hipGetLastError());
-  TRY(lc->jo.scan(jobs, lc->words + W_MATCHES, st));
-  HIP_TRY(hipEventRecord(lc->ev[1], st));
   u64 h[W_WORDS];
-  TRY(fetch(st, { { lc->words, h, sizeof h }, lc->jo.fetch(jobs) }));
-  if (PCK && h[W_ERROR]) { pckidx_set_search_error(h[W_ERROR]); return -1; }
-  HIP_TRY(hipEventElapsedTime(&lc->info.device_ms, lc->ev[0], lc->ev[1]));
-  lc->info.matches = h[W_MATCHES];
-  lc->info.max_matches_of_one_job = h[W_MAXJOB];
-  lc->info.levels_pushed = h[W_LEVELS];
-  lc->info.children_examined = h[W_CHILDREN];
-  lc->info.single_walks = h[W_WALKS];
+  TRY(finish_count(lc, lc->jo, jobs, h, W_ERROR, &lc->info));       // (W_ERROR: 0 behind a walk over .suf)
   lc->info.jobs_finished_alone = h[W_OTHER];
   lc->info.stack_words = lc->stack_words;
   return 0;
 }
 
-int emit(gtamd_locali *lc, u64 *cursor, gtamd_locali_record *out, u64 capacity, int out_on_device, u64 *written) {
-  *written = 0;
-  const u64 total = lc->info.matches, cur = *cursor;
-  if (lc->pck != nullptr) {
-    TRY(refuse_lost_reader(lc));
-    TRY(refuse_other_image(lc));
-    if (!pckidx_can_locate(lc->pck)) {
-      gtamd_set_error("local alignments: the packed index holds no locate information (locate interval 0): "
-                      "positions cannot be had from it, only the counts of gtamd_locali_prepare");
-      return -1;
-    }
-  }
-  TRY(refuse_window(FEATURE, "records", cur, total, capacity, LC_MIN_CAPACITY));
-  if (cur == total) return 0;
-  const u64 w1 = capacity < total - cur ? cur + capacity : total;
-  u64 j0, j1;
-  lc->jo.jobs_of(cur, w1, &j0, &j1);
-  RecordStage<LcRecord> stage(out, out_on_device);
-  if (stage.begin(lc->out, w1 - cur) != hipSuccess) return out_of_memory(FEATURE, w1 - cur, "records");
+// the walk of the jobs [j0, j1) that writes the records [cur, w1) to dst
+void launch_emit(gtamd_locali *lc, u64 j0, u64 j1, u64 cur, u64 w1, LcRecord *dst) {
   const u32 blocks = (u32) std::min<u64>(div_up(j1 - j0, LC_WAVES), lc->blocks);      // (the arena has room for lc->blocks)
-  if (lc->pck != nullptr) {
-    HIP_TRY(hipMemsetAsync(lc->words + W_ERROR, 0, sizeof(u64), lc->st));
-    k_lc_walk_pck<true><<<blocks, LC_THREADS, 0, lc->st>>>(input_pck(lc), j0, j1, nullptr, lc->jo.off, cur, w1, stage.dst,
+  if (lc->index.pck != nullptr)
+    k_lc_walk_pck<true><<<blocks, LC_THREADS, 0, lc->st>>>(input_pck(lc), j0, j1, nullptr, lc->jo.off, cur, w1, dst,
                                                           lc->arena, lc->words);
-  } else if (lc->index.suf_bytes == 4)
-    k_lc_walk<u32, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u32>(lc), j0, j1, nullptr, lc->jo.off, cur, w1,
-                                                             stage.dst, lc->arena, lc->words);
+  else if (lc->index.tab.suf_bytes == 4)
+    k_lc_walk<u32, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u32>(lc), j0, j1, nullptr, lc->jo.off, cur, w1, dst,
+                                                             lc->arena, lc->words);
   else
-    k_lc_walk<u64, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u64>(lc), j0, j1, nullptr, lc->jo.off, cur, w1,
-                                                             stage.dst, lc->arena, lc->words);
-  HIP_TRY(hipGetLastError());
-  TRY(stage.finish(w1 - cur, lc->st));
-  if (lc->pck != nullptr) {
-    u64 error = 0;
-    TRY(fetch(lc->st, { { lc->words + W_ERROR, &error, sizeof error } }));
-    if (error) { pckidx_set_search_error(error); return -1; }
-  }
-  lc->info.emitted += w1 - cur;
-  *cursor = w1;
-  *written = w1 - cur;
-  return 0;
+    k_lc_walk<u64, true><<<blocks, LC_THREADS, 0, lc->st>>>(input<u64>(lc), j0, j1, nullptr, lc->jo.off, cur, w1, dst,
+                                                             lc->arena, lc->words);
 }
 
 }  // namespace
@@ -779,20 +696,13 @@ extern "C" int gtamd_locali_set_index_esa(gtamd_locali *lc, const gtamd_esa_ctx 
 
 extern "C" int gtamd_locali_set_index_pckidx(gtamd_locali *lc, const gtamd_pckidx *px) {
   GTAMD_ABI_BEGIN
-  if (lc == nullptr || px == nullptr) { gtamd_set_error("invalid argument to gtamd_locali_set_index_pckidx"); return -1; }
-  if (!pckidx_is_open(px)) { gtamd_set_error("local alignments: the packed index reader has no image open"); return -1; }
-  if (pckidx_device(px) != lc->device) {
-    gtamd_set_error("local alignments: the packed index lives on device %d, the aligner on %d", pckidx_device(px),
-                    lc->device);
-    return -1;
-  }
+  TRY(IndexSlot::refuse_reader(FEATURE, "locali", "the aligner", lc, px));
   const PkxDec &d = pckidx_dec(px);
   TRY(refuse_image(d));
   HIP_TRY(hipSetDevice(lc->device));
   lc->prepared = false;
-  lc->index.drop();
+  lc->index.set_reader(px);
   lc->cuts.clear();
-  lc->pck = px;
   set_alphabet(lc, d.sigma);
   return 0;
   GTAMD_ABI_END(-1)
@@ -825,14 +735,11 @@ extern "C" int gtamd_locali_prepare(gtamd_locali *lc, const uint8_t *queries, co
     gtamd_set_error("invalid argument to gtamd_locali_prepare");
     return -1;
   }
-  if (!lc->index.set && lc->pck == nullptr) {
-    gtamd_set_error("local alignments: no index is set (gtamd_locali_set_index)");
-    return -1;
-  }
-  if (lc->pck != nullptr) {
+  TRY(lc->index.refuse_unset(FEATURE, "locali"));
+  if (lc->index.pck != nullptr) {
     // the reader may hold another image than when it was set: this prepare is of the one it holds now
-    TRY(refuse_lost_reader(lc));
-    TRY(refuse_image(pckidx_dec(lc->pck)));
+    TRY(lc->index.refuse_lost_reader(FEATURE));
+    TRY(refuse_image(pckidx_dec(lc->index.pck)));
   }
   if (match <= 0 || mismatch >= 0 || gapextend >= 0 || match > LC_MAX_WEIGHT || mismatch < -LC_MAX_WEIGHT ||
       gapextend < -LC_MAX_WEIGHT) {
@@ -852,9 +759,9 @@ extern "C" int gtamd_locali_prepare(gtamd_locali *lc, const uint8_t *queries, co
   }
   HIP_TRY(hipSetDevice(lc->device));
   lc->prepared = false;
-  if (lc->pck != nullptr) {
-    set_alphabet(lc, pckidx_dec(lc->pck).sigma);
-    lc->pck_opens = pckidx_opens(lc->pck);
+  if (lc->index.pck != nullptr) {
+    set_alphabet(lc, pckidx_dec(lc->index.pck).sigma);
+    lc->index.stamp();
   }
   lc->info = gtamd_locali_info();
   lc->Q = Q;
@@ -864,7 +771,7 @@ extern "C" int gtamd_locali_prepare(gtamd_locali *lc, const uint8_t *queries, co
   lc->jo.off_host.assign(1, 0);
   if (Q != 0) {
     TRY(lc->queries.set(FEATURE, "query symbols", queries, offsets, Q, is_device, lc->st));
-    TRY(lc->pck != nullptr ? prepare<void>(lc) : lc->index.suf_bytes == 4 ? prepare<u32>(lc) : prepare<u64>(lc));
+    TRY(lc->index.pck != nullptr ? prepare<void>(lc) : lc->index.tab.suf_bytes == 4 ? prepare<u32>(lc) : prepare<u64>(lc));
   }
   lc->info.device_bytes = held_bytes(lc);
   lc->prepared = true;
@@ -885,7 +792,10 @@ extern "C" int gtamd_locali_emit(gtamd_locali *lc, uint64_t *cursor, gtamd_local
     return -1;
   }
   HIP_TRY(hipSetDevice(lc->device));
-  TRY(emit(lc, cursor, out, capacity, out_on_device, written));
+  TRY(emit_jobs<LcRecord>(FEATURE, "gtamd_locali_prepare", lc->index, lc->jo, lc->info.matches, cursor, capacity,
+                          LC_MIN_CAPACITY, out, out_on_device, lc->out, lc->st, lc->words + W_ERROR, written,
+                          [lc](u64 j0, u64 j1, u64 cur, u64 w1, LcRecord *dst) { launch_emit(lc, j0, j1, cur, w1, dst); }));
+  lc->info.emitted += *written;
   lc->info.device_bytes = held_bytes(lc);
   return 0;
   GTAMD_ABI_END(-1)

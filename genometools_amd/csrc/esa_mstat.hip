@@ -14,7 +14,6 @@
 #include "esa_common.h"
 #include "esa_index.h"
 #include "esa_mstat_search.h"
-#include "esa_pckidx.h"
 #include "../../include/gtamd_mstat.h"
 #include "../../include/gtamd_pckidx.h"
 
@@ -56,8 +55,7 @@ __global__ __launch_bounds__(MST_THREADS) void k_mstat(const u8 *enc, u64 n, con
 }  // namespace
 
 struct gtamd_mstat : ConsumerBase<> {
-  ResidentIndex index;
-  const gtamd_pckidx *pck = nullptr;     // the index is a reader of the packed index
+  IndexSlot index;
   u32 numofchars = 0;
   Dev<u8> query;
   Dev<u32> len;
@@ -82,21 +80,18 @@ int set_index(gtamd_mstat *ms, const IndexView &v, u32 numofchars, bool from_hos
   }
   TRY(refuse_sizes(FEATURE, v.n, 0));
   HIP_TRY(hipSetDevice(ms->device));
-  ms->pck = nullptr;
   ms->numofchars = numofchars;
-  if (from_host) return ms->index.upload_from_host(FEATURE, v);
-  ms->index.borrow(v);
-  return 0;
+  return ms->index.set_tables(FEATURE, v, from_host);
 }
 
 u64 held_bytes(const gtamd_mstat *ms) {
-  return ms->index.bytes() + (ms->pck != nullptr ? pckidx_decoded_bytes(ms->pck) : 0) + ms->query.bytes + ms->len.bytes + ms->pos.bytes + ms->words.bytes;
+  return ms->index.bytes() + ms->query.bytes + ms->len.bytes + ms->pos.bytes + ms->words.bytes;
 }
 
 template <typename S, bool MATSTAT>
 void launch(gtamd_mstat *ms, const u8 *q, u64 m, u32 limit, u32 *len, u64 *pos) {
   k_mstat<S, MATSTAT><<<(u32) div_up(m, MST_TILE), MST_THREADS, 0, ms->st>>>(
-      ms->index.enc, ms->index.n, (const S *) ms->index.suf, q, m, limit, len, pos, ms->words);
+      ms->index.tab.enc, ms->index.tab.n, (const S *) ms->index.tab.suf, q, m, limit, len, pos, ms->words);
 }
 
 int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_device, u32 max_len,
@@ -105,15 +100,8 @@ int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_devi
     gtamd_set_error("invalid argument to gtamd_mstat_%s", matstat ? "matstat" : "uniquesub");
     return -1;
   }
-  if (!ms->index.set && ms->pck == nullptr) {
-    gtamd_set_error("matching statistics: no index is set (gtamd_mstat_set_index)");
-    return -1;
-  }
-  if (ms->pck != nullptr && !pckidx_is_open(ms->pck)) {
-    gtamd_set_error("matching statistics: the packed index reader that is the index has no image open any more "
-                    "(its last gtamd_pckidx_open_* failed)");
-    return -1;
-  }
+  TRY(ms->index.refuse_unset(FEATURE, "mstat"));
+  if (ms->index.pck != nullptr) TRY(ms->index.refuse_lost_reader(FEATURE));
   if (m > MST_MAX_QUERY) {
     gtamd_set_error("matching statistics: query of %llu symbols, at most %llu in one call",
                     (unsigned long long) m, (unsigned long long) MST_MAX_QUERY);
@@ -125,11 +113,7 @@ int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_devi
   if (m == 0) return 0;
   HIP_TRY(hipSetDevice(ms->device));
   const bool want_pos = matstat && subjectpos_out != nullptr;
-  if (ms->pck != nullptr && want_pos && !pckidx_can_locate(ms->pck)) {
-    gtamd_set_error("matching statistics: the packed index holds no locate information (locate interval 0): "
-                    "subject positions cannot be had from it");
-    return -1;
-  }
+  if (ms->index.pck != nullptr && want_pos) TRY(ms->index.refuse_no_locate(FEATURE, "subject positions cannot be had from it"));
   if ((!is_device && ms->query.grow(m) != hipSuccess) ||
       (!out_is_device && (ms->len.grow(m * sizeof(u32)) != hipSuccess ||
                           (want_pos && ms->pos.grow(m * sizeof(u64)) != hipSuccess)))) {
@@ -148,9 +132,9 @@ int run_query(gtamd_mstat *ms, bool matstat, const u8 *query, u64 m, int is_devi
   const u32 limit = max_len == 0 || max_len >= MST_MAX_QUERY ? (u32) MST_MAX_QUERY : max_len + 1;
   HIP_TRY(hipMemsetAsync(ms->words, 0, W_WORDS * sizeof(u64), st));
   HIP_TRY(hipEventRecord(ms->ev[0], st));
-  if (ms->pck != nullptr) {
-    TRY(pckidx_search(ms->pck, st, matstat, q, m, limit, len, pos, &ms->words[W_COMPARED], &ms->words[W_ERROR]));
-  } else if (ms->index.suf_bytes == 4) {
+  if (ms->index.pck != nullptr) {
+    TRY(pckidx_search(ms->index.pck, st, matstat, q, m, limit, len, pos, &ms->words[W_COMPARED], &ms->words[W_ERROR]));
+  } else if (ms->index.tab.suf_bytes == 4) {
     if (matstat) launch<u32, true>(ms, q, m, limit, len, pos); else launch<u32, false>(ms, q, m, limit, len, pos);
   } else {
     if (matstat) launch<u64, true>(ms, q, m, limit, len, pos); else launch<u64, false>(ms, q, m, limit, len, pos);
@@ -211,15 +195,9 @@ extern "C" int gtamd_mstat_set_index_esa(gtamd_mstat *ms, const gtamd_esa_ctx *e
 
 extern "C" int gtamd_mstat_set_index_pckidx(gtamd_mstat *ms, const gtamd_pckidx *px) {
   GTAMD_ABI_BEGIN
-  if (ms == nullptr || px == nullptr) { gtamd_set_error("invalid argument to gtamd_mstat_set_index_pckidx"); return -1; }
-  if (!pckidx_is_open(px)) { gtamd_set_error("matching statistics: the packed index reader has no image open"); return -1; }
-  if (pckidx_device(px) != ms->device) {
-    gtamd_set_error("matching statistics: the packed index lives on device %d, the searcher on %d", pckidx_device(px), ms->device);
-    return -1;
-  }
+  TRY(IndexSlot::refuse_reader(FEATURE, "mstat", "the searcher", ms, px));
   HIP_TRY(hipSetDevice(ms->device));
-  ms->index.drop();
-  ms->pck = px;
+  ms->index.set_reader(px);
   return 0;
   GTAMD_ABI_END(-1)
 }

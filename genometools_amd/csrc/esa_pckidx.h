@@ -1,7 +1,9 @@
-// esa_pckidx.h -- what esa_mstat.hip and esa_tagmatch.hip need of the reader of
-// the packed index (esa_pckidx.hip): the search through a reader's decoded form.
-// A kernel of another file that walks the decoded form itself takes it from
-// pckidx_dec (esa_pckidx_dec.h, which has the lane functions too).
+// esa_pckidx.h -- what the consumers that take a reader of the packed index
+// (esa_pckidx.hip) as their index need of it: esa_mstat.hip, esa_tagmatch.hip and
+// esa_locali.hip, through the IndexSlot of esa_index.h, which includes this.  What
+// a reader holds, and the search through its decoded form.  A kernel of another
+// file that walks the decoded form itself takes it from pckidx_dec
+// (esa_pckidx_dec.h, which has the lane functions too).
 #pragma once
 #include "esa_common.h"
 

@@ -1,8 +1,10 @@
 // esa_pckidx_dec.h -- the decoded form of the packed index as the kernels see it,
 // and what one lane asks of it: rank, rank pair, BWT symbol, locate (the form and
 // the semantics: include/gtamd_pckidx.h).  esa_pckidx.hip decodes into it and
-// searches it for matstat and uniquesub; esa_tagmatch.hip walks it depth first
-// (include/gtamd_pcktag.h).  Only .hip files include this.
+// searches it for matstat and uniquesub; esa_tagmatch.hip and esa_locali.hip walk
+// it depth first (include/gtamd_pcktag.h, include/gtamd_pcklocali.h), through
+// esa_jobs.h, which has the step of such a walk that needs the window of records.
+// Only .hip files include this.
 #pragma once
 #include "esa_common.h"
 #include "esa_pckidx_core.h"
@@ -174,5 +176,25 @@ __device__ inline u64 dec_locate(const PkxDec &d, u64 row, u32 *err) {
     if (row >= d.N) { dev_fail(err, PKX_E_WALK); return 0; }
   }
 }
+
+// ---- the row steps of a walk over intervals of rows --------------------------------
+// dbstart of the match of `len` letters found at `row`: the suffix of the row
+// begins with them, last letter first (gen_pck_overinterval, pck_overcontext)
+__device__ __forceinline__ u64 dec_dbstart(const PkxDec &d, u32 row, u32 len, u32 *err) {
+  const u64 end = dec_locate(d, row, err) + len;
+  if (end > d.N - 1) { dev_fail(err, PKX_E_WALK); return 0; }
+  return d.N - 1 - end;
+}
+
+// count[0 .. sigma] of the index to `count`, the LDS of a wave; sigma, which is
+// returned: the letters of the index, at most `letters`
+__device__ __forceinline__ u32 dec_count_to_lds(const PkxDec &d, u32 *count, u32 letters) {
+  const u32 sigma = d.sigma < letters ? d.sigma : letters;
+  for (u32 c = 0; c <= sigma; c++) count[c] = d.count[c];       // (every lane the same word)
+  return sigma;
+}
+
+// the `todo` of dec_children for a level that has not been expanded yet
+__device__ __forceinline__ u32 dec_all_letters(u32 sigma) { return sigma >= 32 ? ~0u : (1u << sigma) - 1u; }
 
 }  // namespace

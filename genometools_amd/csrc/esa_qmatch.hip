@@ -95,7 +95,7 @@ __global__ __launch_bounds__(QM_THREADS) void k_qm_emit(QmInput<S> in, const u32
   }
   // the kept candidates in front of this one: in its wave, in the waves before
   const u64 mask = __ballot(keep);
-  const u32 before = __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
+  const u32 before = lanes_before(mask);
   const u32 wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) wave_kept[wave] = (u32) __popcll(mask);
   __syncthreads();

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_select(SpIndex<S> x, u32 L, u
 #pragma unroll
     for (u32 k = 0; k < K_KINDS; k++) {
       const u64 mask = __ballot(sel[k][e]);
-      before[k][e] = __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
+      before[k][e] = lanes_before(mask);
       if ((threadIdx.x & 63) == 0) groups[k][e * SP_WAVES + wave] = (u32) __popcll(mask);
     }
   }

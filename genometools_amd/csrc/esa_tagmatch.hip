@@ -22,8 +22,6 @@
 #include "esa_common.h"
 #include "esa_jobs.h"
 #include "esa_tagmatch_core.h"
-#include "esa_pckidx.h"
-#include "esa_pckidx_dec.h"
 #include "../../include/gtamd_tagmatch.h"
 #include "../../include/gtamd_pcktag.h"
 
@@ -33,6 +31,7 @@ constexpr int TM_THREADS = SC_THREADS;
 constexpr u32 TM_WAVES = TM_THREADS / 64;          // jobs of one workgroup: one a wave
 constexpr u32 TM_LEVELS = 128;                     // depths 0 .. m + K - 1 <= 126 have a level
 constexpr u32 TM_BATCH = IV_BATCH;                 // suffixes the lanes of a wave take at once
+static_assert(TM_BATCH == DEC_BATCH, "and as many rows of a packed index");
 constexpr u64 TM_MIN_CAPACITY = TM_BATCH;
 constexpr u64 TM_MAX_TAGS = 1ull << 30;
 constexpr u32 TM_STRANDS = GTAMD_TAGMATCH_FORWARD | GTAMD_TAGMATCH_REVCOMP;
@@ -53,8 +52,6 @@ template <typename S> struct TmInput {
   const u8 *tags; const u64 *toff; u64 T;
   u32 strands, wild;
 };
-
-__device__ __forceinline__ u32 uni(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // what job j is: its tag, its strand and its K; false if this pass has nothing to
 // do for it (EMIT: its tag has no K'; else: its tag has one already)
@@ -188,10 +185,6 @@ struct PkInput {
   u32 strands;
 };
 
-__device__ __forceinline__ u32 lanes_before(u64 mask) {
-  return __builtin_amdgcn_mbcnt_hi((u32) (mask >> 32), __builtin_amdgcn_mbcnt_lo((u32) mask, 0u));
-}
-
 // The children step, one letter a lane: lane c of `todo` gets the rows [*clo, *chi)
 // of the child of letter c of the interval [lo, hi) -- one rank pair, all lanes
 // in the same one or two lines -- and, where the child is not empty, *ccol = col
@@ -227,14 +220,6 @@ __device__ __forceinline__ u32 pk_walk(const PkxDec &d, const u32 *count, const 
   return 0;
 }
 
-// dbstart of the match of `len` letters found at `row`: the suffix of the row
-// begins with them, last letter first (gen_pck_overinterval, pck_overcontext)
-__device__ __forceinline__ u64 pk_dbstart(const PkxDec &d, u32 row, u32 len, u32 *err) {
-  const u64 end = dec_locate(d, row, err) + len;
-  if (end > d.N - 1) { dev_fail(err, PKX_E_WALK); return 0; }
-  return d.N - 1 - end;
-}
-
 // k_tm_walk for a packed index: the same jobs, counts, windows and records.
 template <bool EMIT>
 __global__ __launch_bounds__(TM_THREADS) void k_tm_walk_pck(PkInput in, u64 j0, u64 j1, u32 k_pass, const u32 *kbest,
@@ -258,8 +243,7 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk_pck(PkInput in, u64 j0, 
   u64 *eq = s_eq[wave];
   const u32 m = tm_tag_eq(in.tags, in.toff, job.tag, job.rc, lane, eq);
   u32 *count = s_count[wave];
-  const u32 sigma = d.sigma < TM_LETTERS ? d.sigma : TM_LETTERS;
-  for (u32 c = 0; c <= sigma; c++) count[c] = d.count[c];       // (every lane the same word)
+  const u32 sigma = dec_count_to_lds(d, count, TM_LETTERS);
 
   TmLevel *level = s_level[wave];
   level[0] = TmLevel{ 0, (u32) d.N, 0, K | K << 16, ~0ull, 0 };
@@ -273,7 +257,7 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk_pck(PkInput in, u64 j0, 
   for (;;) {
     if (EMIT && wk.full()) break;
     const u32 lo = uni(level[depth].lo), hi = uni(level[depth].end);
-    const u32 todo = fresh ? (sigma >= 32 ? ~0u : (1u << sigma) - 1u) : uni(level[depth].cur);
+    const u32 todo = fresh ? dec_all_letters(sigma) : uni(level[depth].cur);
     if (todo == 0) {
       if (depth == 0) break;
       depth -= 1;
@@ -303,21 +287,8 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk_pck(PkInput in, u64 j0, 
       ccol.val = __builtin_amdgcn_readlane(my_col.val, c);
       if ((success >> c) & 1u) {
         // all rows of the child match with depth + 1 letters
-        if (!EMIT) { wk.k += chi - clo; continue; }
-        u32 b = clo;
-        if (wk.k < wk.first) {                      // rows whose records lie in front of the window
-          const u64 skip = wk.first - wk.k < chi - clo ? wk.first - wk.k : chi - clo;
-          b += (u32) skip;
-          wk.k += skip;
-        }
-        for (; b < chi; b += TM_BATCH) {
-          if (wk.full()) break;
-          const u32 row = b + lane;                  // (chi <= N <= 2^32 - 4096: no wrap)
-          const u64 place = wk.k + lane;
-          u64 p = 0;
-          if (row < chi && place >= wk.first && place < wk.stop) p = pk_dbstart(d, row, depth + 1, err);
-          wk.give<EMIT>(row < chi, TmRecord{ tagword, p, (u64) (depth + 1) | (u64) ccol.val << 32 });
-        }
+        const u64 lendist = (u64) (depth + 1) | (u64) ccol.val << 32;
+        dec_rows<EMIT>(d, wk, clo, chi, depth + 1, lane, err, [=](u64 p) { return TmRecord{ tagword, p, lendist }; });
         continue;
       }
       if (chi - clo <= TM_BATCH) {
@@ -327,7 +298,7 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_walk_pck(PkInput in, u64 j0, 
         u64 p = 0;
         if (EMIT) {
           const u64 place = wk.k + lanes_before(__ballot(len != 0));
-          if (len != 0 && place >= wk.first && place < wk.stop) p = pk_dbstart(d, at, len, err);
+          if (len != 0 && place >= wk.first && place < wk.stop) p = dec_dbstart(d, at, len, err);
         }
         wk.give<EMIT>(len != 0, TmRecord{ tagword, p, (u64) len | (u64) dist << 32 });
         continue;
@@ -375,8 +346,7 @@ __global__ __launch_bounds__(TM_THREADS) void k_tm_validate(const u8 *tags, cons
 }  // namespace
 
 struct gtamd_tagmatch : ConsumerBase<> {
-  ResidentIndex index;
-  const gtamd_pckidx *pck = nullptr;     // the index is a reader of the packed index
+  IndexSlot index;
   u32 sigma = 0;
   bool prepared = false;
   // what a prepare leaves for the emit calls
@@ -407,27 +377,17 @@ int set_index(gtamd_tagmatch *tm, const IndexView &v, u32 sigma, bool from_host)
   }
   HIP_TRY(hipSetDevice(tm->device));
   tm->prepared = false;
-  tm->pck = nullptr;
   tm->sigma = sigma;
-  if (from_host) return tm->index.upload_from_host(FEATURE, v);
-  tm->index.borrow(v);
-  return 0;
-}
-
-// the reader that is the index must still hold the image it held when it was set
-int refuse_lost_reader(const gtamd_tagmatch *tm) {
-  if (pckidx_is_open(tm->pck)) return 0;
-  gtamd_set_error("tag matches: the packed index reader that is the index has no image open any more "
-                  "(its last gtamd_pckidx_open_* failed)");
-  return -1;
+  return tm->index.set_tables(FEATURE, v, from_host);
 }
 
 u64 held_bytes(const gtamd_tagmatch *tm) {
-  return tm->index.bytes() + (tm->pck != nullptr ? pckidx_decoded_bytes(tm->pck) : 0) + tm->tags.bytes() + tm->jo.bytes() + tm->kbest.bytes + tm->words.bytes + tm->out.bytes;
+  return tm->index.bytes() + tm->tags.bytes() + tm->jo.bytes() + tm->kbest.bytes + tm->words.bytes + tm->out.bytes;
 }
 
 template <typename S> TmInput<S> input(const gtamd_tagmatch *tm) {
-  return TmInput<S>{ { tm->index.enc, tm->index.n, (const S *) tm->index.suf }, (u32) (tm->index.n + 1),
+  const IndexView &v = tm->index.tab;
+  return TmInput<S>{ { v.enc, v.n, (const S *) v.suf }, (u32) (v.n + 1),
                      tm->tags.sym, tm->tags.off, tm->T, tm->flags & TM_STRANDS,
                      (tm->flags & GTAMD_TAGMATCH_WITH_WILDCARDS) ? 1u : 0u };
 }
@@ -458,7 +418,7 @@ int refuse_tag(gtamd_tagmatch *tm, u64 found, u32 K) {
 }
 
 PkInput input_pck(const gtamd_tagmatch *tm) {
-  return PkInput{ pckidx_dec(tm->pck), tm->tags.sym, tm->tags.off, tm->T, tm->flags & TM_STRANDS };
+  return PkInput{ pckidx_dec(tm->index.pck), tm->tags.sym, tm->tags.off, tm->T, tm->flags & TM_STRANDS };
 }
 
 // S: the entries of .suf; void: the index is a reader of the packed index
@@ -486,60 +446,22 @@ template <typename S> int prepare(gtamd_tagmatch *tm, u32 K) {
     k_tm_settle<<<(u32) div_up(T, TM_THREADS), TM_THREADS, 0, st>>>(tm->jo.cnt, per_tag, T, k, tm->kbest);
     HIP_TRY(hipGetLastError());
   }
-  TRY(tm->jo.scan(jobs, tm->words + W_MATCHES, st));
-  HIP_TRY(hipEventRecord(tm->ev[1], st));
   u64 h[W_WORDS];
-  TRY(fetch(st, { { tm->words, h, sizeof h }, tm->jo.fetch(jobs) }));
-  if (h[W_ERROR]) { pckidx_set_search_error(h[W_ERROR]); return -1; }
-  HIP_TRY(hipEventElapsedTime(&tm->info.device_ms, tm->ev[0], tm->ev[1]));
-  tm->info.matches = h[W_MATCHES];
-  tm->info.max_matches_of_one_job = h[W_MAXJOB];
-  tm->info.levels_pushed = h[W_LEVELS];
-  tm->info.children_examined = h[W_CHILDREN];
-  tm->info.single_walks = h[W_WALKS];
-  return 0;
+  return finish_count(tm, tm->jo, jobs, h, W_ERROR, &tm->info);
 }
 
-int emit(gtamd_tagmatch *tm, u64 *cursor, gtamd_tagmatch_record *out, u64 capacity, int out_on_device, u64 *written) {
-  *written = 0;
-  const u64 total = tm->info.matches, cur = *cursor;
-  if (tm->pck != nullptr) {
-    TRY(refuse_lost_reader(tm));
-    if (!pckidx_can_locate(tm->pck)) {
-      gtamd_set_error("tag matches: the packed index holds no locate information (locate interval 0): positions "
-                      "cannot be had from it, only the counts of gtamd_tagmatch_prepare");
-      return -1;
-    }
-  }
-  TRY(refuse_window(FEATURE, "records", cur, total, capacity, TM_MIN_CAPACITY));
-  if (cur == total) return 0;
-  const u64 w1 = capacity < total - cur ? cur + capacity : total;
-  u64 j0, j1;
-  tm->jo.jobs_of(cur, w1, &j0, &j1);
-  RecordStage<TmRecord> stage(out, out_on_device);
-  if (stage.begin(tm->out, w1 - cur) != hipSuccess) return out_of_memory(FEATURE, w1 - cur, "records");
+// the walk of the jobs [j0, j1) that writes the records [cur, w1) to dst
+void launch_emit(gtamd_tagmatch *tm, u64 j0, u64 j1, u64 cur, u64 w1, TmRecord *dst) {
   const u32 blocks = (u32) div_up(j1 - j0, TM_WAVES);
-  if (tm->pck != nullptr) {
-    HIP_TRY(hipMemsetAsync(tm->words + W_ERROR, 0, sizeof(u64), tm->st));
+  if (tm->index.pck != nullptr)
     k_tm_walk_pck<true><<<blocks, TM_THREADS, 0, tm->st>>>(input_pck(tm), j0, j1, 0, tm->kbest, nullptr, tm->jo.off, cur, w1,
-                                                           stage.dst, tm->words);
-  } else if (tm->index.suf_bytes == 4)
+                                                           dst, tm->words);
+  else if (tm->index.tab.suf_bytes == 4)
     k_tm_walk<u32, true><<<blocks, TM_THREADS, 0, tm->st>>>(input<u32>(tm), j0, j1, 0, tm->kbest, nullptr, tm->jo.off, cur,
-                                                             w1, stage.dst, tm->words);
+                                                             w1, dst, tm->words);
   else
     k_tm_walk<u64, true><<<blocks, TM_THREADS, 0, tm->st>>>(input<u64>(tm), j0, j1, 0, tm->kbest, nullptr, tm->jo.off, cur,
-                                                             w1, stage.dst, tm->words);
-  HIP_TRY(hipGetLastError());
-  TRY(stage.finish(w1 - cur, tm->st));
-  if (tm->pck != nullptr) {
-    u64 error = 0;
-    TRY(fetch(tm->st, { { tm->words + W_ERROR, &error, sizeof error } }));
-    if (error) { pckidx_set_search_error(error); return -1; }
-  }
-  tm->info.emitted += w1 - cur;
-  *cursor = w1;
-  *written = w1 - cur;
-  return 0;
+                                                             w1, dst, tm->words);
 }
 
 }  // namespace
@@ -584,12 +506,7 @@ extern "C" int gtamd_tagmatch_set_index_esa(gtamd_tagmatch *tm, const gtamd_esa_
 
 extern "C" int gtamd_tagmatch_set_index_pckidx(gtamd_tagmatch *tm, const gtamd_pckidx *px) {
   GTAMD_ABI_BEGIN
-  if (tm == nullptr || px == nullptr) { gtamd_set_error("invalid argument to gtamd_tagmatch_set_index_pckidx"); return -1; }
-  if (!pckidx_is_open(px)) { gtamd_set_error("tag matches: the packed index reader has no image open"); return -1; }
-  if (pckidx_device(px) != tm->device) {
-    gtamd_set_error("tag matches: the packed index lives on device %d, the matcher on %d", pckidx_device(px), tm->device);
-    return -1;
-  }
+  TRY(IndexSlot::refuse_reader(FEATURE, "tagmatch", "the matcher", tm, px));
   const u32 sigma = pckidx_dec(px).sigma;
   if (sigma == 0 || sigma > TM_LETTERS) {
     gtamd_set_error("tag matches: an alphabet of %u letters, 1 to %u expected", sigma, TM_LETTERS);
@@ -597,8 +514,7 @@ extern "C" int gtamd_tagmatch_set_index_pckidx(gtamd_tagmatch *tm, const gtamd_p
   }
   HIP_TRY(hipSetDevice(tm->device));
   tm->prepared = false;
-  tm->index.drop();
-  tm->pck = px;
+  tm->index.set_reader(px);
   tm->sigma = sigma;
   return 0;
   GTAMD_ABI_END(-1)
@@ -611,12 +527,9 @@ extern "C" int gtamd_tagmatch_prepare(gtamd_tagmatch *tm, const uint8_t *tags, c
     gtamd_set_error("invalid argument to gtamd_tagmatch_prepare");
     return -1;
   }
-  if (!tm->index.set && tm->pck == nullptr) {
-    gtamd_set_error("tag matches: no index is set (gtamd_tagmatch_set_index)");
-    return -1;
-  }
-  if (tm->pck != nullptr) {
-    TRY(refuse_lost_reader(tm));
+  TRY(tm->index.refuse_unset(FEATURE, "tagmatch"));
+  if (tm->index.pck != nullptr) {
+    TRY(tm->index.refuse_lost_reader(FEATURE));
     if (flags & GTAMD_TAGMATCH_WITH_WILDCARDS) {
       gtamd_set_error("tag matches: GTAMD_TAGMATCH_WITH_WILDCARDS is not taken with a packed index as the index "
                       "(include/gtamd_pcktag.h)");
@@ -649,6 +562,7 @@ extern "C" int gtamd_tagmatch_prepare(gtamd_tagmatch *tm, const uint8_t *tags, c
   }
   HIP_TRY(hipSetDevice(tm->device));
   tm->prepared = false;
+  if (tm->index.pck != nullptr) tm->index.stamp();
   tm->info = gtamd_tagmatch_info();
   tm->T = T;
   tm->flags = flags;
@@ -659,7 +573,7 @@ extern "C" int gtamd_tagmatch_prepare(gtamd_tagmatch *tm, const uint8_t *tags, c
     if (tm->jo.grow(tm->jobs) != hipSuccess || tm->kbest.grow(T * 4) != hipSuccess)
       return out_of_memory(FEATURE, tm->jobs, "jobs");
     TRY(tm->tags.set(FEATURE, "tag symbols", tags, offsets, T, is_device, tm->st));
-    TRY(tm->pck != nullptr ? prepare<void>(tm, K) : tm->index.suf_bytes == 4 ? prepare<u32>(tm, K) : prepare<u64>(tm, K));
+    TRY(tm->index.pck != nullptr ? prepare<void>(tm, K) : tm->index.tab.suf_bytes == 4 ? prepare<u32>(tm, K) : prepare<u64>(tm, K));
   }
   tm->info.device_bytes = held_bytes(tm);
   tm->prepared = true;
@@ -680,7 +594,10 @@ extern "C" int gtamd_tagmatch_emit(gtamd_tagmatch *tm, uint64_t *cursor, gtamd_t
     return -1;
   }
   HIP_TRY(hipSetDevice(tm->device));
-  TRY(emit(tm, cursor, out, capacity, out_on_device, written));
+  TRY(emit_jobs<TmRecord>(FEATURE, "gtamd_tagmatch_prepare", tm->index, tm->jo, tm->info.matches, cursor, capacity,
+                          TM_MIN_CAPACITY, out, out_on_device, tm->out, tm->st, tm->words + W_ERROR, written,
+                          [tm](u64 j0, u64 j1, u64 cur, u64 w1, TmRecord *dst) { launch_emit(tm, j0, j1, cur, w1, dst); }));
+  tm->info.emitted += *written;
   tm->info.device_bytes = held_bytes(tm);
   return 0;
   GTAMD_ABI_END(-1)

@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._consumer import Consumer, host_tables, ptr, record_chunks
+from ._consumer import Consumer, SufIndexSetters, gathered, pack_sequences, ptr, record_chunks
 from ._lib import LocaliInfo
 
 DEFAULT_CAPACITY = 1 << 20        # records of one emit call (32 bytes each)
@@ -37,15 +37,7 @@ def geometry():
     return waves.value, least.value, longest.value, stack.value
 
 
-def pack_queries(queries):
-    """(symbols, offsets) of a list of encoded queries: one uint8 array and the
-    len(queries) + 1 uint64 offsets into it"""
-    queries = [np.ascontiguousarray(q, dtype=np.uint8).reshape(-1) for q in queries]
-    offsets = np.zeros(len(queries) + 1, dtype=np.uint64)
-    if queries:
-        offsets[1:] = np.cumsum([q.size for q in queries])
-    symbols = np.concatenate(queries) if queries else np.zeros(0, dtype=np.uint8)
-    return symbols, offsets
+pack_queries = pack_sequences
 
 
 def unpack(records):
@@ -56,27 +48,11 @@ def unpack(records):
             records[:, 3] & low, records[:, 3] >> high)
 
 
-class LocalAlignments(Consumer):
+class LocalAlignments(SufIndexSetters, Consumer):
     """aligner over one index on one device"""
     NAME, INFO = "locali", LocaliInfo
 
     # -- the index: each call replaces the one before -------------------------
-    def set_index(self, enc, suf, numofchars=4):
-        """tables in host memory (numpy): enc uint8, n symbols; suf uint32 or
-        uint64, n + 1 entries; numofchars: letters of the alphabet"""
-        enc, suf = host_tables(enc, suf)
-        self._call("set_index_host", ptr(enc), enc.size, ptr(suf), suf.dtype.itemsize, numofchars)
-
-    def set_index_device(self, enc_ptr, n, suf_ptr, suf_bytes, numofchars=4):
-        """the same for raw device pointers, which must outlive the calls"""
-        self._call("set_index", enc_ptr, n, suf_ptr, suf_bytes, numofchars)
-
-    def set_index_engine(self, engine, enc_device_ptr, n, numofchars=4):
-        """the .suf table an EsaEngine holds after run() with esa.WANT_SUF
-        (forward read mode); enc_device_ptr: the n symbols, on the device.  The
-        engine must outlive the calls."""
-        self._call("set_index_esa", engine._ctx, enc_device_ptr, n, numofchars)
-
     def set_index_packed(self, reader):
         """a `pck.PackedIndexReader` with an open image
         (include/gtamd_pcklocali.h): the matches are those of the text the index
@@ -84,7 +60,7 @@ class LocalAlignments(Consumer):
         for the subject -- in the order of that header, which inside one query
         is not the order of the suffix table.  The reader must outlive the
         calls."""
-        _lib.check(self._lib.gtamd_locali_set_index_pckidx(self._p, reader._p))
+        self._call("set_index_pckidx", reader._p)
 
     def set_limits(self, stack_words=0, cut_depth=AUTO):
         """what the next prepare sizes itself by: the words of one wave's stack
@@ -123,5 +99,4 @@ class LocalAlignments(Consumer):
     def all_records(self, queries, T, match=1, mismatch=-1, gapextend=-1, capacity=DEFAULT_CAPACITY):
         """every record of `queries` as one numpy array of shape (matches, 4)"""
         self.prepare(queries, T, match, mismatch, gapextend)
-        chunks = list(self.records(capacity))
-        return np.concatenate(chunks) if chunks else np.zeros((0, 4), dtype=np.uint64)
+        return gathered(self.records(capacity), columns=4)

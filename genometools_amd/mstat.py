@@ -59,7 +59,7 @@ class MatchStats(Consumer):
         an index of the reversed subject answers for the subject -- and
         subjectpos is the reference's witness.  The reader must outlive the
         searches."""
-        _lib.check(self._lib.gtamd_mstat_set_index_pckidx(self._p, reader._p))
+        self._call("set_index_pckidx", reader._p)
 
     # -- the questions --------------------------------------------------------
     def matstat(self, query, max_len=0):

@@ -21,7 +21,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._consumer import Consumer, host_tables, ptr, record_chunks
+from ._consumer import Consumer, gathered, host_tables, ptr, record_chunks
 from ._lib import QmatchInfo
 
 DEFAULT_CAPACITY = 1 << 20        # records of one emit call (24 bytes each)
@@ -106,5 +106,4 @@ class QueryMatches(Consumer):
         sequence reversed, "rcl": reversed and complemented) as one numpy array
         of shape (matches, 3), in the coordinates of the transformed query"""
         self.prepare(transformed(query, readmode), min_len)
-        chunks = list(self.emit(capacity))
-        return np.concatenate(chunks) if chunks else np.zeros((0, 3), dtype=np.uint64)
+        return gathered(self.emit(capacity))

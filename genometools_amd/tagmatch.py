@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._consumer import Consumer, host_tables, ptr, record_chunks
+from ._consumer import Consumer, SufIndexSetters, gathered, pack_sequences, ptr, record_chunks
 from ._lib import TagmatchInfo
 
 DEFAULT_CAPACITY = 1 << 20        # records of one emit call (24 bytes each)
@@ -37,15 +37,7 @@ def geometry():
     return waves.value, least.value, levels.value
 
 
-def pack_tags(tags):
-    """(symbols, offsets) of a list of encoded tags: one uint8 array and the
-    len(tags) + 1 uint64 offsets into it"""
-    tags = [np.ascontiguousarray(t, dtype=np.uint8).reshape(-1) for t in tags]
-    offsets = np.zeros(len(tags) + 1, dtype=np.uint64)
-    if tags:
-        offsets[1:] = np.cumsum([t.size for t in tags])
-    symbols = np.concatenate(tags) if tags else np.zeros(0, dtype=np.uint8)
-    return symbols, offsets
+pack_tags = pack_sequences
 
 
 def unpack(records):
@@ -56,27 +48,11 @@ def unpack(records):
             records[:, 2] & np.uint64(0xffffffff), records[:, 2] >> np.uint64(32))
 
 
-class TagMatches(Consumer):
+class TagMatches(SufIndexSetters, Consumer):
     """matcher over one index on one device"""
     NAME, INFO = "tagmatch", TagmatchInfo
 
     # -- the index: each call replaces the one before -------------------------
-    def set_index(self, enc, suf, numofchars=4):
-        """tables in host memory (numpy): enc uint8, n symbols; suf uint32 or
-        uint64, n + 1 entries; numofchars: letters of the alphabet"""
-        enc, suf = host_tables(enc, suf)
-        self._call("set_index_host", ptr(enc), enc.size, ptr(suf), suf.dtype.itemsize, numofchars)
-
-    def set_index_device(self, enc_ptr, n, suf_ptr, suf_bytes, numofchars=4):
-        """the same for raw device pointers, which must outlive the calls"""
-        self._call("set_index", enc_ptr, n, suf_ptr, suf_bytes, numofchars)
-
-    def set_index_engine(self, engine, enc_device_ptr, n, numofchars=4):
-        """the .suf table an EsaEngine holds after run() with esa.WANT_SUF
-        (forward read mode); enc_device_ptr: the n symbols, on the device.  The
-        engine must outlive the calls."""
-        self._call("set_index_esa", engine._ctx, enc_device_ptr, n, numofchars)
-
     def set_index_packed(self, reader):
         """a `pck.PackedIndexReader` with an open image (include/gtamd_pcktag.h):
         the matches are those of the text the index was built from read
@@ -84,7 +60,7 @@ class TagMatches(Consumer):
         in the order of that header, which inside one (tag, strand) is not the
         order of the suffix table; WITH_WILDCARDS is refused.  The reader must
         outlive the calls."""
-        _lib.check(self._lib.gtamd_tagmatch_set_index_pckidx(self._p, reader._p))
+        self._call("set_index_pckidx", reader._p)
 
     # -- the enumeration ------------------------------------------------------
     def prepare(self, tags, K, flags=FORWARD | REVCOMP):
@@ -125,5 +101,4 @@ class TagMatches(Consumer):
     def all_records(self, tags, K, flags=FORWARD | REVCOMP, capacity=DEFAULT_CAPACITY):
         """every record of `tags` as one numpy array of shape (matches, 3)"""
         self.prepare(tags, K, flags)
-        chunks = list(self.records(capacity))
-        return np.concatenate(chunks) if chunks else np.zeros((0, 3), dtype=np.uint64)
+        return gathered(self.records(capacity))

@@ -81,7 +81,10 @@ extern "C" {
    replace each other and what was prepared.  Refused with a message: a reader
    without an open image, one on another device.  The reader must outlive the
    calls and keep its image: after an open of the reader that failed, prepare and
-   emit are refused with a message until the reader holds an image again. */
+   emit are refused with a message until the reader holds an image again.  A
+   prepare is of the image the reader holds then; emit is refused with a message
+   once the reader has been opened again since that prepare, gtamd_tagmatch_best_k
+   is not: it reads only what the prepare left. */
 int gtamd_tagmatch_set_index_pckidx(gtamd_tagmatch *tm, const gtamd_pckidx *px);
 
 #ifdef __cplusplus

@@ -443,6 +443,50 @@ def test_refusals(tools):
         tools["matcher"].prepare([np.array([0, 1, 5, 2], dtype=np.uint8)], 1, FORWARD)
 
 
+def test_a_reader_opened_again_since_prepare(tools):
+    """the places of the jobs and K' are of the image that prepare walked: emit,
+    to host or to device memory, refuses the reader once it was opened again, be
+    it on the same bytes; K' stays readable, and a new prepare is of the new image"""
+    enc = _with_specials(2000, 4, 3)
+    tag = _cut(enc, 5, 12)
+    with tagmatch.TagMatches() as f:
+        reader = _open(tools, enc)
+        raw = tools["builder"].image()
+        f.set_index_packed(reader)
+        want = f.all_records([tag], 1)
+        best = f.best_k()
+        assert want.shape[0] >= 1 and best.tolist() == [1]
+        f.prepare([tag], 1)
+        reader.open(raw)
+        for device in (False, True):
+            with pytest.raises(_lib.EsaError, match="tag matches: the packed index reader was opened again since "
+                                                    "gtamd_tagmatch_prepare: what was prepared is of the image before"):
+                list(f.records(device=device))
+        assert np.array_equal(f.best_k(), best) and f.info()["emitted"] == 0
+        assert np.array_equal(f.all_records([tag], 1), want)
+
+
+def test_tables_are_not_held_to_the_image_of_a_reader(tools):
+    """the object goes from the reader to tables: however often the reader is
+    opened after that, before or after the prepare, emit gives the records of the tables"""
+    enc = _with_specials(2000, 4, 3)
+    tag = _cut(enc, 5, 12)
+    suf = ou.esa(enc, 4)["suf"]
+    want, _ = tr.expected(enc, suf, [tag], 1)
+    assert want.shape[0] >= 1
+    with tagmatch.TagMatches() as f:
+        reader = _open(tools, enc)
+        raw = tools["builder"].image()
+        f.set_index_packed(reader)
+        f.prepare([tag], 1)
+        f.set_index(enc, suf)
+        reader.open(raw)
+        f.prepare([tag], 1)
+        reader.open(raw)
+        reader.open(raw)
+        assert np.array_equal(np.concatenate(list(f.records())), want)
+
+
 def test_switching_between_a_suffix_table_and_a_packed_index(tools):
     """on one object, in both directions: the records of the suffix table are those
     of tests/test_tagmatch_gpu.py's small subject, in its order, before and after"""
