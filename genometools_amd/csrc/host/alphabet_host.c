@@ -30,6 +30,12 @@ void gtamd_alphabet_free(gtamd_alphabet *a)
   if (a != NULL) { free(a->alphadef); a->alphadef = NULL; a->lengthofalphadef = 0; }
 }
 
+int gtamd_alphabet_is_dna(const gtamd_alphabet *a)
+{
+  return a->numofchars == 4 && a->symbolmap['a'] == 0 && a->symbolmap['c'] == 1 && a->symbolmap['g'] == 2 &&
+         a->symbolmap['t'] == 3;
+}
+
 int gtamd_alphabet_from_text(const char *text, uint64_t len, const char *mapfile,
                              gtamd_alphabet *a, char *err, size_t errlen)
 {

@@ -83,4 +83,95 @@ void gtamd_analysis_from_summary(const gtamd_encode_summary *s, uint32_t numofch
    src/core/encseq.c:924-949 */
 uint64_t gtamd_swtable_bytes(int width_kind, int withrangelengths, uint64_t n,
                              uint64_t items);
+
+/* What follows is shared between the tools of this directory and stays inside
+   libgtamd_host.so. */
+#define GTAMD_INTERNAL __attribute__((visibility("hidden")))
+
+/* acgt as codes 0..3 and nothing else: the alphabet whose letters have a
+   complement (alphabet_host.c) */
+GTAMD_INTERNAL int gtamd_alphabet_is_dna(const gtamd_alphabet *a);
+
+/* ---- cli_host.c: the pieces of an option parser ---- */
+
+/* -1, with msg (one %s at most, filled from arg) or a format in err */
+GTAMD_INTERNAL int gtamd_fail(char *err, size_t errlen, const char *msg, const char *arg);
+GTAMD_INTERNAL int gtamd_failf(char *err, size_t errlen, const char *fmt, ...)
+  __attribute__((format(printf, 3, 4)));
+
+/* The argument(s) of option argv[*i]; *i moves to the last one taken.  0, or -1
+   with the message of the reference's parser. */
+GTAMD_INTERNAL int gtamd_opt_name(int argc, const char **argv, int *i, const char **name, char *err,
+                                  size_t errlen);
+GTAMD_INTERNAL int gtamd_opt_uint32(int argc, const char **argv, int *i, uint32_t *out, char *err,
+                                    size_t errlen);
+/* a length: 1 .. max */
+GTAMD_INTERNAL int gtamd_opt_length(int argc, const char **argv, int *i, unsigned long long max,
+                                    unsigned long long *out, char *err, size_t errlen);
+/* file names up to the next option, one at least */
+GTAMD_INTERNAL int gtamd_opt_files(int argc, const char **argv, int *i, const char *const **files,
+                                   size_t *numfiles, char *err, size_t errlen);
+/* a switch: on, unless "no" follows (yes|no) or "no" / "false" (yes|true|no|false) */
+GTAMD_INTERNAL int gtamd_opt_yesno(int argc, const char **argv, int *i);
+GTAMD_INTERNAL int gtamd_opt_switch(int argc, const char **argv, int *i);
+
+/* The end of a parser loop, for an argument `a` no clause has taken: -1 with
+   "is not supported" for a name on the NULL-terminated list `refused` (may be
+   NULL), with `unknown` for another option, with `superfluous` for a word.  The
+   reference has two parsers and words both in several ways: */
+#define GTAMD_UNKNOWN_TRY "unknown option: %s (try -help)"
+#define GTAMD_UNKNOWN_SHOWS "unknown option: %s (-help shows possible options)"
+#define GTAMD_SUPERFLUOUS_ONE "superfluous argument \"%s\""
+#define GTAMD_SUPERFLUOUS_MORE "superfluous arguments: \"%s\""
+#define GTAMD_UNNECESSARY "unnecessary arguments"
+GTAMD_INTERNAL int gtamd_opt_unsupported(const char *a, char *err, size_t errlen);
+GTAMD_INTERNAL int gtamd_opt_tail(const char *a, const char *const *refused, const char *unknown,
+                                  const char *superfluous, char *err, size_t errlen);
+
+/* ---- project_host.c: a project read back ----
+   Nothing there calls the engine: it links into a program without it. */
+
+/* the single-build limit of the engine: tables of more entries come in slices */
+#define GTAMD_MAX_ENTRIES ((1ull << 32) - 4096)
+
+/* one "key=value" line of INDEX.prj; -1 when the file or the key is not there */
+GTAMD_INTERNAL int gtamd_prj_value(const char *path, const char *key, unsigned long long *value);
+
+typedef struct { void *p; uint64_t bytes; } gtamd_mapped;
+
+typedef struct {
+  uint8_t *enc;                   /* the symbols the tables describe */
+  uint64_t n;
+  gtamd_alphabet alpha;           /* of INDEX.esq, once have_alpha is set */
+  int have_alpha;
+  gtamd_mapped suf, lcp, llv, bwt;
+  uint32_t suf_bytes;             /* 8, or 4 with -suftabuint, once .suf is mapped */
+  uint64_t *seqstart, numseq;     /* numseq starts and n + 1 behind them */
+} gtamd_project;
+
+/* Each call takes a zeroed or an opened value and leaves one that
+   gtamd_project_close releases; -1 with a message in err. */
+
+/* which projects a tool takes: any, or forward and not mirrored only, refused
+   in one sentence or in one of two; both name `tool` */
+enum { GTAMD_PROJECT_ANY = 0, GTAMD_PROJECT_FORWARD, GTAMD_PROJECT_FORWARD_TWO };
+/* The sequence the tables of a project describe: the symbols of INDEX.esq, then
+   -mirrored, then -dir, as INDEX.prj says.  Refuses a project without whole
+   tables; `verb` words what is not done with the slices of a build in parts. */
+GTAMD_INTERNAL int gtamd_project_open(gtamd_project *p, const char *index, const char *verb, int which,
+                                      const char *tool, char *err, size_t errlen);
+/* INDEX.suf / .lcp / .llv / .bwt into p->suf ..., its size checked against n.
+   required: the reference's wording when the file is not there, with the reason. */
+enum { GTAMD_TABLE_SUF = 0, GTAMD_TABLE_LCP, GTAMD_TABLE_LLV, GTAMD_TABLE_BWT };
+GTAMD_INTERNAL int gtamd_project_map(gtamd_project *p, const char *index, int table, int required,
+                                     char *err, size_t errlen);
+/* p->seqstart and p->numseq; -1 when memory runs out, without a message */
+GTAMD_INTERNAL int gtamd_project_sequence_starts(gtamd_project *p);
+GTAMD_INTERNAL void gtamd_project_close(gtamd_project *p);
+
+/* where the sequences of seq[0..len) start: behind the separators; *num = their
+   number, and one more entry, len + 1, as if one more separator followed */
+GTAMD_INTERNAL uint64_t *gtamd_sequence_starts(const uint8_t *seq, uint64_t len, uint64_t *num);
+/* the last of the numstart ascending starts at or in front of pos */
+GTAMD_INTERNAL uint64_t gtamd_unit_of(const uint64_t *start, uint64_t numstart, uint64_t pos);
 #endif

@@ -9,12 +9,12 @@
    The device gives (dbstart, dblen, score, qstart, qlen) and no edit script: for
    -s the alignment of a match is rebuilt here, from the columns 1 .. dblen of its
    start position with stored traces and the traceback from the row qstart +
-   qlen, by the column rule of the header.
-
-   Not compiled on its own: pck_host.c includes this file at its end, behind
-   tagmatch_host.c and for the same reason (see the head of that file). */
+   qlen, by the column rule of the header. */
 #include "host_internal.h"
 #include "gtamd_locali.h"
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
 
 #define IDXLOCALI_CAPACITY (1u << 20)            /* records of one gtamd_locali_emit */
 
@@ -34,7 +34,7 @@ static int read_queries(const char *const *paths, size_t numfiles, const gtamd_a
   ql->symbols = malloc(cap_sym);
   ql->offsets = malloc(cap_off * sizeof *ql->offsets);
   ql->count = 0;
-  if (ql->symbols == NULL || ql->offsets == NULL) return pfail(err, errlen, "out of memory (%s)", "queries");
+  if (ql->symbols == NULL || ql->offsets == NULL) return gtamd_fail(err, errlen, "out of memory (%s)", "queries");
   ql->offsets[0] = 0;
   for (size_t f = 0; f < numfiles; f++) {
     uint8_t *data = NULL;
@@ -46,7 +46,7 @@ static int read_queries(const char *const *paths, size_t numfiles, const gtamd_a
     }
     if (len > 0 && data[0] != '>') {
       free(data);
-      return pfail(err, errlen, "the first character of fasta file \"%s\" has to be '>'", paths[f]);
+      return gtamd_fail(err, errlen, "the first character of fasta file \"%s\" has to be '>'", paths[f]);
     }
     while (i < len) {
       while (i < len && data[i] != '\n') i++;            /* the description */
@@ -63,14 +63,14 @@ static int read_queries(const char *const *paths, size_t numfiles, const gtamd_a
         }
         if (used == cap_sym) {
           uint8_t *grown = realloc(ql->symbols, cap_sym *= 2);
-          if (grown == NULL) { free(data); return pfail(err, errlen, "out of memory (%s)", "queries"); }
+          if (grown == NULL) { free(data); return gtamd_fail(err, errlen, "out of memory (%s)", "queries"); }
           ql->symbols = grown;
         }
         ql->symbols[used++] = code;
       }
       if (ql->count + 1 == cap_off) {
         uint64_t *grown = realloc(ql->offsets, (cap_off *= 2) * sizeof *ql->offsets);
-        if (grown == NULL) { free(data); return pfail(err, errlen, "out of memory (%s)", "queries"); }
+        if (grown == NULL) { free(data); return gtamd_fail(err, errlen, "out of memory (%s)", "queries"); }
         ql->offsets = grown;
       }
       ql->offsets[++ql->count] = used;
@@ -161,11 +161,11 @@ done:
 static int int_option(int argc, const char **argv, int *i, long *value, char *err, size_t errlen)
 {
   char *end;
-  if (*i + 1 >= argc) return pfail(err, errlen, "missing argument to option \"%s\"", argv[*i]);
+  if (*i + 1 >= argc) return gtamd_fail(err, errlen, "missing argument to option \"%s\"", argv[*i]);
   *value = strtol(argv[*i + 1], &end, 10);
   if (*end != 0 || end == argv[*i + 1]) {
-    if (argv[*i + 1][0] == '-') return pfail(err, errlen, "missing argument to option \"%s\"", argv[*i]);
-    return pfail(err, errlen, "argument to option \"%s\" must be an integer", argv[*i]);
+    if (argv[*i + 1][0] == '-') return gtamd_fail(err, errlen, "missing argument to option \"%s\"", argv[*i]);
+    return gtamd_fail(err, errlen, "argument to option \"%s\" must be an integer", argv[*i]);
   }
   (*i)++;
   return 0;
@@ -177,13 +177,9 @@ int gtamd_idxlocali(int argc, const char **argv, char *err, size_t errlen)
   const char *index = NULL, *const *queryfiles = NULL;
   size_t numqueryfiles = 0;
   long match = 1, mismatch = -3, gapstart = -5, gapextend = -2, threshold = 0;
-  int have_th = 0, showalignment = 0, verbose = 0, have_alpha = 0, rc = -1;
-  char path[4096];
-  uint8_t *enc = NULL;
-  uint64_t n = 0, N, numseq = 1, *seqstart = NULL, next = 0;
-  uint32_t suf_bytes = 8;
-  mapped suf = { NULL, 0 };
-  gtamd_alphabet alpha;
+  int have_th = 0, showalignment = 0, verbose = 0, rc = -1;
+  uint64_t next = 0;
+  gtamd_project prj = { 0 };
   querylist ql = { NULL, NULL, 0 };
   gtamd_locali *lc = NULL;
   gtamd_locali_info info;
@@ -191,26 +187,22 @@ int gtamd_idxlocali(int argc, const char **argv, char *err, size_t errlen)
 
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
-    if (!strcmp(a, "-esa")) {
-      if (i + 1 >= argc) return pfail(err, errlen, "missing argument to option \"%s\"", a);
-      index = argv[++i];
-    } else if (!strcmp(a, "-th")) {
+    if (!strcmp(a, "-esa")) { if (gtamd_opt_name(argc, argv, &i, &index, err, errlen) != 0) return -1; }
+    else if (!strcmp(a, "-th")) {
       /* (an unsigned option of the reference's parser: "-3" is the next option, not a number) */
-      if (i + 1 < argc && argv[i + 1][0] == '-') return pfail(err, errlen, "missing argument to option \"%s\"", a);
+      if (i + 1 < argc && argv[i + 1][0] == '-') return gtamd_fail(err, errlen, "missing argument to option \"%s\"", a);
       if (int_option(argc, argv, &i, &threshold, err, errlen) != 0)
-        return i + 1 < argc ? pfail(err, errlen, "argument to option \"%s\" is out of range", a) : -1;
-      if (threshold < 1) return pfail(err, errlen, "argument to option \"%s\" must be an integer >= 1", a);
+        return i + 1 < argc ? gtamd_fail(err, errlen, "argument to option \"%s\" is out of range", a) : -1;
+      if (threshold < 1) return gtamd_fail(err, errlen, "argument to option \"%s\" must be an integer >= 1", a);
       have_th = 1;
     } else if (!strcmp(a, "-match")) { if (int_option(argc, argv, &i, &match, err, errlen) != 0) return -1; }
     else if (!strcmp(a, "-mismatch")) { if (int_option(argc, argv, &i, &mismatch, err, errlen) != 0) return -1; }
     else if (!strcmp(a, "-gapstart")) { if (int_option(argc, argv, &i, &gapstart, err, errlen) != 0) return -1; }
     else if (!strcmp(a, "-gapextend")) { if (int_option(argc, argv, &i, &gapextend, err, errlen) != 0) return -1; }
     else if (!strcmp(a, "-q")) {
-      queryfiles = argv + i + 1;
-      for (numqueryfiles = 0; i + 1 < argc && argv[i + 1][0] != '-'; i++) numqueryfiles++;
-      if (numqueryfiles == 0) return pfail(err, errlen, "missing argument to option \"%s\"", a);
-    } else if (!strcmp(a, "-s")) showalignment = switch_option(argc, argv, &i);
-    else if (!strcmp(a, "-v")) verbose = switch_option(argc, argv, &i);
+      if (gtamd_opt_files(argc, argv, &i, &queryfiles, &numqueryfiles, err, errlen) != 0) return -1;
+    } else if (!strcmp(a, "-s")) showalignment = gtamd_opt_switch(argc, argv, &i);
+    else if (!strcmp(a, "-v")) verbose = gtamd_opt_switch(argc, argv, &i);
     else if (!strcmp(a, "-help")) {
       puts("Usage: gt-suffixerator-amd idxlocali [options] -q query-file-names -esa indexname\n"
            "Find all local alignments using the suffix table, on the device.\n\n"
@@ -228,18 +220,12 @@ int gtamd_idxlocali(int argc, const char **argv, char *err, size_t errlen)
            "table.  A match score that is not positive, and a mismatch or gap extension score that is not negative,\n"
            "are refused (the reference takes them, and need not end then).  -pck, -online and -cmp are refused.");
       return 0;
-    } else {
-      for (int k = 0; not_here[k] != NULL; k++)
-        if (!strcmp(a, not_here[k]))
-          return pfail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
-      if (a[0] == '-') return pfail(err, errlen, "unknown option: %s (try -help)", a);
-      return pfail(err, errlen, "superfluous arguments: \"%s\"", a);
-    }
+    } else return gtamd_opt_tail(a, not_here, GTAMD_UNKNOWN_TRY, GTAMD_SUPERFLUOUS_MORE, err, errlen);
   }
   (void) gapstart;
-  if (queryfiles == NULL) return pfail(err, errlen, "option \"-%s\" is mandatory", "q");
-  if (!have_th) return pfail(err, errlen, "option \"-%s\" is mandatory", "th");
-  if (index == NULL) return pfail(err, errlen, "either option \"-esa\" or option \"-%s\" is mandatory", "pck");
+  if (queryfiles == NULL) return gtamd_fail(err, errlen, "option \"-%s\" is mandatory", "q");
+  if (!have_th) return gtamd_fail(err, errlen, "option \"-%s\" is mandatory", "th");
+  if (index == NULL) return gtamd_fail(err, errlen, "either option \"-esa\" or option \"-%s\" is mandatory", "pck");
   if (match <= 0 || mismatch >= 0 || gapextend >= 0 || match > 32767 || mismatch < -32767 || gapextend < -32767)
   {
     snprintf(err, errlen, "scores -match %ld -mismatch %ld -gapextend %ld: the match score must be in 1..32767, the "
@@ -253,43 +239,19 @@ int gtamd_idxlocali(int argc, const char **argv, char *err, size_t errlen)
   for (size_t f = 0; f < numqueryfiles; f++) printf("# queryfile=%s\n", queryfiles[f]);
   printf("# threshold=%ld\n", threshold);
 
-  {
-    unsigned long long readmode = 0, mirrored = 0;
-    snprintf(path, sizeof path, "%s.prj", index);
-    (void) prj_value(path, "readmode", &readmode);
-    (void) prj_value(path, "mirrored", &mirrored);
-    if (readmode != 0 || mirrored) {
-      pfail(err, errlen, "file '%s' describes a mirrored index or one of a read mode other than forward: such an "
-           "index is not supported by the MI355X engine's idxlocali", path);
-      goto done;
-    }
-  }
-  if (load_project_sequence(index, "searched", &enc, &n, &alpha, err, errlen) != 0) goto done;
-  have_alpha = 1;
-  N = n + 1;
-  if (map_required(index, ".suf", &suf, path, sizeof path, err, errlen) != 0) goto done;
-  if (suf.bytes == 4 * N) suf_bytes = 4;
-  else if (suf.bytes != 8 * N) {
-    snprintf(err, errlen, "file '%s' has %llu bytes, %llu (-suftabuint) or %llu expected for %llu entries",
-             path, (unsigned long long) suf.bytes, (unsigned long long) (4 * N),
-             (unsigned long long) (8 * N), (unsigned long long) N);
+  if (gtamd_project_open(&prj, index, "searched", GTAMD_PROJECT_FORWARD, "idxlocali", err, errlen) != 0 ||
+      gtamd_project_map(&prj, index, GTAMD_TABLE_SUF, 1, err, errlen) != 0 ||
+      read_queries(queryfiles, numqueryfiles, &prj.alpha, &ql, err, errlen) != 0)
     goto done;
-  }
-  if (read_queries(queryfiles, numqueryfiles, &alpha, &ql, err, errlen) != 0) goto done;
-  for (uint64_t p = 0; p < n; p++) numseq += enc[p] == 255;
-  seqstart = malloc(numseq * sizeof *seqstart);
   rec = malloc(IDXLOCALI_CAPACITY * sizeof *rec);
-  if (seqstart == NULL || rec == NULL) {
-    pfail(err, errlen, "out of memory (%s)", "records");
+  if (gtamd_project_sequence_starts(&prj) != 0 || rec == NULL) {
+    gtamd_fail(err, errlen, "out of memory (%s)", "records");
     goto done;
   }
-  seqstart[0] = 0;
-  for (uint64_t p = 0, k = 1; p < n; p++)
-    if (enc[p] == 255) seqstart[k++] = p + 1;
 
   if (ql.count > 0) {
     if ((lc = gtamd_locali_create(0)) == NULL ||
-        gtamd_locali_set_index_host(lc, enc, n, suf.p, suf_bytes, alpha.numofchars) != 0 ||
+        gtamd_locali_set_index_host(lc, prj.enc, prj.n, prj.suf.p, prj.suf_bytes, prj.alpha.numofchars) != 0 ||
         gtamd_locali_prepare(lc, ql.symbols, ql.offsets, ql.count, 0, (int32_t) match, (int32_t) mismatch,
                              (int32_t) gapextend, (uint32_t) threshold, &info) != 0) {
       snprintf(err, errlen, "%s", gtamd_esa_last_error());
@@ -304,19 +266,15 @@ int gtamd_idxlocali(int argc, const char **argv, char *err, size_t errlen)
         const uint64_t t = rec[k].query, p = rec[k].dbstart;
         const uint32_t dblen = (uint32_t) rec[k].lenscore, score = (uint32_t) (rec[k].lenscore >> 32);
         const uint32_t qstart = (uint32_t) rec[k].qspan, qlen = (uint32_t) (rec[k].qspan >> 32);
-        uint64_t lo = 0, hi = numseq;                   /* the last sequence that starts at or in front of p */
+        const uint64_t seq = gtamd_unit_of(prj.seqstart, prj.numseq, p);
         for (; next <= t; next++)                       /* the lines of the queries up to this one */
           printf("process sequence %llu of length %llu\n", (unsigned long long) next,
                  (unsigned long long) (ql.offsets[next + 1] - ql.offsets[next]));
-        while (hi - lo > 1) {
-          const uint64_t mid = lo + (hi - lo) / 2;
-          if (seqstart[mid] <= p) lo = mid; else hi = mid;
-        }
-        printf("%llu\t%llu\t%u\t\t%llu\t%u\t%u\t%u\n", (unsigned long long) lo, (unsigned long long) (p - seqstart[lo]),
-               dblen, (unsigned long long) t, qstart, qlen, score);
+        printf("%llu\t%llu\t%u\t\t%llu\t%u\t%u\t%u\n", (unsigned long long) seq,
+               (unsigned long long) (p - prj.seqstart[seq]), dblen, (unsigned long long) t, qstart, qlen, score);
         if (showalignment &&
-            (t >= ql.count || p + dblen > n || (uint64_t) qstart + qlen > ql.offsets[t + 1] - ql.offsets[t] ||
-             show_alignment(stdout, &alpha, enc, p, dblen, ql.symbols + ql.offsets[t],
+            (t >= ql.count || p + dblen > prj.n || (uint64_t) qstart + qlen > ql.offsets[t + 1] - ql.offsets[t] ||
+             show_alignment(stdout, &prj.alpha, prj.enc, p, dblen, ql.symbols + ql.offsets[t],
                             (uint32_t) (ql.offsets[t + 1] - ql.offsets[t]), qstart + qlen, (int) match, (int) mismatch,
                             (int) gapextend, 70) != 0)) {
           snprintf(err, errlen, "the match at position %llu of query %llu has no alignment: the index is damaged, or "
@@ -336,13 +294,12 @@ int gtamd_idxlocali(int argc, const char **argv, char *err, size_t errlen)
              (unsigned long long) info.children_examined, (unsigned long long) info.levels_pushed,
              (unsigned long long) info.single_walks, (unsigned long long) info.jobs_finished_alone, info.device_ms);
   }
-  if (fflush(stdout) != 0) { pfail(err, errlen, "cannot write to %s", "stdout"); goto done; }
+  if (fflush(stdout) != 0) { gtamd_fail(err, errlen, "cannot write to %s", "stdout"); goto done; }
   rc = 0;
 done:
   fflush(stdout);
   gtamd_locali_destroy(lc);
-  unmap_file(&suf);
-  if (have_alpha) gtamd_alphabet_free(&alpha);
-  free(rec); free(seqstart); free(ql.offsets); free(ql.symbols); free(enc);
+  gtamd_project_close(&prj);
+  free(rec); free(ql.offsets); free(ql.symbols);
   return rc;
 }

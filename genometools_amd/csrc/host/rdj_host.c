@@ -5,13 +5,13 @@
    as lines or as Readjoiner's binary list X.0.spm (src/match/rdj-spmlist.c:45-124),
    which is what `gt readjoiner assembly` opens.  The stdout is the reference's
    byte for byte but for the order of the match lines, which is the table's here
-   and the reference's traversal's there.
-
-   Not compiled on its own: pck_host.c includes this file at its end, as it does
-   tagmatch_host.c (see there), and takes pfail and switch_option from what stands
-   in front of it. */
+   and the reference's traversal's there. */
 #include "host_internal.h"
 #include "gtamd_spmred.h"
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
 
 #define RDJ_CAPACITY (1u << 20)                  /* records of one gtamd_spmred_emit */
 #define RDJ_VERSION "1.2"                        /* GT_READJOINER_VERSION */
@@ -41,7 +41,7 @@ int gtamd_spmlist_bin32_records(FILE *fp, const gtamd_spmred_record *rec, uint64
       buf[3 * fill + 1] = (uint32_t) rec[k].prefix_read;
       buf[3 * fill + 2] = (uint32_t) (rec[k].len << 2 | rec[k].flags);
     }
-    if (fwrite(buf, 3 * sizeof buf[0], fill, fp) != fill) return pfail(err, errlen, "cannot write %s", "the list of matches");
+    if (fwrite(buf, 3 * sizeof buf[0], fill, fp) != fill) return gtamd_fail(err, errlen, "cannot write %s", "the list of matches");
   }
   return 0;
 }
@@ -52,7 +52,7 @@ int gtamd_readjoiner_overlap(int argc, const char **argv, char *err, size_t errl
   static const char *const refused[] = {
     "-parts", "-memlimit", "-wmax", "-phase2extra", "-radixparts", "-radixsmall", "-onlyallfirstcodes", NULL };
   const char *readset = NULL;
-  int have_l = 0, elimtrans = 1, showspm = 0, quiet = 0, verbose = 0, rc = -1, dnalike;
+  int have_l = 0, elimtrans = 1, showspm = 0, quiet = 0, verbose = 0, rc = -1;
   unsigned long long minlen = 0;
   char path[4096];
   uint8_t *enc = NULL, *both = NULL;
@@ -70,25 +70,23 @@ int gtamd_readjoiner_overlap(int argc, const char **argv, char *err, size_t errl
 
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
-    if (!strcmp(a, "-readset")) {
-      if (i + 1 >= argc) return pfail(err, errlen, "missing argument to option \"%s\"", a);
-      readset = argv[++i];
-    } else if (!strcmp(a, "-l")) {
+    if (!strcmp(a, "-readset")) { if (gtamd_opt_name(argc, argv, &i, &readset, err, errlen) != 0) return -1; }
+    else if (!strcmp(a, "-l")) {
       /* (gt_option_new_uint_min(..., 2U): the words of the reference's parser) */
       char *end;
-      if (i + 1 >= argc || argv[i + 1][0] == '-') return pfail(err, errlen, "missing argument to option \"%s\"", a);
+      if (i + 1 >= argc || argv[i + 1][0] == '-') return gtamd_fail(err, errlen, "missing argument to option \"%s\"", a);
       minlen = strtoull(argv[++i], &end, 10);
       if (*end != 0 || end == argv[i] || minlen > 0xffffffffull)
-        return pfail(err, errlen, "argument to option \"%s\" must be a non-negative integer <= 4294967295", a);
-      if (minlen < 2) return pfail(err, errlen, "argument to option \"%s\" must be an integer >= 2", a);
+        return gtamd_fail(err, errlen, "argument to option \"%s\" must be a non-negative integer <= 4294967295", a);
+      if (minlen < 2) return gtamd_fail(err, errlen, "argument to option \"%s\" must be an integer >= 2", a);
       have_l = 1;
-    } else if (!strcmp(a, "-elimtrans")) elimtrans = switch_option(argc, argv, &i);
-    else if (!strcmp(a, "-showspm")) showspm = switch_option(argc, argv, &i);
-    else if (!strcmp(a, "-q")) quiet = switch_option(argc, argv, &i);
-    else if (!strcmp(a, "-v")) verbose = switch_option(argc, argv, &i);
+    } else if (!strcmp(a, "-elimtrans")) elimtrans = gtamd_opt_switch(argc, argv, &i);
+    else if (!strcmp(a, "-showspm")) showspm = gtamd_opt_switch(argc, argv, &i);
+    else if (!strcmp(a, "-q")) quiet = gtamd_opt_switch(argc, argv, &i);
+    else if (!strcmp(a, "-v")) verbose = gtamd_opt_switch(argc, argv, &i);
     else if (!strcmp(a, "-singlestrand")) {
-      if (!switch_option(argc, argv, &i)) continue;
-      return pfail(err, errlen, "option %s is not implemented", a);
+      if (!gtamd_opt_switch(argc, argv, &i)) continue;
+      return gtamd_fail(err, errlen, "option %s is not implemented", a);
     } else if (!strcmp(a, "-help")) {
       puts("Usage: gt-suffixerator-amd readjoiner overlap -readset X -l L [-elimtrans yes|no] [-showspm] [-q] [-v]\n"
            "Compute the irreducible suffix-prefix matches of the reads of X and their reverse complements on\n"
@@ -110,37 +108,29 @@ int gtamd_readjoiner_overlap(int argc, const char **argv, char *err, size_t errl
            "is refused: filter it with gt readjoiner prefilter.  -singlestrand is not implemented; the options\n"
            "of the reference's own sort are refused.");
       return 0;
-    } else {
-      for (int k = 0; refused[k] != NULL; k++)
-        if (!strcmp(a, refused[k]))
-          return pfail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
-      if (a[0] == '-') return pfail(err, errlen, "unknown option: %s (-help shows possible options)", a);
-      return pfail(err, errlen, "unnecessary %s", "arguments");
-    }
+    } else return gtamd_opt_tail(a, refused, GTAMD_UNKNOWN_SHOWS, GTAMD_UNNECESSARY, err, errlen);
   }
-  if (readset == NULL) return pfail(err, errlen, "option \"-%s\" is mandatory", "readset");
-  if (!have_l) return pfail(err, errlen, "option \"-%s\" is mandatory", "l");
-  if (quiet && verbose) return pfail(err, errlen, "option \"-v\" and option \"-q\" exclude %s", "each other");
+  if (readset == NULL) return gtamd_fail(err, errlen, "option \"-%s\" is mandatory", "readset");
+  if (!have_l) return gtamd_fail(err, errlen, "option \"-%s\" is mandatory", "l");
+  if (quiet && verbose) return gtamd_fail(err, errlen, "option \"-v\" and option \"-q\" exclude %s", "each other");
 
   if (!quiet) printf("# gt readjoiner overlap (version " RDJ_VERSION ")\n");
   if (verbose) printf("# verbose output activated\n");
   snprintf(path, sizeof path, "%s.esq", readset);
-  if (access(path, R_OK) != 0) return pfail(err, errlen, "cannot open file '%s'", path);
+  if (access(path, R_OK) != 0) return gtamd_fail(err, errlen, "cannot open file '%s'", path);
   if (gtamd_read_esq_alpha(readset, &enc, &n, &alpha, &ss, err, errlen) != 0) return -1;
-  dnalike = alpha.numofchars == 4 && alpha.symbolmap['a'] == 0 && alpha.symbolmap['c'] == 1 &&
-            alpha.symbolmap['g'] == 2 && alpha.symbolmap['t'] == 3;
-  if (!dnalike) {
+  if (!gtamd_alphabet_is_dna(&alpha)) {
     snprintf(err, errlen, "mirroring can only be enabled for DNA sequences, this encoded sequence has "
              "alphabet: %.*s", (int) alpha.numofchars, alpha.characters);
     goto done;
   }
-  if (2 * n + 2 > SFXMAP_MAX_ENTRIES) {
+  if (2 * n + 2 > GTAMD_MAX_ENTRIES) {
     snprintf(err, errlen, "%llu symbols on both strands are beyond the limit of a single build (%llu table "
              "entries); the slices of a build in parts are not searched", (unsigned long long) n,
-             SFXMAP_MAX_ENTRIES);
+             GTAMD_MAX_ENTRIES);
     goto done;
   }
-  if (n == 0) { pfail(err, errlen, "readset '%s' holds no symbol", readset); goto done; }
+  if (n == 0) { gtamd_fail(err, errlen, "readset '%s' holds no symbol", readset); goto done; }
   reads = 1;
   for (uint64_t k = 0; k < n; k++) reads += enc[k] == 255;
   if (reads > UINT32_MAX) {
@@ -150,7 +140,7 @@ int gtamd_readjoiner_overlap(int argc, const char **argv, char *err, size_t errl
   if (!quiet) printf("# number of reads in filtered readset = %llu\n", (unsigned long long) reads);
 
   both = gtamd_mirror(enc, n);
-  if (both == NULL) { pfail(err, errlen, "out of memory (%s)", "mirrored reads"); goto done; }
+  if (both == NULL) { gtamd_fail(err, errlen, "out of memory (%s)", "mirrored reads"); goto done; }
   n2 = 2 * n + 1;
   if ((de = gtamd_encoder_create(0, 0)) == NULL || gtamd_encoder_set_symbols(de, both, n2) != 0 ||
       (dev = gtamd_encoder_device_symbols(de)) == NULL ||
@@ -183,11 +173,11 @@ int gtamd_readjoiner_overlap(int argc, const char **argv, char *err, size_t errl
            (unsigned long long) info.device_bytes, info.device_ms, info.spm_ms, info.decide_ms);
   if (!showspm) {
     snprintf(path, sizeof path, "%s.0.spm", readset);
-    if ((list = fopen(path, "wb")) == NULL) { pfail(err, errlen, "cannot open file '%s' for writing", path); goto done; }
-    if (gtamd_spmlist_bin32_header(list) != 0) { pfail(err, errlen, "cannot write file '%s'", path); goto done; }
+    if ((list = fopen(path, "wb")) == NULL) { gtamd_fail(err, errlen, "cannot open file '%s' for writing", path); goto done; }
+    if (gtamd_spmlist_bin32_header(list) != 0) { gtamd_fail(err, errlen, "cannot write file '%s'", path); goto done; }
   }
   rec = malloc(RDJ_CAPACITY * sizeof *rec);
-  if (rec == NULL) { pfail(err, errlen, "out of memory (%s)", "records"); goto done; }
+  if (rec == NULL) { gtamd_fail(err, errlen, "out of memory (%s)", "records"); goto done; }
   do {
     if (gtamd_spmred_emit(sr, &cursor, rec, RDJ_CAPACITY, 0, &written) != 0) {
       snprintf(err, errlen, "%s", gtamd_esa_last_error());
@@ -210,7 +200,7 @@ int gtamd_readjoiner_overlap(int argc, const char **argv, char *err, size_t errl
   if (list != NULL) {
     const int closed = fclose(list);
     list = NULL;
-    if (closed != 0) { pfail(err, errlen, "cannot close file '%s'", path); goto done; }
+    if (closed != 0) { gtamd_fail(err, errlen, "cannot close file '%s'", path); goto done; }
   }
   if (!quiet) {
     /* (gt_readjoiner_overlap.c:350-358) */
@@ -221,7 +211,7 @@ int gtamd_readjoiner_overlap(int argc, const char **argv, char *err, size_t errl
       printf("# number of transitive suffix-prefix matches = %llu\n",
              (unsigned long long) (info.transitive_same_read + (info.transitive_other >> 1)));
   }
-  if (fflush(stdout) != 0) { pfail(err, errlen, "cannot write to %s", "stdout"); goto done; }
+  if (fflush(stdout) != 0) { gtamd_fail(err, errlen, "cannot write to %s", "stdout"); goto done; }
   rc = 0;
 done:
   if (list != NULL) fclose(list);

@@ -3,31 +3,15 @@
    on the device through the C ABI, write INDEX.suf/.lcp/.llv/.bwt/.prj.
    Option names and defaults follow src/core/encseq_options.c:181-290 and
    src/match/index_options.c:298-515; file suffixes src/match/esa-fileend.h. */
-#include "gtamd_host.h"
+#include "host_internal.h"
 #include "gtamd_pck.h"
 #include <stdio.h>
 #include <stdlib.h>
-#include <stdarg.h>
 #include <string.h>
 #include <time.h>
 #include <pthread.h>
 
 #define MAXDB 1024
-
-static int fail(char *err, size_t errlen, const char *msg, const char *arg)
-{
-  snprintf(err, errlen, msg, arg);
-  return -1;
-}
-
-static int failf(char *err, size_t errlen, const char *fmt, ...)
-{
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(err, errlen, fmt, ap);
-  va_end(ap);
-  return -1;
-}
 
 static double now_s(void)
 {
@@ -51,7 +35,7 @@ static int write_bcktab(gtamd_esa_ctx *ctx, const char *index, char *err, size_t
   sec[0] += 1;
   snprintf(path, sizeof path, "%s.bck", index);
   if ((fp = fopen(path, "wb")) == NULL)
-    return fail(err, errlen, "cannot open file '%s' for writing", path);
+    return gtamd_fail(err, errlen, "cannot open file '%s' for writing", path);
   for (int k = 0; k < 3; k++) {
     uint32_t *buf;
     if (sec[k] == 0) continue;
@@ -60,12 +44,12 @@ static int write_bcktab(gtamd_esa_ctx *ctx, const char *index, char *err, size_t
         fwrite(buf, 4, sec[k], fp) != sec[k] ||
         ((4 * sec[k]) % 8 != 0 && fwrite(zero, 1, 4, fp) != 4)) {
       free(buf); fclose(fp);
-      return fail(err, errlen, "cannot write file '%s'", path);
+      return gtamd_fail(err, errlen, "cannot write file '%s'", path);
     }
     free(buf);
     first += sec[k];
   }
-  return fclose(fp) == 0 ? 0 : fail(err, errlen, "cannot close file '%s'", path);
+  return fclose(fp) == 0 ? 0 : gtamd_fail(err, errlen, "cannot close file '%s'", path);
 }
 
 /* entrysize 4 for the suffix table: -suftabuint, 32-bit entries */
@@ -126,7 +110,7 @@ static int write_table(gtamd_esa_ctx *const *ctxs, uint32_t nctx, gtamd_table wh
   pthread_cond_init(&w.cv, NULL);
   if (pthread_create(&thread, NULL, table_writer_main, &w) != 0) {
     free(w.buf[0]); free(w.buf[1]); fclose(w.fp);
-    return fail(err, errlen, "cannot start the writer of file '%s'", path);
+    return gtamd_fail(err, errlen, "cannot start the writer of file '%s'", path);
   }
   for (uint32_t part = 0; part < nctx && rc == 0; part++) {
   gtamd_esa_ctx *ctx = ctxs[part];
@@ -166,7 +150,7 @@ static int write_table(gtamd_esa_ctx *const *ctxs, uint32_t nctx, gtamd_table wh
     snprintf(err, errlen, "cannot write to file '%s'", path);
     rc = -1;
   }
-  if (fclose(w.fp) != 0 && rc == 0) return fail(err, errlen, "cannot close file '%s'", path);
+  if (fclose(w.fp) != 0 && rc == 0) return gtamd_fail(err, errlen, "cannot close file '%s'", path);
   return rc;
 }
 
@@ -220,7 +204,7 @@ static int build_in_parts(const uint8_t *enc, uint64_t n, int numofchars, uint32
   uint64_t expect = 0;
   if (jobs == NULL || threads == NULL || comm == NULL) {
     free(jobs); free(threads); gtamd_comm_destroy(comm);
-    return failf(err, errlen, "cannot set up a build in %u parts", R);
+    return gtamd_failf(err, errlen, "cannot set up a build in %u parts", R);
   }
   if (ndev < 1 || (same != NULL && same[0] == '1')) ndev = 1;
   for (uint32_t r = 0; r < R; r++) {
@@ -229,7 +213,7 @@ static int build_in_parts(const uint8_t *enc, uint64_t n, int numofchars, uint32
     jobs[r].numofchars = numofchars; jobs[r].enc = enc; jobs[r].n = n;
     if (pthread_create(&threads[r], NULL, part_main, &jobs[r]) != 0) {
       gtamd_comm_abort(comm);
-      rc = failf(err, errlen, "cannot start the thread of part %u", r);
+      rc = gtamd_failf(err, errlen, "cannot start the thread of part %u", r);
       break;
     }
     started++;
@@ -244,13 +228,13 @@ static int build_in_parts(const uint8_t *enc, uint64_t n, int numofchars, uint32
       for (uint32_t q = 0; q < started; q++)
         if (jobs[q].rc != 0 && strstr(jobs[q].err, "of the build failed") == NULL &&
             strstr(jobs[q].err, "callback failed") == NULL) { first = q; break; }
-      rc = failf(err, errlen, "part %u of %u: %s", first, R, jobs[first].err);
+      rc = gtamd_failf(err, errlen, "part %u of %u: %s", first, R, jobs[first].err);
     }
   }
   for (uint32_t r = 0; r < R && rc == 0; r++) {
     const gtamd_esa_stats *p = &jobs[r].es;
     if (gtamd_esa_table_offset(ctxs[r]) != expect)
-      rc = failf(err, errlen, "the slices of the parts do not tile the table (part %u)", r);
+      rc = gtamd_failf(err, errlen, "the slices of the parts do not tile the table (part %u)", r);
     expect += gtamd_esa_table_entries(ctxs[r], (want & GTAMD_WANT_SUF) ? GTAMD_TAB_SUF :
                                                (want & GTAMD_WANT_LCP) ? GTAMD_TAB_LCP : GTAMD_TAB_BWT);
     es->totallength = p->totallength;
@@ -266,21 +250,11 @@ static int build_in_parts(const uint8_t *enc, uint64_t n, int numofchars, uint32
     if (p->refine_rounds > es->refine_rounds) es->refine_rounds = p->refine_rounds;
   }
   if (rc == 0 && expect != n + 1)
-    rc = failf(err, errlen, "the parts hold %llu of the %llu table entries",
+    rc = gtamd_failf(err, errlen, "the parts hold %llu of the %llu table entries",
               (unsigned long long) expect, (unsigned long long) (n + 1));
   gtamd_comm_destroy(comm);
   free(jobs); free(threads);
   return rc;
-}
-
-static int yesno(int argc, const char **argv, int *i)
-{
-  /* options like -tis take an optional yes|no argument; returns the value */
-  if (*i + 1 < argc && (!strcmp(argv[*i + 1], "yes") || !strcmp(argv[*i + 1], "no"))) {
-    (*i)++;
-    return !strcmp(argv[*i], "yes");
-  }
-  return 1;
 }
 
 /* (Measured and dropped: allocating the engine's workspace -- 2.4 s of hipMalloc
@@ -334,22 +308,22 @@ static int write_bdx(gtamd_esa_ctx *ctx, const pck_request *pr, uint32_t numofch
     if ((m = malloc(n ? n : 1)) == NULL || gtamd_pck_ctxmap_copy(pck, m, 0, n) != 0 ||
         (mf = fopen(path, "wb")) == NULL) {
       free(m);
-      fail(err, errlen, "cannot write file '%s'", path);
+      gtamd_fail(err, errlen, "cannot write file '%s'", path);
       goto done;
     }
-    if (fwrite(m, 1, n, mf) != n) { fclose(mf); free(m); fail(err, errlen, "cannot write file '%s'", path); goto done; }
+    if (fwrite(m, 1, n, mf) != n) { fclose(mf); free(m); gtamd_fail(err, errlen, "cannot write file '%s'", path); goto done; }
     fclose(mf);
     free(m);
   }
   snprintf(path, sizeof path, "%s.bdx", indexname);
   if ((fp = fopen(path, "wb")) == NULL || (buf = malloc(chunk)) == NULL) {
-    fail(err, errlen, "cannot open file '%s' for writing", path);
+    gtamd_fail(err, errlen, "cannot open file '%s' for writing", path);
     goto done;
   }
   for (uint64_t off = 0; off < info.file_bytes; off += chunk) {
     const uint64_t cnt = info.file_bytes - off < chunk ? info.file_bytes - off : chunk;
     if (gtamd_pck_image_copy(pck, buf, off, cnt) != 0) { snprintf(err, errlen, "%s", gtamd_esa_last_error()); goto done; }
-    if (fwrite(buf, 1, cnt, fp) != cnt) { fail(err, errlen, "cannot write file '%s'", path); goto done; }
+    if (fwrite(buf, 1, cnt, fp) != cnt) { gtamd_fail(err, errlen, "cannot write file '%s'", path); goto done; }
   }
   if (verbose)
     printf("# packed index: blocksize=%u, blocks-per-bucket=%u, locfreq=%u: %llu bytes, %.2f ms on the device\n",
@@ -357,7 +331,7 @@ static int write_bdx(gtamd_esa_ctx *ctx, const pck_request *pr, uint32_t numofch
            (unsigned long long) info.file_bytes, info.build_ms);
   rc = 0;
 done:
-  if (fp != NULL && fclose(fp) != 0 && rc == 0) rc = fail(err, errlen, "cannot close file '%s'", path);
+  if (fp != NULL && fclose(fp) != 0 && rc == 0) rc = gtamd_fail(err, errlen, "cannot close file '%s'", path);
   free(buf);
   gtamd_pck_destroy(pck);
   return rc;
@@ -371,56 +345,43 @@ int gtamd_suffixerator(int argc, const char **argv, char *err, size_t errlen)
   return suffixerator_run(argc, argv, err, errlen, NULL);
 }
 
-static int uint_arg(int argc, const char **argv, int *i, uint32_t *out, char *err, size_t errlen)
-{
-  char *end;
-  unsigned long v;
-  if (*i + 1 >= argc) return fail(err, errlen, "missing argument to option \"%s\"", argv[*i]);
-  v = strtoul(argv[*i + 1], &end, 10);
-  if (*end != 0 || argv[*i + 1][0] == '-')
-    return fail(err, errlen, "argument to option \"%s\" must be a non-negative integer", argv[*i]);
-  *out = (uint32_t) v;
-  (*i)++;
-  return 0;
-}
-
 int gtamd_packedindex_mkindex(int argc, const char **argv, char *err, size_t errlen)
 {
   pck_request pr = { { 8, 8, 16, 0, 1 }, -1, 0, -2 };
   const char **rest = malloc(sizeof *rest * (size_t) (argc + 1));
   int nrest = 0, rc;
-  if (rest == NULL) return fail(err, errlen, "out of memory (%s)", "packedindex mkindex");
+  if (rest == NULL) return gtamd_fail(err, errlen, "out of memory (%s)", "packedindex mkindex");
   rest[nrest++] = argc > 0 ? argv[0] : "mkindex";
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
     rc = 0;
-    if (!strcmp(a, "-bsize")) rc = uint_arg(argc, argv, &i, &pr.params.block_size, err, errlen);
-    else if (!strcmp(a, "-blbuck")) rc = uint_arg(argc, argv, &i, &pr.params.bucket_blocks, err, errlen);
-    else if (!strcmp(a, "-locfreq")) rc = uint_arg(argc, argv, &i, &pr.params.locate_interval, err, errlen);
-    else if (!strcmp(a, "-locbitmap")) pr.locbitmap = yesno(argc, argv, &i);
-    else if (!strcmp(a, "-sprank")) pr.sprank = yesno(argc, argv, &i);
+    if (!strcmp(a, "-bsize")) rc = gtamd_opt_uint32(argc, argv, &i, &pr.params.block_size, err, errlen);
+    else if (!strcmp(a, "-blbuck")) rc = gtamd_opt_uint32(argc, argv, &i, &pr.params.bucket_blocks, err, errlen);
+    else if (!strcmp(a, "-locfreq")) rc = gtamd_opt_uint32(argc, argv, &i, &pr.params.locate_interval, err, errlen);
+    else if (!strcmp(a, "-locbitmap")) pr.locbitmap = gtamd_opt_yesno(argc, argv, &i);
+    else if (!strcmp(a, "-sprank")) pr.sprank = gtamd_opt_yesno(argc, argv, &i);
     else if (!strcmp(a, "-sprankilog")) {
-      if (i + 1 >= argc) rc = fail(err, errlen, "missing argument to option \"%s\"", a);
+      if (i + 1 >= argc) rc = gtamd_fail(err, errlen, "missing argument to option \"%s\"", a);
       else if (atoi(argv[++i]) >= 0) pr.sprank = 1;
     } else if (!strcmp(a, "-ctxilog")) {
-      if (i + 1 >= argc) rc = fail(err, errlen, "missing argument to option \"%s\"", a);
+      if (i + 1 >= argc) rc = gtamd_fail(err, errlen, "missing argument to option \"%s\"", a);
       else {
         pr.ctxilog = atoi(argv[++i]);
         if (pr.ctxilog < -2 || pr.ctxilog > 63)
-          rc = fail(err, errlen, "argument to option \"%s\" must be an integer between -2 and 63", a);
+          rc = gtamd_fail(err, errlen, "argument to option \"%s\" must be an integer between -2 and 63", a);
       }
     }
     else if (!strcmp(a, "-suf") || !strcmp(a, "-lcp") || !strcmp(a, "-bwt") || !strcmp(a, "-bck") ||
              !strcmp(a, "-suftabuint"))
       /* the index options of the packed-index variant have no table switches
          (src/match/index_options.c: gt_index_options_register_packedidx) */
-      rc = fail(err, errlen, "unknown option: %s (try -help)", a);
+      rc = gtamd_fail(err, errlen, "unknown option: %s (try -help)", a);
     else rest[nrest++] = a;
     if (rc != 0) { free(rest); return -1; }
   }
   if (pr.params.block_size < 1 || pr.params.bucket_blocks < 1) {
     free(rest);
-    return fail(err, errlen, "argument to option \"-%s\" must be an integer >= 1",
+    return gtamd_fail(err, errlen, "argument to option \"-%s\" must be an integer >= 1",
                 pr.params.block_size < 1 ? "bsize" : "blbuck");
   }
   rc = suffixerator_run(nrest, rest, err, errlen, &pr);
@@ -459,20 +420,20 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
     const char *a = argv[i];
     if (!strcmp(a, "-db")) {
       while (i + 1 < argc && argv[i + 1][0] != '-') {
-        if (numdb == MAXDB) return fail(err, errlen, "too many arguments to option \"-%s\"", "db");
+        if (numdb == MAXDB) return gtamd_fail(err, errlen, "too many arguments to option \"-%s\"", "db");
         db[numdb++] = argv[++i];
       }
-      if (numdb == 0) return fail(err, errlen, "missing argument to option \"-%s\"", "db");
+      if (numdb == 0) return gtamd_fail(err, errlen, "missing argument to option \"-%s\"", "db");
     } else if (!strcmp(a, "-ii")) {
-      if (i + 1 >= argc) return fail(err, errlen, "missing argument to option \"-%s\"", "ii");
+      if (i + 1 >= argc) return gtamd_fail(err, errlen, "missing argument to option \"-%s\"", "ii");
       inputindex = argv[++i];
     } else if (!strcmp(a, "-indexname")) {
-      if (i + 1 >= argc) return fail(err, errlen, "missing argument to option \"-%s\"", "indexname");
+      if (i + 1 >= argc) return gtamd_fail(err, errlen, "missing argument to option \"-%s\"", "indexname");
       indexname = argv[++i];
     } else if (!strcmp(a, "-dna")) dna = 1;
     else if (!strcmp(a, "-protein")) protein = 1;
     else if (!strcmp(a, "-smap")) {
-      if (i + 1 >= argc) return fail(err, errlen, "missing argument to option \"-%s\"", "smap");
+      if (i + 1 >= argc) return gtamd_fail(err, errlen, "missing argument to option \"-%s\"", "smap");
       smap = argv[++i];
     }
     else if (!strcmp(a, "-suf")) want |= GTAMD_WANT_SUF;
@@ -484,14 +445,14 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
     else if (!strcmp(a, "-pl")) {
       if (i + 1 < argc && argv[i + 1][0] != '-') userpl = (uint32_t) strtoul(argv[++i], NULL, 10);
     } else if (!strcmp(a, "-dir")) {
-      if (i + 1 >= argc) return fail(err, errlen, "missing argument to option \"-%s\"", "dir");
+      if (i + 1 >= argc) return gtamd_fail(err, errlen, "missing argument to option \"-%s\"", "dir");
       i++;
       if (!strcmp(argv[i], "fwd")) readmode = 0;
       else if (!strcmp(argv[i], "rev")) readmode = 1;
       else if (!strcmp(argv[i], "cpl")) readmode = 2;
       else if (!strcmp(argv[i], "rcl")) readmode = 3;
       else
-        return fail(err, errlen, "argument to option -dir must be fwd or rev or cpl or rcl, not %s", argv[i]);
+        return gtamd_fail(err, errlen, "argument to option -dir must be fwd or rev or cpl or rcl, not %s", argv[i]);
     } else if (!strcmp(a, "-mirrored")) {
       mirrored = 1;
     } else if (!strcmp(a, "-gpus")) {
@@ -499,7 +460,7 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
          one per GPU (or all on the one there is) */
       long v = i + 1 < argc ? strtol(argv[i + 1], NULL, 10) : 0;
       if (v < 1 || v > 128)
-        return failf(err, errlen, "argument to option \"-%s\" must be an integer from 1 to 128", "gpus");
+        return gtamd_failf(err, errlen, "argument to option \"-%s\" must be an integer from 1 to 128", "gpus");
       gpus = (uint32_t) v;
       i++;
     } else if (!strcmp(a, "-parts") || !strcmp(a, "-memlimit") || !strcmp(a, "-dc") ||
@@ -513,47 +474,47 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
                !strcmp(a, "-iterscan") || !strcmp(a, "-kmerswithencseqreader") ||
                !strcmp(a, "-noshortreadsort") || !strcmp(a, "-samplewithprefixlengthnull") ||
                !strcmp(a, "-storespecialcodes") || !strcmp(a, "-withradixsort")) {
-      (void) yesno(argc, argv, &i);        /* more strategy switches, same tables */
+      (void) gtamd_opt_yesno(argc, argv, &i);        /* more strategy switches, same tables */
     } else if (!strcmp(a, "-clipdesc")) {
-      clipdesc = yesno(argc, argv, &i);
+      clipdesc = gtamd_opt_yesno(argc, argv, &i);
     } else if (!strcmp(a, "-sat")) {
-      if (i + 1 >= argc) return fail(err, errlen, "missing argument to option \"-%s\"", "sat");
+      if (i + 1 >= argc) return gtamd_fail(err, errlen, "missing argument to option \"-%s\"", "sat");
       sat = argv[++i];
     } else if (!strcmp(a, "-lossless")) {
-      lossless = yesno(argc, argv, &i);
+      lossless = gtamd_opt_yesno(argc, argv, &i);
     } else if (!strcmp(a, "-plain") || !strcmp(a, "-kys") || !strcmp(a, "-lcpdist") ||
                !strcmp(a, "-compressedoutput") || !strcmp(a, "-genomediff") ||
                !strcmp(a, "-sortmaxdepth") || !strcmp(a, "-spmopt") ||
                !strcmp(a, "-swallow-tail") || !strcmp(a, "-onlybucketinsertion")) {
       /* these change what is written; not part of this path */
-      return fail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
-    } else if (!strcmp(a, "-des")) out_des = yesno(argc, argv, &i);
-    else if (!strcmp(a, "-sds")) out_sds = yesno(argc, argv, &i);
-    else if (!strcmp(a, "-md5")) out_md5 = yesno(argc, argv, &i);
-    else if (!strcmp(a, "-ssp")) out_ssp = yesno(argc, argv, &i);
+      return gtamd_fail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
+    } else if (!strcmp(a, "-des")) out_des = gtamd_opt_yesno(argc, argv, &i);
+    else if (!strcmp(a, "-sds")) out_sds = gtamd_opt_yesno(argc, argv, &i);
+    else if (!strcmp(a, "-md5")) out_md5 = gtamd_opt_yesno(argc, argv, &i);
+    else if (!strcmp(a, "-ssp")) out_ssp = gtamd_opt_yesno(argc, argv, &i);
     else if (!strcmp(a, "-encoder")) {
       /* not a reference option: read FASTA on the host instead of the device */
       if (i + 1 >= argc || (strcmp(argv[i + 1], "host") && strcmp(argv[i + 1], "device")))
-        return fail(err, errlen, "argument to option -%s must be host or device", "encoder");
+        return gtamd_fail(err, errlen, "argument to option -%s must be host or device", "encoder");
       host_encoder = !strcmp(argv[++i], "host");
     }
     else if (!strcmp(a, "-tis") || !strcmp(a, "-showprogress")) {
-      (void) yesno(argc, argv, &i);
+      (void) gtamd_opt_yesno(argc, argv, &i);
     } else
-      return fail(err, errlen, "unknown option: %s (try -help)", a);
+      return gtamd_fail(err, errlen, "unknown option: %s (try -help)", a);
   }
   if (pr != NULL) want = GTAMD_WANT_SUF | GTAMD_WANT_BWT;   /* what the packed index is made from */
   /* src/match/sfx-opt.c:78-88 */
   if (numdb == 0 && inputindex == NULL)
-    return fail(err, errlen, "either option \"-db\" or option \"-%s\" is mandatory", "ii");
+    return gtamd_fail(err, errlen, "either option \"-db\" or option \"-%s\" is mandatory", "ii");
   if (dna && protein)
-    return fail(err, errlen, "option \"-dna\" and option \"-%s\" exclude each other", "protein");
+    return gtamd_fail(err, errlen, "option \"-dna\" and option \"-%s\" exclude each other", "protein");
   if (smap != NULL && (dna || protein))
     /* src/core/encseq_options.c:271-272 */
-    return fail(err, errlen, "option \"-smap\" and option \"-%s\" exclude each other",
+    return gtamd_fail(err, errlen, "option \"-smap\" and option \"-%s\" exclude each other",
                 dna ? "dna" : "protein");
   if (inputindex != NULL && (numdb > 0 || dna || protein || sat != NULL || smap != NULL))
-    return fail(err, errlen, "option \"-%s\" and option \"-ii\" exclude each other",
+    return gtamd_fail(err, errlen, "option \"-%s\" and option \"-ii\" exclude each other",
                 numdb > 0 ? "db" : smap != NULL ? "smap" : dna ? "dna" : protein ? "protein" : "sat");
   if (indexname == NULL && inputindex != NULL) {
     const char *base = strrchr(inputindex, '/');
@@ -564,7 +525,7 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
     /* default: basename of the single -db file (encseq_options.c:112-131) */
     const char *base;
     if (numdb > 1)
-      return fail(err, errlen, "if more than one input file is given, then option -%s is mandatory", "indexname");
+      return gtamd_fail(err, errlen, "if more than one input file is given, then option -%s is mandatory", "indexname");
     base = strrchr(db[0], '/');
     snprintf(indexbuf, sizeof indexbuf, "%s", base ? base + 1 : db[0]);
     indexname = indexbuf;
@@ -573,7 +534,7 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
     if (gtamd_alphabet_from_file(smap, &alpha, err, errlen) != 0) return -1;
     if (alpha.numofchars > 28) {
       gtamd_alphabet_free(&alpha);
-      return fail(err, errlen, "symbol map '%s' defines more than 28 letters", smap);
+      return gtamd_fail(err, errlen, "symbol map '%s' defines more than 28 letters", smap);
     }
   } else gtamd_alphabet_standard(&alpha, protein);
   if (inputindex != NULL) {
@@ -583,12 +544,11 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
     if (gtamd_read_esq_alpha(inputindex, &enc, &n, &alpha, &ss, err, errlen) != 0) return -1;
   }
   /* complementing needs a=0 c=1 g=2 t=3 (gt_alphabet_is_dna) */
-  dnalike = alpha.numofchars == 4 && alpha.symbolmap['a'] == 0 && alpha.symbolmap['c'] == 1 &&
-            alpha.symbolmap['g'] == 2 && alpha.symbolmap['t'] == 3;
+  dnalike = gtamd_alphabet_is_dna(&alpha);
   if (!dnalike && (readmode >= 2 || mirrored)) {
     /* wording of src/match/sfx-run.c:566-570 */
     free(enc); gtamd_alphabet_free(&alpha);
-    return fail(err, errlen, "option -%s only can be used for DNA alphabets",
+    return gtamd_fail(err, errlen, "option -%s only can be used for DNA alphabets",
                 mirrored ? "mirrored" : (readmode == 2 ? "cpl" : "rcl"));
   }
   if (inputindex != NULL) {
@@ -615,7 +575,7 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
     if (clipdesc) gtamd_clip_descriptions(desc, &desclen);
     if ((out_des || out_sds) && gtamd_write_des_sds(indexname, desc, desclen, out_des, out_sds) != 0) {
       free(desc); gtamd_encoder_destroy(de);
-      return fail(err, errlen, "cannot write description files of index '%s'", indexname);
+      return gtamd_fail(err, errlen, "cannot write description files of index '%s'", indexname);
     }
     free(desc);
     ts[2] = now_s();
@@ -626,12 +586,12 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
       /* MD5 sums and the -dir / -mirrored transforms work on host symbols */
       if ((enc = malloc(n ? n : 1)) == NULL || gtamd_encoder_copy_symbols(de, enc, 0, n) != 0) {
         free(enc); gtamd_encoder_destroy(de);
-        return fail(err, errlen, "cannot copy the encoded sequence from the device (%s)",
+        return gtamd_fail(err, errlen, "cannot copy the encoded sequence from the device (%s)",
                     gtamd_esa_last_error());
       }
       if (out_md5 && gtamd_write_md5_alpha(indexname, enc, n, &alpha) != 0) {
         free(enc); gtamd_encoder_destroy(de);
-        return fail(err, errlen, "cannot write md5 file of index '%s'", indexname);
+        return gtamd_fail(err, errlen, "cannot write md5 file of index '%s'", indexname);
       }
       if (mirrored || readmode != 0) { gtamd_encoder_destroy(de); de = NULL; }
       else { free(enc); enc = NULL; }
@@ -670,13 +630,13 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
     if (clipdesc) gtamd_clip_descriptions(desc, &desclen);
     if ((out_des || out_sds) && gtamd_write_des_sds(indexname, desc, desclen, out_des, out_sds) != 0) {
       free(enc); free(orig); free(desc); gtamd_encoder_destroy(de);
-      return fail(err, errlen, "cannot write description files of index '%s'", indexname);
+      return gtamd_fail(err, errlen, "cannot write description files of index '%s'", indexname);
     }
     free(desc);
     if (out_md5 && (lossless ? gtamd_write_md5_orig(indexname, enc, orig, n)
                              : gtamd_write_md5_alpha(indexname, enc, n, &alpha)) != 0) {
       free(enc); free(orig); gtamd_encoder_destroy(de);
-      return fail(err, errlen, "cannot write md5 file of index '%s'", indexname);
+      return gtamd_fail(err, errlen, "cannot write md5 file of index '%s'", indexname);
     }
     free(orig);
     orig = NULL;
@@ -690,7 +650,7 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
   }
   if (mirrored) {
     uint8_t *m = gtamd_mirror(enc, n);
-    if (m == NULL) { free(enc); return fail(err, errlen, "out of memory (%s)", "-mirrored"); }
+    if (m == NULL) { free(enc); return gtamd_fail(err, errlen, "out of memory (%s)", "-mirrored"); }
     gtamd_seqstats_mirror(&ss, n > 0 && enc[n - 1] == GTAMD_WILDCARD);
     free(enc);
     enc = m;
@@ -715,25 +675,25 @@ static int suffixerator_run(int argc, const char **argv, char *err, size_t errle
     snprintf(path, sizeof path, "%s.prj", indexname);
     gtamd_alphabet_free(&alpha);
     if (gtamd_write_prj(path, &ss, &es, 0, readmode, mirrored) != 0)
-      return fail(err, errlen, "cannot open file '%s' for writing", path);
+      return gtamd_fail(err, errlen, "cannot open file '%s' for writing", path);
     return 0;
   }
   if (gpus > 1) {
     /* in parts: every part packs the sequence on its own device from the host copy */
     if ((want & GTAMD_WANT_BCK) || pr != NULL) {
-      failf(err, errlen, "option \"-gpus\" cannot be combined with %s: that needs the whole "
+      gtamd_failf(err, errlen, "option \"-gpus\" cannot be combined with %s: that needs the whole "
            "table in one build", pr != NULL ? "the packed index" : "option \"-bck\"");
       goto done;
     }
     if (enc == NULL) {
       if ((enc = malloc(n ? n : 1)) == NULL || gtamd_encoder_copy_symbols(de, enc, 0, n) != 0) {
-        failf(err, errlen, "cannot bring the encoded sequence to the host: %s", gtamd_esa_last_error());
+        gtamd_failf(err, errlen, "cannot bring the encoded sequence to the host: %s", gtamd_esa_last_error());
         goto done;
       }
     }
     gtamd_encoder_destroy(de);
     de = NULL;
-    if ((ctxs = calloc(gpus, sizeof *ctxs)) == NULL) { failf(err, errlen, "out of memory"); goto done; }
+    if ((ctxs = calloc(gpus, sizeof *ctxs)) == NULL) { gtamd_failf(err, errlen, "out of memory"); goto done; }
     nctx = gpus;
     t_create = 0;
     if (build_in_parts(enc, n, (int) ss.numofchars, userpl, want, gpus, ctxs, &es, err, errlen) != 0) goto done;
@@ -769,7 +729,7 @@ built:
     if (write_bdx(ctx, pr, ss.numofchars, indexname, verbose, err, errlen) != 0) goto done;
     snprintf(path, sizeof path, "%s.prj", indexname);
     if (gtamd_write_prj_packedindex(path, &ss, es.prefixlength, readmode, mirrored) != 0) {
-      fail(err, errlen, "cannot open file '%s' for writing", path);
+      gtamd_fail(err, errlen, "cannot open file '%s' for writing", path);
       goto done;
     }
     rc = 0;
@@ -790,7 +750,7 @@ built:
     char path[4096];
     snprintf(path, sizeof path, "%s.prj", indexname);
     if (gtamd_write_prj(path, &ss, &es, (want & GTAMD_WANT_LCP) != 0, readmode, mirrored) != 0) {
-      fail(err, errlen, "cannot open file '%s' for writing", path);
+      gtamd_fail(err, errlen, "cannot open file '%s' for writing", path);
       goto done;
     }
   }
@@ -852,16 +812,16 @@ int gtamd_mergeesa(int argc, const char **argv, char *err, size_t errlen)
 
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "-indexname")) {
-      if (++i >= argc) return fail(err, errlen, "missing argument to option \"%s\"", "-indexname");
+      if (++i >= argc) return gtamd_fail(err, errlen, "missing argument to option \"%s\"", "-indexname");
       indexname = argv[i];
     } else if (!strcmp(argv[i], "-ii")) {
       inputs = argv + i + 1;
       while (i + 1 < argc && argv[i + 1][0] != '-') { i++; numinputs++; }
     } else
-      return fail(err, errlen, "unknown option: %s (try -indexname NAME -ii INDEX...)", argv[i]);
+      return gtamd_fail(err, errlen, "unknown option: %s (try -indexname NAME -ii INDEX...)", argv[i]);
   }
-  if (indexname == NULL) return fail(err, errlen, "option \"%s\" is mandatory", "-indexname");
-  if (numinputs == 0) return fail(err, errlen, "option \"%s\" is mandatory", "-ii");
+  if (indexname == NULL) return gtamd_fail(err, errlen, "option \"%s\" is mandatory", "-indexname");
+  if (numinputs == 0) return gtamd_fail(err, errlen, "option \"%s\" is mandatory", "-ii");
   printf("# storeindex=%s\n", indexname);
   for (size_t k = 0; k < numinputs; k++) {
     uint8_t *enc = NULL, *grown;
@@ -873,20 +833,20 @@ int gtamd_mergeesa(int argc, const char **argv, char *err, size_t errlen)
     printf("# input=%s\n", inputs[k]);
     /* the reference maps SARR_SUFTAB | SARR_LCPTAB of every input */
     snprintf(path, sizeof path, "%s.suf", inputs[k]);
-    if ((fp = fopen(path, "rb")) == NULL) { fail(err, errlen, "cannot open file '%s'", path); goto done; }
+    if ((fp = fopen(path, "rb")) == NULL) { gtamd_fail(err, errlen, "cannot open file '%s'", path); goto done; }
     fclose(fp);
     snprintf(path, sizeof path, "%s.lcp", inputs[k]);
-    if ((fp = fopen(path, "rb")) == NULL) { fail(err, errlen, "cannot open file '%s'", path); goto done; }
+    if ((fp = fopen(path, "rb")) == NULL) { gtamd_fail(err, errlen, "cannot open file '%s'", path); goto done; }
     fclose(fp);
     if (gtamd_read_esq(inputs[k], &enc, &n, &protein, &ss, err, errlen) != 0) goto done;
     if (protein_all >= 0 && protein != protein_all) {
       free(enc);
-      fail(err, errlen, "index '%s' has another alphabet than the indexes before it", inputs[k]);
+      gtamd_fail(err, errlen, "index '%s' has another alphabet than the indexes before it", inputs[k]);
       goto done;
     }
     protein_all = protein;
     grown = realloc(all, total + n + 2);
-    if (grown == NULL) { free(enc); fail(err, errlen, "out of memory (%s)", "mergeesa"); goto done; }
+    if (grown == NULL) { free(enc); gtamd_fail(err, errlen, "out of memory (%s)", "mergeesa"); goto done; }
     all = grown;
     if (k > 0) all[total++] = (uint8_t) GTAMD_SEPARATOR;
     memcpy(all + total, enc, n);

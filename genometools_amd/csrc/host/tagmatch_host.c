@@ -3,18 +3,13 @@
    approximate matches of short tags against an index, on the device through
    include/gtamd_tagmatch.h.  The stdout is the reference's byte for byte but for
    the order of the match lines of one tag and strand, which is the table's here
-   and the reference's stack's there.
-
-   Not compiled on its own: pck_host.c includes this file at its end, and the
-   Makefile lists it as a dependency only.  tests/test_host_sanitized.py links a
-   sanitized gt-suffixerator-amd from a fixed list of the files of this directory,
-   so a function that suffixerator_main.c calls has to come out of one of them;
-   pck_host.c is the one whose static helpers this tool reads a project back with
-   (prj_value, load_project_sequence, map_required, mapped, unmap_file).  The two
-   #include lines below are no-ops there (both headers have guards); they say
-   what the file uses. */
+   and the reference's stack's there.  The project is read back through
+   project_host.c, the options through cli_host.c. */
 #include "host_internal.h"
 #include "gtamd_tagmatch.h"
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
 
 #define TAGERATOR_CAPACITY (1u << 20)            /* records of one gtamd_tagmatch_emit */
 #define MAXTAGSIZE 64
@@ -43,7 +38,7 @@ static int read_tags(const char *const *paths, size_t numfiles, taglist *tl, cha
   tl->text = malloc(cap_text);
   tl->span = malloc(cap_span * sizeof *tl->span);
   tl->textlen = tl->count = 0;
-  if (tl->text == NULL || tl->span == NULL) return pfail(err, errlen, "out of memory (%s)", "tags");
+  if (tl->text == NULL || tl->span == NULL) return gtamd_fail(err, errlen, "out of memory (%s)", "tags");
   for (size_t f = 0; f < numfiles; f++) {
     uint8_t *data = NULL;
     uint64_t len = 0, i = 0;
@@ -54,13 +49,13 @@ static int read_tags(const char *const *paths, size_t numfiles, taglist *tl, cha
     }
     if (len > 0 && data[0] != '>') {
       free(data);
-      return pfail(err, errlen, "the first character of fasta file \"%s\" has to be '>'", paths[f]);
+      return gtamd_fail(err, errlen, "the first character of fasta file \"%s\" has to be '>'", paths[f]);
     }
     while (i < len) {
       while (i < len && data[i] != '\n') i++;            /* the description */
       if (tl->count == cap_span) {
         tagspan *grown = realloc(tl->span, (cap_span *= 2) * sizeof *tl->span);
-        if (grown == NULL) { free(data); return pfail(err, errlen, "out of memory (%s)", "tags"); }
+        if (grown == NULL) { free(data); return gtamd_fail(err, errlen, "out of memory (%s)", "tags"); }
         tl->span = grown;
       }
       tl->span[tl->count].start = tl->textlen;
@@ -68,7 +63,7 @@ static int read_tags(const char *const *paths, size_t numfiles, taglist *tl, cha
         if (data[i] == '\n' || data[i] == '\r' || data[i] == ' ' || data[i] == '\t') continue;
         if (tl->textlen == cap_text) {
           char *grown = realloc(tl->text, cap_text *= 2);
-          if (grown == NULL) { free(data); return pfail(err, errlen, "out of memory (%s)", "tags"); }
+          if (grown == NULL) { free(data); return gtamd_fail(err, errlen, "out of memory (%s)", "tags"); }
           tl->text = grown;
         }
         tl->text[tl->textlen++] = (char) data[i];
@@ -132,9 +127,10 @@ static void show_tag_line(const gtamd_alphabet *alpha, unsigned mode, uint64_t t
 }
 
 /* tgr_showmatch (tagerator.c:81-189) */
-static void show_match(const gtamd_alphabet *alpha, unsigned mode, const uint8_t *enc, uint64_t n,
-                       const uint64_t *seqstart, uint64_t numseq, const gtamd_tagmatch_record *rec)
+static void show_match(const gtamd_project *prj, unsigned mode, const gtamd_tagmatch_record *rec)
 {
+  const gtamd_alphabet *alpha = &prj->alpha;
+  const uint8_t *enc = prj->enc;
   const uint64_t p = rec->dbstart, len = rec->lendist & 0xffffffffu, dist = rec->lendist >> 32;
   int first = 1;
 #define TAB if (first) first = 0; else putchar('\t')
@@ -143,34 +139,19 @@ static void show_match(const gtamd_alphabet *alpha, unsigned mode, const uint8_t
     TAB;
     if (mode & OUT_DBABSPOS) printf("%llu", (unsigned long long) p);
     else {
-      uint64_t lo = 0, hi = numseq;                   /* the last sequence that starts at or in front of p */
-      while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (seqstart[mid] <= p) lo = mid; else hi = mid;
-      }
-      printf("%llu\t%llu", (unsigned long long) lo, (unsigned long long) (p - seqstart[lo]));
+      const uint64_t seq = gtamd_unit_of(prj->seqstart, prj->numseq, p);
+      printf("%llu\t%llu", (unsigned long long) seq, (unsigned long long) (p - prj->seqstart[seq]));
     }
   }
   if (mode & OUT_DBSEQUENCE) {
     TAB;
     /* a match of a sound index ends at or in front of n; a damaged .suf may give one that does not */
-    for (uint64_t i = 0; i < len && p + i < n; i++) putchar(enc[p + i] < 254 ? alpha->characters[enc[p + i]] : alpha->wildcardshow);
+    for (uint64_t i = 0; i < len && p + i < prj->n; i++) putchar(enc[p + i] < 254 ? alpha->characters[enc[p + i]] : alpha->wildcardshow);
   }
   if (mode & OUT_STRAND) { TAB; putchar(rec->tag & 1 ? '-' : '+'); }
   if (mode & OUT_EDIST) { TAB; printf("%llu", (unsigned long long) dist); }
 #undef TAB
   if (!first) putchar('\n');
-}
-
-/* a switch of the reference's parser: on, unless "no" or "false" follows */
-static int switch_option(int argc, const char **argv, int *i)
-{
-  if (*i + 1 < argc) {
-    const char *v = argv[*i + 1];
-    if (!strcmp(v, "yes") || !strcmp(v, "true")) { (*i)++; return 1; }
-    if (!strcmp(v, "no") || !strcmp(v, "false")) { (*i)++; return 0; }
-  }
-  return 1;
 }
 
 int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen)
@@ -179,15 +160,14 @@ int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen)
   const char *index = NULL, *const *tagfiles = NULL;
   size_t numtagfiles = 0;
   long K = -1;
-  int nofwd = 0, norc = 0, best = 0, nowildcards = 1, replacewildcard = 0, verbose = 0, have_alpha = 0, rc = -1;
+  int nofwd = 0, norc = 0, best = 0, nowildcards = 1, replacewildcard = 0, verbose = 0, rc = -1;
   int failed = 0, after_line = 0;
   unsigned mode = 0;
-  char path[4096], tagerr[1024] = "";
-  uint8_t *enc = NULL, *symbols = NULL;
-  uint64_t n = 0, N, numseq = 1, *seqstart = NULL, *offsets = NULL, stop, next = 0;
-  uint32_t suf_bytes = 8, flags;
-  mapped suf = { NULL, 0 };
-  gtamd_alphabet alpha;
+  char tagerr[1024] = "";
+  uint8_t *symbols = NULL;
+  uint64_t *offsets = NULL, stop, next = 0;
+  uint32_t flags;
+  gtamd_project prj = { 0 };
   taglist tl = { NULL, 0, NULL, 0 };
   gtamd_tagmatch *tm = NULL;
   gtamd_tagmatch_info info;
@@ -195,21 +175,17 @@ int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen)
 
   for (int i = 1; i < argc; i++) {
     const char *a = argv[i];
-    if (!strcmp(a, "-esa")) {
-      if (i + 1 >= argc) return pfail(err, errlen, "missing argument to option \"%s\"", a);
-      index = argv[++i];
-    } else if (!strcmp(a, "-e")) {
+    if (!strcmp(a, "-esa")) { if (gtamd_opt_name(argc, argv, &i, &index, err, errlen) != 0) return -1; }
+    else if (!strcmp(a, "-e")) {
       char *end;
-      if (i + 1 >= argc) return pfail(err, errlen, "missing argument to option \"%s\"", a);
+      if (i + 1 >= argc) return gtamd_fail(err, errlen, "missing argument to option \"%s\"", a);
       K = strtol(argv[i + 1], &end, 10);
-      if (*end != 0 || end == argv[i + 1]) return pfail(err, errlen, "argument to option \"%s\" must be an integer", a);
+      if (*end != 0 || end == argv[i + 1]) return gtamd_fail(err, errlen, "argument to option \"%s\" must be an integer", a);
       /* the reference takes a negative number as "no -e"; here it is refused by name */
-      if (K < 0) return pfail(err, errlen, "argument to option \"%s\" must be a non-negative integer", a);
+      if (K < 0) return gtamd_fail(err, errlen, "argument to option \"%s\" must be a non-negative integer", a);
       i++;
     } else if (!strcmp(a, "-q")) {
-      tagfiles = argv + i + 1;
-      for (numtagfiles = 0; i + 1 < argc && argv[i + 1][0] != '-'; i++) numtagfiles++;
-      if (numtagfiles == 0) return pfail(err, errlen, "missing argument to option \"%s\"", a);
+      if (gtamd_opt_files(argc, argv, &i, &tagfiles, &numtagfiles, err, errlen) != 0) return -1;
     } else if (!strcmp(a, "-output")) {
       int given = 0;
       for (; i + 1 < argc && argv[i + 1][0] != '-'; i++, given++) {
@@ -218,22 +194,22 @@ int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen)
         if (keywords[k] == NULL) {
           for (k = 0; maxocc_keywords[k] != NULL; k++)
             if (!strcmp(argv[i + 1], maxocc_keywords[k]))
-              return pfail(err, errlen, "argument \"%s\" to option -output belongs to option -maxocc, which is not "
+              return gtamd_fail(err, errlen, "argument \"%s\" to option -output belongs to option -maxocc, which is not "
                           "supported by the MI355X engine", argv[i + 1]);
-          return pfail(err, errlen, "illegal argument \"%s\" to option -output", argv[i + 1]);
+          return gtamd_fail(err, errlen, "illegal argument \"%s\" to option -output", argv[i + 1]);
         }
-        if (mode & (1u << k)) return pfail(err, errlen, "argument \"%s\" to option -output already specified", argv[i + 1]);
+        if (mode & (1u << k)) return gtamd_fail(err, errlen, "argument \"%s\" to option -output already specified", argv[i + 1]);
         mode |= 1u << k;
       }
-      if (!given) return pfail(err, errlen, "missing argument to option \"%s\"", a);
-    } else if (!strcmp(a, "-nod")) nofwd = switch_option(argc, argv, &i);
-    else if (!strcmp(a, "-nop")) norc = switch_option(argc, argv, &i);
-    else if (!strcmp(a, "-best")) best = switch_option(argc, argv, &i);
+      if (!given) return gtamd_fail(err, errlen, "missing argument to option \"%s\"", a);
+    } else if (!strcmp(a, "-nod")) nofwd = gtamd_opt_switch(argc, argv, &i);
+    else if (!strcmp(a, "-nop")) norc = gtamd_opt_switch(argc, argv, &i);
+    else if (!strcmp(a, "-best")) best = gtamd_opt_switch(argc, argv, &i);
     /* the reference stores this switch as "no wildcards" (gt_tagerator.c:170-174):
        only `-withwildcards no` lets wildcards of the subject pass */
-    else if (!strcmp(a, "-withwildcards")) nowildcards = switch_option(argc, argv, &i);
-    else if (!strcmp(a, "-rw")) replacewildcard = switch_option(argc, argv, &i);
-    else if (!strcmp(a, "-v")) verbose = switch_option(argc, argv, &i);
+    else if (!strcmp(a, "-withwildcards")) nowildcards = gtamd_opt_switch(argc, argv, &i);
+    else if (!strcmp(a, "-rw")) replacewildcard = gtamd_opt_switch(argc, argv, &i);
+    else if (!strcmp(a, "-v")) verbose = gtamd_opt_switch(argc, argv, &i);
     else if (!strcmp(a, "-help")) {
       puts("Usage: gt-suffixerator-amd tagerator [options] -q tagfile -esa indexname\n"
            "Map short sequence tags in given index, on the device.\n\n"
@@ -252,22 +228,16 @@ int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen)
            "suffix table.  -pck, -online, -cmp, -maxocc (and the matching statistics without -e), -skpp and\n"
            "-maxdepth are refused.");
       return 0;
-    } else {
-      for (int k = 0; not_here[k] != NULL; k++)
-        if (!strcmp(a, not_here[k]))
-          return pfail(err, errlen, "option \"%s\" is not supported by the MI355X engine", a);
-      if (a[0] == '-') return pfail(err, errlen, "unknown option: %s (try -help)", a);
-      return pfail(err, errlen, "superfluous arguments: \"%s\"", a);
-    }
+    } else return gtamd_opt_tail(a, not_here, GTAMD_UNKNOWN_TRY, GTAMD_SUPERFLUOUS_MORE, err, errlen);
   }
-  if (tagfiles == NULL) return pfail(err, errlen, "option \"-%s\" is mandatory", "q");
-  if (index == NULL) return pfail(err, errlen, "either option \"-esa\" or option \"-%s\" is mandatory", "pck");
-  if (K < 0 && best) return pfail(err, errlen, "option -best requires option %s", "-e");
+  if (tagfiles == NULL) return gtamd_fail(err, errlen, "option \"-%s\" is mandatory", "q");
+  if (index == NULL) return gtamd_fail(err, errlen, "either option \"-esa\" or option \"-%s\" is mandatory", "pck");
+  if (K < 0 && best) return gtamd_fail(err, errlen, "option -best requires option %s", "-e");
   if (K < 0)
-    return pfail(err, errlen, "option \"-e\" is needed: if option -e is not used then option -maxocc is required, and "
+    return gtamd_fail(err, errlen, "option \"-e\" is needed: if option -e is not used then option -maxocc is required, and "
                 "the matching statistics of %s are not supported by the MI355X engine", "-maxocc");
-  if (K >= MAXTAGSIZE) return pfail(err, errlen, "argument to option \"%s\" must be smaller than 64, the longest tag", "-e");
-  if (nofwd && norc) return pfail(err, errlen, "options -nod and -nop together leave %s to compute", "nothing");
+  if (K >= MAXTAGSIZE) return gtamd_fail(err, errlen, "argument to option \"%s\" must be smaller than 64, the longest tag", "-e");
+  if (nofwd && norc) return gtamd_fail(err, errlen, "options -nod and -nop together leave %s to compute", "nothing");
   if (K == 0) nowildcards = 1;                          /* gt_tagerator_arguments_check */
   if (mode == 0) mode = OUT_TAGNUM | OUT_TAGSEQ | OUT_DBLENGTH | OUT_DBSTARTPOS | OUT_STRAND;
 
@@ -277,34 +247,13 @@ int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen)
   printf("# indexname(esa)=%s\n", index);
   for (size_t f = 0; f < numtagfiles; f++) printf("# queryfile=%s\n", tagfiles[f]);
 
-  {
-    unsigned long long readmode = 0, mirrored = 0;
-    snprintf(path, sizeof path, "%s.prj", index);
-    (void) prj_value(path, "readmode", &readmode);
-    (void) prj_value(path, "mirrored", &mirrored);
-    if (readmode != 0 || mirrored) {
-      pfail(err, errlen, "file '%s' describes a mirrored index or one of a read mode other than forward: such an "
-           "index is not supported by the MI355X engine's tagerator", path);
-      goto done;
-    }
-  }
-  if (load_project_sequence(index, "searched", &enc, &n, &alpha, err, errlen) != 0) goto done;
-  have_alpha = 1;
-  if (!norc && !(alpha.numofchars == 4 && alpha.symbolmap['a'] == 0 && alpha.symbolmap['c'] == 1 &&
-                 alpha.symbolmap['g'] == 2 && alpha.symbolmap['t'] == 3)) {
-    pfail(err, errlen, "reverse complemented matches need a DNA alphabet: the index has none, and its letters have no "
+  if (gtamd_project_open(&prj, index, "searched", GTAMD_PROJECT_FORWARD, "tagerator", err, errlen) != 0) goto done;
+  if (!norc && !gtamd_alphabet_is_dna(&prj.alpha)) {
+    gtamd_fail(err, errlen, "reverse complemented matches need a DNA alphabet: the index has none, and its letters have no "
          "complement; use option \"%s\"", "-nop");
     goto done;
   }
-  N = n + 1;
-  if (map_required(index, ".suf", &suf, path, sizeof path, err, errlen) != 0) goto done;
-  if (suf.bytes == 4 * N) suf_bytes = 4;
-  else if (suf.bytes != 8 * N) {
-    snprintf(err, errlen, "file '%s' has %llu bytes, %llu (-suftabuint) or %llu expected for %llu entries",
-             path, (unsigned long long) suf.bytes, (unsigned long long) (4 * N),
-             (unsigned long long) (8 * N), (unsigned long long) N);
-    goto done;
-  }
+  if (gtamd_project_map(&prj, index, GTAMD_TABLE_SUF, 1, err, errlen) != 0) goto done;
   printf("# for each match show: ");
   for (int k = 0; keywords[k] != NULL; k++)
     if (mode & (1u << k)) printf("%s ", keywords[k]);
@@ -315,19 +264,14 @@ int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen)
   if (read_tags(tagfiles, numtagfiles, &tl, err, errlen) != 0) goto done;
   symbols = malloc(tl.textlen ? tl.textlen : 1);
   offsets = malloc((tl.count + 1) * sizeof *offsets);
-  for (uint64_t p = 0; p < n; p++) numseq += enc[p] == 255;
-  seqstart = malloc(numseq * sizeof *seqstart);
   rec = malloc(TAGERATOR_CAPACITY * sizeof *rec);
-  if (symbols == NULL || offsets == NULL || seqstart == NULL || rec == NULL) {
-    pfail(err, errlen, "out of memory (%s)", "tags and records");
+  if (symbols == NULL || offsets == NULL || gtamd_project_sequence_starts(&prj) != 0 || rec == NULL) {
+    gtamd_fail(err, errlen, "out of memory (%s)", "tags and records");
     goto done;
   }
-  seqstart[0] = 0;
-  for (uint64_t p = 0, k = 1; p < n; p++)
-    if (enc[p] == 255) seqstart[k++] = p + 1;
   offsets[0] = 0;
   for (stop = 0; stop < tl.count; stop++) {
-    if (transform_tag(&tl, stop, &alpha, K, replacewildcard, symbols + offsets[stop], &after_line, tagerr,
+    if (transform_tag(&tl, stop, &prj.alpha, K, replacewildcard, symbols + offsets[stop], &after_line, tagerr,
                       sizeof tagerr) != 0) {
       failed = 1;
       break;
@@ -339,7 +283,7 @@ int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen)
     flags = (nofwd ? 0 : GTAMD_TAGMATCH_FORWARD) | (norc ? 0 : GTAMD_TAGMATCH_REVCOMP) |
             (best ? GTAMD_TAGMATCH_BEST : 0) | (nowildcards ? 0 : GTAMD_TAGMATCH_WITH_WILDCARDS);
     if ((tm = gtamd_tagmatch_create(0)) == NULL ||
-        gtamd_tagmatch_set_index_host(tm, enc, n, suf.p, suf_bytes, alpha.numofchars) != 0 ||
+        gtamd_tagmatch_set_index_host(tm, prj.enc, prj.n, prj.suf.p, prj.suf_bytes, prj.alpha.numofchars) != 0 ||
         gtamd_tagmatch_prepare(tm, symbols, offsets, stop, 0, (uint32_t) K, flags, &info) != 0) {
       snprintf(err, errlen, "%s", gtamd_esa_last_error());
       goto done;
@@ -352,11 +296,11 @@ int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen)
       for (uint64_t k = 0; k < written; k++) {
         const uint64_t t = rec[k].tag >> 1;
         for (; next <= t; next++)          /* the lines of the tags up to this one */
-          show_tag_line(&alpha, mode, next, symbols + offsets[next], tl.span[next].len);
-        show_match(&alpha, mode, enc, n, seqstart, numseq, &rec[k]);
+          show_tag_line(&prj.alpha, mode, next, symbols + offsets[next], tl.span[next].len);
+        show_match(&prj, mode, &rec[k]);
       }
     }
-    for (; next < stop; next++) show_tag_line(&alpha, mode, next, symbols + offsets[next], tl.span[next].len);
+    for (; next < stop; next++) show_tag_line(&prj.alpha, mode, next, symbols + offsets[next], tl.span[next].len);
     if (verbose && gtamd_tagmatch_get_info(tm, &info) == 0)
       printf("# %llu jobs, %llu matches, at most %llu of one tag and strand, %llu children examined, %llu levels, "
              "%llu single-suffix walks, %.3f ms on the device\n", (unsigned long long) info.jobs,
@@ -366,18 +310,17 @@ int gtamd_tagerator(int argc, const char **argv, char *err, size_t errlen)
   }
   if (failed) {
     /* (the characters of the tag as read: its code is not complete) */
-    if (after_line) show_tag_line(&alpha, mode, stop, symbols + offsets[stop], tl.span[stop].len);
+    if (after_line) show_tag_line(&prj.alpha, mode, stop, symbols + offsets[stop], tl.span[stop].len);
     fflush(stdout);
     snprintf(err, errlen, "%s", tagerr);
     goto done;
   }
-  if (fflush(stdout) != 0) { pfail(err, errlen, "cannot write to %s", "stdout"); goto done; }
+  if (fflush(stdout) != 0) { gtamd_fail(err, errlen, "cannot write to %s", "stdout"); goto done; }
   rc = 0;
 done:
   fflush(stdout);
   gtamd_tagmatch_destroy(tm);
-  unmap_file(&suf);
-  if (have_alpha) gtamd_alphabet_free(&alpha);
-  free(rec); free(seqstart); free(offsets); free(symbols); free(tl.span); free(tl.text); free(enc);
+  gtamd_project_close(&prj);
+  free(rec); free(offsets); free(symbols); free(tl.span); free(tl.text);
   return rc;
 }

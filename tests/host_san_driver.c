@@ -1,6 +1,6 @@
 /* host_san_driver.c -- TEST INFRASTRUCTURE ONLY.  The host layer's file readers
    and writers (-DDRIVER_HOST: esq_host.c alphabet_host.c encseq_host.c md5_host.c
-   ois_host.c) or the CPU oracle (-DDRIVER_ORACLE: esa_oracle.c pck_oracle.c)
+   ois_host.c cli_host.c project_host.c) or the CPU oracle (-DDRIVER_ORACLE: esa_oracle.c pck_oracle.c)
    behind one small command reader, so that tests/test_host_sanitized.py can
    run thousands of inputs through an AddressSanitizer/UBSan build in one
    process.  Never opens a device; nothing here links the engine.
@@ -27,6 +27,12 @@
                               .ois (LOSSLESS 1) .esq .ssp .des .sds .md5 as the
                               tool writes them, input names stored without
                               directories
+     project INDEX VERB WHICH TOOL REQUIRED TABLES|-
+                              gtamd_project_open(INDEX, VERB, WHICH, TOOL), then
+                              gtamd_project_map with REQUIRED for every letter of
+                              TABLES (s .suf, l .lcp, v .llv, b .bwt), then the
+                              sequence starts; output: the symbols; more: bytes of
+                              a .suf entry, number of sequences
    Work items with -DDRIVER_ORACLE:
      fasta PROTEIN FILE       ora_encode_fasta; output: the symbols
      tables SIGMA K ENC BSIZE BLBUCK LOCFREQ LOCBITMAP MKINDEX SPRANK
@@ -330,8 +336,42 @@ said:
   return 0;
 }
 
+/* a project through the reader of project_host.c, the calls in a tool's order */
+static int do_project(char **fld, int nf)
+{
+  gtamd_project prj;
+  char err[2048] = "", more[64] = "";
+  uint32_t crc = 0;
+  uint64_t n = 0;
+  int rc;
+  if (nf != 7) return -1;
+  memset(&prj, 0, sizeof prj);
+  gtamd_project_close(&prj);                       /* (a zeroed value: nothing to release) */
+  rc = gtamd_project_open(&prj, fld[1], fld[2], atoi(fld[3]), fld[4], err, sizeof err);
+  for (const char *t = fld[6]; rc == 0 && *t != '-' && *t != '\0'; t++) {
+    const char *at = strchr("slvb", *t);
+    if (at == NULL) return -1;
+    rc = gtamd_project_map(&prj, fld[1], (int) (at - "slvb"), atoi(fld[5]), err, sizeof err);
+  }
+  if (rc == 0 && gtamd_project_sequence_starts(&prj) != 0) return -1;
+  if (rc == 0) {
+    /* the starts with their sentinel, and the sequence of the last position */
+    if (prj.seqstart[0] != 0 || prj.seqstart[prj.numseq] != prj.n + 1 ||
+        (prj.n > 0 && gtamd_unit_of(prj.seqstart, prj.numseq, prj.n - 1) != prj.numseq - 1))
+      return -1;
+    n = prj.n;
+    crc = crc_more(0, prj.enc, prj.n);
+    snprintf(more, sizeof more, "%u\t%" PRIu64, (unsigned) prj.suf_bytes, prj.numseq);
+  }
+  gtamd_project_close(&prj);
+  gtamd_project_close(&prj);
+  report(rc, err, n, crc, more);
+  return 0;
+}
+
 static int dispatch(char **fld, int nf)
 {
+  if (strcmp(fld[0], "project") == 0) return do_project(fld, nf);
   if (strcmp(fld[0], "base") == 0) return do_base(fld, nf);
   if (strcmp(fld[0], "mut") == 0) return do_mut(fld, nf);
   if (strcmp(fld[0], "cut") == 0) return do_cut(fld, nf);

@@ -37,8 +37,10 @@ STD_FLAGS = ["-Wall", "-Wextra", "-std=c99", "-D_POSIX_C_SOURCE=200809L", "-D_DE
              "-I" + os.path.join(ROOT, "include")]
 SAN_FLAGS = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
              "-static-libasan"]
-READER_CORE = ("esq_host.c", "alphabet_host.c", "encseq_host.c", "md5_host.c", "ois_host.c")
-TOOL_ONLY = ("suffixerator_main.c", "suffixerator_tool.c", "device_host.c", "pck_host.c")
+READER_CORE = ("esq_host.c", "alphabet_host.c", "encseq_host.c", "md5_host.c", "ois_host.c", "cli_host.c",
+               "project_host.c")
+# every other file of the directory: the tools and what calls the engine
+TOOL_ONLY = tuple(sorted(f for f in os.listdir(HOST_DIR) if f.endswith(".c") and f not in READER_CORE))
 ORACLE = ("esa_oracle.c", "pck_oracle.c")
 WORKERS = max(1, min(8, len(os.sched_getaffinity(0))))
 REPORT_WORDS = ("Sanitizer", "runtime error")
@@ -75,8 +77,8 @@ def drivers(tmp_path_factory):
             ["gcc"] + SAN_FLAGS + STD_FLAGS + flags + ["-c", "-o", obj, src],
             stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
 
-    for f in (TOOL_ONLY[1],) + READER_CORE + TOOL_ONLY[:1] + TOOL_ONLY[2:]:   # the longest first
-        compile_(f, os.path.join(HOST_DIR, f), ["-I" + HOST_DIR])
+    for f in sorted(READER_CORE + TOOL_ONLY, key=lambda f: -os.path.getsize(os.path.join(HOST_DIR, f))):
+        compile_(f, os.path.join(HOST_DIR, f), ["-I" + HOST_DIR])           # (the longest first)
     for f in ORACLE:
         compile_(f, os.path.join(ou.ORACLE_DIR, f), [])
     compile_("driver_host", DRIVER_SRC, ["-DDRIVER_HOST", "-I" + HOST_DIR])
@@ -262,6 +264,125 @@ def test_reader_on_the_reference_files_under_the_sanitizer(drivers, host, tmp_pa
         want, protein, _ = th._read_esq(host, os.path.join(th.ESQ_DIR, stem))
         assert rc == 0 and int(bad) == 0 and int(numofchars) == (20 if protein else 4), (stem, msg)
         assert np.array_equal(np.fromfile(str(tmp_path / (stem + ".sym")), dtype=np.uint8), want), stem
+
+
+# ---- the project reader ----
+
+def _project(host, tmp_path, stem, flag, fixture):
+    """(index, symbols) of a project the unsanitized tool's host side writes;
+    the reader checks the size of a table, not its entries: the tables are
+    zeros of the right size, .suf with 8 bytes an entry, .llv with one pair"""
+    idx = str(tmp_path / stem)
+    assert th._run_tool(host, flag, "-db", ou.fixture_path(fixture), "-indexname", idx) == (0, "")
+    enc = th._read_esq(host, idx)[0]
+    for ext, size in (("suf", 8 * (enc.size + 1)), ("lcp", enc.size + 1), ("llv", 16), ("bwt", enc.size + 1)):
+        with open("%s.%s" % (idx, ext), "wb") as f:
+            f.write(bytes(size))
+    return idx, enc
+
+
+def _damaged(idx, name, prj_lines=(), **tables):
+    """a copy of project idx under `name`: the sequence files linked, INDEX.prj
+    with prj_lines appended (the last line of a key counts), every table
+    linked but those of `tables`: {ext: size in bytes, or None for no file}"""
+    other = os.path.join(os.path.dirname(idx), name)
+    for ext in ("esq", "ssp", "suf", "lcp", "llv", "bwt"):
+        if ext in tables:
+            if tables[ext] is not None:
+                with open("%s.%s" % (other, ext), "wb") as f:
+                    f.write(bytes(tables[ext]))
+        elif os.path.exists("%s.%s" % (idx, ext)):
+            os.symlink("%s.%s" % (idx, ext), "%s.%s" % (other, ext))
+    with open(other + ".prj", "w") as f:
+        f.write(open(idx + ".prj").read() + "".join(line + "\n" for line in prj_lines))
+    return other
+
+
+def test_project_reader_under_the_sanitizer(drivers, host, tmp_path):
+    """gtamd_project_open / _map / _sequence_starts / _close of project_host.c on
+    a DNA and a protein project and on damaged copies of them: the symbols, the
+    entry size and the number of sequences, or -1 with the message the tools
+    gave for such a file before they shared this reader -- the strings below are
+    those of the tools' own copies of these checks, word for word.  No report,
+    no leak."""
+    ANY, FORWARD, FORWARD_TWO = 0, 1, 2
+    dna, dna_enc = _project(host, tmp_path, "dna", "-dna", "Atinsert.fna")
+    prot, prot_enc = _project(host, tmp_path, "prot", "-protein", "sw100K1.fsa")
+    n, N = dna_enc.size, dna_enc.size + 1
+    reversed_enc = dna_enc.copy()
+    host.gtamd_apply_readmode(reversed_enc.ctypes.data, reversed_enc.size, 1)
+    assert not np.array_equal(reversed_enc, dna_enc)
+    forward_one = ("file '%s.prj' describes a mirrored index or one of a read mode other than forward: such an "
+                   "index is not supported by the MI355X engine's %s")
+    cases = []         # (index, verb, which, tool, required, tables, expected)
+
+    def ok(index, which, tool, required, tables, enc, suf_bytes):
+        cases.append((index, "searched", which, tool, required, tables,
+                      (0, "", enc.size, zlib.crc32(enc.tobytes()), str(suf_bytes),
+                       str(1 + int(np.count_nonzero(enc == 255))))))
+
+    def bad(index, which, tool, required, tables, message, verb="searched"):
+        cases.append((index, verb, which, tool, required, tables, (-1, message, 0, 0)))
+
+    ok(dna, ANY, "-", 0, "slvb", dna_enc, 8)
+    ok(dna, FORWARD, "tagerator", 1, "s", dna_enc, 8)
+    ok(dna, FORWARD_TWO, "repfind", 1, "slv", dna_enc, 8)
+    ok(dna, ANY, "-", 0, "-", dna_enc, 0)
+    ok(prot, ANY, "-", 0, "slvb", prot_enc, 8)
+    ok(prot, FORWARD_TWO, "querymatch", 1, "s", prot_enc, 8)
+    ok(_damaged(dna, "suf4", suf=4 * N), FORWARD, "idxlocali", 1, "s", dna_enc, 4)
+    ok(_damaged(dna, "suf8", suf=8 * N), ANY, "-", 0, "s", dna_enc, 8)
+    ok(_damaged(dna, "llv0", llv=0), ANY, "-", 0, "slv", dna_enc, 8)
+    short = _damaged(dna, "short", suf=8 * N - 1)
+    for which, tool, required in ((ANY, "-", 0), (FORWARD, "tagerator", 1)):
+        bad(short, which, tool, required, "s",
+            "file '%s.suf' has %d bytes, %d (-suftabuint) or %d expected for %d entries"
+            % (short, 8 * N - 1, 4 * N, 8 * N, N))
+    llv8 = _damaged(dna, "llv8", llv=8)
+    bad(llv8, ANY, "-", 0, "slvb",
+        "file '%s.llv' has 8 bytes, not a multiple of 16 (pairs of two 64-bit numbers)" % llv8)
+    bad(llv8, FORWARD_TWO, "repfind", 1, "slv",
+        "file '%s.llv' has 8 bytes, not a multiple of 16 (pairs of two 64-bit numbers)" % llv8)
+    lcp = _damaged(dna, "lcp", lcp=N - 1)
+    bad(lcp, ANY, "-", 0, "slvb", "file '%s.lcp' has %d bytes, %d expected" % (lcp, N - 1, N))
+    bwt = _damaged(dna, "bwt", bwt=N + 1)
+    bad(bwt, ANY, "-", 0, "slvb", "file '%s.bwt' has %d bytes, %d expected" % (bwt, N + 1, N))
+    nosuf = _damaged(dna, "nosuf", suf=None)
+    bad(nosuf, ANY, "-", 0, "s", "cannot open file '%s.suf'" % nosuf)
+    bad(nosuf, FORWARD, "tagerator", 1, "s", 'cannot open file "%s.suf": No such file or directory' % nosuf)
+    nollv = _damaged(dna, "nollv", llv=None)
+    bad(nollv, FORWARD_TWO, "repfind", 1, "slv", 'cannot open file "%s.llv": No such file or directory' % nollv)
+    bad(str(tmp_path / "nosuch"), ANY, "-", 0, "s", "cannot open file '%s.prj'" % (tmp_path / "nosuch"))
+    rev = _damaged(dna, "rev", ["readmode=1"])
+    ok(rev, ANY, "-", 0, "slvb", reversed_enc, 8)
+    bad(rev, FORWARD, "tagerator", 1, "s", forward_one % (rev, "tagerator"))
+    bad(rev, FORWARD, "idxlocali", 1, "s", forward_one % (rev, "idxlocali"))
+    bad(rev, FORWARD_TWO, "repfind", 1, "slv",
+        "file '%s.prj' gives a read mode other than forward: such an index is not supported by the MI355X "
+        "engine's repfind" % rev)
+    mir = _damaged(prot, "mir", ["mirrored=1"])
+    bad(mir, ANY, "-", 0, "s",
+        "file '%s.prj' asks for complemented symbols of an alphabet that is not DNA" % mir, verb="checked")
+    bad(mir, FORWARD, "tagerator", 1, "s", forward_one % (mir, "tagerator"))
+    bad(mir, FORWARD_TWO, "querymatch", 1, "s",
+        "file '%s.prj' describes a mirrored index: such an index is not supported by the MI355X engine's "
+        "querymatch" % mir)
+    packed = _damaged(dna, "packed", ["numberofallsortedsuffixes=0"])
+    bad(packed, ANY, "-", 0, "s",
+        "file '%s.prj' describes the project of a packed index (numberofallsortedsuffixes=0): it has no tables "
+        "to check" % packed, verb="checked")
+    big = (1 << 32) - 4096
+    parts = _damaged(dna, "parts", ["totallength=%d" % big, "numberofallsortedsuffixes=%d" % (big + 1)])
+    for verb in ("checked", "searched"):
+        bad(parts, ANY, "-", 0, "s",
+            "sequence of %d symbols is beyond the limit of a single build (%d table entries); the slices of a "
+            "build in parts are not %s" % (big, big, verb), verb=verb)
+    longer = _damaged(dna, "longer", ["totallength=%d" % (n + 1), "numberofallsortedsuffixes=%d" % (n + 2)])
+    bad(longer, ANY, "-", 0, "s", "INDEX.esq and INDEX.prj of '%s' disagree on the total length" % longer)
+    res = run(drivers["host"], [("project",) + c[:6] for c in cases], tmp_path, "project")
+    for c, r in zip(cases, res):
+        assert r == c[6], c[:6]
+    assert len(cases) == 30 and sum(c[6][0] == 0 for c in cases) == 10
 
 
 # ---- the command line tool ----

@@ -34,8 +34,8 @@ REFUSED = ["-parts", "-memlimit", "-wmax", "-phase2extra", "-radixparts", "-radi
 STD_FLAGS = ["-Wall", "-Wextra", "-std=c99", "-D_POSIX_C_SOURCE=200809L", "-D_DEFAULT_SOURCE",
              "-I" + os.path.join(ROOT, "include"), "-I" + HOST_DIR]
 SAN_FLAGS = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan"]
-HOST_FILES = ("esq_host.c", "alphabet_host.c", "encseq_host.c", "md5_host.c", "ois_host.c", "suffixerator_tool.c",
-              "device_host.c", "pck_host.c")
+# every file of the host layer but the one with the tool's main
+HOST_FILES = tuple(sorted(f for f in os.listdir(HOST_DIR) if f.endswith(".c") and f != "suffixerator_main.c"))
 
 with open(os.path.join(ou.GOLDEN_DIR, "golden_rdjoverlap.json")) as _f:
     GOLDEN = json.load(_f)
