@@ -987,7 +987,9 @@ extern "C" int gtamd_encoder_set_symbols(gtamd_encoder *e, const uint8_t *symbol
   HIP_TRY(hipSetDevice(e->device));
   enc_free(e);
   e->finished = false;
+  e->declined = false;
   e->files.clear();
+  e->rec_seqlen.clear(); e->rec_desclen.clear(); e->rec_file.clear();   // (of an earlier FASTQ input)
   memset(&e->sum, 0, sizeof e->sum);
   e->input_bytes = n;
   e->ndesc = 0;

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_util as ou
+from esq_sections_reference import _expected_summary, _runs  # noqa: F401
 from genometools_amd import encode, synth
 from genometools_amd._lib import EsaError
 from test_host import EncInfo, host  # noqa: F401  (fixture)
@@ -41,39 +42,6 @@ def _host_encode(host, paths, protein):
     libc.free(ptr)
     libc.free(dptr)
     return enc, desc, orig, [tuple(int(x) for x in row) for row in fl]
-
-
-def _runs(mask):
-    """lengths of the maximal runs of True"""
-    m = np.concatenate([[False], mask, [False]]).astype(np.int8)
-    d = np.diff(m)
-    return np.flatnonzero(d == -1) - np.flatnonzero(d == 1)
-
-
-def _expected_summary(enc, sigma):
-    sp, wc = _runs(enc >= 254), _runs(enc == 254)
-    seqs, nonsp = _runs(enc != 255), _runs(enc < 254)
-
-    def lead(mask):
-        return int(np.argmin(mask)) if not mask.all() else mask.size
-
-    def pieces(r, maxv):
-        return int(((r + maxv) // (maxv + 1)).sum())
-    return {
-        "totallength": enc.size, "numofsequences": int((enc == 255).sum()) + 1,
-        "specialcharacters": int((enc >= 254).sum()), "realspecialranges": sp.size,
-        "specialrangestab": [pieces(sp, 255), pieces(sp, 65535), sp.size],
-        "lengthofspecialprefix": lead(enc >= 254),
-        "lengthofspecialsuffix": lead((enc >= 254)[::-1]),
-        "wildcards": int((enc == 254).sum()), "realwildcardranges": wc.size,
-        "wildcardrangestab": [pieces(wc, 255), pieces(wc, 65535), wc.size],
-        "lengthofwildcardprefix": lead(enc == 254),
-        "lengthofwildcardsuffix": lead((enc == 254)[::-1]),
-        "lengthoflongestnonspecial": int(nonsp.max()) if nonsp.size else 0,
-        "minseqlen": int(seqs.min()), "maxseqlen": int(seqs.max()),
-        "equallength": int(seqs.min() == seqs.max() and not (enc == 254).any()),
-        "characterdistribution": [int((enc == c).sum()) for c in range(sigma)] + [0] * (32 - sigma),
-    }
 
 
 def _check(host, paths, protein):
