@@ -4284,6 +4284,12 @@ struct Build {
     TRY(fetch_stats(c));
     return 0;
   }
+  // GTAMD_DEBUG: which call of direct_ties() this was and whether it settled its list
+  void report_direct(const char *call) const {
+    if (debug)
+      fprintf(stderr, "gtamd: part %u: direct ties: call=%s tied=%llu gaveup=%d\n", c->part, call,
+              (unsigned long long) m0, c->h_stats->dfallback != 0);
+  }
   // discard the partial statistics of a direct attempt that gave up
   int drop_direct_stats() {
     HIP_TRY(hipMemsetAsync(&c->d_stats->dsum, 0, 8, st));
@@ -4697,6 +4703,7 @@ struct Build {
         HIP_TRY(hipGetLastError());
       }
       TRY(direct_ties(uidx0, ugrp, false));
+      report_direct("first");
     }
     u64 gaveup = bad ? 1 : c->h_stats->dfallback;
     if (R > 1) TRY(allgather_word(c, bad, RED_OR, &gaveup));
@@ -4943,6 +4950,7 @@ struct Build {
     m0_tied_all = m0;                        // (what the statistics report)
     if (dist || m0 == 0 || m0 > direct_limit()) return 0;
     TRY(direct_ties(ar.uidx0, ar.ugrp, true));
+    report_direct("left");
     if (c->h_stats->dfallback == 0) {
       m0 = 0;
       anyleft = 0;

@@ -41,7 +41,7 @@ def _part():
     return {"switches": None, "run": None, "msd": None, "level_d": None, "msd_local": None,
             "pair_resolve": None, "apply": [], "win_filter": [], "rank_windows": [],
             "rank_whole": [], "rank_exchange_all": False, "ranks_travel": [], "ties": None,
-            "rounds": 0, "across": [], "tile": None, "other": []}
+            "rounds": 0, "across": [], "tile": None, "direct": [], "other": []}
 
 
 def parse(err):
@@ -74,6 +74,8 @@ def parse(err):
             p["pair_resolve"] = _kv(rest)
         elif topic == "apply":
             p["apply"].append(_kv(rest))
+        elif topic == "direct ties":          # call=first|left tied=M0 gaveup=0|1, one per call
+            p["direct"].append(_kv(rest))
         elif topic == "win filter":
             p["win_filter"].append(_kv(rest))
         elif topic == "rank table" and _RANK_SEL.match(rest):
