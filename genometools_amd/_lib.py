@@ -15,7 +15,7 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in
            ("esa_prims.hip", "esa_engine.hip", "esa_synth.hip", "esa_encode.hip",
             "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip",
             "esa_maxpairs.hip", "esa_qmatch.hip", "esa_spm.hip", "esa_tagmatch.hip",
-            "esa_locali.hip", "esa_pckidx.hip", "esa_spmred.hip")]
+            "esa_locali.hip", "esa_pckidx.hip", "esa_spmred.hip", "esa_contained.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_index.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
                                                      "esa_jobs.h", "esa_ivwalk.h",
                                                      "esa_pck_replay.h", "esa_mstat_search.h",
@@ -23,14 +23,15 @@ HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", 
                                                      "esa_spm_core.h", "esa_tagmatch_core.h",
                                                      "esa_locali_core.h", "esa_pckidx_core.h",
                                                      "esa_pckidx.h", "esa_pckidx_dec.h",
-                                                     "esa_spm_state.h", "esa_spmred_core.h")] + \
+                                                     "esa_spm_state.h", "esa_spmred_core.h",
+                                                     "esa_contained_core.h")] + \
           [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
                                                        "gtamd_check.h", "gtamd_mstat.h",
                                                        "gtamd_maxpairs.h", "gtamd_qmatch.h",
                                                        "gtamd_spm.h", "gtamd_tagmatch.h",
                                                        "gtamd_locali.h", "gtamd_pckidx.h",
                                                        "gtamd_pcktag.h", "gtamd_pcklocali.h",
-                                                       "gtamd_spmred.h")]
+                                                       "gtamd_spmred.h", "gtamd_contained.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -159,6 +160,12 @@ class SpmredInfo(ctypes.Structure):      # gtamd_spmred_info, include/gtamd_spmr
                  "transitive_other", "contained_sequences", "candidates_examined",
                  "max_candidates_of_one_pair", "letters_compared", "device_bytes")] + \
                [(name, ctypes.c_float) for name in ("device_ms", "spm_ms", "decide_ms")]
+
+
+class ContainedInfo(ctypes.Structure):   # gtamd_contained_info, include/gtamd_contained.h
+    _fields_ = [(name, ctypes.c_uint64) for name in ("table_entries", "sequences", "reads")] + \
+               [("count", ctypes.c_uint64 * 5), ("device_bytes", ctypes.c_uint64)] + \
+               [(name, ctypes.c_float) for name in ("device_ms", "lists_ms")]
 
 
 class TagmatchInfo(ctypes.Structure):    # gtamd_tagmatch_info, include/gtamd_tagmatch.h
@@ -401,6 +408,26 @@ SPMRED_ABI = {
     "gtamd_spmred_get_info": (_INT, [_P, ctypes.POINTER(SpmredInfo)]),
 }
 
+# every symbol include/gtamd_contained.h declares
+CONTAINED_ABI = {
+    "gtamd_contained_create": (_P, [_INT]),
+    "gtamd_contained_destroy": (None, [_P]),
+    "gtamd_contained_geometry": (None, [ctypes.POINTER(_U32)]),
+    "gtamd_contained_set_index": (_INT, [_P, _P, _U64, _P, _U32, _P, _P, _U64]),
+    "gtamd_contained_set_index_host": (_INT, [_P, _P, _U64, _P, _U32, _P, _P, _U64]),
+    "gtamd_contained_set_index_esa": (_INT, [_P, _P, _P, _U64]),
+    "gtamd_contained_decide": (_INT, [_P, ctypes.POINTER(ContainedInfo)]),
+    "gtamd_contained_verdicts": (_INT, [_P, _P, _INT]),
+    "gtamd_contained_compact": (_INT, [_P, _U32, _P, _U64, ctypes.POINTER(_P), ctypes.POINTER(_U64)]),
+    "gtamd_contained_result": (_INT, [_P, _P, _INT]),
+    "gtamd_contained_get_info": (_INT, [_P, ctypes.POINTER(ContainedInfo)]),
+    "gtamd_contained_mirror": (_INT, [_P, _P, _U64, _P]),
+    "gtamd_contained_wildcard_flags": (_INT, [_P, _P, _INT]),
+    "gtamd_contained_mirror_result": (_INT, [_P, ctypes.POINTER(_P), ctypes.POINTER(_U64)]),
+    "gtamd_contained_drop_wildcards": (_INT, [_P, _P, _U64, _P, _U64, ctypes.POINTER(_P), ctypes.POINTER(_U64),
+                                              ctypes.POINTER(_U64)]),
+}
+
 _lib = None
 
 
@@ -426,7 +453,7 @@ def load():
         for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()) + \
                 list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()) + list(SPM_ABI.items()) + list(TAGMATCH_ABI.items()) + \
                 list(LOCALI_ABI.items()) + list(PCKIDX_ABI.items()) + list(PCKTAG_ABI.items()) + \
-                list(PCKLOCALI_ABI.items()) + list(SPMRED_ABI.items()):
+                list(PCKLOCALI_ABI.items()) + list(SPMRED_ABI.items()) + list(CONTAINED_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

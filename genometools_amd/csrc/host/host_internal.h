@@ -84,6 +84,29 @@ void gtamd_analysis_from_summary(const gtamd_encode_summary *s, uint32_t numofch
 uint64_t gtamd_swtable_bytes(int width_kind, int withrangelengths, uint64_t n,
                              uint64_t items);
 
+/* ---- prefilter_host.c: what `readjoiner prefilter` writes, from figures and
+   symbols in host memory; nothing here calls the engine ---- */
+
+/* an input file of `readjoiner prefilter`: its bytes, its reads with a wildcard
+   and their symbols, the reads that are left and their letters */
+typedef struct {
+  uint64_t filesize, invalid_reads, invalid_letters, kept_reads, kept_letters;
+} gtamd_prefilter_file;
+/* The file table of X.esq as the reference computes it (src/match/reads2twobit.c:
+   852-892, 1460-1482): the raw length is the file's without the symbols of its
+   reads with a wildcard and three bytes for each of them, the effective length
+   the letters of the reads that are left with a separator between two. */
+void gtamd_prefilter_filetable(const gtamd_prefilter_file *f, size_t numfiles, gtamd_filelength *tab);
+/* X.esq (and X.ssp where the access type has one) of the n kept symbols, with that
+   table and the original file names */
+int gtamd_prefilter_write_readset(const char *readset, const char *const *paths, size_t numfiles,
+                                  const gtamd_prefilter_file *f, const uint8_t *kept, uint64_t n, char *err,
+                                  size_t errlen);
+/* X.cnt, Readjoiner's list of contained reads in its bit format
+   (src/match/rdj-cntlist.c:49-58): removed[k] != 0 for read k of `reads` */
+int gtamd_prefilter_write_cntlist(const char *path, const uint8_t *removed, uint64_t reads, char *err,
+                                  size_t errlen);
+
 /* What follows is shared between the tools of this directory and stays inside
    libgtamd_host.so. */
 #define GTAMD_INTERNAL __attribute__((visibility("hidden")))

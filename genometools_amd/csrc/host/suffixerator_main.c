@@ -8,6 +8,7 @@
    `gt-suffixerator-amd querymatch ...` is `gt repfind ...` with -q, -r or -p,
    `gt-suffixerator-amd encseq2spm ...` is `gt encseq2spm ...`,
    `gt-suffixerator-amd readjoiner overlap ...` is `gt readjoiner overlap ...`,
+   `gt-suffixerator-amd readjoiner prefilter ...` is `gt readjoiner prefilter ...`,
    `gt-suffixerator-amd tagerator ...` is `gt tagerator ...`,
    `gt-suffixerator-amd idxlocali ...` is `gt dev idxlocali ...` */
 #include <stdio.h>
@@ -56,6 +57,14 @@ int main(int argc, char **argv)
   if (argc > 1 && !strcmp(argv[1], "encseq2spm")) {
     if (gtamd_encseq2spm(argc - 1, (const char **) argv + 1, err, sizeof err) != 0) {
       fprintf(stderr, "gt encseq2spm: error: %s\n", err);
+      return 1;
+    }
+    return 0;
+  }
+  /* (a bare `readjoiner prefilter`, without an option, is answered below as it always was) */
+  if (argc > 3 && !strcmp(argv[1], "readjoiner") && !strcmp(argv[2], "prefilter")) {
+    if (gtamd_readjoiner_prefilter(argc - 2, (const char **) argv + 2, err, sizeof err) != 0) {
+      fprintf(stderr, "gt readjoiner prefilter: error: %s\n", err);
       return 1;
     }
     return 0;

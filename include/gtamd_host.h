@@ -29,6 +29,10 @@
     gtamd_readjoiner_overlap  `gt readjoiner overlap -readset X -l L`
                             (src/tools/gt_readjoiner_overlap.c), on the device
                             through the engine and include/gtamd_spmred.h
+    gtamd_readjoiner_prefilter  `gt readjoiner prefilter -db FILE... -readset X`
+                            (src/tools/gt_readjoiner_prefilter.c), on the device
+                            through the encoder, the engine and
+                            include/gtamd_contained.h
     gtamd_tagerator         `gt tagerator -e K -esa INDEX -q TAGS`
                             (src/tools/gt_tagerator.c), on the device through
                             include/gtamd_tagmatch.h
@@ -452,6 +456,42 @@ int gtamd_encseq2spm(int argc, const char **argv, char *err, size_t errlen);
    Returns 0, or -1 with the message in err (the caller prints "gt readjoiner
    overlap: error: <err>" and exits 1). */
 int gtamd_readjoiner_overlap(int argc, const char **argv, char *err, size_t errlen);
+
+/* `gt readjoiner prefilter -db FILE... [-readset X] [-q] [-v] [-encodeonly]
+   [-fasta] [-cnt] [-strict]` (tool function src/tools/gt_readjoiner_prefilter.c;
+   what it replaces: src/match/reads2twobit.c, src/match/rdj-contfinder.c): the
+   reads of FASTA or FASTQ files without those that hold a wildcard (the
+   reference's "low-quality" reads), without the duplicates and without the reads
+   that are a proper prefix or suffix of another read, on either strand
+   (definition, tie rule and what -strict adds: include/gtamd_contained.h).  The
+   sub-command `readjoiner prefilter`, followed by an option at least; the
+   command answers the two words alone as it did before the tool was there.
+     -db FILE...   unpaired libraries; a name with ':' (a paired library) is refused
+     -readset X    the name of the output; default: the first file
+     -encodeonly   nothing is decided: the reads without a wildcard are the output
+     -fasta        X.p.fas: `>` and the read on a line each, lower case
+     -cnt          X.cnt: the list of removed reads, bit format (rdj-cntlist.c)
+     -strict       this tool's own: the reads that stand strictly inside another
+                   and those equal to their own reverse complement go as well;
+                   two more '#' lines behind the reference's give their numbers
+     -q, -v        no '#' lines; the reference's verbose lines.  They exclude each other
+   Writes X.esq, and X.ssp where its access type has one; no X.des, X.sds, X.md5,
+   as the reference by default.  For reads of one length stdout, X.esq, X.p.fas
+   and X.cnt are the reference's byte for byte: the file table of X.esq holds the
+   original names, the effective lengths of the reads that are left and the raw
+   lengths as src/match/reads2twobit.c:852-892 computes them (for a FASTA read over
+   several lines whose wildcard is not on its last line the reference counts the
+   letters up to the end of that line only; here the whole read counts).  For
+   reads of several lengths the reference departs from its definition
+   (include/gtamd_contained.h) and this tool does not.  X.rlt is not written and
+   -libtable is refused: the reference's file holds an address of the process
+   that wrote it.  -singlestrand -maxlow -lowqual -phred64 -des -clipdes -memdes
+   -copynum -seqnums -encseq -testrs* are refused ("option \"-X\" is not supported
+   ...").  A read set whose mirrored set is beyond one build is refused as in
+   `readjoiner overlap`.
+   Returns 0, or -1 with the message in err (the caller prints "gt readjoiner
+   prefilter: error: <err>" and exits 1). */
+int gtamd_readjoiner_prefilter(int argc, const char **argv, char *err, size_t errlen);
 
 /* Readjoiner's bin32 list of matches (src/match/rdj-spmlist.c:45-124): one
    header byte, then three uint32 a match in host byte order: suffix_read,
