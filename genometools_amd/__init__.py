@@ -3,3 +3,4 @@ path of `gt suffixerator` (GenomeTools).  See DESIGN.md."""
 from .esa import EsaEngine, EsaResult, suffixerator_tables  # noqa: F401
 from . import synth  # noqa: F401
 from .contained import ContainedReads, prefilter  # noqa: F401
+from .strgraph import StringGraph, assemble  # noqa: F401

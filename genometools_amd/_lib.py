@@ -15,7 +15,8 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in
            ("esa_prims.hip", "esa_engine.hip", "esa_synth.hip", "esa_encode.hip",
             "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip",
             "esa_maxpairs.hip", "esa_qmatch.hip", "esa_spm.hip", "esa_tagmatch.hip",
-            "esa_locali.hip", "esa_pckidx.hip", "esa_spmred.hip", "esa_contained.hip")]
+            "esa_locali.hip", "esa_pckidx.hip", "esa_spmred.hip", "esa_contained.hip",
+            "esa_strgraph.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_index.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
                                                      "esa_jobs.h", "esa_ivwalk.h",
                                                      "esa_pck_replay.h", "esa_mstat_search.h",
@@ -24,14 +25,15 @@ HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", 
                                                      "esa_locali_core.h", "esa_pckidx_core.h",
                                                      "esa_pckidx.h", "esa_pckidx_dec.h",
                                                      "esa_spm_state.h", "esa_spmred_core.h",
-                                                     "esa_contained_core.h")] + \
+                                                     "esa_contained_core.h", "esa_strgraph_core.h")] + \
           [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
                                                        "gtamd_check.h", "gtamd_mstat.h",
                                                        "gtamd_maxpairs.h", "gtamd_qmatch.h",
                                                        "gtamd_spm.h", "gtamd_tagmatch.h",
                                                        "gtamd_locali.h", "gtamd_pckidx.h",
                                                        "gtamd_pcktag.h", "gtamd_pcklocali.h",
-                                                       "gtamd_spmred.h", "gtamd_contained.h")]
+                                                       "gtamd_spmred.h", "gtamd_contained.h",
+                                                       "gtamd_strgraph.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -166,6 +168,14 @@ class ContainedInfo(ctypes.Structure):   # gtamd_contained_info, include/gtamd_c
     _fields_ = [(name, ctypes.c_uint64) for name in ("table_entries", "sequences", "reads")] + \
                [("count", ctypes.c_uint64 * 5), ("device_bytes", ctypes.c_uint64)] + \
                [(name, ctypes.c_float) for name in ("device_ms", "lists_ms")]
+
+
+class StrgraphInfo(ctypes.Structure):    # gtamd_strgraph_info, include/gtamd_strgraph.h
+    _fields_ = [(name, ctypes.c_uint64) for name in
+                ("reads", "vertices", "matches", "edges", "internal_vertices", "junctions", "paths", "cycles",
+                 "cycle_vertices", "contigs", "elements", "total_length", "longest_contig", "device_bytes")] + \
+               [(name, ctypes.c_uint32) for name in ("doubling_rounds", "cycle_rounds")] + \
+               [(name, ctypes.c_float) for name in ("device_ms", "build_ms", "rank_ms", "select_ms", "scatter_ms", "spell_ms")]
 
 
 class TagmatchInfo(ctypes.Structure):    # gtamd_tagmatch_info, include/gtamd_tagmatch.h
@@ -428,6 +438,19 @@ CONTAINED_ABI = {
                                               ctypes.POINTER(_U64)]),
 }
 
+# every symbol include/gtamd_strgraph.h declares
+STRGRAPH_ABI = {
+    "gtamd_strgraph_create": (_P, [_INT]),
+    "gtamd_strgraph_destroy": (None, [_P]),
+    "gtamd_strgraph_geometry": (None, [ctypes.POINTER(_U32), ctypes.POINTER(_U32), ctypes.POINTER(_U64)]),
+    "gtamd_strgraph_set_reads": (_INT, [_P, _P, _U64, _INT]),
+    "gtamd_strgraph_set_matches": (_INT, [_P, _P, _U64, _INT]),
+    "gtamd_strgraph_prepare": (_INT, [_P, _U32, _U32, _U32, ctypes.POINTER(StrgraphInfo)]),
+    "gtamd_strgraph_emit": (_INT, [_P, ctypes.POINTER(_U64), _P, _U64, _INT, ctypes.POINTER(_U64)]),
+    "gtamd_strgraph_emit_symbols": (_INT, [_P, ctypes.POINTER(_U64), _P, _U64, _INT, ctypes.POINTER(_U64)]),
+    "gtamd_strgraph_get_info": (_INT, [_P, ctypes.POINTER(StrgraphInfo)]),
+}
+
 _lib = None
 
 
@@ -453,7 +476,8 @@ def load():
         for name, (res, args) in list(ABI.items()) + list(CHECK_ABI.items()) + list(MSTAT_ABI.items()) + \
                 list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()) + list(SPM_ABI.items()) + list(TAGMATCH_ABI.items()) + \
                 list(LOCALI_ABI.items()) + list(PCKIDX_ABI.items()) + list(PCKTAG_ABI.items()) + \
-                list(PCKLOCALI_ABI.items()) + list(SPMRED_ABI.items()) + list(CONTAINED_ABI.items()):
+                list(PCKLOCALI_ABI.items()) + list(SPMRED_ABI.items()) + list(CONTAINED_ABI.items()) + \
+                list(STRGRAPH_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -9,6 +9,7 @@
    `gt-suffixerator-amd encseq2spm ...` is `gt encseq2spm ...`,
    `gt-suffixerator-amd readjoiner overlap ...` is `gt readjoiner overlap ...`,
    `gt-suffixerator-amd readjoiner prefilter ...` is `gt readjoiner prefilter ...`,
+   `gt-suffixerator-amd assembly ...` is `gt readjoiner assembly ...` with default options,
    `gt-suffixerator-amd tagerator ...` is `gt tagerator ...`,
    `gt-suffixerator-amd idxlocali ...` is `gt dev idxlocali ...` */
 #include <stdio.h>
@@ -57,6 +58,13 @@ int main(int argc, char **argv)
   if (argc > 1 && !strcmp(argv[1], "encseq2spm")) {
     if (gtamd_encseq2spm(argc - 1, (const char **) argv + 1, err, sizeof err) != 0) {
       fprintf(stderr, "gt encseq2spm: error: %s\n", err);
+      return 1;
+    }
+    return 0;
+  }
+  if (argc > 1 && !strcmp(argv[1], "assembly")) {
+    if (gtamd_assembly(argc - 1, (const char **) argv + 1, err, sizeof err) != 0) {
+      fprintf(stderr, "gt readjoiner assembly: error: %s\n", err);
       return 1;
     }
     return 0;

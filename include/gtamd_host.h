@@ -33,6 +33,9 @@
                             (src/tools/gt_readjoiner_prefilter.c), on the device
                             through the encoder, the engine and
                             include/gtamd_contained.h
+    gtamd_assembly          `gt readjoiner assembly -readset X` with default
+                            options (src/tools/gt_readjoiner_assembly.c), on
+                            the device through include/gtamd_strgraph.h
     gtamd_tagerator         `gt tagerator -e K -esa INDEX -q TAGS`
                             (src/tools/gt_tagerator.c), on the device through
                             include/gtamd_tagmatch.h
@@ -501,6 +504,36 @@ int gtamd_readjoiner_prefilter(int argc, const char **argv, char *err, size_t er
 int gtamd_spmlist_bin32_header(FILE *fp);
 int gtamd_spmlist_bin32_records(FILE *fp, const gtamd_spmred_record *rec, uint64_t count, char *err,
                                 size_t errlen);
+
+/* The reader of that list: the `*count` records of the file at `path`, in the
+   order of the file, in memory the caller frees; readlen: the lengths of the
+   `reads` reads the list numbers.  Each of these is refused with a message of
+   its own: a file that cannot be opened or is empty, a format byte that is not
+   bin32's, a TRUNCATED list (the bytes behind the format byte are no whole
+   number of matches), a READ NUMBER beyond the set, a match LONGER than either
+   of its reads, a match with both reads reversed.  0, or -1 with the message. */
+int gtamd_spmlist_bin32_read(const char *path, const uint32_t *readlen, uint64_t reads,
+                             gtamd_spmred_record **rec, uint64_t *count, char *err, size_t errlen);
+
+/* `gt readjoiner assembly -readset X [-l L] [-depthcutoff D] [-lengthcutoff C]
+   [-spmfiles 1] [-q]` (tool function src/tools/gt_readjoiner_assembly.c with
+   default options): the string graph of the list X.0.spm -- the reference's or
+   `readjoiner overlap`'s of this project -- over the reads of X.esq (+ .ssp),
+   its unbranched paths and their contigs, on the device (semantics and order:
+   include/gtamd_strgraph.h).  The sub-command `assembly`: the words `readjoiner
+   assembly` keep the dispatcher's answer.  Writes X.contigs.fas (`>contig_N
+   length=.. depth=.. <first>-->...--><last>`, lines of 60 letters) and prints the
+   reference's lines, the progress lines, the statistics block or `# no contigs
+   respect the given cutoff parameters`, both byte for byte; -q prints none.
+   X.paths, the reference's intermediate file, is not written.  Every other
+   option of the reference's tool is refused by name, and so is -spmfiles above
+   1.  Returns 0, or -1 with the message in err (the caller prints "gt
+   readjoiner assembly: error: <err>" and exits 1). */
+int gtamd_assembly(int argc, const char **argv, char *err, size_t errlen);
+/* The statistics block of the contig lengths as the lines the tool prints, "# "
+   in front of each (gt_assembly_stats_calculator_show: quartiles, N50/L50,
+   N80/L80), or the one line for no contig, into out; -1 when outlen is too small. */
+int gtamd_assembly_statistics(const uint64_t *lengths, uint64_t count, char *out, size_t outlen);
 
 /* `gt tagerator -e K -esa INDEX -q FILE...` (tool function
    src/tools/gt_tagerator.c, gt_runtagerator src/match/tagerator.c:538-773): the
