@@ -16,7 +16,7 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in
             "esa_pck.hip", "esa_comm.hip", "esa_check.hip", "esa_mstat.hip",
             "esa_maxpairs.hip", "esa_qmatch.hip", "esa_spm.hip", "esa_tagmatch.hip",
             "esa_locali.hip", "esa_pckidx.hip", "esa_spmred.hip", "esa_contained.hip",
-            "esa_strgraph.hip")]
+            "esa_strgraph.hip", "esa_kcorrect.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", "esa_index.h", "esa_prims.h", "esa_devutil.h", "esa_msd.h", "esa_msd_blocks.h",
                                                      "esa_jobs.h", "esa_ivwalk.h",
                                                      "esa_pck_replay.h", "esa_mstat_search.h",
@@ -25,7 +25,8 @@ HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", 
                                                      "esa_locali_core.h", "esa_pckidx_core.h",
                                                      "esa_pckidx.h", "esa_pckidx_dec.h",
                                                      "esa_spm_state.h", "esa_spmred_core.h",
-                                                     "esa_contained_core.h", "esa_strgraph_core.h")] + \
+                                                     "esa_contained_core.h", "esa_strgraph_core.h",
+                                                     "esa_kcorrect_core.h")] + \
           [os.path.join(ROOT, "include", h) for h in ("gtamd_esa.h", "gtamd_encode.h", "gtamd_pck.h",
                                                        "gtamd_check.h", "gtamd_mstat.h",
                                                        "gtamd_maxpairs.h", "gtamd_qmatch.h",
@@ -33,7 +34,7 @@ HEADERS = [os.path.join(HERE, "csrc", f) for f in ("esa_common.h", "esa_own.h", 
                                                        "gtamd_locali.h", "gtamd_pckidx.h",
                                                        "gtamd_pcktag.h", "gtamd_pcklocali.h",
                                                        "gtamd_spmred.h", "gtamd_contained.h",
-                                                       "gtamd_strgraph.h")]
+                                                       "gtamd_strgraph.h", "gtamd_kcorrect.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -168,6 +169,13 @@ class ContainedInfo(ctypes.Structure):   # gtamd_contained_info, include/gtamd_c
     _fields_ = [(name, ctypes.c_uint64) for name in ("table_entries", "sequences", "reads")] + \
                [("count", ctypes.c_uint64 * 5), ("device_bytes", ctypes.c_uint64)] + \
                [(name, ctypes.c_float) for name in ("device_ms", "lists_ms")]
+
+
+class KcorrectInfo(ctypes.Structure):    # gtamd_kcorrect_info, include/gtamd_kcorrect.h
+    _fields_ = [(name, ctypes.c_uint64) for name in
+                ("table_entries", "suffixes", "groups", "untrusted_groups", "records", "dependent", "rounds", "changed")] + \
+               [("delta", ctypes.c_int64 * 4), ("device_bytes", ctypes.c_uint64), ("device_ms", ctypes.c_float),
+                ("k", ctypes.c_uint32), ("c", ctypes.c_uint32)]
 
 
 class StrgraphInfo(ctypes.Structure):    # gtamd_strgraph_info, include/gtamd_strgraph.h
@@ -451,6 +459,21 @@ STRGRAPH_ABI = {
     "gtamd_strgraph_get_info": (_INT, [_P, ctypes.POINTER(StrgraphInfo)]),
 }
 
+# every symbol include/gtamd_kcorrect.h declares
+KCORRECT_ABI = {
+    "gtamd_kcorrect_create": (_P, [_INT]),
+    "gtamd_kcorrect_destroy": (None, [_P]),
+    "gtamd_kcorrect_geometry": (None, [ctypes.POINTER(_U32)]),
+    "gtamd_kcorrect_set_index": (_INT, [_P, _P, _U64, _P, _U32, _P, _INT]),
+    "gtamd_kcorrect_set_index_host": (_INT, [_P, _P, _U64, _P, _U32, _P, _INT]),
+    "gtamd_kcorrect_set_index_esa": (_INT, [_P, _P, _P, _U64, _INT]),
+    "gtamd_kcorrect_decide": (_INT, [_P, _U32, _U32, ctypes.POINTER(KcorrectInfo)]),
+    "gtamd_kcorrect_records": (_INT, [_P, _P, _INT]),
+    "gtamd_kcorrect_apply": (_INT, [_P, _P, _U64, ctypes.POINTER(_P), ctypes.POINTER(_U64)]),
+    "gtamd_kcorrect_result": (_INT, [_P, _P, _INT]),
+    "gtamd_kcorrect_get_info": (_INT, [_P, ctypes.POINTER(KcorrectInfo)]),
+}
+
 _lib = None
 
 
@@ -477,7 +500,7 @@ def load():
                 list(MAXPAIRS_ABI.items()) + list(QMATCH_ABI.items()) + list(SPM_ABI.items()) + list(TAGMATCH_ABI.items()) + \
                 list(LOCALI_ABI.items()) + list(PCKIDX_ABI.items()) + list(PCKTAG_ABI.items()) + \
                 list(PCKLOCALI_ABI.items()) + list(SPMRED_ABI.items()) + list(CONTAINED_ABI.items()) + \
-                list(STRGRAPH_ABI.items()):
+                list(STRGRAPH_ABI.items()) + list(KCORRECT_ABI.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

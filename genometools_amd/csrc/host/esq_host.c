@@ -484,6 +484,48 @@ static int sw_apply(infile *in, int kind, int withlengths, uint64_t n, uint64_t 
   return idx == items ? 0 : -1;
 }
 
+/* where the sections that `readjoiner correct` rewrites lie in the bytes of an
+   INDEX.esq: the header is walked as gtamd_read_esq_alpha walks it */
+int gtamd_esq_locate(const uint8_t *data, uint64_t len, uint64_t *sat, uint64_t *n, uint64_t *chardist_off,
+                     uint64_t *numofchars, uint64_t *twobit_off)
+{
+  infile in;
+  uint64_t version, numfiles, namelen, alphatype, alphadeflen, chars = 4;
+  const uint8_t *is64;
+  in.p = data; in.len = len; in.off = 0; in.bad = 0;
+  is64 = take(&in, 1);
+  if (is64 == NULL || *is64 != 1) return -1;
+  version = take_word(&in);
+  *sat = take_word(&in);
+  *n = take_word(&in);
+  (void) take_word(&in);                               /* numofdbsequences */
+  numfiles = take_word(&in);
+  namelen = take_word(&in);
+  (void) take(&in, 14 * 8);
+  (void) take_word(&in); (void) take_word(&in);       /* min/max sequence length */
+  alphatype = take_word(&in);
+  alphadeflen = take_word(&in);
+  if (in.bad || version != 3 || alphatype > 2) return -1;
+  if (alphatype == 1) chars = 20;
+  if (alphadeflen > 0) {                               /* a custom alphabet: not one the 2-bit words hold */
+    if (alphatype != 2) return -1;
+    (void) take(&in, alphadeflen);
+    chars = 0;
+  }
+  (void) take(&in, namelen);
+  (void) take(&in, 1);                                 /* maxsubalphasize */
+  (void) take_word(&in);                               /* numofallchars */
+  (void) take_items(&in, sizeof (gtamd_filelength), numfiles);
+  *chardist_off = in.off;
+  *numofchars = chars;
+  (void) take_items(&in, 8, chars);
+  *twobit_off = in.off;
+  if (in.bad || chars == 0) return -1;
+  if (*sat >= GTAMD_SAT_EQUALLENGTH && *sat <= GTAMD_SAT_UINT32TABLES &&
+      (*n < 32 ? 2 : 2 + (*n - 1) / 32) > bytes_left(&in) / 8) return -1;
+  return 0;
+}
+
 int gtamd_read_esq(const char *indexname, uint8_t **enc_out, uint64_t *n_out,
                    int *protein_out, gtamd_seqstats *ss, char *err, size_t errlen)
 {

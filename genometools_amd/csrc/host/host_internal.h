@@ -107,6 +107,26 @@ int gtamd_prefilter_write_readset(const char *readset, const char *const *paths,
 int gtamd_prefilter_write_cntlist(const char *path, const uint8_t *removed, uint64_t reads, char *err,
                                   size_t errlen);
 
+/* ---- correct_host.c, esq_host.c: what `readjoiner correct` rewrites; nothing
+   here calls the engine ---- */
+
+/* The sections of the bytes of an INDEX.esq that an edit touches: the access
+   type, the symbols, the offset of the character distribution with its entries
+   and the offset of the 2-bit words.  -1 for bytes that are no such file. */
+int gtamd_esq_locate(const uint8_t *data, uint64_t len, uint64_t *sat, uint64_t *n, uint64_t *chardist_off,
+                     uint64_t *numofchars, uint64_t *twobit_off);
+/* INDEX.esq edited IN PLACE as gt_twobitenc_editor_edit does it
+   (src/match/rdj-twobitenc-editor.c:75-96), record by record in the order given:
+   letters[r] (0..3) at positions[r].  Only the 2-bit words of those positions
+   and the character distribution are written.  The distribution is kept as the
+   reference keeps it: the letter an edit replaces is taken off its count only at
+   the last four positions of a 2-bit word, elsewhere the count of letter 0 goes
+   down (the reference casts the masked word to a byte before it shifts it).  A
+   file whose access type is not the equal-length one is refused with the
+   reference's sentence, and nothing is written. */
+int gtamd_correct_patch_esq(const char *indexname, const uint64_t *positions, const uint8_t *letters,
+                            uint64_t count, char *err, size_t errlen);
+
 /* What follows is shared between the tools of this directory and stays inside
    libgtamd_host.so. */
 #define GTAMD_INTERNAL __attribute__((visibility("hidden")))

@@ -9,6 +9,7 @@
    `gt-suffixerator-amd encseq2spm ...` is `gt encseq2spm ...`,
    `gt-suffixerator-amd readjoiner overlap ...` is `gt readjoiner overlap ...`,
    `gt-suffixerator-amd readjoiner prefilter ...` is `gt readjoiner prefilter ...`,
+   `gt-suffixerator-amd readjoiner correct ...` is `gt readjoiner correct ...`,
    `gt-suffixerator-amd assembly ...` is `gt readjoiner assembly ...` with default options,
    `gt-suffixerator-amd tagerator ...` is `gt tagerator ...`,
    `gt-suffixerator-amd idxlocali ...` is `gt dev idxlocali ...` */
@@ -73,6 +74,13 @@ int main(int argc, char **argv)
   if (argc > 3 && !strcmp(argv[1], "readjoiner") && !strcmp(argv[2], "prefilter")) {
     if (gtamd_readjoiner_prefilter(argc - 2, (const char **) argv + 2, err, sizeof err) != 0) {
       fprintf(stderr, "gt readjoiner prefilter: error: %s\n", err);
+      return 1;
+    }
+    return 0;
+  }
+  if (argc > 3 && !strcmp(argv[1], "readjoiner") && !strcmp(argv[2], "correct")) {
+    if (gtamd_readjoiner_correct(argc - 2, (const char **) argv + 2, err, sizeof err) != 0) {
+      fprintf(stderr, "gt readjoiner correct: error: %s\n", err);
       return 1;
     }
     return 0;

@@ -33,6 +33,9 @@
                             (src/tools/gt_readjoiner_prefilter.c), on the device
                             through the encoder, the engine and
                             include/gtamd_contained.h
+    gtamd_readjoiner_correct  `gt readjoiner correct -ii INDEX -k K -c C`
+                            (src/tools/gt_readjoiner_correct.c), on the device
+                            through the engine and include/gtamd_kcorrect.h
     gtamd_assembly          `gt readjoiner assembly -readset X` with default
                             options (src/tools/gt_readjoiner_assembly.c), on
                             the device through include/gtamd_strgraph.h
@@ -495,6 +498,26 @@ int gtamd_readjoiner_overlap(int argc, const char **argv, char *err, size_t errl
    Returns 0, or -1 with the message in err (the caller prints "gt readjoiner
    prefilter: error: <err>" and exits 1). */
 int gtamd_readjoiner_prefilter(int argc, const char **argv, char *err, size_t errlen);
+
+/* `gt readjoiner correct -ii INDEX [-k K] [-c C]` (tool function
+   src/tools/gt_readjoiner_correct.c; what it replaces: src/match/rdj-errfind.c
+   and the traversal under it): the k-mer based error correction of the reads of
+   INDEX.esq, on both strands (definition and order rules:
+   include/gtamd_kcorrect.h).  The sub-command `readjoiner correct`, followed by
+   an option at least.
+     -ii INDEX   INDEX.prj and INDEX.esq (and INDEX.ssp where the reader wants
+                 it); no table is read: .suf and .lcp of the mirrored reads are
+                 built on the device in this process
+     -k K        k-mer length, 1 at least, default 31; above 255 refused in words
+     -c C        minimal trusted count, 1 at least, default 3
+   INDEX.esq is edited IN PLACE as the reference edits it: the 2-bit words of the
+   changed positions and the character distribution.  Nothing is printed.
+   INDEX.suf and INDEX.lcp, if present, are left alone.  A sequence file whose
+   access type is not the equal-length one is refused with the reference's
+   sentence.  The development options -encseq and -dbg are refused by name.
+   Returns 0, or -1 with the message in err (the caller prints "gt readjoiner
+   correct: error: <err>" and exits 1). */
+int gtamd_readjoiner_correct(int argc, const char **argv, char *err, size_t errlen);
 
 /* Readjoiner's bin32 list of matches (src/match/rdj-spmlist.c:45-124): one
    header byte, then three uint32 a match in host byte order: suffix_read,
